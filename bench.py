@@ -3,6 +3,17 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--channels all|rgb] [--rays 4096] [--samples 512]
                     [--grid permuto|hash] [--raymarch ray|voxel --occupancy 0.1] [--pose-opt] [--dry-run]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`cpu_baseline` null; `roofline` null
+too, except with --graphs off, whose timed steps carry the roofline events themselves in both modes).  Everything else
+the record below carries - the eager roofline pass after graph-replayed steps, per-entry-point tables, sustained / eager /
+rgb-only / lin-assignment lines, the other configurations, the best.yaml regimes, render lines, scaling regimes at N > 1
+and the CPU baseline - runs only with --full.  --dump-outputs DIR writes what the last timed step computed (its loss, the
+rendered channels, the parameters after its Adam step) as DIR/<name>.npy in float32 (float64 for integer and bool
+arrays); an array of more than DUMP_SAMPLE elements is written as the elements at DUMP_SAMPLE fixed, seeded flat
+indices.  The inputs are seeded: the same arguments give the same inputs in every run, so two builds can be compared
+output for output.
 
 Workload at N = 1 (BASELINE.json configs[1]): PanopticDeltaNeF + permutohedral grids (L = 24, F = 2,
 T = 2^18, main + delta), 4096 rays x 512 'ray'-mode samples (M = 2 097 152 packed samples, dense
@@ -53,6 +64,8 @@ HBM_PEAK_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0
 MFMA_PEAK_TFLOPS = 2500.0    # same guide: dense bf16 MFMA ~2.5 PFLOP/s
 SETTLE_STEPS = 6             # untimed steps between the interpreter's garbage collection and the barrier that opens a timed region (Job.timed)
 LINE_BUDGET = 4096           # the driver parses the LAST stdout line: round 5's grew to 32 KB and was recorded as `parsed: null`
+DUMP_SAMPLE = 1 << 20        # --dump-outputs: elements kept of a larger array (4 MB in float32)
+DUMP_BUDGET = 64 << 20       # --dump-outputs: bytes written in all at most
 
 
 # --------------------------------------------------------------------------------------------- the result line and its detail file
@@ -191,9 +204,9 @@ def parse(argv=None):
     ap.add_argument("--images", type=int, default=6, help="--pose-opt: images per step (rays are split evenly over them)")
     ap.add_argument("--table-dtype", default="fp32", choices=["fp32", "fp16"], help="grid tables (BASELINE configs[4]: fp16 features)")
     ap.add_argument("--fp32-coords", action="store_true", help="permuto grids: skip the fp16 coordinate rounding of the reference's autocast")
-    ap.add_argument("--sustain-steps", type=int, default=300, help="extra timed region after the K steps (0 = off)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-aux", action="store_true", help="skip the rgb-only / sustained / configs / strong measurements")
+    ap.add_argument("--sustain-steps", type=int, default=300, help="--full: extra timed region after the K steps (0 = off)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-aux", action="store_true", help="--full without the rgb-only / sustained / configs / strong measurements (the roofline events stay)")
     ap.add_argument("--graphs", default="on", choices=["on", "off", "static"],
                     help="PanopticPackedRFTracer(use_graphs=...): on = replay the post-march part of the step as HIP graphs (no pose-opt; at N > 1 the "
                          "backward is captured as two graphs so the delta table's all-reduce starts between them); static = static padded buffers + "
@@ -205,7 +218,18 @@ def parse(argv=None):
                     help="N > 1: table gradients travel as the union of the ranks' touched rows (shard.SparseRows): bounded = slots sized from earlier steps, the "
                          "host never waits; exact = the host reads the per-level counts each step.  The --dry-run regime lines always run it (bounded unless said otherwise)")
     ap.add_argument("--dry-run", action="store_true", help="CPU + gloo: process group, shard collectives, timing and JSON plumbing only")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline's timed steps: the eager roofline pass, per-entry-point tables, sustained / eager / rgb-only / lin-assignment "
+                         "lines, other configurations, best.yaml regimes, render lines, scaling regimes at N > 1 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the last step's loss, rendered channels and updated parameters as DIR/<name>.npy (float32; "
+                         "float64 for integer and bool arrays)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU run (a dry run computes no outputs)")
+    return args
 
 
 # ------------------------------------------------------------------------------------ self-launch (parent, never touches a GPU)
@@ -424,16 +448,21 @@ class ReferenceFormulationThingsLoss:
         return loss
 
 
-def train_step(nef, tracer, opt, rays, gt, channels, world, sync=None, lin_assign=None, images=1, points_fn=None, seg_reg=False, overlap=False):
+def train_step(nef, tracer, opt, rays, gt, channels, world, sync=None, lin_assign=None, images=1, points_fn=None, seg_reg=False, overlap=False,
+               outputs=None):
     """images / points_fn / seg_reg: the instance term over a batch of `images` images as pc_nerf/trainer.py:483-533 forms it under
     configs/bup20/best.yaml - LinAssignmentThingsLoss per image (outlier rejection from the rendered depth's 3-D points when points_fn is
-    given, :508-518) + segment_consistency_regularizer on the same probabilities (:525-527, weight 1.0)."""
+    given, :508-518) + segment_consistency_regularizer on the same probabilities (:525-527, weight 1.0).
+    outputs (a dict, --dump-outputs): receives the step's rendered channels, detached (no reference to the autograd graph, whose nodes hold
+    the forward's activations), under "render"."""
     import torch
     import torch.nn.functional as F
     opt.zero_grad(set_to_none=True)
     if callable(rays):
         rays = rays()            # pose optimisation: this step's rays from the current extrinsics
     rb = tracer(nef, channels=channels, rays=rays, stage="train")
+    if outputs is not None:
+        outputs["render"] = {k: v.detach() for k, v in vars(rb).items() if isinstance(v, torch.Tensor)}
     # trainer.py:443-446 / best.yaml:116 rgb L1; trainer.py:465-467 nll_loss(log(p + 1e-27), gt); the instance term stands for the
     # per-image linear-assignment NLL (trainer.py:499-520 -> loss/lin_assignment_things.py:80), same arithmetic on a fixed target.
     # pagnerf_amd.loss.render_loss evaluates exactly that sum in one launch (and its gradients in one more).
@@ -483,6 +512,30 @@ def train_step(nef, tracer, opt, rays, gt, channels, world, sync=None, lin_assig
         sync.finish()       # delta-table all-reduce was launched from the backward; the rest goes as one flat RCCL all-reduce
     opt.step()
     return loss
+
+
+def dump_outputs(path, loss, render, params):
+    """--dump-outputs: `loss`, the rendered channels `render` (a dict) and the (name, tensor) pairs `params` as path/<name>.npy - floating-point
+    arrays in float32, integer and bool ones in float64.
+    An array of more than DUMP_SAMPLE elements is written as its elements at DUMP_SAMPLE sorted flat indices drawn without replacement by
+    numpy's generator seeded with 0 - the same indices in every run."""
+    import numpy as np
+    import torch
+    arrays = [("loss", loss)] + [("render." + k, v) for k, v in sorted(render.items())] + \
+             [("param." + k, v) for k, v in params]
+    out, total = {}, 0
+    for name, t in arrays:
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device))
+        out[name] = (t.float() if t.is_floating_point() else t.double()).cpu().numpy()      # integers exactly beyond 2^24
+        total += out[name].nbytes
+    if total > DUMP_BUDGET:
+        raise RuntimeError("bench.py: --dump-outputs would write %d bytes, more than %d" % (total, DUMP_BUDGET))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(n_rays, n_samples, budget_s=9.0, points=((256, 64), (4096, 64)), point_budget_s=14.0):
@@ -997,8 +1050,21 @@ def run_rank(args):
                                            sparse=(sparse if sparse is not None else (False if args.sparse_sync == "off" else args.sparse_sync)))
 
         def step(self, channels=None):
-            return train_step(self.nef, self.tracer, self.opt, self.rays, self.gt, channels or self.channels, world, self.sync,
-                              lin_assign=self.lin_assign, images=self.images, points_fn=self.points_fn, seg_reg=self.seg_reg, overlap=self.overlap)
+            out = {} if args.dump_outputs else None         # a plain run keeps nothing of a step
+            loss = train_step(self.nef, self.tracer, self.opt, self.rays, self.gt, channels or self.channels, world, self.sync,
+                              lin_assign=self.lin_assign, images=self.images, points_fn=self.points_fn, seg_reg=self.seg_reg, overlap=self.overlap,
+                              outputs=out)
+            if out is not None:
+                out["loss"] = loss.detach()
+                self.last = out
+            return loss
+
+        def dump(self, path):
+            """--dump-outputs: what the last step computed (its loss and render buffer, the parameters after its Adam step)."""
+            params = list(self.nef.named_parameters())
+            if hasattr(self, "pose"):
+                params += [("camera_extrinsics", p_) for p_ in self.pose.parameters()]
+            dump_outputs(path, self.last["loss"], self.last["render"], params)
 
         def timed(self, n_steps, channels=None, profile=None):
             """profile (a set of C-ABI entry points): HIP events around those calls - which only exist on the EAGER path (a graph replay
@@ -1068,12 +1134,16 @@ def run_rank(args):
     # call exists to bracket with events: the roofline kernel's duration is then measured over K further EAGER steps right after the
     # timed region (same process, same inputs, HIP events on the launch stream around its C-ABI call).  With --graphs off the events
     # sit inside the timed region itself, as in rounds 1 - 2.
+    # The K timed steps are the same in a plain and a --full run; only --full adds the eager pass after them.
     graphs_on = bool(job.tracer.use_graphs)       # pose-optimisation steps replay graphs too (d origins / d dirs are outputs of the backward graph)
     if graphs_on:
-        dt, _ = job.timed(args.steps)
-        _, prof = job.timed(args.steps, profile={enc_name})
+        dt, prof = job.timed(args.steps)
     else:
         dt, prof = job.timed(args.steps, profile=None if os.environ.get("PAG_BENCH_PROFILE_ALL") else {enc_name})
+    if rank == 0 and args.dump_outputs:
+        job.dump(args.dump_outputs)
+    if graphs_on and args.full:
+        _, prof = job.timed(args.steps, profile={enc_name})
 
     M = job.samples_per_step() if (args.raymarch == "voxel" or args.pose_opt) else args.rays * args.samples
     L_, F_ = (24, 2) if args.grid == "permuto" else (16, 2)
@@ -1106,7 +1176,8 @@ def run_rank(args):
                                 "replay HIP graphs: no per-launch host call to bracket)" % args.steps) if graphs_on else
                                "HIP events around the kernel's C-ABI call inside the timed steps")
 
-    if roofline is not None and not args.no_aux:
+    aux = args.full and not args.no_aux
+    if roofline is not None and aux:
         roofline["request_rate"] = request_rate(job.nef, job.rays, job.tracer, roofline["avg_launch_ms"], args.table_dtype)
     line = dict(
         metric="rays/sec (train step) on BUP20-shape scene", value=round(world * args.rays * args.steps / dt, 1), unit="rays/s",
@@ -1127,7 +1198,7 @@ def run_rank(args):
         rccl_ranks_seen=ranks_seen, backend=backend, grad_sync=((job.sync.auto_decision or args.grad_sync) if world > 1 else None), roofline=roofline,
         graphs=(dict(job.graph_stats(), priming_steps=priming) if job.graph_stats() is not None else None))
 
-    if not args.no_aux:
+    if aux:
         # ---- per-entry-point device time: a separate, untimed pass with events around every C-ABI call
         n_bd = max(1, min(5, args.steps))
         barrier()
@@ -1427,7 +1498,7 @@ def run_rank(args):
             line["render_sharded"] = dict(rays=n_val, ms=round(d * 1e3, 3), rays_s=round(n_val / d, 1), gathered_bytes_per_rank=n_val * 211 * 4,
                                           gathered_equals_local=same)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(64, 512)
     elif rank == 0:
         line["cpu_baseline"] = None
