@@ -163,20 +163,11 @@ EXPORTS = tuple(_SIGS)
 _lib = None
 
 
-def library_path():
-    """The in-tree library; PAG_LIB_VARIANT=<tag> (kernel experiments only, scripts/build_variant.sh) loads lib/libpagnerf_hip_<tag>.so -
-    the same sources built with extra -D flags - so that variants can be A/B-timed on one box without rebuilding there."""
-    tag = os.environ.get("PAG_LIB_VARIANT")
-    if tag:
-        return os.path.join(os.path.dirname(_build.LIB), "libpagnerf_hip_%s.so" % tag)
-    return _build.LIB
-
-
 def load():
     """dlopen the C-ABI library (building is __graft_entry__.build()'s job); raises if absent."""
     global _lib
     if _lib is None:
-        path = library_path()
+        path = _build.LIB
         if not os.path.exists(path):
             raise RuntimeError("libpagnerf_hip.so not found at %s - run `python -m pagnerf_amd.build` "
                                "(there is no CPU fallback for the HIP path)" % path)

@@ -14,7 +14,6 @@
 // order of the oracle (oracle/hash_encode.py, oracle/permuto_encode.py); the file is compiled with
 // -ffp-contract=off.  With fp32 tables and fp32 output the result is bit-identical to the oracle.
 #include "encode_common.h"
-#include "blocktime.h"
 
 using namespace pag_enc;
 
@@ -51,19 +50,17 @@ __device__ __forceinline__ void store_grouped(float *, int64_t, int, int64_t, ..
 
 // Workgroup size of the per-sample, XCD-pinned kernels (forward gathers, position gradients).  A workgroup of the permutohedral forward lives ~5 us (12 gathers per thread, combine, store) and the launch has
 // 8 * M / threads of them: at 256 threads the dispatcher handed a CU a new workgroup only every ~0.5 us and the CUs held 3.3 workgroups
-// on average where their registers allow 6 (scripts/block_timeline.py) - half of the gathers that could be in flight were not.  512
+// on average where their registers allow 6 - half of the gathers that could be in flight were not.  512
 // threads halve the number of workgroups: 399 -> 328 us on the bench workload (two 256-sample tiles per workgroup in a loop measure the
 // same but cost 10 VGPRs; 1024 threads lose a little again: 344).
-#ifndef PAG_ENC_FWD_THREADS
-#define PAG_ENC_FWD_THREADS 512
-#endif
+constexpr int ENC_FWD_THREADS = 512;
 template <typename TableT, typename OutT, int F, int LPX>
-__global__ __launch_bounds__(PAG_ENC_FWD_THREADS) void hash_fwd_kernel(const float *__restrict__ xyz, int64_t M,
+__global__ __launch_bounds__(ENC_FWD_THREADS) void hash_fwd_kernel(const float *__restrict__ xyz, int64_t M,
                                                        const TableT *__restrict__ tables, HashParams p,
                                                        OutT *__restrict__ out, int64_t sm, int64_t sc, int grouped,
                                                        const bf16_t *__restrict__ addend) {
     const int g = blockIdx.x & 7;
-    const int64_t i = (int64_t)(blockIdx.x >> 3) * PAG_ENC_FWD_THREADS + threadIdx.x;
+    const int64_t i = (int64_t)(blockIdx.x >> 3) * ENC_FWD_THREADS + threadIdx.x;
     if (i >= M) return;
     float x[3];
     load_xyz(xyz, i, p.half_coords, x);
@@ -130,11 +127,11 @@ __global__ __launch_bounds__(PAG_ENC_FWD_THREADS) void hash_fwd_kernel(const flo
 }
 
 template <typename GradT, int F, int LPX>
-__global__ __launch_bounds__(PAG_ENC_FWD_THREADS) void hash_bwd_kernel(const float *__restrict__ xyz, int64_t M,
+__global__ __launch_bounds__(ENC_FWD_THREADS) void hash_bwd_kernel(const float *__restrict__ xyz, int64_t M,
                                                        const GradT *__restrict__ go, int64_t sm, int64_t sc,
                                                        HashParams p, float *__restrict__ gtab) {
     const int g = blockIdx.x & 7;
-    const int64_t i = (int64_t)(blockIdx.x >> 3) * PAG_ENC_FWD_THREADS + threadIdx.x;
+    const int64_t i = (int64_t)(blockIdx.x >> 3) * ENC_FWD_THREADS + threadIdx.x;
     if (i >= M) return;
     float x[3];
     load_xyz(xyz, i, p.half_coords, x);
@@ -162,14 +159,11 @@ __global__ __launch_bounds__(PAG_ENC_FWD_THREADS) void hash_bwd_kernel(const flo
     }
 }
 
-#ifdef PAG_EXP_JAC
-__device__ bf16_t *g_exp_jac = nullptr;
-#endif
 template <typename TableT, typename OutT, int F, int LPX>
 __device__ __forceinline__ void permuto_fwd_body(const float *__restrict__ xyz, int64_t M, const TableT *__restrict__ tables, const PermutoParams &p,
                                                  OutT *__restrict__ out, int64_t sm, int64_t sc, int grouped, const bf16_t *__restrict__ addend) {
     const int g = blockIdx.x & 7;
-    const int64_t i = (int64_t)(blockIdx.x >> 3) * PAG_ENC_FWD_THREADS + threadIdx.x;
+    const int64_t i = (int64_t)(blockIdx.x >> 3) * ENC_FWD_THREADS + threadIdx.x;
     if (i >= M) return;
     float x[3];
     load_xyz(xyz, i, p.half_coords, x);
@@ -184,29 +178,8 @@ __device__ __forceinline__ void permuto_fwd_body(const float *__restrict__ xyz, 
         int l = xcd8_level(g, j);
         int le = l < p.L ? l : p.L - 1;
         uint32_t idx[4];
-#ifdef PAG_DBG_ONLY_J      // experiment: only the j-th level of every XCD group (what a level-phased launch would run per phase)
-        if (j != PAG_DBG_ONLY_J) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                bary[j][r] = 0.0f;
-#pragma unroll
-                for (int f = 0; f < F; ++f) e[j][r][f] = 0.0f;
-            }
-            continue;
-        }
-#endif
         permuto_simplex(x, p.shift[le], p.sf[le], p.capacity, p.pow2mask, idx, bary[j]);
         const TableT *tab = tables + (int64_t)le * p.capacity * F;
-#ifdef PAG_DBG_HOTIDX      // experiment: all gathers hit 256 hot rows (isolates the arithmetic + store cost)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) idx[r] &= 0xFFu;
-#endif
-#ifdef PAG_DBG_CHEAPIDX    // experiment: random rows from a 2-instruction hash (isolates the gather cost)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) idx[r] = (((uint32_t)i * 4u + r + le * 77u) * 2654435761u) >> 14;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bary[j][r] = 0.25f;
-#endif
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             gather_row<F>(tab, idx[r], e[j][r]);
@@ -228,58 +201,29 @@ __device__ __forceinline__ void permuto_fwd_body(const float *__restrict__ xyz, 
     }
     if constexpr (LPX * F <= 8 && sizeof(OutT) == 2)
         if (grouped) store_grouped<LPX * F>(out, M, g, i, gvals, addend != nullptr, addv);
-#ifdef PAG_EXP_JAC      // experiment (scripts/exp_jac_store.py): what would it cost the forward to write d feat / d xyz (6 values per level) next to the features?
-    if (g_exp_jac != nullptr && addend == nullptr) {
-        bf16_t jv[24];
-#pragma unroll
-        for (int q = 0; q < 24; ++q) jv[q] = (bf16_t)0.0f;
-#pragma unroll
-        for (int j = 0; j < LPX; ++j) {
-            const int l = xcd8_level(g, j), le = l < p.L ? l : p.L - 1;
-#pragma unroll
-            for (int f = 0; f < F; ++f) {
-                const float d01 = e[j][0][f] - e[j][1][f], d12 = e[j][1][f] - e[j][2][f], d23 = e[j][2][f] - e[j][3][f], d30 = e[j][3][f] - e[j][0][f];
-                if (j * 6 + f * 3 + 2 < 24) {
-                    jv[j * 6 + f * 3 + 0] = (bf16_t)(0.25f * (d01 - d12) * p.sf[le][0]);
-                    jv[j * 6 + f * 3 + 1] = (bf16_t)(0.25f * (d01 + d12 - 2.0f * d23) * p.sf[le][1]);
-                    jv[j * 6 + f * 3 + 2] = (bf16_t)(0.25f * (d01 + d12 + d23 - 3.0f * d30) * p.sf[le][2]);
-                }
-            }
-        }
-        typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-        u32x4_t *dst = reinterpret_cast<u32x4_t *>(g_exp_jac + ((int64_t)g * M + i) * PAG_EXP_JAC);
-        const u32x4_t *srcv = reinterpret_cast<const u32x4_t *>(jv);
-#pragma unroll
-        for (int q = 0; q < PAG_EXP_JAC / 8; ++q) dst[q] = srcv[q];
-    }
-#endif
 }
 
 // Two kernel symbols for the same body: the plain launch (the roofline kernel of bench.py) and the `_add` launch of the delta grid, so that
 // rocprofv3's per-kernel statistics and PMC counters keep them apart.
-#ifndef PAG_ENC_FWD_WAVES
-#define PAG_ENC_FWD_WAVES 1      // minimum waves per SIMD asked of the compiler for the permutohedral forward (experiments: 8 = 64 VGPRs)
-#endif
+constexpr int ENC_FWD_WAVES = 1;      // minimum waves per SIMD asked of the compiler for the permutohedral forward (8 would mean 64 VGPRs)
 template <typename TableT, typename OutT, int F, int LPX>
-__global__ __launch_bounds__(PAG_ENC_FWD_THREADS, PAG_ENC_FWD_WAVES) void permuto_fwd_kernel(const float *__restrict__ xyz, int64_t M, const TableT *__restrict__ tables, PermutoParams p,
+__global__ __launch_bounds__(ENC_FWD_THREADS, ENC_FWD_WAVES) void permuto_fwd_kernel(const float *__restrict__ xyz, int64_t M, const TableT *__restrict__ tables, PermutoParams p,
                                                           OutT *__restrict__ out, int64_t sm, int64_t sc, int grouped) {
-    PAG_BLOCK_TIMER(1);
     permuto_fwd_body<TableT, OutT, F, LPX>(xyz, M, tables, p, out, sm, sc, grouped, nullptr);
 }
 template <typename TableT, typename OutT, int F, int LPX>
-__global__ __launch_bounds__(PAG_ENC_FWD_THREADS, PAG_ENC_FWD_WAVES) void permuto_fwd_add_kernel(const float *__restrict__ xyz, int64_t M, const TableT *__restrict__ tables, PermutoParams p,
+__global__ __launch_bounds__(ENC_FWD_THREADS, ENC_FWD_WAVES) void permuto_fwd_add_kernel(const float *__restrict__ xyz, int64_t M, const TableT *__restrict__ tables, PermutoParams p,
                                                               OutT *__restrict__ out, int64_t sm, int64_t sc, int grouped,
                                                               const bf16_t *__restrict__ addend) {
-    PAG_BLOCK_TIMER(2);
     permuto_fwd_body<TableT, OutT, F, LPX>(xyz, M, tables, p, out, sm, sc, grouped, addend);
 }
 
 template <typename GradT, int F, int LPX>
-__global__ __launch_bounds__(PAG_ENC_FWD_THREADS) void permuto_bwd_kernel(const float *__restrict__ xyz, int64_t M,
+__global__ __launch_bounds__(ENC_FWD_THREADS) void permuto_bwd_kernel(const float *__restrict__ xyz, int64_t M,
                                                           const GradT *__restrict__ go, int64_t sm, int64_t sc,
                                                           PermutoParams p, float *__restrict__ gtab) {
     const int g = blockIdx.x & 7;
-    const int64_t i = (int64_t)(blockIdx.x >> 3) * PAG_ENC_FWD_THREADS + threadIdx.x;
+    const int64_t i = (int64_t)(blockIdx.x >> 3) * ENC_FWD_THREADS + threadIdx.x;
     if (i >= M) return;
     float x[3];
     load_xyz(xyz, i, p.half_coords, x);
@@ -441,11 +385,11 @@ __device__ __forceinline__ void xyz_grad_sample(const float *__restrict__ xyz, i
 }
 
 template <int KIND, typename TableT, typename GradT, int F, int LPX>
-__global__ __launch_bounds__(PAG_ENC_FWD_THREADS) void xyz_grad_kernel(const float *__restrict__ xyz, int64_t M, const TableT *__restrict__ tables,
+__global__ __launch_bounds__(ENC_FWD_THREADS) void xyz_grad_kernel(const float *__restrict__ xyz, int64_t M, const TableT *__restrict__ tables,
                                                        const GradT *__restrict__ go, int64_t sm, int64_t sc, int grouped,
                                                        HashParams hp, PermutoParams pp, float *__restrict__ part) {
     const int g = blockIdx.x & 7;
-    const int64_t i = (int64_t)(blockIdx.x >> 3) * PAG_ENC_FWD_THREADS + threadIdx.x;
+    const int64_t i = (int64_t)(blockIdx.x >> 3) * ENC_FWD_THREADS + threadIdx.x;
     if (i >= M) return;
     float dx[3];
     xyz_grad_sample<KIND, TableT, GradT, F, LPX>(xyz, i, M, g, tables, go, sm, sc, grouped, hp, pp, dx);
@@ -461,13 +405,13 @@ __global__ __launch_bounds__(PAG_ENC_FWD_THREADS) void xyz_grad_kernel(const flo
 // along the samples: every (wave, ray) pair has a row of its own, `waves + N` rows per group) - 3 B per sample on 512-sample rays.  ray_slots_sum_kernel
 // adds a ray's rows (fixed order: bitwise reproducible).
 template <int KIND, typename TableT, typename GradT, int F, int LPX>
-__global__ __launch_bounds__(PAG_ENC_FWD_THREADS) void xyz_grad_rays_kernel(const float *__restrict__ xyz, int64_t M, const TableT *__restrict__ tables,
+__global__ __launch_bounds__(ENC_FWD_THREADS) void xyz_grad_rays_kernel(const float *__restrict__ xyz, int64_t M, const TableT *__restrict__ tables,
                                                        const GradT *__restrict__ go, int64_t sm, int64_t sc, int grouped,
                                                        HashParams hp, PermutoParams pp, const int32_t *__restrict__ ridx,
                                                        const float *__restrict__ depths, float *__restrict__ slots, int64_t slot_rows) {
     const int g = blockIdx.x & 7;
     const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)(blockIdx.x >> 3) * PAG_ENC_FWD_THREADS + threadIdx.x;
+    const int64_t i = (int64_t)(blockIdx.x >> 3) * ENC_FWD_THREADS + threadIdx.x;
     const int64_t wave = i >> 6;
     if ((wave << 6) >= M) return;                    // whole wave past the end (wave-uniform)
     const bool in_range = i < M;
@@ -556,15 +500,11 @@ __global__ __launch_bounds__(256) void xyz_grad_sum_kernel(const float *__restri
 //       table in LDS, walks every tile's segment for its slice (coalesced reads, each entry read
 //       exactly once), accumulates in 64-bit fixed point with ds_add_u64 (order-independent, hence
 //       bitwise reproducible) and finally adds the slice to the table with plain coalesced stores.
-#ifndef PAG_TS
-#define PAG_TS 1024
-#endif
-#ifndef PAG_TS_HASH
-#define PAG_TS_HASH 512
-#endif
 // samples per pass-1 tile (= threads per workgroup): 1024 with 4 vertices per level (permutohedral), 512 with 8 (hash) - the hash
 // variant needs ~100 VGPRs, and two workgroups per CU (block barriers!) as well as a 32 KiB staging tile only fit with the smaller tile
-constexpr int tile_samples(int nv) { return nv == 8 ? PAG_TS_HASH : PAG_TS; }
+constexpr int TILE_SAMPLES = 1024;
+constexpr int TILE_SAMPLES_HASH = 512;
+constexpr int tile_samples(int nv) { return nv == 8 ? TILE_SAMPLES_HASH : TILE_SAMPLES; }
 constexpr int SLICE_SHIFT = 13;   // upper bound; bin_plan() shrinks it so a slice's int64 accumulators fit 64 KiB
 constexpr int NS_MAX = 256;       // slices per level supported (T <= 2^21)
 
@@ -582,17 +522,6 @@ struct BinLayout {
 // instead of a 4-byte key + 8-byte value: a third less pass-1 -> pass-2 traffic and one store / load per entry instead of two.
 // Word form (round 4; before: row | a << 12 | b << 38 in one 64-bit integer - the 64-bit shifts and ors were ~10 VALU instructions per
 // entry in the bin pass and ~8 in the reduce pass): pack = 2 adds + 1 shift + 2 v_bfi_b32, unpack = 3 ands + 1 v_lshl_or_b32.  Same values.
-#ifdef PAG_PACK_U64
-__device__ __forceinline__ uint64_t pack_entry(uint32_t key12, float v0, float v1) {
-    const uint64_t a = (uint64_t)((__float_as_uint(v0) + 0x20u) >> 6), b = (uint64_t)((__float_as_uint(v1) + 0x20u) >> 6);
-    return (uint64_t)key12 | (a << 12) | (b << 38);
-}
-__device__ __forceinline__ void unpack_entry(uint64_t e, uint32_t &key12, float &v0, float &v1) {
-    key12 = (uint32_t)e & 0xFFFu;
-    v0 = __uint_as_float(((uint32_t)(e >> 12) & 0x3FFFFFFu) << 6);
-    v1 = __uint_as_float((uint32_t)(e >> 38) << 6);
-}
-#else
 __device__ __forceinline__ uint64_t pack_entry(uint32_t key12, float v0, float v1) {
     const uint32_t a = __float_as_uint(v0) + 0x20u, b = __float_as_uint(v1) + 0x20u;
     const uint32_t lo = (a & ~63u) | (key12 & 63u), hi = (b & ~63u) | (key12 >> 6);       // key12 < 4096: v_bfi_b32
@@ -604,7 +533,6 @@ __device__ __forceinline__ void unpack_entry(uint64_t e, uint32_t &key12, float 
     v0 = __uint_as_float(lo & ~63u);
     v1 = __uint_as_float(hi & ~63u);
 }
-#endif
 
 // merge runs of equal keys in adjacent lanes: on return `emit` is set on the last lane of every run
 // and that lane's v[] holds the run's sum.  Skipped (wave-uniformly) when the wave has few repeats.
@@ -632,13 +560,6 @@ __device__ __forceinline__ void run_combine(uint32_t key, bool pair, unsigned lo
     emit = live;
     // 32-bit counts: the scalar unit has no ordered 64-bit compare, and a 64-bit popcount compare ends up on the vector unit
     if (__builtin_popcount((unsigned)m) + __builtin_popcount((unsigned)(m >> 32)) < 8) return;
-#ifdef PAG_BIN_FAKE_COMBINE
-    {
-        const bool ns = (m >> ((lane + 1) & 63)) & 1ull;
-        emit = live && (lane == 63 || !ns);
-        return;
-    }
-#endif
     if constexpr (F == 2) {
         // The production width.  The head flag travels as nf = 1.0 (no head between source and this lane) / 0.0, which turns one step
         // into v += dpp(v) * nf ; nf *= dpp(nf): three DPP-form instructions (v_fmac_f32_dpp / v_mul_f32_dpp) instead of a DPP move,
@@ -674,45 +595,23 @@ __device__ __forceinline__ void run_combine(uint32_t key, bool pair, unsigned lo
     emit = live && (lane == 63 || !next_same);
 }
 
-#ifdef PAG_BIN_TIMING      // experiment builds only (scripts/bin_phases.py): wave 0 / wave 15 of every workgroup stamp the phases into LDS, flushed at the end
-__device__ unsigned long long pag_bin_times[32768 * 32];
-#define PAG_BSTAMP(k) do { if (lane == 0 && (wave == 0 || wave == 15)) pag_bstamps[wave ? 1 : 0][k] = __builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int pag_debug_bin_times(void *dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(pag_bin_times), bytes); }
-#else
-#define PAG_BSTAMP(k)
-#endif
-
-template <int KIND /*0 hash, 1 permuto*/, typename GradT, int F, int LPX, bool PACK>
 // TWO 1024-thread workgroups per CU (8 waves per SIMD, <= 64 VGPRs): with one, every block barrier of the counting sort / staging
 // stalls the whole CU - nothing else is resident to run.  The permutohedral variant fits 64 VGPRs with 48 B of scratch and the encode
 // backward drops from 2.18 to 1.75 ms per step; the hash variant (8 vertices) would spill 140 - 300 B and is measured separately.
-#ifndef PAG_BIN_WAVES
-#define PAG_BIN_WAVES 8
-#endif
-#ifndef PAG_BIN_WAVES_HASH
-#define PAG_BIN_WAVES_HASH 4
-#endif
-__global__ __launch_bounds__(tile_samples(KIND == 0 ? 8 : 4), (KIND == 1 ? PAG_BIN_WAVES : PAG_BIN_WAVES_HASH)) void bin_kernel(const float *__restrict__ xyz, int64_t M, const GradT *__restrict__ go,
+constexpr int BIN_WAVES = 8;
+constexpr int BIN_WAVES_HASH = 4;
+template <int KIND /*0 hash, 1 permuto*/, typename GradT, int F, int LPX, bool PACK>
+__global__ __launch_bounds__(tile_samples(KIND == 0 ? 8 : 4), (KIND == 1 ? BIN_WAVES : BIN_WAVES_HASH)) void bin_kernel(const float *__restrict__ xyz, int64_t M, const GradT *__restrict__ go,
                                                  int64_t sm, int64_t sc, int grouped, HashParams hp, PermutoParams pp, BinLayout lay) {
-    PAG_BLOCK_TIMER(0);
     constexpr int NV = KIND == 0 ? 8 : 4;
     constexpr int TS = tile_samples(NV);
-#ifndef PAG_BIN_NO_STAGE
     constexpr bool STAGE = PACK && TS * NV * 8 <= 32768;      // packed 8-byte entries, tile fits 32 KiB of LDS (permutohedral: 4 vertices)
-#else
-    constexpr bool STAGE = false;
-#endif
     __shared__ uint64_t stage[STAGE ? TS * NV : 1];
     __shared__ uint32_t cnt[LPX][NS_MAX + 2];     // [.][NS_MAX + 1] = max |g| of this (tile, level)
     __shared__ uint32_t offs[LPX][NS_MAX + 1];
     const int L = KIND == 0 ? hp.L : pp.L;
     const int64_t tile = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef PAG_BIN_TIMING
-    __shared__ unsigned long long pag_bstamps[2][16];
-    if (lane == 0 && (wave == 0 || wave == 15)) pag_bstamps[wave ? 1 : 0][13] = __builtin_amdgcn_s_memrealtime();
-#endif
-    PAG_BSTAMP(0);
     const int64_t i = tile * TS + tid;
     const bool live = i < M;
     const int64_t ic = live ? i : M - 1;
@@ -738,10 +637,6 @@ __global__ __launch_bounds__(tile_samples(KIND == 0 ? 8 : 4), (KIND == 1 ? PAG_B
     const bool has_scale = KIND == 0 ? hp.has_scale : pp.has_scale;
     for (int s = tid; s < LPX * (NS_MAX + 2); s += TS) (&cnt[0][0])[s] = 0;
     __syncthreads();
-#ifdef PAG_BIN_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(x[0]), "+v"(gpiece[0]) : : "memory");
-#endif
-    PAG_BSTAMP(1);
     uint32_t idx[LPX][NV];
     float ev[LPX][NV][F];
     bool emit[LPX][NV];
@@ -770,11 +665,9 @@ __global__ __launch_bounds__(tile_samples(KIND == 0 ? 8 : 4), (KIND == 1 ? PAG_B
         } else {
             uint32_t id4[4];
             float b4[4];
-#ifndef PAG_BIN_NO_LDS_SORT
             if constexpr (STAGE)      // the staging tile is idle until the placement phase: 32 bytes of it per lane serve the rank sort
                 permuto_simplex_lds(x, pp.shift[lc], pp.sf[lc], pp.capacity, pp.pow2mask, id4, b4, reinterpret_cast<float *>(stage) + tid * 8);
             else
-#endif
                 permuto_simplex(x, pp.shift[lc], pp.sf[lc], pp.capacity, pp.pow2mask, id4, b4);
 #pragma unroll
             for (int k = 0; k < NV; ++k) {
@@ -807,17 +700,11 @@ __global__ __launch_bounds__(tile_samples(KIND == 0 ? 8 : 4), (KIND == 1 ? PAG_B
 #pragma unroll
             for (int f = 0; f < F; ++f) ev[j][k][f] = gv[f] * w[k];
             const bool lk = live && lv;
-#ifdef PAG_BIN_NO_COMBINE
-            emit[j][k] = lk;
-#else
             run_combine<F>(idx[j][k], pair_l, pair_m, lk, ev[j][k], emit[j][k], lane);
-#endif
             if (emit[j][k]) rank[j][k] = atomicAdd(&cnt[j][idx[j][k] >> lay.shift], 1u);      // read only where emit is set
         }
-        PAG_BSTAMP(2 + j);
     }
     __syncthreads();
-    PAG_BSTAMP(6);
     if (wave < LPX) {   // wave j: exclusive prefix over level j's NS slice counters
         uint32_t carry = 0;
         for (int s0 = 0; s0 < lay.NS; s0 += 64) {
@@ -835,7 +722,6 @@ __global__ __launch_bounds__(tile_samples(KIND == 0 ? 8 : 4), (KIND == 1 ? PAG_B
         if (lane == 0) offs[wave][lay.NS] = carry;
     }
     __syncthreads();
-    PAG_BSTAMP(7);
 #pragma unroll
     for (int j = 0; j < LPX; ++j) {
         const int level = grouped ? xcd8_level((int)blockIdx.y, j) : (int)blockIdx.y;
@@ -851,13 +737,10 @@ __global__ __launch_bounds__(tile_samples(KIND == 0 ? 8 : 4), (KIND == 1 ? PAG_B
                     stage[offs[j][idx[j][k] >> lay.shift] + rank[j][k]] =
                         pack_entry(idx[j][k] & ((1u << lay.shift) - 1u), ev[j][k][0], ev[j][k][F - 1]);
             __syncthreads();
-            if (j == 0) PAG_BSTAMP(8);
             const uint32_t total = offs[j][lay.NS];
             uint64_t *dst = reinterpret_cast<uint64_t *>(lay.vals) + region;
             for (uint32_t q = tid; q < total; q += TS) dst[q] = stage[q];
-            if (j == 0) PAG_BSTAMP(9);
             __syncthreads();      // the next level reuses the staging tile
-            if (j == 0) PAG_BSTAMP(10);
         }
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
@@ -876,14 +759,6 @@ __global__ __launch_bounds__(tile_samples(KIND == 0 ? 8 : 4), (KIND == 1 ? PAG_B
         for (int s = tid; s <= lay.NS; s += TS) lay.header[((int64_t)level * (lay.NS + 1) + s) * lay.ntiles + tile] = offs[j][s];
         if (tid == 0) lay.tile_max[(int64_t)level * lay.ntiles + tile] = cnt[j][NS_MAX + 1];
     }
-#ifdef PAG_BIN_TIMING
-    PAG_BSTAMP(11);
-    if (lane == 0 && (wave == 0 || wave == 15)) {
-        const unsigned b = blockIdx.x + gridDim.x * blockIdx.y;
-        pag_bstamps[wave ? 1 : 0][14] = __builtin_amdgcn_s_memrealtime();
-        if (b < 32768) for (int k = 0; k < 16; ++k) pag_bin_times[b * 32 + (wave ? 16 : 0) + k] = pag_bstamps[wave ? 1 : 0][k];
-    }
-#endif
 }
 
 // Add one wave's 64 (key, value) entries into the LDS slice.  LDS float atomics (ds_add_f32) serialise
@@ -953,36 +828,15 @@ __device__ __forceinline__ long long to_fixed(float v, int S) {
     else return __float2ll_rn(ldexpf(v, S));
 }
 
-#ifdef PAG_REDUCE_TIMING      // experiment builds only (scripts/reduce_phases.py): lane 0 of wave 0 / wave 15 of every block stamps the phases.
-// The stamps (shader clock; slots 13 / 14 the 100 MHz clock all CUs share) wait in LDS until the end of the kernel: kept in registers
-// they push the kernel past 64 VGPRs and halve its occupancy, stored to memory as they are taken they join the vmcnt waits.
-__device__ unsigned long long pag_dbg_times[8192 * 32];
-#define PAG_STAMP(k) do { if (lane == 0 && (wave == 0 || wave == 15)) pag_stamps[wave ? 1 : 0][k] = __builtin_amdgcn_s_memtime(); } while (0)
-#define PAG_STAMP_RT(k) do { if (lane == 0 && (wave == 0 || wave == 15)) pag_stamps[wave ? 1 : 0][k] = __builtin_amdgcn_s_memrealtime(); } while (0)
-extern "C" int pag_debug_reduce_times(void *dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(pag_dbg_times), bytes); }
-#else
-#define PAG_STAMP(k)
-#define PAG_STAMP_RT(k)
-#endif
-// Experiment switches (scripts/build_variant.sh; profiles/README.md round 4 has the A/B numbers):
-//   PAG_RED_SGPRS  SGPR budget.  With 81 SGPRs (what the compiler takes when left alone: next_free_sgpr 75 + 6) a gfx950 SIMD holds 7 waves of this
-//                  kernel, not 8 - the runtime's occupancy query still answers "2 workgroups per CU", the hardware runs ONE 1024-thread workgroup per
-//                  CU (scripts/exp/lds_occupancy.hip: the step is between next_free_sgpr 74 and 75).  80 costs no spill and no VGPR.
-//   PAG_RED_ORDER  0 = blocks in (level, slice) order, 1 = finest level first, 2 = + each XCD takes 8 neighbouring slices, 3 = + the coarsest
-//                  PAG_RED_HEAD levels stay in front.
-#ifndef PAG_RED_SGPRS
-#define PAG_RED_SGPRS 80
-#endif
-#ifndef PAG_RED_ORDER
-#define PAG_RED_ORDER 3
-#endif
-#ifndef PAG_RED_HEAD
-#define PAG_RED_HEAD 8
-#endif
+// SGPR budget of reduce_kernel.  With 81 SGPRs (what the compiler takes when left alone: next_free_sgpr 75 + 6) a gfx950 SIMD holds 7 waves
+// of this kernel, not 8 - the runtime's occupancy query still answers "2 workgroups per CU", the hardware runs ONE 1024-thread workgroup per
+// CU (scripts/exp/lds_occupancy.hip: the step is between next_free_sgpr 74 and 75).  80 costs no spill and no VGPR (profiles/README.md
+// round 4 has the A/B numbers).
+constexpr int RED_SGPRS = 80;
+constexpr int RED_HEAD = 8;          // coarsest levels that keep their place at the front of the block order
 
 template <int F, int NV, bool PACK>
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(PAG_RED_SGPRS))) void reduce_kernel(BinLayout lay, int64_t rows_per_level, float *__restrict__ gtab, int overwrite) {
-    PAG_BLOCK_TIMER(3);
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(RED_SGPRS))) void reduce_kernel(BinLayout lay, int64_t rows_per_level, float *__restrict__ gtab, int overwrite) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];      // [2^shift][F] fixed point
     constexpr int TS = tile_samples(NV);
     // Block -> (level, slice).  Blocks are handed out in blockIdx order and run for very different times: the fine levels hold most of the
@@ -998,7 +852,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(PAG_RED_SGPRS)
     {
         const int nl = (int)(gridDim.x / lay.NS);
         int q;                                                  // position in the launch order -> q-th (level, slice) pair, slices fastest
-        if (PAG_RED_ORDER >= 2 && lay.NS % 8 == 0) {
+        if (lay.NS % 8 == 0) {
             const int per = lay.NS / 8, x = blockIdx.x & 7, j = blockIdx.x >> 3;
             q = (j / per) * lay.NS + x * per + j % per;
         } else {
@@ -1006,17 +860,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(PAG_RED_SGPRS)
         }
         const int k = q / lay.NS;
         slice = q % lay.NS;
-        const int head = PAG_RED_ORDER == 3 ? min(PAG_RED_HEAD, nl / 3) : 0;      // the coarsest levels keep their place at the front
-        level = PAG_RED_ORDER == 0 ? k : k < head ? k : nl - 1 - (k - head);
+        const int head = min(RED_HEAD, nl / 3);      // the coarsest levels keep their place at the front
+        level = k < head ? k : nl - 1 - (k - head);
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
     const int slice_rows = 1 << lay.shift;
     __shared__ uint32_t lvl_max;
-#ifdef PAG_REDUCE_TIMING
-    __shared__ unsigned long long pag_stamps[2][16];
-#endif
-    PAG_STAMP_RT(13);
-    PAG_STAMP(0);
     // The level's largest |gradient| (the fixed-point scale) from the bin pass's per-tile maxima.  The accumulators are cleared while those loads
     // are in flight and under the same barrier that publishes lvl_max = 0: one barrier and one exposed load round trip less per workgroup than
     // max-then-clear (the fixed part of a workgroup is what the small batches of the post-prune regime pay: 1536 workgroups whatever M is).
@@ -1045,8 +894,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(PAG_RED_SGPRS)
     int ex;
     frexpf(poisoned ? 1.0f : maxabs, &ex);            // maxabs < 2^ex
     const int S = 38 - ex;                            // |val| * 2^S < 2^38 ; 2^23 addends stay below 2^61
-    PAG_STAMP(1);
-    PAG_STAMP(2);
     const uint32_t *hb = lay.header + ((int64_t)level * (lay.NS + 1) + slice) * lay.ntiles;
     const uint32_t *he = hb + lay.ntiles;
     // A (tile, slice) segment holds ~20 entries on average (the fine levels fill all 64 slices evenly), so walking one
@@ -1067,11 +914,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(PAG_RED_SGPRS)
         const bool has = lane < G && tl < lay.ntiles;
         const uint32_t mb = has ? hb[tl] : 0u, me = has ? he[tl] : 0u;
         uint32_t incl = me - mb;
-#ifdef PAG_REDUCE_TIMING
-        const bool first_group = t0 == (int64_t)wave * G;      // the in-loop stamps describe a wave's first group of tiles
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(incl) : : "memory");
-        if (first_group) PAG_STAMP(7);
-#endif
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
@@ -1090,11 +932,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(PAG_RED_SGPRS)
         // pass - a row appears a handful of times at most: the loop's test (a leader key through the LDS crossbar, a ballot, a count per chunk)
         // can only fail there, and is skipped.  (Before: only levels still holding >= 15/16 of a tile's entries took this path - level 23 alone
         // on the bench rays; 155 -> 152 us.)  The sums are integers: identical either way.
-#ifndef PAG_RED_DISTINCT_SEG
-#define PAG_RED_DISTINCT_SEG 12
-#endif
+        constexpr int DISTINCT_SEG = 12;
         const int tiles_here = (int)min((int64_t)G, lay.ntiles - t0);
-        const bool distinct = total >= (uint32_t)(PAG_RED_DISTINCT_SEG) * (uint32_t)tiles_here;
+        const bool distinct = total >= (uint32_t)DISTINCT_SEG * (uint32_t)tiles_here;
         int ts = 0;
         auto fetch = [&](uint32_t c0, RawEntry<F, PACK> &raw) __attribute__((always_inline)) {
             const uint32_t i = c0 + lane;
@@ -1133,9 +973,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(PAG_RED_SGPRS)
         RawEntry<F, PACK> raw_a, raw_b;
         bool ok_a = fetch(0, raw_a);
         bool ok_b = fetch(64, raw_b);
-#ifdef PAG_REDUCE_TIMING
-        if (first_group) PAG_STAMP(3);
-#endif
         auto stage = [&](RawEntry<F, PACK> &raw, bool &ok_r, uint32_t c_next) __attribute__((always_inline)) {
             uint32_t key;
             float fv[F];
@@ -1156,16 +993,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(PAG_RED_SGPRS)
             stage(raw_a, ok_a, c0 + 128);
             stage(raw_b, ok_b, c0 + 192);          // past the end: ok_b is false, nothing is added
         }
-#ifdef PAG_REDUCE_TIMING
-        if (first_group) {
-            PAG_STAMP(9);
-            if (lane == 0 && (wave == 0 || wave == 15)) pag_stamps[wave ? 1 : 0][10] = total;
-        }
-#endif
     }
-    PAG_STAMP(4);
     __syncthreads();
-    PAG_STAMP(5);
     const int64_t row0 = (int64_t)slice * slice_rows;
     float *dst = gtab + ((int64_t)level * rows_per_level + row0) * F;
     const int64_t valid = min((int64_t)slice_rows, rows_per_level - row0) * F;
@@ -1173,26 +1002,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(PAG_RED_SGPRS)
         const float v = poisoned ? __uint_as_float(0x7FC00000u) : (float)ldexp((double)(long long)acc[j], -S);
         dst[j] = overwrite ? v : dst[j] + v;
     }
-#ifdef PAG_REDUCE_TIMING
-    PAG_STAMP(6);
-    PAG_STAMP_RT(14);
-    if (lane == 0 && (wave == 0 || wave == 15) && blockIdx.x < 8192) {
-        pag_stamps[wave ? 1 : 0][11] = (unsigned long long)level;
-        pag_stamps[wave ? 1 : 0][12] = (unsigned long long)slice;
-        pag_stamps[wave ? 1 : 0][15] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);      // HW_ID, XCC_ID
-        for (int k = 0; k < 16; ++k) pag_dbg_times[blockIdx.x * 32 + (wave ? 16 : 0) + k] = pag_stamps[wave ? 1 : 0][k];
-    }
-#endif
 }
-
-#ifdef PAG_REDUCE_TIMING
-extern "C" int pag_debug_reduce_occupancy(int threads, int dyn_bytes) {
-    int occ = -1;
-    hipFuncSetAttribute((const void *)reduce_kernel<2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, dyn_bytes);
-    hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reduce_kernel<2, 4, true>, threads, dyn_bytes);
-    return occ;
-}
-#endif
 
 struct BinPlan {
     int64_t ntiles, keys_bytes, vals_bytes, header_bytes, total;
@@ -1258,7 +1068,7 @@ int launch_binned(const float *xyz, int64_t M, const void *grad_out, int grad_dt
     return PAG_OK;
 }
 
-inline unsigned encode_grid(int64_t M) { return (unsigned)(((M + PAG_ENC_FWD_THREADS - 1) / PAG_ENC_FWD_THREADS) * 8); }
+inline unsigned encode_grid(int64_t M) { return (unsigned)(((M + ENC_FWD_THREADS - 1) / ENC_FWD_THREADS) * 8); }
 
 // ---- dispatch helpers: (table dtype, out dtype, F, LPX) -> kernel instantiation
 #define PAG_DISPATCH_F_LPX(F_, LPX_, CALL)                 \
@@ -1320,7 +1130,7 @@ static int hash_encode_fwd_impl(const float *xyz, int64_t M, const void *tables,
     for (int c = 0; c < n_levels * n_feat; ++c) p.scale[c] = feat_scale_host ? feat_scale_host[c] : 1.0f;
     const int lpx = (n_levels + 7) / 8;
     hipStream_t st = (hipStream_t)stream;
-    dim3 grid(encode_grid(M)), block(PAG_ENC_FWD_THREADS);
+    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
     bool launched = false;
     if (table_dtype == PAG_F32 && out_dtype == PAG_F32) {
         PAG_DISPATCH_ALL((hash_fwd_kernel<float, float, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const float *)tables, p, (float *)out, out_stride_m, out_stride_c, grouped, addend)))
@@ -1382,7 +1192,7 @@ static int hash_encode_bwd_impl(bool overwrite, const float *xyz, int64_t M, con
         PAG_CHECK_LAUNCH("pag_hash_encode_bwd");
         return PAG_OK;
     }
-    dim3 grid(encode_grid(M)), block(PAG_ENC_FWD_THREADS);
+    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
     bool launched = false;
     if (grad_dtype == PAG_F32) {
         PAG_DISPATCH_ALL((hash_bwd_kernel<float, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const float *)grad_out, g_stride_m, g_stride_c, p, grad_tables)))
@@ -1432,7 +1242,7 @@ static int permuto_encode_fwd_impl(const float *xyz, int64_t M, const void *tabl
     fill_permuto(p, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host, flags);
     const int lpx = (n_levels + 7) / 8;
     hipStream_t st = (hipStream_t)stream;
-    dim3 grid(encode_grid(M)), block(PAG_ENC_FWD_THREADS);
+    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
     bool launched = false;
 #define PFWD(TT, OT)                                                                                                                 \
     PAG_DISPATCH_ALL((permuto_fwd_kernel<TT, OT, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const TT *)tables, p, (OT *)out, out_stride_m, \
@@ -1498,7 +1308,7 @@ static int permuto_encode_bwd_impl(bool overwrite, const float *xyz, int64_t M, 
         PAG_CHECK_LAUNCH("pag_permuto_encode_bwd");
         return PAG_OK;
     }
-    dim3 grid(encode_grid(M)), block(PAG_ENC_FWD_THREADS);
+    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
     bool launched = false;
     if (grad_dtype == PAG_F32) {
         PAG_DISPATCH_ALL((permuto_bwd_kernel<float, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const float *)grad_out, g_stride_m, g_stride_c, p, grad_tables)))
@@ -1531,7 +1341,7 @@ static int launch_xyz_grad(const char *name, const float *xyz, int64_t M, const 
     PAG_CHECK_ARG(tables && grad_out && d_xyz && workspace, "%s: NULL tables/grad_out/d_xyz/workspace", name);
     const int groups = n_levels < 8 ? n_levels : 8;
     const int lpx = (n_levels + 7) / 8;
-    dim3 grid(encode_grid(M)), block(PAG_ENC_FWD_THREADS);
+    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
     bool launched = false;
     if (ra.ridx) {       // reduced per ray inside the pass: d_xyz = out f32 [N,6] (d origin | d dir)
         PAG_CHECK_ARG(ra.depths && ra.pack_start && ra.N >= 1, "%s: per-ray form needs ridx, depths, pack_start and N >= 1", name);
@@ -1687,9 +1497,3 @@ extern "C" int pag_permuto_encode_bwd_set(const float *xyz, int64_t M, const voi
     return permuto_encode_bwd_impl(true, xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, n_levels, n_feat, capacity, scale_factor_host,
                                    shift_host, feat_scale_host, grad_tables, workspace, workspace_bytes, flags, stream);
 }
-
-PAG_BLOCK_TIMING_EXPORT(encode)
-
-#ifdef PAG_EXP_JAC
-extern "C" int pag_debug_set_jac(void *ptr) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_exp_jac), &ptr, sizeof(ptr)); }
-#endif

@@ -22,7 +22,6 @@
 // FP32 path (PAG_MLP_FP32): one lane per sample, fp32 FMA chains in k order with the weights
 // broadcast from LDS - the parity path (tolerance 1e-5 against the fp32 oracle).
 #include "common.h"
-#include "blocktime.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -33,9 +32,7 @@ typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef PAG_WIDE_BWD_WAVES
-#define PAG_WIDE_BWD_WAVES 8      // waves per workgroup of mlp_bwd_wide_mfma (8 or 16; one workgroup per CU)
-#endif
+constexpr int WIDE_BWD_WAVES = 8;      // waves per workgroup of mlp_bwd_wide_mfma (8 or 16; one workgroup per CU)
 constexpr int RS = 72;          // LDS row stride (bf16 elements) of a 64-wide weight row: 144 B
 constexpr int HID = 64;
 
@@ -107,7 +104,7 @@ struct BwdParams {
 // optional bit-2/3 swap of the column index (see header).
 // Every decoder kernel starts with 3 - 8 of these matrices.  As a loop of one element per iteration (a predicated load, then its store) the
 // prologue ran at one L2 round trip per element - 80 dependent round trips per thread, 23 - 27 k clocks = 10 us per launch whatever the batch
-// (-DPAG_FUSED_PROF).  Here eight loads are issued back to back - unconditionally, from clamped addresses, so that no branch separates them -
+// (in-kernel clocks: profiles/README.md, round 3).  Here eight loads are issued back to back - unconditionally, from clamped addresses, so that no branch separates them -
 // and the padding is applied to the values afterwards.
 constexpr int STAGE_BATCH = 8;      // 16: slower (registers / code size)
 __device__ void stage_weight(bf16_t *dst, int stride, int rows_pad, int cols_pad, const float *W, int n_out, int n_in,
@@ -626,14 +623,10 @@ __device__ __forceinline__ void static_for(Fn &&f) {
 }
 
 // ------------------------------------------------------------------------------------------ forward
+constexpr int FWD_WAVES_WIDE = 3;
+constexpr int FWD_WAVES_NARROW = 1;
 template <typename X1T, typename OutT, int NL, int OBMAX>
-#ifndef PAG_FWD_WAVES_WIDE
-#define PAG_FWD_WAVES_WIDE 3
-#endif
-#ifndef PAG_FWD_WAVES_NARROW
-#define PAG_FWD_WAVES_NARROW 1
-#endif
-__global__ __launch_bounds__(256, (OBMAX > 2 ? PAG_FWD_WAVES_WIDE : PAG_FWD_WAVES_NARROW)) void mlp_fwd_mfma(FwdParams p) {
+__global__ __launch_bounds__(256, (OBMAX > 2 ? FWD_WAVES_WIDE : FWD_WAVES_NARROW)) void mlp_fwd_mfma(FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int OB = (p.out_dim + 31) / 32;
     bf16_t *W0s = reinterpret_cast<bf16_t *>(smem);                  // [64][RS] natural k
@@ -917,7 +910,6 @@ __device__ __forceinline__ void tile64_store_buf_rows(bf16_t *stg, RS_T rs, unsi
 // SAVE: write the hidden activations (hsave[0], and hsave[1] with three layers) - the backward that recomputes them passes none.
 template <int NL, int KIND, bool SAVE>
 __global__ __launch_bounds__(256, 2) void mlp_fwd_fast(FwdParams p) {
-    PAG_BLOCK_TIMER(0);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool GRP = KIND != 1;
     constexpr int NKS0 = GRP ? 4 : 3;
@@ -1054,10 +1046,8 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_fast(FwdParams p) {
 // before (the backward reads them) and handed to the colour decoder in registers - as the bf16 values the store rounds to, brought from the accumulator
 // layout (a lane holds channels 0-3, 8-11 or 4-7, 12-15 of its sample) to the natural k order of the standalone launch (8 consecutive channels per
 // half) by two v_permlane32_swap: same fragments, same MFMA sequence, bit-identical outputs - the backward's recomputation stays consistent.
-#ifndef PAG_CD_WAVES
-#define PAG_CD_WAVES 2      // waves per SIMD asked of the compiler (146 VGPRs: three resident, grid cap 768 = one round; asking for 4 = 128 VGPRs: 123 us against 98; caps 512 / 1024: 101 / 105)
-#endif
-__global__ __launch_bounds__(256, PAG_CD_WAVES) void mlp_fwd_density_colour(FwdParams pd, FwdParams pc) {
+constexpr int CD_WAVES = 2;      // waves per SIMD asked of the compiler (146 VGPRs: three resident, grid cap 768 = one round; asking for 4 = 128 VGPRs: 123 us against 98; caps 512 / 1024: 101 / 105)
+__global__ __launch_bounds__(256, CD_WAVES) void mlp_fwd_density_colour(FwdParams pd, FwdParams pc) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr float LOG2E = 1.4426950408889634f;
     bf16_t *W0d = reinterpret_cast<bf16_t *>(smem);                  // density: [64][RS] natural k, [32][RS] permuted k
@@ -1173,12 +1163,9 @@ __global__ __launch_bounds__(256, PAG_CD_WAVES) void mlp_fwd_density_colour(FwdP
 // PAIR: a second, narrow softmax decoder on the same input (the semantic head next to the instance head: both read the panoptic
 // features) is evaluated on the tile while it is in registers - its own launch was one more 268 MB read of the features.  The weights
 // of both decoders then take 66 KiB: 8 waves share them (512 threads, one workgroup per CU) instead of two 4-wave workgroups.
+constexpr int WIDE_FWD_PAIR_THREADS = 1024;
 template <bool SAVE0, bool PAIR>
-#ifndef PAG_WIDE_FWD_PAIR_THREADS
-#define PAG_WIDE_FWD_PAIR_THREADS 1024
-#endif
-__global__ __launch_bounds__(PAIR ? PAG_WIDE_FWD_PAIR_THREADS : 256, PAIR ? 1 : 2) void mlp_fwd_wide_stats(FwdParams p) {
-    PAG_BLOCK_TIMER(1);
+__global__ __launch_bounds__(PAIR ? WIDE_FWD_PAIR_THREADS : 256, PAIR ? 1 : 2) void mlp_fwd_wide_stats(FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int OB = 7;
     constexpr float LOG2E = 1.4426950408889634f;
@@ -1308,13 +1295,11 @@ __global__ __launch_bounds__(PAIR ? PAG_WIDE_FWD_PAIR_THREADS : 256, PAIR ? 1 : 
 }
 
 // ----------------------------------------------------------------------------------------- backward
-template <typename OutT, typename DxT, int NL, int OBMAX>
 // 2 waves per SIMD: without the bound the 3-layer narrow variants took 252 VGPRs + 36 AGPRs (1 wave per SIMD); asking for 2 makes them fit 254 with no
 // scratch.  The 33..64-output variants (OBMAX 2) would spill 150 - 350 B and stay at 1.
-#ifndef PAG_BWD_WAVES
-#define PAG_BWD_WAVES 2
-#endif
-__global__ __launch_bounds__(256, (OBMAX == 2 ? 1 : PAG_BWD_WAVES)) void mlp_bwd_mfma(BwdParams p) {
+constexpr int BWD_WAVES = 2;
+template <typename OutT, typename DxT, int NL, int OBMAX>
+__global__ __launch_bounds__(256, (OBMAX == 2 ? 1 : BWD_WAVES)) void mlp_bwd_mfma(BwdParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int OB = (p.out_dim + 31) / 32;
     const int RSL = OB * 32 + 8;
@@ -1688,21 +1673,9 @@ __global__ __launch_bounds__(256, (OBMAX == 2 ? 1 : PAG_BWD_WAVES)) void mlp_bwd
 // cores (dz_0^T . S with S[sample][j] = 1 where the sample belongs to the tile's j-th ray: the A fragments are the ones layer 0's weight gradient
 // reads anyway) and one 64-float row per (tile, ray) leaves the kernel (p.dz0_slots, row = tile + ray: strictly increasing along the samples, so
 // every pair owns a row): 8 B per sample on 512-sample rays instead of 128 written and 128 read again by the per-ray sum.
-#ifdef PAG_FUSED_PROF      // debug build: where a workgroup of mlp_bwd_fused spends its clocks outside the tile loop (printed per launch by pag_mlp_bwd)
-__device__ unsigned long long g_fused_prof[8];      // shader clocks summed over workgroups: [0] staging, [1] tile loop, [2] cross-wave sum, [4] workgroups
-#endif
-// Experiment switches (scripts/build_variant.sh; never set in the shipped build): PAG_EXP_NO_WGRAD drops the weight-gradient MFMAs (wrong
-// results, timing only: what the backward-data chain alone costs), PAG_EXP_FUSED_WAVES = minimum waves per SIMD asked of the compiler and
-// workgroups per CU launched - together they measure the producer half of a producer / consumer split at two waves per SIMD.
-#ifndef PAG_EXP_FUSED_WAVES
-#define PAG_EXP_FUSED_WAVES 1
-#endif
+constexpr int FUSED_WAVES = 1;      // minimum waves per SIMD asked of the compiler for mlp_bwd_fused, and its workgroups per CU (fused_grid)
 template <int NL, int KIND, bool DXACC, int OBL = 1 /* 32-row blocks of the output layer; 2 only with KIND 0 */, int DZ0 = 0 /* 1: dz_0 rows, 2: per-(tile, ray) sums */>
-__global__ __launch_bounds__(256, PAG_EXP_FUSED_WAVES) void mlp_bwd_fused(BwdParams p) {
-    PAG_BLOCK_TIMER(2);
-#ifdef PAG_FUSED_PROF
-    const unsigned long long pt0 = __builtin_amdgcn_s_memtime();
-#endif
+__global__ __launch_bounds__(256, FUSED_WAVES) void mlp_bwd_fused(BwdParams p) {
     static_assert(OBL == 1 || KIND == 0, "a 64-wide output layer exists for the dense-gradient form only");
     constexpr bool GRP = KIND != 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1728,9 +1701,6 @@ __global__ __launch_bounds__(256, PAG_EXP_FUSED_WAVES) void mlp_bwd_fused(BwdPar
     bf16_t *Tx = reinterpret_cast<bf16_t *>(b1s + 64) + (threadIdx.x >> 6) * ((NL + 1) * TW_ELEMS);      // wave-private swizzled tiles
     bf16_t *Th0 = Tx + TW_ELEMS, *Th1 = Th0 + (NL == 3 ? TW_ELEMS : 0), *Tz = Th1 + TW_ELEMS;
     __syncthreads();
-#ifdef PAG_FUSED_PROF
-    const unsigned long long pt1 = __builtin_amdgcn_s_memtime();
-#endif
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -1892,9 +1862,6 @@ __global__ __launch_bounds__(256, PAG_EXP_FUSED_WAVES) void mlp_bwd_fused(BwdPar
     // dW[ob][ib] += dz(Tz block ob)^T . input(Tin block ib) over this tile's 32 samples; dbcol >= 0: bias gradients into dbacc
     auto wgrad_tile = [&](const bf16_t *Tin, auto &aw, int dbcol) __attribute__((always_inline)) {      // aw: f32x16 [out blocks][2]
         constexpr int NOB = (int)(sizeof(aw) / sizeof(aw[0]));
-#ifdef PAG_EXP_NO_WGRAD
-        return;
-#endif
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 bfr[2], afr[NOB];
@@ -2100,9 +2067,6 @@ __global__ __launch_bounds__(256, PAG_EXP_FUSED_WAVES) void mlp_bwd_fused(BwdPar
         else return dbacc;
     };
     __syncthreads();
-#ifdef PAG_FUSED_PROF
-    const unsigned long long pt2 = __builtin_amdgcn_s_memtime();
-#endif
     float *red = reinterpret_cast<float *>(smem);                      // [NBLK][4][64 lanes] x 4 floats
 #pragma unroll 1
     for (int w = 0; w < 4; ++w) {
@@ -2129,15 +2093,6 @@ __global__ __launch_bounds__(256, PAG_EXP_FUSED_WAVES) void mlp_bwd_fused(BwdPar
         }
         __syncthreads();
     }
-#ifdef PAG_FUSED_PROF
-    if (threadIdx.x == 0) {
-        const unsigned long long pt3 = __builtin_amdgcn_s_memtime();
-        atomicAdd(&g_fused_prof[0], pt1 - pt0);
-        atomicAdd(&g_fused_prof[1], pt2 - pt1);
-        atomicAdd(&g_fused_prof[2], pt3 - pt2);
-        atomicAdd(&g_fused_prof[4], 1ull);
-    }
-#endif
     static_for<NBLK>([&](auto bi) {
         constexpr int bb = decltype(bi)::value;
         if ((bb & 3) != wave) return;
@@ -2186,10 +2141,6 @@ struct PairParams {
     BwdParams i, s;
 };
 __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
-    PAG_BLOCK_TIMER(3);
-#ifdef PAG_FUSED_PROF
-    const unsigned long long pt0 = __builtin_amdgcn_s_memtime();
-#endif
     const BwdParams &pi = pp.i, &ps = pp.s;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int RSLI = 72, RSLS = 40;
@@ -2212,9 +2163,6 @@ __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
     bf16_t *Tx = reinterpret_cast<bf16_t *>(b0S + 64) + (threadIdx.x >> 6) * (4 * TW_ELEMS);      // wave-private swizzled tiles
     bf16_t *ThI = Tx + TW_ELEMS, *ThS = ThI + TW_ELEMS, *Tz = ThS + TW_ELEMS;
     __syncthreads();
-#ifdef PAG_FUSED_PROF
-    const unsigned long long pt1 = __builtin_amdgcn_s_memtime();
-#endif
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -2270,9 +2218,6 @@ __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
     };
     auto wgrad_tile = [&](const bf16_t *Tin, auto &aw, int dbcol) __attribute__((always_inline)) {      // aw: f32x16 [out blocks][2]
         constexpr int NOB = (int)(sizeof(aw) / sizeof(aw[0]));
-#ifdef PAG_EXP_NO_WGRAD
-        return;
-#endif
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 bfr[2], afr[NOB];
@@ -2461,9 +2406,6 @@ __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
         else return dbacc;
     };
     __syncthreads();
-#ifdef PAG_FUSED_PROF
-    const unsigned long long pt2 = __builtin_amdgcn_s_memtime();
-#endif
     float *red = reinterpret_cast<float *>(smem);                      // [NBLK][4][64 lanes] x 4 floats
     // wave 0 stores, waves 1 - 3 add in turn (same order of summation as a read-modify-write by all four); a block's four 16-byte reads are issued
     // together.  (Written as two code paths: the single loop with `w == 0 ? v : *dst + v` ran one dependent LDS round trip per access, and the form
@@ -2494,15 +2436,6 @@ __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
         }
         __syncthreads();
     }
-#ifdef PAG_FUSED_PROF
-    if (threadIdx.x == 0) {
-        const unsigned long long pt3 = __builtin_amdgcn_s_memtime();
-        atomicAdd(&g_fused_prof[0], pt1 - pt0);
-        atomicAdd(&g_fused_prof[1], pt2 - pt1);
-        atomicAdd(&g_fused_prof[2], pt3 - pt2);
-        atomicAdd(&g_fused_prof[4], 1ull);
-    }
-#endif
     static_for<NBLK>([&](auto bi) {
         constexpr int bb = decltype(bi)::value;
         if ((bb & 3) != wave) return;
@@ -2561,17 +2494,13 @@ __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
 //                                   chain(it-2) : W_L^T . dz, ReLU mask, hidden gradient of tile it-2 -> global
 // LDS rings: activations 4 deep (tiles it-2 .. it+1), dz fragments / partial dots / gradient rows 2 deep.  Tiles that do not exist
 // (the two drain iterations, tiles past the end) run with scale 0: their dz is zero, their stores go to a dump tile.
-// OB + 1 = 8 waves per workgroup, one workgroup per CU: two waves per SIMD.  0.43 ms; per-wave barrier waits (-DPAG_WB_PROF): the
+// OB + 1 = 8 waves per workgroup, one workgroup per CU: two waves per SIMD.  0.43 ms; per-wave barrier waits (in-kernel clocks: profiles/README.md, round 3): the
 // block waves that share a SIMD with another block wave wait 4-30 %, the helper 5 % - the roles are balanced, what is left is the
 // issue time of two waves per SIMD.
 constexpr int WR_RS = 256;         // floats per staged gradient row
-#ifdef PAG_WB_PROF
-__device__ unsigned long long g_wb_prof[2][8];      // [0] cycles at the barrier, [1] loop cycles (slots 0-3: helper segments on top); summed over workgroups
-#endif
 constexpr int WB_RMAX = 4;         // rays whose gradient rows are staged per tile; tiles spanning more read their rows from global
 template <int OB>
 __global__ __launch_bounds__((OB + 1) * 64) void mlp_bwd_wide_blocks(BwdParams p) {
-    PAG_BLOCK_TIMER(4);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int RSL = OB * 32 + 8;
     constexpr float LOG2E = 1.4426950408889634f;
@@ -2634,19 +2563,9 @@ __global__ __launch_bounds__((OB + 1) * 64) void mlp_bwd_wide_blocks(BwdParams p
     const int n_own = tile0 < ntiles ? (int)((ntiles - 1 - tile0) / tile_step) + 1 : 0;      // tiles of this workgroup
     // The two roles run their own loops (same number of barriers) so that neither carries the other's registers.  The barrier is
     // the bare instruction behind an LDS-only wait: __syncthreads() would also drain the global loads that are meant to stay in flight.
-#ifdef PAG_WB_PROF
-    unsigned long long prof_wait = 0, prof_t0 = __builtin_amdgcn_s_memtime(), prof_seg[4] = {0, 0, 0, 0};
-    auto wg_barrier = [&]() __attribute__((always_inline)) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        asm volatile("s_barrier" ::: "memory");
-        prof_wait += __builtin_amdgcn_s_memtime() - t0;
-    };
-#else
     auto wg_barrier = [&]() __attribute__((always_inline)) {
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     };
-#endif
     if (!is_block) {
         // =========================================================================================== helper wave
         bf16x8 vt[4];
@@ -2675,24 +2594,13 @@ __global__ __launch_bounds__((OB + 1) * 64) void mlp_bwd_wide_blocks(BwdParams p
             const int64_t tile = tile0 + (int64_t)it * tile_step;
             // ---------------- tile it+1 registers -> LDS, tile it+2 global -> registers (in flight for a whole iteration).  The ring slot
             // written here was last read by this wave's own ReLU mask one iteration ago.
-#ifdef PAG_WB_PROF
-            const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
-#endif
             tw_put_rows(Th + ((it + 1) & 3) * TW_ELEMS, vt, lane);
             put_rows(grow + ((it + 1) & 1) * (WB_RMAX * WR_RS), vr);
             asm volatile("" ::: "memory");
-#ifdef PAG_WB_PROF
-            const unsigned long long ts1 = __builtin_amdgcn_s_memtime();
-            prof_seg[0] += ts1 - ts0;
-#endif
             load_tile(vt, tile + 2 * tile_step);
             load_rows(vr, __builtin_amdgcn_readfirstlane(ray_nn), __builtin_amdgcn_readlane(ray_nn, 31));
             ray_nn = load_ray(tile + 3 * tile_step);
             asm volatile("" ::: "memory");
-#ifdef PAG_WB_PROF
-            const unsigned long long ts2 = __builtin_amdgcn_s_memtime();
-            prof_seg[1] += ts2 - ts1;
-#endif
             // ---------------- chain(it-2): dA = W_L^T . dz_L masked by the saved ReLU output -> global.  The stores are unconditional (the
             // buffer has a padding tile and a dump tile): a predicated store is a branch, and past a branch the compiler no longer counts
             // the operations in flight - it would wait for ALL of them, stores included, before the next iteration's LDS writes.
@@ -2717,11 +2625,6 @@ __global__ __launch_bounds__((OB + 1) * 64) void mlp_bwd_wide_blocks(BwdParams p
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 2 * OB, 0);
             asm volatile("" ::: "memory");
-#ifdef PAG_WB_PROF
-            asm volatile("s_nop 0" : "+v"(acc[0]), "+v"(acc[1]));
-            const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
-            prof_seg[2] += ts3 - ts2;
-#endif
             // ReLU mask and bf16 rounding on PAIRS: the saved activation is 0 or positive, so min(max(h as i16, 0), 1) is the 0 / 1
             // mask of a half-word and a 16-bit multiply applies it - 4 instructions per pair instead of 7
             typedef short i16x2 __attribute__((ext_vector_type(2)));
@@ -2758,19 +2661,8 @@ __global__ __launch_bounds__((OB + 1) * 64) void mlp_bwd_wide_blocks(BwdParams p
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4{lo[0], lo[1], hi[0], hi[1]}, rs_d, voff + k * (8 * HID * 2), 0, 0);
                 }
             }
-#ifdef PAG_WB_PROF
-            prof_seg[3] += __builtin_amdgcn_s_memtime() - ts3;
-#endif
             wg_barrier();
         }
-#ifdef PAG_WB_PROF
-        if (lane == 0)
-            for (int k = 0; k < 4; ++k) atomicAdd(&g_wb_prof[1][k], prof_seg[k]);
-        if (lane == 0) {
-            atomicAdd(&g_wb_prof[0][wave], prof_wait);
-            atomicAdd(&g_wb_prof[1][wave], __builtin_amdgcn_s_memtime() - prof_t0);
-        }
-#endif
         return;
     }
     // =============================================================================================== block waves
@@ -2907,12 +2799,6 @@ __global__ __launch_bounds__((OB + 1) * 64) void mlp_bwd_wide_blocks(BwdParams p
         }
         wg_barrier();
     }
-#ifdef PAG_WB_PROF
-    if (lane == 0) {
-        atomicAdd(&g_wb_prof[0][wave], prof_wait);
-        atomicAdd(&g_wb_prof[1][wave], __builtin_amdgcn_s_memtime() - prof_t0);
-    }
-#endif
     // ---- every block wave owns its 32 rows of the workgroup's slab [OB*32][96]: cols 0..63 dW_L, col 64 db
     {
         float *sl = p.slabs[0] + (int64_t)blockIdx.x * (OB * 32) * WG_SLAB_COLS_F;
@@ -3188,9 +3074,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_bwd_wide_mfma(BwdParams p) {
 // them by the sample weight and keeps the 7 x 16 per-lane partial sums in registers until the ray is finished.  The
 // sum over a tile's 32 samples is a sum over lanes: DPP row_shr 1/2/4/8 + row_bcast:15 put it on lanes 31 / 63, LDS
 // combines the four waves.  Reads 128 B per sample instead of 400 B, and the 839 MB tensor is never written.
-#ifndef PAG_HC_PER_WAVE_P
-#define PAG_HC_PER_WAVE_P 2048
-#endif
+constexpr int HC_PER_WAVE_P = 2048;      // pack count from which each pack gets its own wave (why: pag_head_composite_fwd)
 struct HeadCompParams {
     const int64_t *pack_start;
     const int32_t *ray_of_pack;
@@ -3215,7 +3099,6 @@ __device__ __forceinline__ float dpp_add(float v) {
 // and every block ran as reads -> 4 chained MFMAs -> 16 exponentials, nothing overlapping at two waves per SIMD).
 template <int OBT>
 __global__ __launch_bounds__(256, 2) void head_composite_fwd_kernel(HeadCompParams p) {      // two waves per SIMD: 256 registers
-    PAG_BLOCK_TIMER(5);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int OB = OBT ? OBT : (p.out_dim + 31) / 32;
     bf16_t *WLs = reinterpret_cast<bf16_t *>(smem);                  // [OB*32][RS] permuted k (forward layout)
@@ -3364,7 +3247,6 @@ __global__ __launch_bounds__(256, 2) void head_composite_fwd_kernel(HeadCompPara
 // exponentials is formed directly instead of online over the blocks, so 1 / sum - and with it the outputs - may differ in the last bit.
 template <bool PAIR>
 __global__ __launch_bounds__(256, 1) void head_fwd_once_kernel(FwdParams p, HeadCompParams c) {
-    PAG_BLOCK_TIMER(7);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int OB = 7;
     constexpr float LOG2E = 1.4426950408889634f;
@@ -3840,7 +3722,6 @@ template <typename A1T, int APW /* accumulator blocks per wave */, int NWV = 4 /
 // registers.  Wide layers (up to 224 outputs = 21 block pairs): 8 waves x 3 pairs instead of 4 x 6 - 48 accumulator
 // registers per wave leave room for the prefetch and for 4 waves per SIMD (the 4 x 6 form ran 2 waves per SIMD, no prefetch).
 __global__ __launch_bounds__(NWV * 64, (APW == 2 ? 5 : (APW == 3 ? 4 : 1))) void mlp_wgrad_kernel(WgradBatch batch) {
-    PAG_BLOCK_TIMER(6);
     const WgradParams &p = batch.p[blockIdx.y];       // blockIdx.y = layer: the layers of one decoder share a launch
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int OB = (p.n_out + 31) / 32;
@@ -4024,12 +3905,9 @@ extern "C" int pag_mlp_fwd_pair_supported(const pag_mlp_fwd_args *a, const pag_m
     return wide && narrow ? 1 : 0;
 }
 
-#ifndef PAG_FAST_FWD_GRID_CAP
-#define PAG_FAST_FWD_GRID_CAP 768      // three workgroups per CU are resident: one round, tiles grid-strided (1536 ran two rounds with a ragged second: colour forward 63 -> 57 us)
-#endif
+constexpr int FAST_FWD_GRID_CAP = 768;      // three workgroups per CU are resident: one round, tiles grid-strided (1536 ran two rounds with a ragged second: colour forward 63 -> 57 us)
 extern "C" int pag_mlp_fwd_producer_supported(const pag_mlp_fwd_args *a, const pag_mlp_fwd_args *d, int64_t M) {
-    static const bool no_fast = getenv("PAG_NO_FAST_FWD") != nullptr;
-    if (!a || !d || no_fast || M < 1 || M > PAG_MLP_FUSED_WIDE_MAX_M) return 0;
+    if (!a || !d || M < 1 || M > PAG_MLP_FUSED_WIDE_MAX_M) return 0;
     const bool density = d->mode == PAG_MLP_MFMA_BF16 && d->x1_dtype == PAG_BF16 && d->x1_layout == PAG_LAYOUT_XCD8 && d->k1 == 64 && !d->x2 && d->n_layers == 2 &&
                          d->out && d->out_dtype == PAG_BF16 && d->out_act == PAG_ACT_NONE && d->out_dim == 16 && !d->hidden_save[0] && !d->hidden_save[1] &&
                          !d->softmax_stats && !d->x1_col0_relu && !d->pair && !d->composite && !d->x1_producer && d->W[0] && d->W[1] && d->b[0] && d->b[1] &&
@@ -4041,8 +3919,7 @@ extern "C" int pag_mlp_fwd_producer_supported(const pag_mlp_fwd_args *a, const p
 }
 
 extern "C" int pag_mlp_fwd_composite_supported(const pag_mlp_fwd_args *a, int64_t M) {
-    static const bool no_fast = getenv("PAG_NO_FAST_FWD") != nullptr;
-    if (!a || no_fast || M < 1 || M > PAG_MLP_FUSED_WIDE_MAX_M) return 0;
+    if (!a || M < 1 || M > PAG_MLP_FUSED_WIDE_MAX_M) return 0;
     const bool wide = a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && a->x1_layout == PAG_LAYOUT_XCD8 && !a->out && a->n_layers == 3 &&
                       a->softmax_stats && a->out_act == PAG_ACT_SOFTMAX && a->out_dim > 192 && a->out_dim <= 224 && a->hidden_save[1] && !a->hidden_save[0];
     return wide && (!a->pair || pag_mlp_fwd_pair_supported(a, a->pair) == 1) ? 1 : 0;
@@ -4102,9 +3979,8 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
         p.in_pad = 64;
     }
     hipStream_t st = (hipStream_t)stream;
-    // ---- the panoptic nef's decoder shapes on the bf16 path: dedicated straight-line kernels (PAG_NO_FAST_FWD: the generic one, for A/B runs)
-    static const bool no_fast = getenv("PAG_NO_FAST_FWD") != nullptr;
-    if (!no_fast && a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && M <= PAG_MLP_FUSED_WIDE_MAX_M) {
+    // ---- the panoptic nef's decoder shapes on the bf16 path: dedicated straight-line kernels
+    if (a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && M <= PAG_MLP_FUSED_WIDE_MAX_M) {
         const bool grp = p.grp_L > 0;
         const bool save_all = a->hidden_save[0] && (a->n_layers == 2 || a->hidden_save[1]);
         const bool save_none = !a->hidden_save[0] && !a->hidden_save[1];
@@ -4132,17 +4008,15 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
                 PAG_CHECK_ARG(!a->hidden_save[0] && a->hidden_save[1] && a->softmax_stats, "pag_mlp_fwd: composite needs softmax_stats and hidden_save[1] only");
                 if (hc->P == 0) return PAG_OK;
                 HeadCompParams c{hc->pack_start, hc->ray_of_pack, hc->P, nullptr, nullptr, nullptr, a->out_dim, nullptr, 0, hc->weights, hc->alpha, hc->out};
-                c.per_wave = ((hc->n_samples > 0 && hc->n_samples < 160 * hc->P) || hc->P >= PAG_HC_PER_WAVE_P) ? 1 : 0;
+                c.per_wave = ((hc->n_samples > 0 && hc->n_samples < 160 * hc->P) || hc->P >= HC_PER_WAVE_P) ? 1 : 0;
                 static bool attr_once = false;
                 if (!attr_once) {
                     hipFuncSetAttribute((const void *)head_fwd_once_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                     hipFuncSetAttribute((const void *)head_fwd_once_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                     attr_once = true;
                 }
-#ifndef PAG_HEAD_ONCE_GRID
-#define PAG_HEAD_ONCE_GRID 256
-#endif
-                const unsigned grid = (unsigned)std::min<int64_t>(c.per_wave ? (hc->P + 3) / 4 : hc->P, PAG_HEAD_ONCE_GRID);
+                constexpr int HEAD_ONCE_GRID = 256;
+                const unsigned grid = (unsigned)std::min<int64_t>(c.per_wave ? (hc->P + 3) / 4 : hc->P, HEAD_ONCE_GRID);
                 if (a->pair) {
                     const pag_mlp_fwd_args *b = a->pair;
                     p.W2[0] = b->W[0];
@@ -4168,15 +4042,13 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
                 p.b2[1] = b->b[1];
                 p.out2 = b->out;
                 p.out2_dim = b->out_dim;
-                constexpr int NWP = PAG_WIDE_FWD_PAIR_THREADS / 64;      // waves per workgroup (one workgroup per CU shares the 66 KiB of weights)
+                constexpr int NWP = WIDE_FWD_PAIR_THREADS / 64;      // waves per workgroup (one workgroup per CU shares the 66 KiB of weights)
                 const size_t lds = (size_t)(128 + 224 + 96) * RS * sizeof(bf16_t) + (128 + 224 + 96) * sizeof(float) + NWP * ST_BYTES;
                 // one workgroup per CU is all that fits (LDS): a grid of 1.5 x 256 ran a full round and a half-empty one (220 us, of which
-                // the second round's 110 us kept 128 CUs idle: scripts/block_timeline.py) - at most ONE round, tiles grid-strided
-#ifndef PAG_WIDE_FWD_PAIR_GRID
-#define PAG_WIDE_FWD_PAIR_GRID 256
-#endif
-                const unsigned grid = std::min<unsigned>((mlp_grid(M) * 4 + NWP - 1) / NWP, PAG_WIDE_FWD_PAIR_GRID);
-                hipLaunchKernelGGL((mlp_fwd_wide_stats<false, true>), dim3(grid), dim3(PAG_WIDE_FWD_PAIR_THREADS), lds, st, p);
+                // the second round's 110 us kept 128 CUs idle: profiles/README.md, round 4 timelines) - at most ONE round, tiles grid-strided
+                constexpr int WIDE_FWD_PAIR_GRID = 256;
+                const unsigned grid = std::min<unsigned>((mlp_grid(M) * 4 + NWP - 1) / NWP, WIDE_FWD_PAIR_GRID);
+                hipLaunchKernelGGL((mlp_fwd_wide_stats<false, true>), dim3(grid), dim3(WIDE_FWD_PAIR_THREADS), lds, st, p);
             } else {
                 const size_t lds = (size_t)(128 + 224) * RS * sizeof(bf16_t) + (128 + 224) * sizeof(float) + 4 * ST_BYTES;
                 if (a->hidden_save[0]) hipLaunchKernelGGL((mlp_fwd_wide_stats<true, false>), dim3(mlp_grid(M)), dim3(256), lds, st, p);
@@ -4210,13 +4082,13 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
             pd.grp_L = d->x1_levels;
             pd.grp_F = d->x1_feats;
             const size_t lds = (size_t)(64 + 32 + 64 + 64 + 32) * RS * sizeof(bf16_t) + (64 + 32 + 64 + 64 + 32) * sizeof(float);
-            hipLaunchKernelGGL(mlp_fwd_density_colour, dim3(std::min<unsigned>(mlp_grid(M), PAG_FAST_FWD_GRID_CAP)), dim3(256), lds, st, pd, p);
+            hipLaunchKernelGGL(mlp_fwd_density_colour, dim3(std::min<unsigned>(mlp_grid(M), FAST_FWD_GRID_CAP)), dim3(256), lds, st, pd, p);
             PAG_CHECK_LAUNCH("pag_mlp_fwd (density + colour)");
             return PAG_OK;
         }
         if (kind >= 0 && (save_all || save_none)) {
             const size_t lds = (size_t)(64 + (a->n_layers == 3 ? 64 : 0) + 32) * RS * sizeof(bf16_t) + (128 + 32) * sizeof(float) + 4 * ST_BYTES;
-#define FWD_FAST(NL_, K_, S_) hipLaunchKernelGGL((mlp_fwd_fast<NL_, K_, S_>), dim3(std::min<unsigned>(mlp_grid(M), PAG_FAST_FWD_GRID_CAP)), dim3(256), lds, st, p)
+#define FWD_FAST(NL_, K_, S_) hipLaunchKernelGGL((mlp_fwd_fast<NL_, K_, S_>), dim3(std::min<unsigned>(mlp_grid(M), FAST_FWD_GRID_CAP)), dim3(256), lds, st, p)
 #define FWD_FAST_K(K_)                                                        \
     do {                                                                      \
         if (a->n_layers == 2) { if (save_all) FWD_FAST(2, K_, true); else FWD_FAST(2, K_, false); } \
@@ -4233,7 +4105,7 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
     }
     PAG_CHECK_ARG(!a->composite, "pag_mlp_fwd: composite rides only in the straight-line wide-head launch (pag_mlp_fwd_composite_supported)");
     PAG_CHECK_ARG(!a->x1_producer, "pag_mlp_fwd: x1_producer rides only in the straight-line colour launch (pag_mlp_fwd_producer_supported)");
-    PAG_CHECK_ARG(!a->pair, "pag_mlp_fwd: pair rides only in the straight-line wide-head launch (M <= %lld, PAG_NO_FAST_FWD unset)", (long long)PAG_MLP_FUSED_WIDE_MAX_M);
+    PAG_CHECK_ARG(!a->pair, "pag_mlp_fwd: pair rides only in the straight-line wide-head launch (M <= %lld)", (long long)PAG_MLP_FUSED_WIDE_MAX_M);
     if (a->mode == PAG_MLP_MFMA_BF16) {
         const int OB = (a->out_dim + 31) / 32;
         const size_t lds = (size_t)(64 + (a->n_layers == 3 ? 64 : 0) + OB * 32) * RS * sizeof(bf16_t) + (128 + OB * 32) * sizeof(float) + 4 * ST_BYTES;
@@ -4320,7 +4192,7 @@ __global__ __launch_bounds__(WF_SPLITS * WG_SLAB_COLS) void wgrad_finish_kernel(
 
 static unsigned fused_grid(int64_t M) {
     const int64_t tiles = (M + 31) / 32;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, 256 * PAG_EXP_FUSED_WAVES));      // one 4-wave workgroup per CU, tiles grid-strided
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, 256 * FUSED_WAVES));      // one 4-wave workgroup per CU, tiles grid-strided
 }
 
 // which mlp_bwd_fused instantiation serves these arguments: 0 density-like, 1 colour-like, 2 semantic-like, -1 none
@@ -4513,18 +4385,6 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
         }
         hipLaunchKernelGGL((mlp_bwd_wide_blocks<OBW>), dim3(grid), dim3((OBW + 1) * 64), ldsA, st, pa);
         PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, wide head)");
-#ifdef PAG_WB_PROF
-        {
-            unsigned long long hp[2][8];
-            hipStreamSynchronize(st);
-            hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_wb_prof), sizeof(hp));
-            fprintf(stderr, "[wb_prof] grid %u:", grid);
-            for (int w = 0; w < 8; ++w) fprintf(stderr, " w%d %.0f/%.0f", w, (double)hp[0][w] / grid, (double)hp[1][w] / grid);
-            fprintf(stderr, "\n");
-            for (auto &row : hp) for (auto &v : row) v = 0;
-            hipMemcpyToSymbol(HIP_SYMBOL(g_wb_prof), hp, sizeof(hp));
-        }
-#endif
         BwdParams pb = p;
         pb.grad_out = dzh;
         pb.out = dzh;
@@ -4556,18 +4416,6 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
             PairParams pp{pb, ps};
             hipLaunchKernelGGL(mlp_bwd_pair, dim3(grid), dim3(256), ldsP, st, pp);
             PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, layers below the wide head + companion head)");
-#ifdef PAG_FUSED_PROF
-            {
-                unsigned long long hp[8];
-                hipStreamSynchronize(st);
-                hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_fused_prof), sizeof(hp));
-                const double n = hp[4] ? (double)hp[4] : 1.0;
-                fprintf(stderr, "[fused_prof] pair M %lld grid %u: staging %.0f  tiles %.0f  cross-wave sum %.0f  (shader clocks per workgroup)\n", (long long)M, grid,
-                        hp[0] / n, hp[1] / n, hp[2] / n);
-                for (auto &v : hp) v = 0;
-                hipMemcpyToSymbol(HIP_SYMBOL(g_fused_prof), hp, sizeof(hp));
-            }
-#endif
             fb.p[3] = FinishParams{slabS0, (int)grid, HID, 64, b->in_dim, p.grp_L, p.grp_F, b->dW[0], b->db[0]};
             fb.p[4] = FinishParams{slabS1, (int)grid, b->out_dim, 32, HID, 0, 0, b->dW[1], b->db[1]};
             n_fin = 5;
@@ -4638,18 +4486,6 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
         }
 #undef MLP_BWD_FUSED
         PAG_CHECK_LAUNCH("pag_mlp_bwd (fused)");
-#ifdef PAG_FUSED_PROF
-        {
-            unsigned long long hp[8];
-            hipStreamSynchronize(st);
-            hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_fused_prof), sizeof(hp));
-            const double n = hp[4] ? (double)hp[4] : 1.0;
-            fprintf(stderr, "[fused_prof] kind %d M %lld grid %u: staging %.0f  tiles %.0f  cross-wave sum %.0f  (shader clocks per workgroup)\n", kind, (long long)M,
-                    grid, hp[0] / n, hp[1] / n, hp[2] / n);
-            for (auto &v : hp) v = 0;
-            hipMemcpyToSymbol(HIP_SYMBOL(g_fused_prof), hp, sizeof(hp));
-        }
-#endif
         FinishBatch fb{};
         int max_out = 0;
         for (int l = 0; l < a->n_layers; ++l) {
@@ -4665,7 +4501,7 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
     const bool wide_rebuild = a->mode == PAG_MLP_MFMA_BF16 && a->out_dim > 64 && a->out_act == PAG_ACT_SOFTMAX && a->softmax_stats &&
                               a->b_last && !out_f32 && (a->g_ray || (a->grad_out && a->out_dim % 8 == 0));
     if (wide_rebuild) {
-        constexpr int NW = PAG_WIDE_BWD_WAVES;
+        constexpr int NW = WIDE_BWD_WAVES;
         const int OB = (a->out_dim + 31) / 32;
         const size_t lds = (size_t)(64 * (OB * 32 + 8) + OB * 32 * RS + (a->n_layers == 3 ? 64 * RS : 0) + 64 * RS) * sizeof(bf16_t) +
                            (size_t)OB * 32 * sizeof(float) + (size_t)NW * ST_BYTES + (size_t)NW * OB * 32 * sizeof(float);
@@ -4879,23 +4715,16 @@ extern "C" int pag_head_composite_fwd(const int64_t *pack_start, const int32_t *
     PAG_CHECK_ARG(pack_start && ray_of_pack && hidden && W_last && b_last && softmax_stats && weights && alpha && out,
                   "pag_head_composite_fwd: NULL input/output");
     HeadCompParams p{pack_start, ray_of_pack, P, (const bf16_t *)hidden, W_last, b_last, out_dim, softmax_stats, 0, weights, alpha, out};
-#ifndef PAG_HC_PER_WAVE_P
-#define PAG_HC_PER_WAVE_P 2048
-#endif
     // one wave per pack when packs are short (fewer than ~5 tiles on average) - and whenever there are enough packs to fill the chip that way
     // (2048 = 512 workgroups of 4 waves): the lane reduction of the 7 x 16 partial sums at the end of a pack costs as much as two tiles, and four
     // waves sharing a pack each pay it
-    p.per_wave = ((samples_hint > 0 && samples_hint < 160 * P) || P >= PAG_HC_PER_WAVE_P) ? 1 : 0;
+    p.per_wave = ((samples_hint > 0 && samples_hint < 160 * P) || P >= HC_PER_WAVE_P) ? 1 : 0;
     const int OB = (out_dim + 31) / 32;
     const size_t lds = (size_t)OB * 32 * RS * sizeof(bf16_t) + (size_t)5 * OB * 32 * sizeof(float) + 4 * ST_BYTES;
-#ifndef PAG_HC_GRID
-#define PAG_HC_GRID 512
-#endif
-    const unsigned grid = (unsigned)std::min<int64_t>(p.per_wave ? (P + 3) / 4 : P, PAG_HC_GRID);
+    constexpr int HC_GRID = 512;
+    const unsigned grid = (unsigned)std::min<int64_t>(p.per_wave ? (P + 3) / 4 : P, HC_GRID);
     if (OB == 7) hipLaunchKernelGGL(head_composite_fwd_kernel<7>, dim3(grid), dim3(256), lds, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(head_composite_fwd_kernel<0>, dim3(grid), dim3(256), lds, (hipStream_t)stream, p);
     PAG_CHECK_LAUNCH("pag_head_composite_fwd");
     return PAG_OK;
 }
-
-PAG_BLOCK_TIMING_EXPORT(mlp)

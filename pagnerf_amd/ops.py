@@ -412,7 +412,6 @@ def _recompute_hidden(x1, x2, x2_index, Wc, bc, in_dim, k1, grouped, mode, hidde
     return full
 
 
-_NO_FAST_FWD = os.environ.get("PAG_NO_FAST_FWD") is not None
 _OUTER_GRAD = True          # grad mode of the code that called the decoder op (see _apply_decoder)
 
 
@@ -549,7 +548,7 @@ class _FusedMLP(torch.autograd.Function):
             hold["args"], hold["M"] = a, M
             hold["keep"] = [v for v in locals().values() if isinstance(v, (torch.Tensor, list, tuple))]
         elif M:
-            if pair_hold is not None and pair_hold.get("args") is not None and M <= L.MLP_FUSED_WIDE_MAX_M and not _NO_FAST_FWD \
+            if pair_hold is not None and pair_hold.get("args") is not None and M <= L.MLP_FUSED_WIDE_MAX_M \
                     and L.load().pag_mlp_fwd_pair_supported(ctypes.byref(a), ctypes.byref(pair_hold["args"])) == 1:
                 a.pair = ctypes.pointer(pair_hold["args"])
                 pair_hold["taken"] = True

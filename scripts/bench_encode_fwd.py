@@ -1,5 +1,5 @@
 """Time the permutohedral encode forward (production layout: bf16 [8,M,8], fp16-rounded coordinates) on the bench's own samples:
-   [PAG_LIB_VARIANT=tag] python scripts/bench_encode_fwd.py [rays] [samples]      (kernel experiments: scripts/build_variant.sh)"""
+   python scripts/bench_encode_fwd.py [rays] [samples] [fp16]"""
 import os
 import sys
 import numpy as np
@@ -43,5 +43,4 @@ with torch.no_grad():
     t2 = timeit(lambda: ops.encode(xyz, tab, spec, None, torch.bfloat16, layout="xcd8", addend=other))
 tb = 2 if tdt == torch.float16 else 4
 bps = 12 + L * 4 * F * tb + L * F * 2
-print("variant %-8s M %d  fwd %.4f ms (%.3f of 8 TB/s)   fwd_add %.4f ms" % (os.environ.get("PAG_LIB_VARIANT", "-") + ("/generic" if os.environ.get("PAG_NO_FAST_ENCODE") else ""),
-                                                                           M, t1, bps * M / t1 / 1e6 / 8000.0, t2))
+print("M %d  fwd %.4f ms (%.3f of 8 TB/s)   fwd_add %.4f ms" % (M, t1, bps * M / t1 / 1e6 / 8000.0, t2))
