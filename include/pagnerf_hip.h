@@ -610,6 +610,27 @@ int pag_segment_reg_bwd(const float *prob, int B, int64_t P, int64_t image_strid
                         const void *workspace, int64_t workspace_bytes, const float *grad, float *d_prob, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Supervised-contrastive instance loss (loss/sup_contrastive.py::SupConLoss as pc_nerf/trainer.py:499-503 and :477-480 call it) - three launches
+ * forward, two backward, no [n, n] matrix in memory, no host synchronisation.  Additive to ABI 14.
+ * ------------------------------------------------------------------------------------------ */
+
+/* Per image b of features [B, P, D] (f32 or bf16 `dtype`, element (b, p, k) at b*image_stride + p*row_stride + k) and labels i64 [B,P] (contiguous):
+ * the anchors S are the rows with anchor_mask u8 [B,P] != 0, in row order (anchor_mask NULL: every row).  f = x / max(||x||, 1e-12);
+ * A_ij = f_i.f_j / temperature for i, j in S; m_i = max_j A_ij (j = i included, treated as a constant); LSE_i = log Sum_{j != i} exp(A_ij - m_i);
+ * M_ij = [label_i == label_j][j != i], cnt_i = Sum_j M_ij;
+ * loss_i = -(temperature / base_temperature) * (Sum_j M_ij (pos_weight (A_ij - m_i) - neg_weight LSE_i)) / (cnt_i + 1e-16).
+ * An image with anchor_mask given whose anchor set is empty or holds a single label value is skipped.  loss f32 [B,P] (contiguous) gets loss_i at each
+ * anchor's row and 0 at every other row and in skipped images.  The workspace (pag_supcon_workspace_bytes(B, P, D) bytes) keeps the normalised anchors
+ * and the row statistics for pag_supcon_bwd, which writes EVERY element of d_features [B,P,D] (contiguous, `dtype`) from grad_loss f32 [B,P]
+ * (contiguous): zero rows for non-anchors and skipped images.  1 <= D <= 512, P <= 2^24; sums run in a fixed order (bitwise reproducible). */
+int64_t pag_supcon_workspace_bytes(int B, int64_t P, int D);
+int pag_supcon_fwd(const void *features, int dtype, int B, int64_t P, int D, int64_t image_stride, int64_t row_stride, const int64_t *labels,
+                   const uint8_t *anchor_mask, float temperature, float base_temperature, float pos_weight, float neg_weight, void *workspace,
+                   int64_t workspace_bytes, float *loss, void *stream);
+int pag_supcon_bwd(int dtype, int B, int64_t P, int D, float temperature, float base_temperature, float pos_weight, float neg_weight, void *workspace,
+                   int64_t workspace_bytes, const float *grad_loss, void *d_features, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-ray training loss of the rendered buffers (pc_nerf/trainer.py:443-446 rgb, :459-465 semantics,
  * loss/lin_assignment_things.py:80 instance term after the assignment) - one launch forward, one backward
  * ------------------------------------------------------------------------------------------ */

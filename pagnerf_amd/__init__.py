@@ -7,6 +7,7 @@
     pose  : BAPipeline (learnable extrinsics)     (ba_pipeline.py) <- pc_nerf/ba_pipeline.py
     dd    : PanopticDDensityNeF / ...PackedRFTracer (dd.py)     <- pc_nerf/panoptic_dd_nef.py, tracers/panoptic_dd_packed_rf_tracer.py
     shard : ray sharding + RCCL gather/all-reduce (shard.py)
+    loss  : LinAssignmentThingsLoss, LinAssignmentLoss, SupConLoss (loss.py) <- loss/lin_assignment*.py, loss/sup_contrastive.py
     optim : Adam (torch.optim.Adam's interface on pag_adam_step) (optim.py) <- config_parser.py:667-673, trainer.py:583
 
 All compute goes through libpagnerf_hip.so (include/pagnerf_hip.h); there is no CPU fallback.

@@ -3,6 +3,7 @@ hot path), with the cost matrix built on the GPU.
 
   LinAssignmentThingsLoss  <- loss/lin_assignment_things.py::LinAssignmentThingsLoss
   LinAssignmentLoss        <- loss/lin_assignment.py::LinAssignmentLoss
+  SupConLoss               <- loss/sup_contrastive.py::SupConLoss (csrc/supcon.hip: no [n, n] matrix, no host synchronisation)
 
 The reference builds cost[l, :] = -(sum of the probabilities of the rays labelled l) / (count + 1e-4)
 with one masked sum + one device-to-host copy per label (lin_assignment_things.py:31-33).  Here ONE
@@ -459,3 +460,98 @@ class LinAssignmentLoss(nn.Module):
             nll = -torch.log(s.gather(1, virt[:, None])[:, 0] + 1e-27).mean()               # :33
             loss = loss + torch.where(wrong, nll, torch.zeros_like(nll))
         return loss / inst_embeddings.shape[0]
+
+
+class _SupCon(torch.autograd.Function):
+    """Per-row supervised-contrastive loss f32 [B, P] (0 at rows that are not anchors and in skipped images): pag_supcon_fwd (three launches) and
+    pag_supcon_bwd (two).  The workspace holds the normalised anchors and the row statistics between the two."""
+
+    @staticmethod
+    def forward(ctx, x, labels, mask, T, Tb, pw, nw):
+        B, P, D = x.shape
+        dev = x.device
+        nbytes = int(L.load().pag_supcon_workspace_bytes(B, P, D))
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        loss = torch.empty(B, P, device=dev)
+        ops._call("pag_supcon_fwd", x.data_ptr(), L.dtype_code(x), B, P, D, x.stride(0), x.stride(1), labels.data_ptr(),
+                  mask.data_ptr() if mask is not None else None, T, Tb, pw, nw, ws.data_ptr(), nbytes, loss.data_ptr(), L.stream())
+        ctx.save_for_backward(ws)
+        ctx.args = (x.dtype, B, P, D, T, Tb, pw, nw)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        ws, = ctx.saved_tensors
+        dtype, B, P, D, T, Tb, pw, nw = ctx.args
+        g = g.contiguous().float()
+        d = torch.empty(B, P, D, device=g.device, dtype=dtype)
+        ops._call("pag_supcon_bwd", L.dtype_code(d), B, P, D, T, Tb, pw, nw, ws.data_ptr(), ws.numel(), g.data_ptr(), d.data_ptr(), L.stream())
+        return d, None, None, None, None, None, None
+
+
+class SupConLoss(nn.Module):
+    """loss/sup_contrastive.py::SupConLoss on the GPU: pc_nerf/trainer.py:63-65 builds it for `inst_loss: sup_contrastive` (picking constructor arguments
+    from __init__.__code__.co_varnames, so the four parameters are named exactly as there) and calls it on the rendered instance embeddings (:499-503,
+    with anchor_mask) and, with contrast_sem_weight > 0, on the semantic probabilities + 1e-27 (:477-480, without).
+
+    Per image: f = x / max(||x||, 1e-12); anchors S = the anchor_mask rows (all rows without a mask); A = f_S f_S^T / temperature; m_i = the row max
+    (diagonal included, detached); loss_i = -(temperature / base_temperature) * Sum_j M_ij (pw (A_ij - m_i) - nw LSE_i) / (cnt_i + 1e-16) with
+    LSE_i = log Sum_{j != i} exp(A_ij - m_i), M_ij = same label and j != i, cnt_i = Sum_j M_ij, pw = min(1, 2 pn_ratio), nw = min(1, 2 (1 - pn_ratio)).
+    With anchor_mask, an image without anchors or whose anchors share one label contributes 0 and no gradient.
+
+    Return shapes follow the reference: 'mean' -> [1] with anchor_mask (Sum of the anchors' losses / anchor_mask.sum()), 0-d without (mean over [B, P]);
+    'sum' -> the same two shapes; 'none' / None -> [B, P] without anchor_mask, with it a list of [1, |S_b|] tensors per image (0-d zero for a skipped
+    image; this form reads the anchor counts on the host).  The loss is fp32 for f32 and bf16 features alike; the gradient has the features' dtype.
+
+    Divergences: with anchor_mask.sum() == 0 the reference returns the float 0.0 - here a zero tensor of the usual shape that takes part in autograd.
+    Without anchor_mask and P == 1 the value is NaN, as in the reference (0 * inf).  `mask` is accepted and ignored, as the reference's forward ignores
+    it; labels=None (SimCLR) is not supported.  contrast_mode 'one' equals 'all' here: every call has a single view."""
+
+    def __init__(self, temperature=0.07, contrast_mode='all', base_temperature=0.07, pn_ratio=0.5):
+        super().__init__()
+        if contrast_mode not in ('all', 'one'):
+            raise ValueError('Unknown mode: {}'.format(contrast_mode))
+        self.temperature = temperature
+        self.contrast_mode = contrast_mode
+        self.base_temperature = base_temperature
+        self.pos_weight = min(1, pn_ratio * 2)
+        self.neg_weight = min(1, (1 - pn_ratio) * 2)
+
+    def forward(self, features, labels=None, mask=None, reduction='mean', anchor_mask=None, *args, **kwargs):
+        if labels is None:
+            raise NotImplementedError("SupConLoss: labels=None (the SimCLR form) is not supported; the trainer always passes labels")
+        if features.dim() < 3:
+            raise ValueError('`features` needs to be [bsz, n_rays, ...], at least 3 dimensions are required')
+        ops._check_gpu(features, labels, anchor_mask)
+        if reduction not in ('sum', 'mean', 'none', None):
+            raise NotImplementedError(f"Unsupported reduction method {reduction}. Posible options are ['sum', 'mean', 'none']")
+        B, P = features.shape[:2]
+        x = features.reshape(B, P, -1)
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            x = x.float()
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        lab = labels.detach().reshape(B, P).long().contiguous()
+        am = None
+        if anchor_mask is not None:
+            assert anchor_mask.shape == labels.shape, \
+                f'anchor_mask and labes must be the same size, but got {anchor_mask.shape} and {labels.shape}'
+            am = anchor_mask.detach().reshape(B, P).to(torch.uint8).contiguous()
+        loss = _SupCon.apply(x, lab, am, float(self.temperature), float(self.base_temperature), float(self.pos_weight), float(self.neg_weight))
+        if reduction in ('none', None):
+            if am is None:
+                return loss
+            out = []
+            for b in range(B):
+                sel = am[b].bool()
+                if not bool(sel.any()) or lab[b][sel].unique().numel() < 2:
+                    out.append(torch.zeros((), device=loss.device))
+                else:
+                    out.append(loss[b][sel].view(1, -1))
+            return out
+        if am is None:
+            return loss.sum() if reduction == 'sum' else loss.mean()
+        if reduction == 'sum':
+            return loss.sum().reshape(1)
+        norm = am.sum().clamp(min=1)                          # 0 anchors: every row is 0, and so is the value (the reference returns the float 0.0)
+        return (loss.sum(1) / norm).sum().reshape(1)

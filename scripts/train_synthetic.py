@@ -6,6 +6,11 @@ reference, tracers/panoptic_packed_rf_tracer.py:197-205, so they cannot be super
 Trains the bench's model / optimizer / loss (bench.py, BUP20 hyper-parameters) for --steps steps on fresh random rays and reports
 PSNR, semantic and instance accuracy on held-out rays, once on the bf16 MFMA path and once on the fp32 parity path (the one the
 oracle tests pin), same seeds.  usage: python3 scripts/train_synthetic.py [--steps 600] [--rays 4096] [--samples 128]
+
+--inst-loss sup_contrastive trains the instance head as configs/bup20/best_contrast_delta.yaml does: a raw 200-wide embedding (no softmax),
+inst_weight 0.1 x pagnerf_amd.loss.SupConLoss(temperature 0.07, pn_ratio 0.5) on the rays that hit (anchor_mask), next to the rgb and
+semantic terms; instance accuracy is then nearest-centroid: held-out rays take the id whose mean normalised training-ray embedding is
+closest in cosine.  The default (nll) keeps the per-ray NLL instance term.
 """
 import argparse
 import json
@@ -45,10 +50,13 @@ def run(precision, a, dev):
     nef, tracer = bench.make_model(args, dev, seed=0), bench.make_tracer(args)
     opt = bench.make_optimizer(nef)
     chans = ["rgb", "semantics", "inst_embedding"]
+    contrastive = a.inst_loss == "sup_contrastive"
+    if contrastive:
+        nef.inst_softmax = False                                     # best_contrast_delta.yaml: inst_softmax false
     gen = torch.Generator().manual_seed(123)
     for step in range(a.steps):
         rays, gt = scene_rays(a.rays, gen, dev)
-        loss = bench.train_step(nef, tracer, opt, rays, gt, chans, 1)
+        loss = contrastive_step(nef, tracer, opt, rays, gt, chans) if contrastive else bench.train_step(nef, tracer, opt, rays, gt, chans, 1)
     gen = torch.Generator().manual_seed(999)
     rays, gt = scene_rays(4 * a.rays, gen, dev)
     with torch.no_grad():
@@ -70,9 +78,43 @@ def run(precision, a, dev):
                          psnr_hip_vs_gt_db=round(-10 * math.log10(float(((r["rgb_hip"] - g) ** 2).mean())), 2),
                          psnr_oracle_vs_gt_db=round(-10 * math.log10(float(((r["rgb_oracle"] - g) ** 2).mean())), 2),
                          sem_max_abs_diff=round(r["sem_max_abs_diff"], 5), inst_max_abs_diff=round(r["inst_max_abs_diff"], 5))
-    return dict(precision=precision, vs_oracle=vs_oracle, final_loss=float(loss.detach()), psnr_db=round(-10 * math.log10(mse), 2),
+    if contrastive:
+        gen = torch.Generator().manual_seed(321)                     # training-distribution rays (not the held-out set) for the centroids
+        train_rays, train_gt = scene_rays(4 * a.rays, gen, dev)
+        with torch.no_grad():
+            import pagnerf_amd
+            tb = pagnerf_amd.batch_render(pagnerf_amd.Pipeline(nef, tracer), train_rays, channels=chans, render_batch=a.rays)
+        inst_pred = nearest_centroid(tb.inst_embedding, train_gt["inst"], rb.inst_embedding)
+    else:
+        inst_pred = rb.inst_embedding.argmax(-1)
+    return dict(precision=precision, inst_loss=a.inst_loss, vs_oracle=vs_oracle, final_loss=float(loss.detach()), psnr_db=round(-10 * math.log10(mse), 2),
                 sem_acc=round(float((rb.semantics.argmax(-1) == gt["sem"])[gt["sem"] >= 0].float().mean()), 4),
-                inst_acc=round(float((rb.inst_embedding.argmax(-1) == gt["inst"])[gt["inst"] >= 0].float().mean()), 4))
+                inst_acc=round(float((inst_pred == gt["inst"])[gt["inst"] >= 0].float().mean()), 4))
+
+
+def contrastive_step(nef, tracer, opt, rays, gt, channels):
+    """rgb L1 (weight 10) + semantic NLL (0.1) as bench.train_step forms them, + inst_weight 0.1 x SupConLoss on the rays that hit
+    (pc_nerf/trainer.py:499-503 with best_contrast_delta.yaml's weights)."""
+    from pagnerf_amd.loss import render_loss, NllTerm, SupConLoss
+    opt.zero_grad(set_to_none=True)
+    rb = tracer(nef, channels=channels, rays=rays, stage="train")
+    loss, _ = render_loss(rb.rgb, gt["rgb"], 10.0, NllTerm(rb.semantics, gt["sem"], weight=0.1))
+    emb = rb.inst_embedding.reshape(1, -1, rb.inst_embedding.shape[-1])
+    ids = gt["inst"].reshape(1, -1)
+    loss = loss + 0.1 * SupConLoss(temperature=0.07, pn_ratio=0.5)(emb, ids, reduction="mean", anchor_mask=ids >= 0)
+    loss.backward()
+    opt.step()
+    return loss
+
+
+def nearest_centroid(train_emb, train_ids, emb):
+    """Per id the mean of the normalised training embeddings; each row of `emb` takes the id of the closest centroid in cosine."""
+    f = torch.nn.functional.normalize(train_emb.float(), dim=-1)
+    keep = train_ids >= 0
+    ids = torch.unique(train_ids[keep])
+    cent = torch.stack([f[train_ids == i].mean(0) for i in ids.tolist()])
+    sim = torch.nn.functional.normalize(emb.float(), dim=-1) @ torch.nn.functional.normalize(cent, dim=-1).T
+    return ids[sim.argmax(-1)]
 
 
 if __name__ == "__main__":
@@ -84,6 +126,8 @@ if __name__ == "__main__":
     ap.add_argument("--oracle-psnr", type=int, default=0, metavar="RAYS",
                     help="also render RAYS held-out rays of the trained model with the CPU oracle (tests/test_gpu_trajectory.py) and report the "
                          "PSNR of the HIP render against it, next to both renders' PSNR against the ground truth")
+    ap.add_argument("--inst-loss", choices=("nll", "sup_contrastive"), default="nll",
+                    help="instance term: per-ray NLL on the softmaxed head (default), or the supervised-contrastive loss on a raw embedding")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     import __graft_entry__ as ge
