@@ -631,6 +631,42 @@ int pag_supcon_bwd(int dtype, int B, int64_t P, int D, float temperature, float 
                    int64_t workspace_bytes, const float *grad_loss, void *d_features, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mean-shift clustering of the instance embedding (utils/clustering/mean_shift.py::MeanShift with utils/embedding.py::mean_class_embedding and sklearn's
+ * estimate_bandwidth / MeanShift / predict; pc_nerf/clustering_nef.py, called at pc_nerf/trainer.py:948-970 and :737-738) - every pass on the device,
+ * no K x K matrix in memory, no float atomics, bitwise reproducible.  Additive to ABI 14.
+ * ------------------------------------------------------------------------------------------ */
+
+/* Workspace of pag_meanshift_fit for B*P rows of D dimensions (0 for sizes past the limits: B*P <= 2^24, 1 <= D <= 512); O(B*P + K*D) bytes. */
+int64_t pag_meanshift_workspace_bytes(int B, int64_t P, int D);
+
+/* features [B, P, D] (f32 or bf16 `dtype`, element (b, p, k) at b*image_stride + p*row_stride + k), labels i64 [B,P] contiguous.
+ * Stage 1 (utils/embedding.py:3-27, mean_class_embedding): one class mean per (image, distinct label), images in order and labels ascending within an
+ *   image, negative labels included; each is the fp32 sum of its rows divided by the count -> means f32 [Kcap, D] rows 0 .. K-1, Kcap = min(B*P, 32768).
+ *   labels NULL: every row is its own class (K = B*P <= 32768; the rows are copied), which is how the centres of estimate_bandwidth are passed in.
+ * Stage 2 (mean_shift.py:22, sklearn estimate_bandwidth(centres, quantile)): k = max(1, int(K quantile)); per centre the exact k-th smallest Euclidean
+ *   distance to all centres (itself included, at 0), from the fp32 values with fp64 accumulation; bandwidth f64 [1] = their mean.  For K < 1/quantile
+ *   k = 1 and the bandwidth is exactly 0, and stage 3 makes every distinct centre its own cluster.  This differs from the reference there: sklearn's
+ *   ~1e-9 bandwidth is at the size of its rounding of a centre's distance to itself, so it drops some seeds, and for a bandwidth of exactly 0 (K = 1,
+ *   identical centres) its MeanShift raises instead of fitting.
+ * Stage 3 (mean_shift.py:24, sklearn MeanShift(bandwidth, bin_seeding=False, cluster_all=True, max_iter).fit): every centre seeds
+ *   m <- mean of the centres with ||c - m|| <= bw, summed in ascending index order in fp64 and rounded to fp32, until ||m_new - m_old|| <= 1e-3 bw or
+ *   max_iter iterations; intensity = the neighbour count of the last iteration (a seed whose neighbourhood empties is dropped).  Equal converged means
+ *   are one entry (sklearn's dict) with the last such seed's intensity; the entries are ordered by (intensity, coordinates lexicographically)
+ *   descending and each kept entry removes every later one within bw -> centers f32 [Kcap, D] rows 0 .. C-1 = cluster_centers_.
+ * info i32 [4] = {K, C, n_iter (the largest completed-iteration count of any seed), flags}; flags bit 0: K > 32768 (the fit stops after counting; K
+ * then reads 32769).  Nothing is read back to the host: the caller reads info once at the end.  stages 1, 2, 3 run the passes up to that stage. */
+int pag_meanshift_fit(const void *features, int dtype, int B, int64_t P, int D, int64_t image_stride, int64_t row_stride, const int64_t *labels,
+                      double quantile, int max_iter, int stages, void *workspace, int64_t workspace_bytes, float *means, double *bandwidth,
+                      float *centers, int32_t *info, void *stream);
+
+/* mean_shift.py:34-42 (sklearn MeanShift.predict = pairwise_distances_argmin): labels_out i64 [N] = argmin_c ||x_n - c|| over centers f32 [C, D]
+ * (contiguous), exact ties to the lowest index.  x: N rows (f32 or bf16 `dtype`) of D elements, row n at n*row_stride.  Scores ||c||^2 - 2 x.c on the
+ * f32-input MFMA; a row whose two best scores are closer than the bound of their rounding error is recomputed in fp64, so the result equals the fp64
+ * argmin.  1 <= D <= 512, 1 <= C <= 32768, any N (0: no-op); no host synchronisation (capturable in a graph). */
+int pag_meanshift_predict(const void *x, int dtype, int64_t N, int D, int64_t row_stride, const float *centers, int C, int64_t *labels_out,
+                          void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-ray training loss of the rendered buffers (pc_nerf/trainer.py:443-446 rgb, :459-465 semantics,
  * loss/lin_assignment_things.py:80 instance term after the assignment) - one launch forward, one backward
  * ------------------------------------------------------------------------------------------ */

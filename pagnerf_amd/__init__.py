@@ -8,6 +8,8 @@
     dd    : PanopticDDensityNeF / ...PackedRFTracer (dd.py)     <- pc_nerf/panoptic_dd_nef.py, tracers/panoptic_dd_packed_rf_tracer.py
     shard : ray sharding + RCCL gather/all-reduce (shard.py)
     loss  : LinAssignmentThingsLoss, LinAssignmentLoss, SupConLoss (loss.py) <- loss/lin_assignment*.py, loss/sup_contrastive.py
+    cluster: MeanShift, mean_class_embedding, estimate_bandwidth, MeanShift*NeF (cluster.py) <- utils/clustering/mean_shift.py,
+             utils/embedding.py, pc_nerf/clustering_nef.py
     optim : Adam (torch.optim.Adam's interface on pag_adam_step) (optim.py) <- config_parser.py:667-673, trainer.py:583
 
 All compute goes through libpagnerf_hip.so (include/pagnerf_hip.h); there is no CPU fallback.
@@ -18,6 +20,8 @@ from .nef import PanopticDeltaNeF, PanopticNeF, BasicDecoder                    
 from .tracer import PanopticPackedRFTracer                         # noqa: F401
 from .ba_pipeline import BAPipeline                                # noqa: F401
 from .dd import PanopticDDensityNeF, PanopticDDensityPackedRFTracer    # noqa: F401
+from .cluster import (ClusteringNeF, MeanShift, MeanShiftPanopticDDensityNeF, MeanShiftPanopticDeltaNeF,    # noqa: F401
+                      MeanShiftPanopticNeF, estimate_bandwidth, mean_class_embedding)
 from . import optim                                                # noqa: F401
 
 __version__ = "0.1.0"

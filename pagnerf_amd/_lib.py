@@ -153,6 +153,10 @@ _SIGS = {
     "pag_supcon_workspace_bytes": (c_i64, [c_i32, c_i64, c_i32]),
     "pag_supcon_fwd": (c_i32, [c_vp, c_i32, c_i32, c_i64, c_i32, c_i64, c_i64, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp]),
     "pag_supcon_bwd": (c_i32, [c_i32, c_i32, c_i64, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "pag_meanshift_workspace_bytes": (c_i64, [c_i32, c_i64, c_i32]),
+    "pag_meanshift_fit": (c_i32, [c_vp, c_i32, c_i32, c_i64, c_i32, c_i64, c_i64, c_vp, ctypes.c_double, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp]),
+    "pag_meanshift_predict": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp]),
     "pag_mlp_dz0_slots_bytes": (c_i64, [c_i64, c_i64]),
     "pag_mlp_dz0_slots_sum": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pag_encode_bwd_rays_workspace_bytes": (c_i64, [c_i64, c_i64]),

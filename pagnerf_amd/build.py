@@ -32,6 +32,7 @@ SOURCES = {
     "pose.hip": ["-ffp-contract=off"],       # the camera transform in the tensor-op form's op order
     "regularizer.hip": ["-ffp-contract=off"],
     "supcon.hip": ["-ffp-contract=off"],     # the contrastive loss: the row statistics in the written op order
+    "cluster.hip": ["-ffp-contract=off"],    # mean-shift clustering: the fp64 distances and sums in the written op order
     "sparse.hip": [],                         # the touched-rows exchange's mask / plan / pack / unpack passes: integer and copy work only
 }
 

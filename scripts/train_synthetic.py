@@ -10,7 +10,8 @@ oracle tests pin), same seeds.  usage: python3 scripts/train_synthetic.py [--ste
 --inst-loss sup_contrastive trains the instance head as configs/bup20/best_contrast_delta.yaml does: a raw 200-wide embedding (no softmax),
 inst_weight 0.1 x pagnerf_amd.loss.SupConLoss(temperature 0.07, pn_ratio 0.5) on the rays that hit (anchor_mask), next to the rgb and
 semantic terms; instance accuracy is then nearest-centroid: held-out rays take the id whose mean normalised training-ray embedding is
-closest in cosine.  The default (nll) keeps the per-ray NLL instance term.
+closest in cosine (inst_acc), and - the configs' own route - mean-shift clusters of the training rays named by their majority id
+(inst_acc_mean_shift, n_clusters; pagnerf_amd.cluster.MeanShift).  The default (nll) keeps the per-ray NLL instance term.
 """
 import argparse
 import json
@@ -85,11 +86,16 @@ def run(precision, a, dev):
             import pagnerf_amd
             tb = pagnerf_amd.batch_render(pagnerf_amd.Pipeline(nef, tracer), train_rays, channels=chans, render_batch=a.rays)
         inst_pred = nearest_centroid(tb.inst_embedding, train_gt["inst"], rb.inst_embedding)
+        ms_pred, n_clusters = mean_shift_ids(tb.inst_embedding, train_gt["inst"], rb.inst_embedding)
     else:
         inst_pred = rb.inst_embedding.argmax(-1)
-    return dict(precision=precision, inst_loss=a.inst_loss, vs_oracle=vs_oracle, final_loss=float(loss.detach()), psnr_db=round(-10 * math.log10(mse), 2),
-                sem_acc=round(float((rb.semantics.argmax(-1) == gt["sem"])[gt["sem"] >= 0].float().mean()), 4),
-                inst_acc=round(float((inst_pred == gt["inst"])[gt["inst"] >= 0].float().mean()), 4))
+    hit = gt["inst"] >= 0
+    out = dict(precision=precision, inst_loss=a.inst_loss, vs_oracle=vs_oracle, final_loss=float(loss.detach()), psnr_db=round(-10 * math.log10(mse), 2),
+               sem_acc=round(float((rb.semantics.argmax(-1) == gt["sem"])[gt["sem"] >= 0].float().mean()), 4),
+               inst_acc=round(float((inst_pred == gt["inst"])[hit].float().mean()), 4))
+    if contrastive:
+        out.update(inst_acc_mean_shift=round(float((ms_pred == gt["inst"])[hit].float().mean()), 4), n_clusters=n_clusters)
+    return out
 
 
 def contrastive_step(nef, tracer, opt, rays, gt, channels):
@@ -105,6 +111,22 @@ def contrastive_step(nef, tracer, opt, rays, gt, channels):
     loss.backward()
     opt.step()
     return loss
+
+
+def mean_shift_ids(train_emb, train_ids, emb, images=16):
+    """The contrastive configs' own route to ids (pc_nerf/trainer.py:948-970 and :737-738): MeanShift fitted on the normalised embeddings of the
+    training rays that hit, split into `images` pseudo-images (class means per image and id, so K >= 25), then predict on the raw held-out
+    embeddings.  Each cluster is named by the majority id of the training rays it predicts.  -> (ids of emb's rows, number of clusters)."""
+    from pagnerf_amd.cluster import MeanShift
+    keep = train_ids >= 0
+    f, ids = train_emb[keep], train_ids[keep]
+    m = f.shape[0] // images
+    ms = MeanShift(num_clustering_workers=6)
+    ms.train_clustering(torch.nn.functional.normalize(f[:images * m].float(), dim=-1).reshape(images, m, -1), ids[:images * m].reshape(images, m))
+    C = ms.cluster_centers_.shape[0]
+    n_ids = int(ids.max()) + 1
+    votes = torch.bincount(ms.predict_clusters(f) * n_ids + ids, minlength=C * n_ids).reshape(C, n_ids)
+    return votes.argmax(1)[ms.predict_clusters(emb)], C
 
 
 def nearest_centroid(train_emb, train_ids, emb):
