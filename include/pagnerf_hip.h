@@ -667,6 +667,49 @@ int pag_meanshift_predict(const void *x, int dtype, int64_t N, int D, int64_t ro
                           void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Panoptic evaluation of a validation image (pc_nerf/trainer.py:651-941 evaluate_metrics): the instance cleanup of :750-772, the panoptic quality
+ * update of utils/metrics/panoptic_quality{,_func}.py and the confusion matrix of the semantic IoU (:670-671, :720).  Every pass on the device, no
+ * [K, H, W] masks, no float atomics, integer sums only (bitwise reproducible), no host synchronisation (capturable in a graph).  Additive to ABI 14.
+ * ------------------------------------------------------------------------------------------ */
+enum { PAG_I32 = 3, PAG_I64 = 4 };          /* id / label dtypes of the panoptic evaluation */
+
+/* Workspace of pag_panoptic_pq_update (0 past the limits: B*H*W <= 2^28, 2 <= n_cat <= 1024); O(B*H*W) bytes. */
+int64_t pag_panoptic_pq_workspace_bytes(int B, int64_t H, int64_t W, int n_cat);
+
+/* One PanopticQuality.update(preds, target): both [B, 2, H, W] (int32 / int64 `*_dtype`, element (b, c, y, x) at the dot product with the host arrays
+ * `*_strides` [4]); never written.  cat_ids i64 [n_cat] (device) = things and stuff ids in ascending order, cat_cont i32 [n_cat] (device) = their
+ * continuous ids (things in set iteration order first: 0 .. n_things-1, then stuff).
+ * Preprocessing (_prepocess_image): instance ids of image b get the cumulative offset sum_{b' < b} max(raw instance channel of b'); stuff pixels get
+ *   instance 0; categories outside cat_ids become the void colour.  Segments are the distinct (category, instance) colours.
+ * Matching (_panoptic_quality_update): a (pred, target) pair with a non-void target of the same category matches when the f32 quotient of the int64
+ *   intersection and union = pred_area - pred_void_area + target_area - void_target_area - intersection is > 0.5; every such pair adds 1 to tp and
+ *   its IoU to iou_sum.  An unmatched non-void target (pred) segment adds 1 to fn (fp) unless its void area over its area (f32) is > 0.5.
+ * The call's sums are added to the state iou_sum f64 [n_cat], true_positives / false_positives / false_negatives i32 [n_cat] (device).  The IoUs of
+ * a call are exact multiples of 2^-24 in (0.5, 1] and summed exactly as integers, so iou_sum equals the reference's f64 sum in any order.
+ * The first 4 bytes of the workspace receive this call's flags: bit 0 an unknown pred category (then, with allow_unknown == 0, the state is left
+ * unchanged and the caller raises); bit 1 a thing instance id outside int32 after the offsets, which is also OR-ed into state_flags i32 [1]. */
+int pag_panoptic_pq_update(const void *preds, int preds_dtype, const int64_t *preds_strides, const void *target, int target_dtype,
+                           const int64_t *target_strides, int B, int64_t H, int64_t W, const int64_t *cat_ids, const int32_t *cat_cont, int n_cat,
+                           int n_things, int allow_unknown, void *workspace, int64_t workspace_bytes, double *iou_sum, int32_t *true_positives,
+                           int32_t *false_positives, int32_t *false_negatives, int32_t *state_flags, void *stream);
+
+/* Workspace of pag_panoptic_clean (0 past the limits: H, W <= 32768, H*W <= 2^28); O(H*W) bytes. */
+int64_t pag_panoptic_clean_workspace_bytes(int64_t H, int64_t W);
+
+/* trainer.py:750-772 on an id image [H, W] (int32 / int64 `dtype`, element (y, x) at y*stride_y + x*stride_x; never written) -> out [H, W]
+ * (contiguous, same dtype).  The background is the smallest id.  Every other id's mask gets a flat 3x3 opening when num_openings > 0 (opening is
+ * idempotent; erosion counts pixels outside the image as inside, dilation as outside), then with outlier_rejection its pixels farther from the
+ * mask's centre of mass than mean + std_threshold * std of the mask's distances (population std) are dropped, then masks of fewer than min_area
+ * pixels are dropped.  Dropped pixels get the background id.  Moments are exact integers, distances fp64, their sums 2^-20 fixed point. */
+int pag_panoptic_clean(const void *ids, int dtype, int64_t H, int64_t W, int64_t stride_y, int64_t stride_x, int num_openings, int outlier_rejection,
+                       int64_t min_area, double std_threshold, void *workspace, int64_t workspace_bytes, void *out, void *stream);
+
+/* confmat i64 [C, C] (device, contiguous) += counts of (target, pred) over shape[4] elements (host array; element (i0..i3) of preds at the dot
+ * product with preds_strides [4], likewise target); pairs with a value outside [0, C) are ignored.  1 <= C <= 65536. */
+int pag_confusion_matrix(const void *preds, int preds_dtype, const int64_t *preds_strides, const void *target, int target_dtype,
+                         const int64_t *target_strides, const int64_t *shape, int C, int64_t *confmat, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-ray training loss of the rendered buffers (pc_nerf/trainer.py:443-446 rgb, :459-465 semantics,
  * loss/lin_assignment_things.py:80 instance term after the assignment) - one launch forward, one backward
  * ------------------------------------------------------------------------------------------ */

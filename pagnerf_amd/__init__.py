@@ -10,6 +10,8 @@
     loss  : LinAssignmentThingsLoss, LinAssignmentLoss, SupConLoss (loss.py) <- loss/lin_assignment*.py, loss/sup_contrastive.py
     cluster: MeanShift, mean_class_embedding, estimate_bandwidth, MeanShift*NeF (cluster.py) <- utils/clustering/mean_shift.py,
              utils/embedding.py, pc_nerf/clustering_nef.py
+    metrics: PanopticQuality, panoptic_quality, clean_instances, MulticlassIoU (metrics.py) <- utils/metrics/panoptic_quality{,_func}.py,
+             pc_nerf/trainer.py:670-673, :750-772 (validation)
     optim : Adam (torch.optim.Adam's interface on pag_adam_step) (optim.py) <- config_parser.py:667-673, trainer.py:583
 
 All compute goes through libpagnerf_hip.so (include/pagnerf_hip.h); there is no CPU fallback.
@@ -22,6 +24,7 @@ from .ba_pipeline import BAPipeline                                # noqa: F401
 from .dd import PanopticDDensityNeF, PanopticDDensityPackedRFTracer    # noqa: F401
 from .cluster import (ClusteringNeF, MeanShift, MeanShiftPanopticDDensityNeF, MeanShiftPanopticDeltaNeF,    # noqa: F401
                       MeanShiftPanopticNeF, estimate_bandwidth, mean_class_embedding)
+from .metrics import MulticlassIoU, PanopticQuality, clean_instances, panoptic_quality    # noqa: F401
 from . import optim                                                # noqa: F401
 
 __version__ = "0.1.0"

@@ -11,6 +11,7 @@ import torch
 from . import build as _build
 
 F32, F16, BF16 = 0, 1, 2
+I32, I64 = 3, 4
 ACT_NONE, ACT_SIGMOID, ACT_SOFTMAX = 0, 1, 2
 MLP_MFMA_BF16, MLP_FP32 = 0, 1
 BG_BLACK, BG_WHITE = 0, 1
@@ -157,6 +158,12 @@ _SIGS = {
     "pag_meanshift_fit": (c_i32, [c_vp, c_i32, c_i32, c_i64, c_i32, c_i64, c_i64, c_vp, ctypes.c_double, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                   c_vp]),
     "pag_meanshift_predict": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp]),
+    "pag_panoptic_pq_workspace_bytes": (c_i64, [c_i32, c_i64, c_i64, c_i32]),
+    "pag_panoptic_pq_update": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp, c_vp]),
+    "pag_panoptic_clean_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "pag_panoptic_clean": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i64, ctypes.c_double, c_vp, c_i64, c_vp, c_vp]),
+    "pag_confusion_matrix": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "pag_mlp_dz0_slots_bytes": (c_i64, [c_i64, c_i64]),
     "pag_mlp_dz0_slots_sum": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pag_encode_bwd_rays_workspace_bytes": (c_i64, [c_i64, c_i64]),
