@@ -18,14 +18,18 @@ LIB = os.path.join(LIBDIR, "libpagnerf_hip.so")
 ARCH = "gfx950"
 
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-munsafe-fp-atomics", "-Wno-unused-value"]
+# MFMA results in VGPRs wherever they fit: the fused backward kernels keep 224 accumulator registers in the AGPR half, and with the
+# default (AGPR-form MFMAs for the whole function) every per-tile result paid a v_accvgpr_read per register - 160 of 520 VALU per tile
+MLP = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
+# Longest compile first (the pool takes them in this order, so that the build does not end on one long source started last).
 # encode / render reproduce the oracle's fp32 op order: no FMA contraction there
 SOURCES = {
-    "api.cpp": ["-x", "hip"],
+    "mlp.hip": MLP,
     "encode.hip": ["-ffp-contract=off"],
+    "mlp_wgrad.hip": MLP,
     "render.hip": ["-ffp-contract=off"],
-    # MFMA results in VGPRs wherever they fit: the fused backward kernels keep 224 accumulator registers in the AGPR half, and with the
-    # default (AGPR-form MFMAs for the whole function) every per-tile result paid a v_accvgpr_read per register - 160 of 520 VALU per tile
-    "mlp.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+    "mlp_affine.hip": MLP,
+    "api.cpp": ["-x", "hip"],
     "assign.hip": ["-ffp-contract=off"],
     "loss.hip": ["-ffp-contract=off"],
     "optim.hip": ["-ffp-contract=off"],      # Adam: torch's op order, no contraction beyond the explicit fmaf
@@ -36,6 +40,16 @@ SOURCES = {
     "panoptic.hip": ["-ffp-contract=off"],   # panoptic evaluation: the f32 IoU quotients and fp64 distances in the written op order
     "sparse.hip": [],                         # the touched-rows exchange's mask / plan / pack / unpack passes: integer and copy work only
 }
+
+
+def _jobs():
+    """Compile processes at a time: the CPUs of this machine, 16 at most, and no more than MAX_JOBS when that is set."""
+    n = min(16, os.cpu_count() or 4)
+    try:
+        n = min(n, int(os.environ.get("MAX_JOBS", "")))
+    except ValueError:
+        pass
+    return max(1, n)
 
 
 def _hipcc():
@@ -92,7 +106,7 @@ def build(force=False, verbose=True):
             print("[pagnerf_amd.build] up to date:", LIB, file=sys.stderr)
         return LIB
     objs = {s: os.path.join(LIBDIR, "obj", os.path.splitext(s)[0] + ".o") for s in SOURCES}
-    with concurrent.futures.ThreadPoolExecutor(max_workers=4) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=_jobs()) as ex:
         futs = [ex.submit(_compile, s, f, objs[s]) for s, f in SOURCES.items()]
         for f in concurrent.futures.as_completed(futs):
             if verbose:

@@ -281,7 +281,7 @@ constexpr int SOLVE_STAGE = 12288;      // fp32 entries of the cost matrix kept 
 // of the cost row, the relaxation, and TWO wave reductions on DPP moves: the minimum of the float64 path costs (compared as float64, as SciPy does), then - among the lanes
 // that hold it - the minimum of q, which encodes SciPy's tie rule in one number: a column without a row gets q = 255 - position (the LAST free one in scan order
 // wins), a column with a row q = 256 + position (only if no free column shares the minimum; the FIRST in scan order wins).  ~3x fewer cycles per pass than the
-// first form (every per-column array in LDS, six rounds of shuffles on a three-field record): 0.44 -> see profiles/README.md round 6.
+// first form (every per-column array in LDS, six rounds of shuffles on a three-field record); per-launch times of both forms: profiles/README.md round 6, "Hungarian step on the device".
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ uint32_t solve_dpp(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xF, false);      // lanes without a source keep their own value

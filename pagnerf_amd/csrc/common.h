@@ -12,6 +12,13 @@
 // waited for that one XCD: 0.458 -> 0.386 ms per launch (scripts/bench_encode_levels.py).  Levels >= n_levels are padding.
 __host__ __device__ __forceinline__ int xcd8_level(int g, int j) { return (j & 1) ? 8 * j + 7 - g : 8 * j + g; }
 
+// Staged position 63 (group 7, element 7) of a levels x feats XCD8 row is padding.  The fused decoder backward needs it: it sets that input column
+// to 1, so that the column's weight gradient is the first layer's bias gradient.
+__host__ __device__ __forceinline__ bool xcd8_has_bias_slot(int levels, int feats) {
+    const int j = 7 / feats;
+    return !(j < (levels + 7) / 8 && xcd8_level(7, j) < levels);
+}
+
 #define PAG_WAVE 64
 
 typedef __bf16 bf16_t;

@@ -15,41 +15,21 @@
 //     (softmax over the registers of a lane + one cross-half shuffle).
 //   * one 256-thread workgroup = 4 waves x 32-sample tiles, grid-strided; weights are converted to
 //     bf16 and staged once per workgroup (<= 51 KiB LDS, rows padded by 16 B against bank conflicts).
-// The backward kernel runs the same structure on the transposed weights and emits the per-layer
-// pre-activation gradients dz (bf16) and dx; weight gradients are dz^T . input, a plain GEMM that is
-// left to the BLAS library.
+// The backward kernels run the same structure on the transposed weights and emit dx; the weight gradients dz^T . input are
+// accumulated by the same launch (mlp_bwd_fused, mlp_bwd_pair, mlp_bwd_wide_blocks) or, from the dz tensors mlp_bwd_mfma writes, by
+// mlp_wgrad_kernel (mlp_wgrad.hip); wgrad_finish_kernel below sums either kind of per-workgroup slab.
 //
 // FP32 path (PAG_MLP_FP32): one lane per sample, fp32 FMA chains in k order with the weights
 // broadcast from LDS - the parity path (tolerance 1e-5 against the fp32 oracle).
-#include "common.h"
-#include <algorithm>
-#include <type_traits>
+#include "mlp_common.h"
 
 namespace {
-
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WIDE_BWD_WAVES = 8;      // waves per workgroup of mlp_bwd_wide_mfma (8 or 16; one workgroup per CU)
 constexpr int RS = 72;          // LDS row stride (bf16 elements) of a 64-wide weight row: 144 B
 constexpr int HID = 64;
 
-__device__ __forceinline__ int rho(int q, int h) { return (q & 3) + 8 * (q >> 2) + 4 * h; }
 __device__ __forceinline__ int swap23(int a) { return (a & ~12) | ((a & 4) << 1) | ((a & 8) >> 1); }
-
-// staged position (8*g + e) of the XCD8 layout -> column level*F + f of the [M, L*F] feature row, or -1 (padding)
-// (a / d for the wave-uniform divisors of the staging loops: a shift when d is a power of two - the feature width and the pad sizes always
-// are - instead of the ~40-instruction software division; the loops below were bound by those: 25 k of a launch's clocks per workgroup)
-__device__ __forceinline__ int udiv_uniform(int a, int d) { return (d & (d - 1)) == 0 ? a >> (31 - __clz(d)) : a / d; }
-__device__ __forceinline__ int grp_col(int pos, int L, int F) {
-    const int g = pos >> 3, e = pos & 7;
-    const int j = udiv_uniform(e, F), f = e - j * F;
-    const int level = xcd8_level(g, j);
-    return (j < (L + 7) / 8 && level < L) ? level * F + f : -1;
-}
-
 struct FwdParams {
     const void *x1;
     const float *x2;
@@ -180,26 +160,6 @@ __device__ void stage_weight_both(bf16_t *dst_s, int stride_s, bool permute_s, b
     }
 }
 
-__device__ __forceinline__ bf16x8 load8(const float *p) {
-    f32x4 a = *reinterpret_cast<const f32x4 *>(p);
-    f32x4 b = *reinterpret_cast<const f32x4 *>(p + 4);
-    bf16x8 r;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        r[j] = (bf16_t)a[j];
-        r[j + 4] = (bf16_t)b[j];
-    }
-    return r;
-}
-__device__ __forceinline__ bf16x8 load8(const bf16_t *p) { return *reinterpret_cast<const bf16x8 *>(p); }
-
-__device__ __forceinline__ bf16x8 zero8() {
-    bf16x8 r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = (bf16_t)0.0f;
-    return r;
-}
-
 // accumulator block -> two B fragments (k-steps 2*blk, 2*blk+1)
 __device__ __forceinline__ void pack_block(const f32x16 &acc, bf16x8 &lo, bf16x8 &hi) {
 #pragma unroll
@@ -242,29 +202,7 @@ __device__ __forceinline__ void store_block(T *row_ptr, int ch_base, int h, cons
     }
 }
 
-template <typename T>
-__device__ __forceinline__ void load_block(const T *row_ptr, int ch_base, int h, f32x16 &acc, int n_valid, bool vec_ok) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        int c0 = ch_base + 8 * g + 4 * h;
-        if (vec_ok && c0 + 3 < n_valid) {
-            if constexpr (sizeof(T) == 4) {
-                f32x4 v = *reinterpret_cast<const f32x4 *>(row_ptr + c0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[4 * g + j] = v[j];
-            } else {
-                bf16x4 v = *reinterpret_cast<const bf16x4 *>(row_ptr + c0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[4 * g + j] = (float)v[j];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[4 * g + j] = (c0 + j < n_valid) ? pag_ld(row_ptr + c0 + j) : 0.0f;
-        }
-    }
-}
-
-// two-phase variant of load_block: issue every load of a block first (raw registers), convert later, so that
+// load one 32-row block of sample m in two phases: issue every load of a block first (raw registers), convert later, so that
 // the compiler can keep all of a tile's loads in flight instead of waiting on each one before its conversion
 template <typename T> struct RawVec { typedef f32x4 type; };
 template <> struct RawVec<bf16_t> { typedef bf16x4 type; };
@@ -296,17 +234,6 @@ __device__ __forceinline__ void load_block_raw(const T *row_ptr, int ch_base, in
             raw[g] = v;
         }
     }
-}
-// whole 64-wide rows (hidden activations): no range checks at all
-template <typename T>
-__device__ __forceinline__ void load_block_full(const T *row_ptr, int ch_base, int h, f32x16 &acc) {
-    typename RawVec<T>::type raw[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) raw[g] = *reinterpret_cast<const typename RawVec<T>::type *>(row_ptr + ch_base + 8 * g + 4 * h);
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[4 * g + j] = (float)raw[g][j];
 }
 template <typename T>
 __device__ __forceinline__ void store_block_full(T *row_ptr, int ch_base, int h, const f32x16 &acc) {
@@ -595,12 +522,6 @@ __device__ __forceinline__ void relu_mask_pack_put(const bf16_t *Th, bf16_t *Tz,
         hb[2 * mb + 1] = __builtin_bit_cast(bf16x8, u32x4_t{zp[4], zp[5], zp[6], zp[7]});
     }
 }
-__device__ __forceinline__ void tw_get_raw(const bf16_t *T, int r, int h, bf16x4 (&raw)[2][4]) {
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) raw[mb][g] = *reinterpret_cast<const bf16x4 *>(T + tw_off(r, 8 * mb + 2 * g + h));
-}
 // MFMA 32x32x16 operand fragment with k = sample: lane (c = lane & 31, h) gets samples 16ks + 8h .. +7 of channel 32 blk + c
 __device__ __forceinline__ bf16x8 tw_frag(const bf16_t *T, int blk, int ks, int lane) {
     typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
@@ -613,7 +534,6 @@ __device__ __forceinline__ bf16x8 tw_frag(const bf16_t *T, int blk, int ks, int 
     u.v[1] = hi;
     return u.f;
 }
-constexpr int WG_SLAB_COLS_F = 96;      // = WG_SLAB_COLS (declared with the weight-gradient kernels below)
 template <int N, typename Fn>
 __device__ __forceinline__ void static_for(Fn &&f) {
     if constexpr (N > 0) {
@@ -2101,28 +2021,28 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void mlp_bwd_fused(BwdParams p) {
         for (int q4 = 0; q4 < 4; ++q4) sv[q4] = (reinterpret_cast<const f32x4 *>(red) + (bb * 4 + q4) * 64 + lane)[0];
         auto srcv = [&](int q) __attribute__((always_inline)) { return sv[q >> 2][q & 3]; };
         if constexpr (bb < BM) {
-            float *sl = p.slabs[NL - 1] + (int64_t)blockIdx.x * (OBL * 32) * WG_SLAB_COLS_F;
+            float *sl = p.slabs[NL - 1] + (int64_t)blockIdx.x * (OBL * 32) * WG_SLAB_COLS;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) sl[(32 * (bb >> 1) + rho(q, h)) * WG_SLAB_COLS_F + 32 * (bb & 1) + r] = srcv(q);
+            for (int q = 0; q < 16; ++q) sl[(32 * (bb >> 1) + rho(q, h)) * WG_SLAB_COLS + 32 * (bb & 1) + r] = srcv(q);
         } else if constexpr (bb < B0) {
-            float *sl = p.slabs[1] + (int64_t)blockIdx.x * 64 * WG_SLAB_COLS_F;
+            float *sl = p.slabs[1] + (int64_t)blockIdx.x * 64 * WG_SLAB_COLS;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) sl[(32 * ((bb - BM) >> 1) + rho(q, h)) * WG_SLAB_COLS_F + 32 * ((bb - BM) & 1) + r] = srcv(q);
+            for (int q = 0; q < 16; ++q) sl[(32 * ((bb - BM) >> 1) + rho(q, h)) * WG_SLAB_COLS + 32 * ((bb - BM) & 1) + r] = srcv(q);
         } else if constexpr (bb < NBLK - 1) {
             constexpr int ob = (bb - B0) >> 1, ib = (bb - B0) & 1;
-            float *sl = p.slabs[0] + (int64_t)blockIdx.x * 64 * WG_SLAB_COLS_F;
+            float *sl = p.slabs[0] + (int64_t)blockIdx.x * 64 * WG_SLAB_COLS;
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const float v = srcv(q);
-                sl[(32 * ob + rho(q, h)) * WG_SLAB_COLS_F + 32 * ib + r] = v;
-                if (ib == 1 && r == 31) sl[(32 * ob + rho(q, h)) * WG_SLAB_COLS_F + 64] = v;      // input column 63 (the ones column) = db of layer 0
+                sl[(32 * ob + rho(q, h)) * WG_SLAB_COLS + 32 * ib + r] = v;
+                if (ib == 1 && r == 31) sl[(32 * ob + rho(q, h)) * WG_SLAB_COLS + 64] = v;      // input column 63 (the ones column) = db of layer 0
             }
         } else {      // dbacc: column ob -> last layer's block ob; column OBL + ob -> middle layer's block ob
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const float v = srcv(q);
-                if (r < OBL) p.slabs[NL - 1][((int64_t)blockIdx.x * (OBL * 32) + 32 * r + rho(q, h)) * WG_SLAB_COLS_F + 64] = v;
-                if (NL == 3 && r >= OBL && r < OBL + 2) p.slabs[1][((int64_t)blockIdx.x * 64 + 32 * (r - OBL) + rho(q, h)) * WG_SLAB_COLS_F + 64] = v;
+                if (r < OBL) p.slabs[NL - 1][((int64_t)blockIdx.x * (OBL * 32) + 32 * r + rho(q, h)) * WG_SLAB_COLS + 64] = v;
+                if (NL == 3 && r >= OBL && r < OBL + 2) p.slabs[1][((int64_t)blockIdx.x * 64 + 32 * (r - OBL) + rho(q, h)) * WG_SLAB_COLS + 64] = v;
             }
         }
     });
@@ -2446,25 +2366,25 @@ __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
         if constexpr (bb < 4 || (bb >= 8 && bb < 10)) {               // output-layer blocks: rows = output channels
             constexpr bool S = bb >= 8;
             constexpr int ob = S ? 0 : (bb >> 1), ib = S ? (bb - 8) : (bb & 1);
-            float *sl = (S ? ps.slabs[1] + (int64_t)blockIdx.x * 32 * WG_SLAB_COLS_F : pi.slabs[1] + (int64_t)blockIdx.x * 64 * WG_SLAB_COLS_F);
+            float *sl = (S ? ps.slabs[1] + (int64_t)blockIdx.x * 32 * WG_SLAB_COLS : pi.slabs[1] + (int64_t)blockIdx.x * 64 * WG_SLAB_COLS);
 #pragma unroll
-            for (int q = 0; q < 16; ++q) sl[(32 * ob + rho(q, h)) * WG_SLAB_COLS_F + 32 * ib + r] = srcv(q);
+            for (int q = 0; q < 16; ++q) sl[(32 * ob + rho(q, h)) * WG_SLAB_COLS + 32 * ib + r] = srcv(q);
         } else if constexpr (bb < 14) {                               // layer-0 blocks; input column 63 (the ones column) = db of layer 0
             constexpr bool S = bb >= 10;
             constexpr int k = S ? bb - 10 : bb - 4, ob = k >> 1, ib = k & 1;
-            float *sl = (S ? ps.slabs[0] : pi.slabs[0]) + (int64_t)blockIdx.x * 64 * WG_SLAB_COLS_F;
+            float *sl = (S ? ps.slabs[0] : pi.slabs[0]) + (int64_t)blockIdx.x * 64 * WG_SLAB_COLS;
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const float v = srcv(q);
-                sl[(32 * ob + rho(q, h)) * WG_SLAB_COLS_F + 32 * ib + r] = v;
-                if (ib == 1 && r == 31) sl[(32 * ob + rho(q, h)) * WG_SLAB_COLS_F + 64] = v;
+                sl[(32 * ob + rho(q, h)) * WG_SLAB_COLS + 32 * ib + r] = v;
+                if (ib == 1 && r == 31) sl[(32 * ob + rho(q, h)) * WG_SLAB_COLS + 64] = v;
             }
         } else {      // dbacc: columns 0, 1 -> .i upper layer's blocks; column 2 -> .s output layer
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const float v = srcv(q);
-                if (r < 2) pi.slabs[1][((int64_t)blockIdx.x * 64 + 32 * r + rho(q, h)) * WG_SLAB_COLS_F + 64] = v;
-                if (r == 2) ps.slabs[1][((int64_t)blockIdx.x * 32 + rho(q, h)) * WG_SLAB_COLS_F + 64] = v;
+                if (r < 2) pi.slabs[1][((int64_t)blockIdx.x * 64 + 32 * r + rho(q, h)) * WG_SLAB_COLS + 64] = v;
+                if (r == 2) ps.slabs[1][((int64_t)blockIdx.x * 32 + rho(q, h)) * WG_SLAB_COLS + 64] = v;
             }
         }
     });
@@ -2801,13 +2721,13 @@ __global__ __launch_bounds__((OB + 1) * 64) void mlp_bwd_wide_blocks(BwdParams p
     }
     // ---- every block wave owns its 32 rows of the workgroup's slab [OB*32][96]: cols 0..63 dW_L, col 64 db
     {
-        float *sl = p.slabs[0] + (int64_t)blockIdx.x * (OB * 32) * WG_SLAB_COLS_F;
+        float *sl = p.slabs[0] + (int64_t)blockIdx.x * (OB * 32) * WG_SLAB_COLS;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const int row = 32 * ob + rho(q, h);
-            sl[row * WG_SLAB_COLS_F + r] = aw[0][q];
-            sl[row * WG_SLAB_COLS_F + 32 + r] = aw[1][q];
-            if (r == 0) sl[row * WG_SLAB_COLS_F + 64] = dbacc[q];
+            sl[row * WG_SLAB_COLS + r] = aw[0][q];
+            sl[row * WG_SLAB_COLS + 32 + r] = aw[1][q];
+            if (r == 0) sl[row * WG_SLAB_COLS + 64] = dbacc[q];
         }
     }
 }
@@ -3089,10 +3009,19 @@ struct HeadCompParams {
     float *out;                // [N,out_dim]
 };
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, true));
-}
+// One step of a sum over lanes on 16 values at once: v[q] += v[q] of the lane that the DPP control `ctl` names, for float v[16].  Written as one asm
+// block of 16 v_add_f32_dpp: left to itself the compiler pairs the values into v_pk_add_f32 fed by two DPP moves each - 1.5 instructions per value
+// and step instead of 1.  Inside a block every DPP source was written 16 instructions earlier.
+#define PAG_DPP_ADD16(v, ctl)                                                                                                           \
+    asm("s_nop 1\n\t"                                                                                                                   \
+        "v_add_f32_dpp %0, %0, %0 " ctl "\n\tv_add_f32_dpp %1, %1, %1 " ctl "\n\tv_add_f32_dpp %2, %2, %2 " ctl "\n\t"                  \
+        "v_add_f32_dpp %3, %3, %3 " ctl "\n\tv_add_f32_dpp %4, %4, %4 " ctl "\n\tv_add_f32_dpp %5, %5, %5 " ctl "\n\t"                  \
+        "v_add_f32_dpp %6, %6, %6 " ctl "\n\tv_add_f32_dpp %7, %7, %7 " ctl "\n\tv_add_f32_dpp %8, %8, %8 " ctl "\n\t"                  \
+        "v_add_f32_dpp %9, %9, %9 " ctl "\n\tv_add_f32_dpp %10, %10, %10 " ctl "\n\tv_add_f32_dpp %11, %11, %11 " ctl "\n\t"            \
+        "v_add_f32_dpp %12, %12, %12 " ctl "\n\tv_add_f32_dpp %13, %13, %13 " ctl "\n\tv_add_f32_dpp %14, %14, %14 " ctl "\n\t"         \
+        "v_add_f32_dpp %15, %15, %15 " ctl                                                                                              \
+        : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]),                   \
+          "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]))
 
 // OBT = 7 (193 - 224 outputs: the 200-instance head): the block loop is compile-time, so the output blocks' MFMA chains are issued one block
 // AHEAD of the exponentials that consume them (the run-time `ob < OB` guards of the generic form, OBT = 0, end a scheduling region per block
@@ -3196,27 +3125,14 @@ __global__ __launch_bounds__(256, 2) void head_composite_fwd_kernel(HeadCompPara
             if (ob < OB) {
                 // step by step over all 16 values: consecutive DPP adds are independent (a chain per value would put two wait states
                 // between every pair - 459 s_nop in the first listing of this epilogue)
-                // (written as asm blocks of 16 v_add_f32_dpp: left to itself the compiler pairs the values into v_pk_add_f32 fed by two DPP moves
-                // each - 1.5 instructions per value and step instead of 1.  Inside a block every DPP source was written 16 instructions earlier.)
                 float v[16];
 #pragma unroll
                 for (int q = 0; q < 16; ++q) v[q] = acc[ob][q];
-#define PAG_DPP_ADD16(ctl)                                                                                                         \
-                asm("s_nop 1\n\t"                                                                                                   \
-                    "v_add_f32_dpp %0, %0, %0 " ctl "\n\tv_add_f32_dpp %1, %1, %1 " ctl "\n\tv_add_f32_dpp %2, %2, %2 " ctl "\n\t"   \
-                    "v_add_f32_dpp %3, %3, %3 " ctl "\n\tv_add_f32_dpp %4, %4, %4 " ctl "\n\tv_add_f32_dpp %5, %5, %5 " ctl "\n\t"   \
-                    "v_add_f32_dpp %6, %6, %6 " ctl "\n\tv_add_f32_dpp %7, %7, %7 " ctl "\n\tv_add_f32_dpp %8, %8, %8 " ctl "\n\t"   \
-                    "v_add_f32_dpp %9, %9, %9 " ctl "\n\tv_add_f32_dpp %10, %10, %10 " ctl "\n\tv_add_f32_dpp %11, %11, %11 " ctl "\n\t" \
-                    "v_add_f32_dpp %12, %12, %12 " ctl "\n\tv_add_f32_dpp %13, %13, %13 " ctl "\n\tv_add_f32_dpp %14, %14, %14 " ctl "\n\t" \
-                    "v_add_f32_dpp %15, %15, %15 " ctl                                                                             \
-                    : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]),     \
-                      "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]))
-                PAG_DPP_ADD16("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1");
-                PAG_DPP_ADD16("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1");
-                PAG_DPP_ADD16("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1");
-                PAG_DPP_ADD16("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1");      // lane 15 of every 16-lane row holds the row sum
-                PAG_DPP_ADD16("row_bcast:15 row_mask:0xa bank_mask:0xf");                // into rows 1, 3: lanes 31 / 63 hold the half's sum
-#undef PAG_DPP_ADD16
+                PAG_DPP_ADD16(v, "row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+                PAG_DPP_ADD16(v, "row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+                PAG_DPP_ADD16(v, "row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+                PAG_DPP_ADD16(v, "row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1");      // lane 15 of every 16-lane row holds the row sum
+                PAG_DPP_ADD16(v, "row_bcast:15 row_mask:0xa bank_mask:0xf");                // into rows 1, 3: lanes 31 / 63 hold the half's sum
                 if (r == 31) {
 #pragma unroll
                     for (int q = 0; q < 16; ++q) red[wave * OB * 32 + 32 * ob + rho(q, h)] = v[q];
@@ -3417,22 +3333,11 @@ __global__ __launch_bounds__(256, 1) void head_fwd_once_kernel(FwdParams p, Head
             float v[16];
 #pragma unroll
             for (int q = 0; q < 16; ++q) v[q] = acc[ob][q];
-#define PAG_DPP_ADD16(ctl)                                                                                                         \
-            asm("s_nop 1\n\t"                                                                                                   \
-                "v_add_f32_dpp %0, %0, %0 " ctl "\n\tv_add_f32_dpp %1, %1, %1 " ctl "\n\tv_add_f32_dpp %2, %2, %2 " ctl "\n\t"   \
-                "v_add_f32_dpp %3, %3, %3 " ctl "\n\tv_add_f32_dpp %4, %4, %4 " ctl "\n\tv_add_f32_dpp %5, %5, %5 " ctl "\n\t"   \
-                "v_add_f32_dpp %6, %6, %6 " ctl "\n\tv_add_f32_dpp %7, %7, %7 " ctl "\n\tv_add_f32_dpp %8, %8, %8 " ctl "\n\t"   \
-                "v_add_f32_dpp %9, %9, %9 " ctl "\n\tv_add_f32_dpp %10, %10, %10 " ctl "\n\tv_add_f32_dpp %11, %11, %11 " ctl "\n\t" \
-                "v_add_f32_dpp %12, %12, %12 " ctl "\n\tv_add_f32_dpp %13, %13, %13 " ctl "\n\tv_add_f32_dpp %14, %14, %14 " ctl "\n\t" \
-                "v_add_f32_dpp %15, %15, %15 " ctl                                                                             \
-                : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]),     \
-                  "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]))
-            PAG_DPP_ADD16("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1");
-            PAG_DPP_ADD16("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1");
-            PAG_DPP_ADD16("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1");
-            PAG_DPP_ADD16("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1");
-            PAG_DPP_ADD16("row_bcast:15 row_mask:0xa bank_mask:0xf");
-#undef PAG_DPP_ADD16
+            PAG_DPP_ADD16(v, "row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+            PAG_DPP_ADD16(v, "row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+            PAG_DPP_ADD16(v, "row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+            PAG_DPP_ADD16(v, "row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+            PAG_DPP_ADD16(v, "row_bcast:15 row_mask:0xa bank_mask:0xf");
             if (r == 31) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) red[wave * OB * 32 + 32 * ob + rho(q, h)] = v[q];
@@ -3466,75 +3371,10 @@ __global__ __launch_bounds__(256, 1) void head_fwd_once_kernel(FwdParams p, Head
     }
 }
 
-// ---------------------------------------------------------- one affine map of the XCD8 features (decoder without activations)
-// pc_nerf/panoptic_dd_nef.py:49-56 `decoder_delta_density` has no activation: any number of its layers compose to one [n_out, in_dim]
-// matrix (n_out = 1).  out[m][o] = b[o] + sum_p W[o][col(p)] x[p / 8][m][p % 8] on the encoders' bf16 [8][M][8] layout, one lane per
-// sample, 128 bytes in / 4 n_out bytes out per sample; backward-data is the transposed product, written back in the same layout.
-// (Weight gradients: pag_mlp_wgrad_batch with the upstream gradient as `dz`.)
-constexpr int AFF_MAX_OUT = 8;
-__global__ __launch_bounds__(256) void affine_xcd8_fwd_kernel(const bf16_t *__restrict__ x8, int64_t M, int grp_L, int grp_F, const float *__restrict__ W,
-                                                              const float *__restrict__ b, int n_out, int in_dim, float *__restrict__ out) {
-    __shared__ float Ws[AFF_MAX_OUT][64];
-    for (int e = threadIdx.x; e < n_out * 64; e += blockDim.x) {
-        const int o = e >> 6, col = grp_col(e & 63, grp_L, grp_F);
-        Ws[o][e & 63] = (col >= 0 && col < in_dim) ? W[(int64_t)o * in_dim + col] : 0.0f;
-    }
-    __syncthreads();
-    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (m >= M) return;
-    float acc[AFF_MAX_OUT];
-#pragma unroll
-    for (int o = 0; o < AFF_MAX_OUT; ++o) acc[o] = o < n_out ? b[o] : 0.0f;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8 *>(x8 + ((int64_t)g * M + m) * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float xv = (float)v[e];
-#pragma unroll
-            for (int o = 0; o < AFF_MAX_OUT; ++o)
-                if (o < n_out) acc[o] = fmaf(xv, Ws[o][8 * g + e], acc[o]);
-        }
-    }
-    for (int o = 0; o < n_out; ++o) out[m * n_out + o] = acc[o];
-}
-__global__ __launch_bounds__(256) void affine_xcd8_bwd_dx_kernel(const float *__restrict__ gout, int64_t M, int grp_L, int grp_F, const float *__restrict__ W,
-                                                                 int n_out, int in_dim, bf16_t *__restrict__ dx8) {
-    __shared__ float Ws[AFF_MAX_OUT][64];
-    for (int e = threadIdx.x; e < n_out * 64; e += blockDim.x) {
-        const int o = e >> 6, col = grp_col(e & 63, grp_L, grp_F);
-        Ws[o][e & 63] = (col >= 0 && col < in_dim) ? W[(int64_t)o * in_dim + col] : 0.0f;
-    }
-    __syncthreads();
-    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (m >= M) return;
-    float g[AFF_MAX_OUT];
-#pragma unroll
-    for (int o = 0; o < AFF_MAX_OUT; ++o) g[o] = o < n_out ? gout[m * n_out + o] : 0.0f;
-#pragma unroll
-    for (int gp = 0; gp < 8; ++gp) {
-        bf16x8 v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float a = 0.0f;
-#pragma unroll
-            for (int o = 0; o < AFF_MAX_OUT; ++o)
-                if (o < n_out) a = fmaf(g[o], Ws[o][8 * gp + e], a);
-            v[e] = (bf16_t)a;
-        }
-        *reinterpret_cast<bf16x8 *>(dx8 + ((int64_t)gp * M + m) * 8) = v;
-    }
-}
-
 // ------------------------------------------------------------------------------------ FP32 parity path
 // One lane per sample.  Weights transposed in LDS ([k][j]) so the 64 outputs of a layer are 16
 // broadcast ds_read_b128; the per-sample activation column lives in LDS ([k][lane]).
 constexpr int PT = 128;   // threads per block on this path
-
-struct F32Fwd {
-    FwdParams p;
-    float *hsave32[2];
-};
 
 __device__ void stage_f32_t(float *dst, const float *W, int n_out, int n_in, int out_pad) {   // dst[k][out_pad]
     for (int e = threadIdx.x; e < n_in * out_pad; e += blockDim.x) {
@@ -3687,189 +3527,6 @@ __global__ __launch_bounds__(PT) void mlp_bwd_f32(BwdParams p, int n_layers) {
     }
 }
 
-
-// ------------------------------------------------------------------------------- weight gradients
-// dW[out][in] = sum_m dz[m][out] * a[m][in]  and  db[out] = sum_m dz[m][out]: a GEMM whose reduction
-// runs over the M ~ 2e6 samples with both operands K-major in memory, which BLAS libraries handle
-// badly (2.5 ms per layer measured).  Here each workgroup walks 64-sample chunks: the [64 x n_out] dz
-// tile and the [64 x n_in] input tile are transposed into LDS (lane = sample, so the ds_write_b16
-// stores are conflict-free), every wave owns up to 6 of the 32x32 (out-block, in-block) pairs and
-// feeds them with ds_read_b128 fragments; an extra in-block whose B fragment is the constant
-// "1 in column 0" yields db for free.  Partial sums are written as per-workgroup fp32 slabs
-// [blocks][OB*32][96] (cols 0..63 = dW, col 64 = db) and summed by the caller - deterministic, no atomics.
-struct WgradParams {
-    const bf16_t *dz;
-    int dz_cols, n_out;
-    const void *a1;
-    int k1;
-    const float *a2;
-    int k2p;
-    const int32_t *a2_index;
-    int n_in;
-    float *slabs;
-    int64_t M;
-    int a1_grouped;        // a1 is bf16 [8][M][8] (PAG_LAYOUT_XCD8); slab columns are then staged positions
-};
-constexpr int WG_MAX_BATCH = 6;
-struct WgradBatch {
-    WgradParams p[WG_MAX_BATCH];
-};
-constexpr int WG_RS = 72;       // LDS row stride (bf16) of the transposed tiles: 64 samples + 8 pad
-constexpr int WG_SLAB_COLS = 96;
-
-template <typename A1T, int APW /* accumulator blocks per wave */, int NWV = 4 /* waves per workgroup */>
-// narrow variant (APW 2, 4 waves): asking for 5 waves per SIMD keeps every accumulator in VGPRs (no AGPR copies) under 102
-// registers.  Wide layers (up to 224 outputs = 21 block pairs): 8 waves x 3 pairs instead of 4 x 6 - 48 accumulator
-// registers per wave leave room for the prefetch and for 4 waves per SIMD (the 4 x 6 form ran 2 waves per SIMD, no prefetch).
-__global__ __launch_bounds__(NWV * 64, (APW == 2 ? 5 : (APW == 3 ? 4 : 1))) void mlp_wgrad_kernel(WgradBatch batch) {
-    const WgradParams &p = batch.p[blockIdx.y];       // blockIdx.y = layer: the layers of one decoder share a launch
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int OB = (p.n_out + 31) / 32;
-    const int IB = (p.n_in + 31) / 32;                 // 1 or 2
-    bf16_t *Zt = reinterpret_cast<bf16_t *>(smem);      // [OB*32][WG_RS]
-    bf16_t *At = Zt + OB * 32 * WG_RS;                  // [IB*32][WG_RS]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int npairs = OB * (IB + 1);
-    f32x16 acc[APW];
-#pragma unroll
-    for (int i = 0; i < APW; ++i)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[i][q] = 0.0f;
-    bf16x8 ones;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ones[j] = (bf16_t)(r == 0 ? 1.0f : 0.0f);
-    const A1T *a1 = reinterpret_cast<const A1T *>(p.a1);
-    const bool dz_vec = (p.dz_cols % 8) == 0 && (p.n_out % 8) == 0;
-    const int64_t nchunks = (p.M + 63) / 64;
-    // global -> register fetch of one 8-column piece of this lane's sample row (dz tile / input tile)
-    auto fetch_z = [&](int64_t chunk, int cg) __attribute__((always_inline)) {
-        const int64_t m = chunk * 64 + lane;
-        const bool live = m < p.M;
-        const int64_t mc = live ? m : p.M - 1;
-        const int c0 = 8 * cg;
-        bf16x8 v = zero8();
-        if (live && c0 < p.n_out) {      // n_out <= dz_cols: dz may point at a band of columns of a wider row
-            if (dz_vec) {
-                v = load8(p.dz + mc * p.dz_cols + c0);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (c0 + j < p.n_out) v[j] = p.dz[mc * p.dz_cols + c0 + j];
-            }
-        }
-        return v;
-    };
-    auto fetch_a = [&](int64_t chunk, int cg) __attribute__((always_inline)) {
-        const int64_t m = chunk * 64 + lane;
-        const bool live = m < p.M;
-        const int64_t mc = live ? m : p.M - 1;
-        const int c0 = 8 * cg;
-        bf16x8 v = zero8();
-        if (live && p.a1_grouped)
-            v = load8(reinterpret_cast<const bf16_t *>(p.a1) + ((int64_t)cg * p.M + mc) * 8);
-        else if (live && c0 < p.k1)
-            v = load8(a1 + mc * p.k1 + c0);
-        else if (live && p.a2 && c0 < p.k1 + p.k2p)
-            v = load8(p.a2 + (int64_t)p.a2_index[mc] * p.k2p + (c0 - p.k1));
-        return v;
-    };
-    // APW == 2 (<= 64 x 64 layers, 76 VGPRs): the next chunk's four 16-byte pieces are fetched into registers while the
-    // current chunk goes through LDS and the MFMAs - the kernel sat waiting on memory 77 % of its wave cycles (SQ_WAIT_ANY)
-    // with nothing in flight between the two barriers.  The wide variant has no registers to spare for this.
-    constexpr bool PF = APW <= 3;
-    constexpr int ZG = (NWV == 8) ? 4 : 2, AG = (NWV == 8) ? 1 : 2;      // 16-byte pieces per wave: dz (<= 224 / 64 cols), input (64 cols)
-    bf16x8 pz[ZG], pa[AG];
-    if constexpr (PF) {
-#pragma unroll
-        for (int i = 0; i < ZG; ++i) {
-            const int cg = wave + NWV * i;
-            pz[i] = (blockIdx.x < nchunks && cg < OB * 4) ? fetch_z(blockIdx.x, cg) : zero8();
-        }
-#pragma unroll
-        for (int i = 0; i < AG; ++i) {
-            const int cg = wave + NWV * i;
-            pa[i] = (blockIdx.x < nchunks && cg < IB * 4) ? fetch_a(blockIdx.x, cg) : zero8();
-        }
-    }
-    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        // ---- dz tile, transposed: Zt[col][sample]
-        if constexpr (PF) {
-#pragma unroll
-            for (int i = 0; i < ZG; ++i) {
-                const int cg = wave + NWV * i, c0 = 8 * cg;
-                if (cg < OB * 4) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) Zt[(c0 + j) * WG_RS + lane] = pz[i][j];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < AG; ++i) {
-                const int cg = wave + NWV * i, c0 = 8 * cg;
-                if (cg < IB * 4) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) At[(c0 + j) * WG_RS + lane] = (c0 + j < p.n_in) ? pa[i][j] : (bf16_t)0.0f;
-                }
-            }
-        } else {
-            for (int cg = wave; cg < OB * 4; cg += NWV) {
-                const int c0 = 8 * cg;
-                const bf16x8 v = fetch_z(chunk, cg);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) Zt[(c0 + j) * WG_RS + lane] = v[j];
-            }
-            // ---- input tile, transposed: At[col][sample]
-            for (int cg = wave; cg < IB * 4; cg += NWV) {
-                const int c0 = 8 * cg;
-                const bf16x8 v = fetch_a(chunk, cg);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) At[(c0 + j) * WG_RS + lane] = (c0 + j < p.n_in) ? v[j] : (bf16_t)0.0f;
-            }
-        }
-        __syncthreads();
-        if constexpr (PF) {
-            const int64_t next = chunk + gridDim.x;
-            if (next < nchunks) {
-#pragma unroll
-                for (int i = 0; i < ZG; ++i) {
-                    const int cg = wave + NWV * i;
-                    if (cg < OB * 4) pz[i] = fetch_z(next, cg);
-                }
-#pragma unroll
-                for (int i = 0; i < AG; ++i) {
-                    const int cg = wave + NWV * i;
-                    if (cg < IB * 4) pa[i] = fetch_a(next, cg);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < APW; ++i) {
-            const int pr = wave + NWV * i;
-            if (pr < npairs) {
-                const int ob = pr / (IB + 1), ib = pr - ob * (IB + 1);
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    bf16x8 a = *reinterpret_cast<const bf16x8 *>(Zt + (32 * ob + r) * WG_RS + 16 * ks + 8 * h);
-                    bf16x8 b = ones;
-                    if (ib < IB) b = *reinterpret_cast<const bf16x8 *>(At + (32 * ib + r) * WG_RS + 16 * ks + 8 * h);
-                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[i], 0, 0, 0);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    float *slab = p.slabs + (int64_t)blockIdx.x * OB * 32 * WG_SLAB_COLS;
-#pragma unroll
-    for (int i = 0; i < APW; ++i) {
-        const int pr = wave + NWV * i;
-        if (pr < npairs) {
-            const int ob = pr / (IB + 1), ib = pr - ob * (IB + 1);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) slab[(32 * ob + rho(q, h)) * WG_SLAB_COLS + (ib < IB ? 32 * ib : 64) + r] = acc[i][q];
-        }
-    }
-}
-
 inline unsigned mlp_grid(int64_t M) {
     int64_t tiles = (M + 31) / 32;
     int64_t blocks = (tiles + 3) / 4;
@@ -3877,27 +3534,106 @@ inline unsigned mlp_grid(int64_t M) {
     return (unsigned)(blocks < cap ? (blocks > 0 ? blocks : 1) : cap);
 }
 
-}  // namespace
+// Kernels that ask for more than 64 KiB of dynamic LDS opt in once per kernel and process (gfx950 has 160 KiB per workgroup)
+constexpr int LDS_MAX_BYTES = 160 * 1024;
+template <auto Kernel>
+void raise_lds_limit(int bytes = LDS_MAX_BYTES) {
+    static const hipError_t once = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    (void)once;
+}
 
-#define MLP_FWD_LAUNCH(X1T, OutT, NL_, OBM)                                                            \
-    hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL_, OBM>), dim3(mlp_grid(M)), dim3(256), lds, st, p)
-#define MLP_FWD_OB(X1T, OutT, NL_)                                   \
-    do {                                                             \
-        if (OB <= 1) MLP_FWD_LAUNCH(X1T, OutT, NL_, 1);              \
-        else if (OB <= 2) MLP_FWD_LAUNCH(X1T, OutT, NL_, 2);         \
-        else if (OB <= 4) MLP_FWD_LAUNCH(X1T, OutT, NL_, 4);         \
-        else MLP_FWD_LAUNCH(X1T, OutT, NL_, 7);                      \
-    } while (0)
-#define MLP_FWD_NL(X1T, OutT)                                        \
-    do {                                                             \
-        if (a->n_layers == 2) MLP_FWD_OB(X1T, OutT, 2);              \
-        else MLP_FWD_OB(X1T, OutT, 3);                               \
-    } while (0)
+// the wide softmax head whose forward writes softmax statistics and the last hidden layer instead of its [M, out_dim] output (mlp_fwd_wide_stats, head_fwd_once_kernel)
+bool is_wide_stats_head(const pag_mlp_fwd_args *a) {
+    return a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && a->x1_layout == PAG_LAYOUT_XCD8 && !a->out && a->n_layers == 3 && a->softmax_stats &&
+           a->out_act == PAG_ACT_SOFTMAX && a->out_dim > 192 && a->out_dim <= 224 && a->hidden_save[1];
+}
+
+// the companion narrow head of a wide head (args->pair, validated by pag_mlp_fwd_pair_supported)
+void set_pair_head(FwdParams &p, const pag_mlp_fwd_args *b) {
+    p.W2[0] = b->W[0];
+    p.W2[1] = b->W[1];
+    p.b2[0] = b->b[0];
+    p.b2[1] = b->b[1];
+    p.out2 = b->out;
+    p.out2_dim = b->out_dim;
+}
+
+template <typename X1T, typename OutT, int NL>
+void launch_fwd_mfma_nl(const FwdParams &p, int OB, size_t lds, hipStream_t st) {
+    const dim3 grid(mlp_grid(p.M)), block(256);
+    if (OB <= 1) hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 1>), grid, block, lds, st, p);
+    else if (OB <= 2) hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 2>), grid, block, lds, st, p);
+    else if (OB <= 4) hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 4>), grid, block, lds, st, p);
+    else hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 7>), grid, block, lds, st, p);
+}
+template <typename X1T, typename OutT>
+void launch_fwd_mfma(const FwdParams &p, int n_layers, int OB, size_t lds, hipStream_t st) {
+    if (n_layers == 2) launch_fwd_mfma_nl<X1T, OutT, 2>(p, OB, lds, st);
+    else launch_fwd_mfma_nl<X1T, OutT, 3>(p, OB, lds, st);
+}
+
+template <typename OutT, typename DxT, int NL>
+void launch_bwd_mfma_nl(const BwdParams &p, int OB, size_t lds, hipStream_t st) {
+    const dim3 grid(mlp_grid(p.M)), block(256);
+    if (OB <= 1) hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 1>), grid, block, lds, st, p);
+    else if (OB <= 2) hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 2>), grid, block, lds, st, p);
+    else if (OB <= 4) hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 4>), grid, block, lds, st, p);
+    else hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 7>), grid, block, lds, st, p);
+}
+template <typename OutT, typename DxT>
+void launch_bwd_mfma(const BwdParams &p, int n_layers, int OB, size_t lds, hipStream_t st) {
+    if (n_layers == 2) launch_bwd_mfma_nl<OutT, DxT, 2>(p, OB, lds, st);
+    else launch_bwd_mfma_nl<OutT, DxT, 3>(p, OB, lds, st);
+}
+
+template <typename OutT, typename DxT>
+void launch_bwd_f32(const BwdParams &p, int n_layers, dim3 grid, size_t lds, hipStream_t st) {
+    raise_lds_limit<mlp_bwd_f32<OutT, DxT>>((int)lds);      // 128 KiB
+    hipLaunchKernelGGL((mlp_bwd_f32<OutT, DxT>), grid, dim3(PT), lds, st, p, n_layers);
+}
+
+template <int NL, int KIND, bool DXACC, int OBL = 1, int DZ0 = 0>
+void launch_bwd_fused(const BwdParams &p, unsigned grid, size_t lds, hipStream_t st) {
+    raise_lds_limit<mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>>();
+    hipLaunchKernelGGL((mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>), dim3(grid), dim3(256), lds, st, p);
+}
+template <int NL>
+void launch_bwd_fused_kind(const BwdParams &p, int kind, bool acc, int dz0, unsigned grid, size_t lds, hipStream_t st) {
+    if (kind == 0) launch_bwd_fused<NL, 0, false>(p, grid, lds, st);
+    else if (kind == 1 && dz0 == 2) launch_bwd_fused<NL, 1, false, 1, 2>(p, grid, lds + 4 * 64 * sizeof(int), st);
+    else if (kind == 1 && dz0 == 1) launch_bwd_fused<NL, 1, false, 1, 1>(p, grid, lds, st);
+    else if (kind == 1) launch_bwd_fused<NL, 1, false>(p, grid, lds, st);
+    else if (acc) launch_bwd_fused<NL, 2, true>(p, grid, lds, st);
+    else launch_bwd_fused<NL, 2, false>(p, grid, lds, st);
+}
+
+// stage A of the fused wide-head backward
+void launch_bwd_wide_blocks(const BwdParams &p, unsigned grid, hipStream_t st) {
+    constexpr int OBW = 7;
+    const size_t lds = (size_t)(64 * (OBW * 32 + 8) + OBW * 32 * RS) * sizeof(bf16_t) + (size_t)OBW * 32 * sizeof(float) +
+                       (size_t)(5 + OBW) * TW_ELEMS * sizeof(bf16_t) + (size_t)2 * WB_RMAX * WR_RS * sizeof(float) +
+                       (size_t)2 * OBW * 64 * sizeof(float) + (size_t)2 * OBW * 2 * 64 * 16;
+    raise_lds_limit<mlp_bwd_wide_blocks<OBW>>();
+    hipLaunchKernelGGL((mlp_bwd_wide_blocks<OBW>), dim3(grid), dim3((OBW + 1) * 64), lds, st, p);
+}
+
+template <typename DxT, int NL>
+void launch_bwd_wide_mfma(const BwdParams &p, hipStream_t st) {
+    constexpr int NW = WIDE_BWD_WAVES;
+    const int OB = (p.out_dim + 31) / 32;
+    const size_t lds = (size_t)(64 * (OB * 32 + 8) + OB * 32 * RS + (NL == 3 ? 64 * RS : 0) + 64 * RS) * sizeof(bf16_t) +
+                       (size_t)OB * 32 * sizeof(float) + (size_t)NW * ST_BYTES + (size_t)NW * OB * 32 * sizeof(float);
+    const int64_t tiles = (p.M + 31) / 32;
+    const unsigned grid = (unsigned)std::min<int64_t>((tiles + NW - 1) / NW, 256);      // one workgroup per CU, tiles grid-strided
+    raise_lds_limit<mlp_bwd_wide_mfma<DxT, NL, NW>>();
+    hipLaunchKernelGGL((mlp_bwd_wide_mfma<DxT, NL, NW>), dim3(grid), dim3(NW * 64), lds, st, p);
+}
+
+}  // namespace
 
 extern "C" int pag_mlp_fwd_pair_supported(const pag_mlp_fwd_args *a, const pag_mlp_fwd_args *b) {
     if (!a || !b || b->pair) return 0;
-    const bool wide = a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && a->x1_layout == PAG_LAYOUT_XCD8 && !a->out && a->n_layers == 3 &&
-                      a->softmax_stats && a->out_act == PAG_ACT_SOFTMAX && a->out_dim > 192 && a->out_dim <= 224 && a->hidden_save[1] && !a->hidden_save[0];
+    const bool wide = is_wide_stats_head(a) && !a->hidden_save[0];
     const bool narrow = b->mode == PAG_MLP_MFMA_BF16 && b->x1 == a->x1 && b->x1_dtype == PAG_BF16 && b->x1_layout == PAG_LAYOUT_XCD8 && b->x1_levels == a->x1_levels &&
                         b->x1_feats == a->x1_feats && b->in_dim == a->in_dim && b->n_layers == 2 && b->out && b->out_dtype == PAG_BF16 &&
                         b->out_act == PAG_ACT_SOFTMAX && b->out_dim >= 1 && b->out_dim <= 8 && !b->hidden_save[0] && !b->hidden_save[1] && !b->x2 &&
@@ -3920,8 +3656,7 @@ extern "C" int pag_mlp_fwd_producer_supported(const pag_mlp_fwd_args *a, const p
 
 extern "C" int pag_mlp_fwd_composite_supported(const pag_mlp_fwd_args *a, int64_t M) {
     if (!a || M < 1 || M > PAG_MLP_FUSED_WIDE_MAX_M) return 0;
-    const bool wide = a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && a->x1_layout == PAG_LAYOUT_XCD8 && !a->out && a->n_layers == 3 &&
-                      a->softmax_stats && a->out_act == PAG_ACT_SOFTMAX && a->out_dim > 192 && a->out_dim <= 224 && a->hidden_save[1] && !a->hidden_save[0];
+    const bool wide = is_wide_stats_head(a) && !a->hidden_save[0];
     return wide && (!a->pair || pag_mlp_fwd_pair_supported(a, a->pair) == 1) ? 1 : 0;
 }
 
@@ -3990,17 +3725,11 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
                  a->out_dim <= 4 && a->x1_col0_relu)
             kind = 1;
         else if (grp && a->out && a->out_dtype == PAG_BF16 && a->out_act == PAG_ACT_SOFTMAX && a->out_dim <= 8) kind = 2;
-        else if (grp && !a->out && a->n_layers == 3 && p.stats && a->out_act == PAG_ACT_SOFTMAX && a->out_dim > 192 && a->hidden_save[1]) kind = 3;
+        else if (grp && is_wide_stats_head(a)) kind = 3;
         PAG_CHECK_ARG(!a->pair || (kind == 3 && pag_mlp_fwd_pair_supported(a, a->pair) == 1), "pag_mlp_fwd: pair is not supported for these arguments (pag_mlp_fwd_pair_supported)");
         PAG_CHECK_ARG(!a->composite || kind == 3, "pag_mlp_fwd: composite rides only in the statistics-only wide softmax head (pag_mlp_fwd_composite_supported)");
         if (kind == 3) {
-            static bool attr = false;
-            if (!attr) {
-                hipFuncSetAttribute((const void *)mlp_fwd_wide_stats<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                hipFuncSetAttribute((const void *)mlp_fwd_wide_stats<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                hipFuncSetAttribute((const void *)mlp_fwd_wide_stats<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr = true;
-            }
+            if (a->pair) set_pair_head(p, a->pair);
             if (a->composite) {      // decoder + per-ray weighted sum in one pass over the logits (head_fwd_once_kernel)
                 const pag_head_composite_args *hc = a->composite;
                 PAG_CHECK_ARG(hc->P >= 0 && (hc->P == 0 || (hc->pack_start && hc->ray_of_pack && hc->weights && hc->alpha && hc->out)),
@@ -4009,50 +3738,38 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
                 if (hc->P == 0) return PAG_OK;
                 HeadCompParams c{hc->pack_start, hc->ray_of_pack, hc->P, nullptr, nullptr, nullptr, a->out_dim, nullptr, 0, hc->weights, hc->alpha, hc->out};
                 c.per_wave = ((hc->n_samples > 0 && hc->n_samples < 160 * hc->P) || hc->P >= HC_PER_WAVE_P) ? 1 : 0;
-                static bool attr_once = false;
-                if (!attr_once) {
-                    hipFuncSetAttribute((const void *)head_fwd_once_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    hipFuncSetAttribute((const void *)head_fwd_once_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    attr_once = true;
-                }
                 constexpr int HEAD_ONCE_GRID = 256;
                 const unsigned grid = (unsigned)std::min<int64_t>(c.per_wave ? (hc->P + 3) / 4 : hc->P, HEAD_ONCE_GRID);
                 if (a->pair) {
-                    const pag_mlp_fwd_args *b = a->pair;
-                    p.W2[0] = b->W[0];
-                    p.W2[1] = b->W[1];
-                    p.b2[0] = b->b[0];
-                    p.b2[1] = b->b[1];
-                    p.out2 = b->out;
-                    p.out2_dim = b->out_dim;
                     const size_t lds = (size_t)(128 + 224 + 96) * RS * sizeof(bf16_t) + (size_t)(128 + 224 + 96 + 4 * 224) * sizeof(float) + 4 * ST_BYTES;
+                    raise_lds_limit<head_fwd_once_kernel<true>>();
                     hipLaunchKernelGGL((head_fwd_once_kernel<true>), dim3(grid), dim3(256), lds, st, p, c);
                 } else {
                     const size_t lds = (size_t)(128 + 224) * RS * sizeof(bf16_t) + (size_t)(128 + 224 + 4 * 224) * sizeof(float) + 4 * ST_BYTES;
+                    raise_lds_limit<head_fwd_once_kernel<false>>();
                     hipLaunchKernelGGL((head_fwd_once_kernel<false>), dim3(grid), dim3(256), lds, st, p, c);
                 }
                 PAG_CHECK_LAUNCH("pag_mlp_fwd (wide head, decoder + per-ray sum)");
                 return PAG_OK;
             }
             if (a->pair) {
-                const pag_mlp_fwd_args *b = a->pair;
-                p.W2[0] = b->W[0];
-                p.W2[1] = b->W[1];
-                p.b2[0] = b->b[0];
-                p.b2[1] = b->b[1];
-                p.out2 = b->out;
-                p.out2_dim = b->out_dim;
                 constexpr int NWP = WIDE_FWD_PAIR_THREADS / 64;      // waves per workgroup (one workgroup per CU shares the 66 KiB of weights)
                 const size_t lds = (size_t)(128 + 224 + 96) * RS * sizeof(bf16_t) + (128 + 224 + 96) * sizeof(float) + NWP * ST_BYTES;
                 // one workgroup per CU is all that fits (LDS): a grid of 1.5 x 256 ran a full round and a half-empty one (220 us, of which
                 // the second round's 110 us kept 128 CUs idle: profiles/README.md, round 4 timelines) - at most ONE round, tiles grid-strided
                 constexpr int WIDE_FWD_PAIR_GRID = 256;
                 const unsigned grid = std::min<unsigned>((mlp_grid(M) * 4 + NWP - 1) / NWP, WIDE_FWD_PAIR_GRID);
+                raise_lds_limit<mlp_fwd_wide_stats<false, true>>();
                 hipLaunchKernelGGL((mlp_fwd_wide_stats<false, true>), dim3(grid), dim3(WIDE_FWD_PAIR_THREADS), lds, st, p);
             } else {
                 const size_t lds = (size_t)(128 + 224) * RS * sizeof(bf16_t) + (128 + 224) * sizeof(float) + 4 * ST_BYTES;
-                if (a->hidden_save[0]) hipLaunchKernelGGL((mlp_fwd_wide_stats<true, false>), dim3(mlp_grid(M)), dim3(256), lds, st, p);
-                else hipLaunchKernelGGL((mlp_fwd_wide_stats<false, false>), dim3(mlp_grid(M)), dim3(256), lds, st, p);
+                if (a->hidden_save[0]) {
+                    raise_lds_limit<mlp_fwd_wide_stats<true, false>>();
+                    hipLaunchKernelGGL((mlp_fwd_wide_stats<true, false>), dim3(mlp_grid(M)), dim3(256), lds, st, p);
+                } else {
+                    raise_lds_limit<mlp_fwd_wide_stats<false, false>>();
+                    hipLaunchKernelGGL((mlp_fwd_wide_stats<false, false>), dim3(mlp_grid(M)), dim3(256), lds, st, p);
+                }
             }
             PAG_CHECK_LAUNCH("pag_mlp_fwd (wide head statistics)");
             return PAG_OK;
@@ -4109,10 +3826,10 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
     if (a->mode == PAG_MLP_MFMA_BF16) {
         const int OB = (a->out_dim + 31) / 32;
         const size_t lds = (size_t)(64 + (a->n_layers == 3 ? 64 : 0) + OB * 32) * RS * sizeof(bf16_t) + (128 + OB * 32) * sizeof(float) + 4 * ST_BYTES;
-        if (a->x1_dtype == PAG_F32 && a->out_dtype == PAG_F32) MLP_FWD_NL(float, float);
-        else if (a->x1_dtype == PAG_F32) MLP_FWD_NL(float, bf16_t);
-        else if (a->out_dtype == PAG_F32) MLP_FWD_NL(bf16_t, float);
-        else MLP_FWD_NL(bf16_t, bf16_t);
+        if (a->x1_dtype == PAG_F32 && a->out_dtype == PAG_F32) launch_fwd_mfma<float, float>(p, a->n_layers, OB, lds, st);
+        else if (a->x1_dtype == PAG_F32) launch_fwd_mfma<float, bf16_t>(p, a->n_layers, OB, lds, st);
+        else if (a->out_dtype == PAG_F32) launch_fwd_mfma<bf16_t, float>(p, a->n_layers, OB, lds, st);
+        else launch_fwd_mfma<bf16_t, bf16_t>(p, a->n_layers, OB, lds, st);
     } else {
         const size_t lds = (size_t)(64 * PT + 64 * 64) * sizeof(float);
         dim3 grid((unsigned)((M + PT - 1) / PT)), block(PT);
@@ -4129,33 +3846,10 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
     return PAG_OK;
 }
 
-#define MLP_BWD_LAUNCH(OutT, DxT, NL_, OBM)                                                            \
-    hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL_, OBM>), dim3(mlp_grid(M)), dim3(256), lds, st, p)
-#define MLP_BWD_OB(OutT, DxT, NL_)                                   \
-    do {                                                             \
-        if (OB <= 1) MLP_BWD_LAUNCH(OutT, DxT, NL_, 1);              \
-        else if (OB <= 2) MLP_BWD_LAUNCH(OutT, DxT, NL_, 2);         \
-        else if (OB <= 4) MLP_BWD_LAUNCH(OutT, DxT, NL_, 4);         \
-        else MLP_BWD_LAUNCH(OutT, DxT, NL_, 7);                      \
-    } while (0)
-#define MLP_BWD_NL(OutT, DxT)                                        \
-    do {                                                             \
-        if (a->n_layers == 2) MLP_BWD_OB(OutT, DxT, 2);              \
-        else MLP_BWD_OB(OutT, DxT, 3);                               \
-    } while (0)
-
 // Sum the per-workgroup slabs of pag_mlp_wgrad into the final dW [n_out][n_in] / db [n_out] (fixed order: deterministic).
 // One workgroup per output row, 4 slab quarters x 96 columns; XCD8 inputs: slab column p is a staged position and lands in
 // feature column grp_col(p).
 constexpr int WF_SPLITS = 10;      // slab range split over 10 x 96 threads of the row's workgroup
-struct FinishParams {
-    const float *slabs;
-    int n_blocks, n_out, rows_pad, n_in, grp_L, grp_F;
-    float *dW, *db;
-};
-struct FinishBatch {
-    FinishParams p[WG_MAX_BATCH];
-};
 __global__ __launch_bounds__(WF_SPLITS * WG_SLAB_COLS) void wgrad_finish_kernel(FinishBatch batch) {
     __shared__ float part[WF_SPLITS][WG_SLAB_COLS];
     const FinishParams &fp = batch.p[blockIdx.y];     // blockIdx.y = layer
@@ -4190,6 +3884,10 @@ __global__ __launch_bounds__(WF_SPLITS * WG_SLAB_COLS) void wgrad_finish_kernel(
     }
 }
 
+void pagmlp::launch_wgrad_finish(const FinishBatch &fb, int max_out, int n_layers, hipStream_t st) {
+    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(max_out, n_layers), dim3(WF_SPLITS * WG_SLAB_COLS), 0, st, fb);
+}
+
 static unsigned fused_grid(int64_t M) {
     const int64_t tiles = (M + 31) / 32;
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, 256 * FUSED_WAVES));      // one 4-wave workgroup per CU, tiles grid-strided
@@ -4205,15 +3903,11 @@ static int fused_kind(const pag_mlp_bwd_args *a) {
         if (a->out_dim <= 192 || a->out_dim > 224 || a->n_layers != 3 || !a->g_ray || !a->g_scale || !a->g_index || !a->g_ray_scale) return -1;
         if (a->out_act != PAG_ACT_SOFTMAX || !a->softmax_stats || !a->b_last || a->out_dtype != PAG_BF16 || !a->dx1 || a->dx1_dtype != PAG_BF16) return -1;
         if (!a->x1 || a->x1_dtype != PAG_BF16 || a->x1_layout != PAG_LAYOUT_XCD8 || a->k1 != 64 || a->x2 || a->dx1_col0_add || a->dx1_accumulate) return -1;
-        if (a->x1_levels < 1 || a->x1_feats < 1 || ((a->x1_levels + 7) / 8) * a->x1_feats > 8) return -1;
-        const int j = 7 / a->x1_feats;
-        if (j < (a->x1_levels + 7) / 8 && xcd8_level(7, j) < a->x1_levels) return -1;
+        if (a->x1_levels < 1 || a->x1_feats < 1 || ((a->x1_levels + 7) / 8) * a->x1_feats > 8 || !xcd8_has_bias_slot(a->x1_levels, a->x1_feats)) return -1;
         return 3;
     }
     if (a->x1_layout == PAG_LAYOUT_XCD8) {
-        if (a->k1 != 64 || a->x1_levels < 1 || a->x1_feats < 1 || ((a->x1_levels + 7) / 8) * a->x1_feats > 8) return -1;
-        const int j = 7 / a->x1_feats;                            // staged position 63 = group 7, element 7: must be padding
-        if (j < (a->x1_levels + 7) / 8 && xcd8_level(7, j) < a->x1_levels) return -1;
+        if (a->k1 != 64 || a->x1_levels < 1 || a->x1_feats < 1 || ((a->x1_levels + 7) / 8) * a->x1_feats > 8 || !xcd8_has_bias_slot(a->x1_levels, a->x1_feats)) return -1;
         if (a->x2 || a->dx1_col0_add) return -1;
         if (!rank1 && a->grad_out && a->out_dtype == PAG_BF16 && a->out_act == PAG_ACT_NONE && a->out_dim % 4 == 0 && !a->dx1_accumulate) return 0;
         if (rank1 && a->g_scale && a->g_index && a->g_ray_scale && a->out && a->out_dtype == PAG_BF16 && a->out_act == PAG_ACT_SOFTMAX &&
@@ -4337,16 +4031,6 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
         pa.hsave[0] = a->hidden_save[1];
         pa.dz[0] = dzh;
         pa.slabs[0] = slabA;
-        constexpr int OBW = 7;
-        const size_t ldsA = (size_t)(64 * (OBW * 32 + 8) + OBW * 32 * RS) * sizeof(bf16_t) + (size_t)OBW * 32 * sizeof(float) +
-                            (size_t)(5 + OBW) * TW_ELEMS * sizeof(bf16_t) + (size_t)2 * WB_RMAX * WR_RS * sizeof(float) +
-                            (size_t)2 * OBW * 64 * sizeof(float) + (size_t)2 * OBW * 2 * 64 * 16;
-        static bool attrA = false;
-        if (!attrA) {
-            hipFuncSetAttribute((const void *)mlp_bwd_wide_blocks<OBW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipFuncSetAttribute((const void *)mlp_bwd_fused<2, 0, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attrA = true;
-        }
         // ---- a companion head on the same input (args->pair): validated before anything is launched
         const pag_mlp_bwd_args *b = a->pair;
         BwdParams ps{};
@@ -4383,7 +4067,7 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
             ps.slabs[0] = slabS0;
             ps.slabs[1] = slabS1;
         }
-        hipLaunchKernelGGL((mlp_bwd_wide_blocks<OBW>), dim3(grid), dim3((OBW + 1) * 64), ldsA, st, pa);
+        launch_bwd_wide_blocks(pa, grid, st);
         PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, wide head)");
         BwdParams pb = p;
         pb.grad_out = dzh;
@@ -4408,11 +4092,7 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
         if (b) {
             // the companion head runs in the same launch as the layers below the wide head: one read of the input, one write of the summed gradient
             const size_t ldsP = (size_t)(64 * 72 * 5 + 64 * 40) * sizeof(bf16_t) + 128 * sizeof(float) + (size_t)4 * 4 * TW_ELEMS * sizeof(bf16_t);
-            static bool attrP = false;
-            if (!attrP) {
-                hipFuncSetAttribute((const void *)mlp_bwd_pair, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attrP = true;
-            }
+            raise_lds_limit<mlp_bwd_pair>();
             PairParams pp{pb, ps};
             hipLaunchKernelGGL(mlp_bwd_pair, dim3(grid), dim3(256), ldsP, st, pp);
             PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, layers below the wide head + companion head)");
@@ -4421,10 +4101,10 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
             n_fin = 5;
         } else {
             const size_t ldsB = (size_t)(64 * (64 + 8) + 2 * 64 * RS) * sizeof(bf16_t) + 128 * sizeof(float) + (size_t)4 * 3 * TW_ELEMS * sizeof(bf16_t);
-            hipLaunchKernelGGL((mlp_bwd_fused<2, 0, false, 2>), dim3(grid), dim3(256), ldsB, st, pb);
+            launch_bwd_fused<2, 0, false, 2>(pb, grid, ldsB, st);
             PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, layers below the wide head)");
         }
-        hipLaunchKernelGGL(wgrad_finish_kernel, dim3(a->out_dim, n_fin), dim3(WF_SPLITS * WG_SLAB_COLS), 0, st, fb);
+        launch_wgrad_finish(fb, a->out_dim, n_fin, st);
         PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, finish)");
         return PAG_OK;
     }
@@ -4438,53 +4118,12 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
         }
         const size_t lds = (size_t)(64 * (32 + 8) + 2 * (a->n_layers == 3 ? 64 * RS : 0) + 2 * 64 * RS) * sizeof(bf16_t) + 128 * sizeof(float) +
                            (size_t)4 * (a->n_layers + 1) * TW_ELEMS * sizeof(bf16_t);
-#define MLP_BWD_FUSED(NL_, KIND_, ACC_)                                                                                              \
-    do {                                                                                                                              \
-        static bool attr_done = false;                                                                                                \
-        if (!attr_done) {                                                                                                             \
-            hipFuncSetAttribute((const void *)mlp_bwd_fused<NL_, KIND_, ACC_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            attr_done = true;                                                                                                         \
-        }                                                                                                                             \
-        hipLaunchKernelGGL((mlp_bwd_fused<NL_, KIND_, ACC_>), dim3(grid), dim3(256), lds, st, p);                                     \
-    } while (0)
-        const bool acc = a->dx1_accumulate != 0;
         p.dz[0] = kind == 1 ? a->dz[0] : nullptr;
         p.dz0_slots = kind == 1 ? a->dz0_slots : nullptr;
-        if (kind == 1 && a->dz0_slots) {      // colour-like, per-ray input's gradient requested, samples packed ray by ray: per-(tile, ray) sums of dz_0
-            static bool attr2s = false, attr3s = false;
-            const size_t lds_s = lds + 4 * 64 * sizeof(int);
-            if (a->n_layers == 2) {
-                if (!attr2s) hipFuncSetAttribute((const void *)mlp_bwd_fused<2, 1, false, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr2s = true;
-                hipLaunchKernelGGL((mlp_bwd_fused<2, 1, false, 1, 2>), dim3(grid), dim3(256), lds_s, st, p);
-            } else {
-                if (!attr3s) hipFuncSetAttribute((const void *)mlp_bwd_fused<3, 1, false, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr3s = true;
-                hipLaunchKernelGGL((mlp_bwd_fused<3, 1, false, 1, 2>), dim3(grid), dim3(256), lds_s, st, p);
-            }
-        } else if (kind == 1 && a->dz[0]) {      // colour-like with the per-ray input's gradient requested: dz_0 is written as well
-            static bool attr2 = false, attr3 = false;
-            if (a->n_layers == 2) {
-                if (!attr2) hipFuncSetAttribute((const void *)mlp_bwd_fused<2, 1, false, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr2 = true;
-                hipLaunchKernelGGL((mlp_bwd_fused<2, 1, false, 1, 1>), dim3(grid), dim3(256), lds, st, p);
-            } else {
-                if (!attr3) hipFuncSetAttribute((const void *)mlp_bwd_fused<3, 1, false, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr3 = true;
-                hipLaunchKernelGGL((mlp_bwd_fused<3, 1, false, 1, 1>), dim3(grid), dim3(256), lds, st, p);
-            }
-        } else if (a->n_layers == 2) {
-            if (kind == 0) MLP_BWD_FUSED(2, 0, false);
-            else if (kind == 1) MLP_BWD_FUSED(2, 1, false);
-            else if (acc) MLP_BWD_FUSED(2, 2, true);
-            else MLP_BWD_FUSED(2, 2, false);
-        } else {
-            if (kind == 0) MLP_BWD_FUSED(3, 0, false);
-            else if (kind == 1) MLP_BWD_FUSED(3, 1, false);
-            else if (acc) MLP_BWD_FUSED(3, 2, true);
-            else MLP_BWD_FUSED(3, 2, false);
-        }
-#undef MLP_BWD_FUSED
+        // colour-like with the per-ray input's gradient requested: dz_0 is written as well (1) or, samples packed ray by ray, summed per (tile, ray) (2)
+        const int dz0 = kind != 1 ? 0 : (a->dz0_slots ? 2 : (a->dz[0] ? 1 : 0));
+        if (a->n_layers == 2) launch_bwd_fused_kind<2>(p, kind, a->dx1_accumulate != 0, dz0, grid, lds, st);
+        else launch_bwd_fused_kind<3>(p, kind, a->dx1_accumulate != 0, dz0, grid, lds, st);
         PAG_CHECK_LAUNCH("pag_mlp_bwd (fused)");
         FinishBatch fb{};
         int max_out = 0;
@@ -4494,191 +4133,33 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
             fb.p[l] = FinishParams{p.slabs[l], (int)grid, n_out, (n_out + 31) / 32 * 32, n_in, l == 0 ? p.grp_L : 0, p.grp_F, a->dW[l], a->db[l]};
             max_out = std::max(max_out, n_out);
         }
-        hipLaunchKernelGGL(wgrad_finish_kernel, dim3(max_out, a->n_layers), dim3(WF_SPLITS * WG_SLAB_COLS), 0, st, fb);
+        launch_wgrad_finish(fb, max_out, a->n_layers, st);
         PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, finish)");
         return PAG_OK;
     }
     const bool wide_rebuild = a->mode == PAG_MLP_MFMA_BF16 && a->out_dim > 64 && a->out_act == PAG_ACT_SOFTMAX && a->softmax_stats &&
                               a->b_last && !out_f32 && (a->g_ray || (a->grad_out && a->out_dim % 8 == 0));
     if (wide_rebuild) {
-        constexpr int NW = WIDE_BWD_WAVES;
-        const int OB = (a->out_dim + 31) / 32;
-        const size_t lds = (size_t)(64 * (OB * 32 + 8) + OB * 32 * RS + (a->n_layers == 3 ? 64 * RS : 0) + 64 * RS) * sizeof(bf16_t) +
-                           (size_t)OB * 32 * sizeof(float) + (size_t)NW * ST_BYTES + (size_t)NW * OB * 32 * sizeof(float);
-        const int64_t tiles = (M + 31) / 32;
-        const unsigned grid = (unsigned)std::min<int64_t>((tiles + NW - 1) / NW, 256);      // one workgroup per CU, tiles grid-strided
-#define MLP_BWD_WIDE(DxT, NL_)                                                                                              \
-    do {                                                                                                                    \
-        static bool attr_done = false;                                                                                      \
-        if (!attr_done) {                                                                                                   \
-            hipFuncSetAttribute((const void *)mlp_bwd_wide_mfma<DxT, NL_, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            attr_done = true;                                                                                               \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((mlp_bwd_wide_mfma<DxT, NL_, NW>), dim3(grid), dim3(NW * 64), lds, st, p);                     \
-    } while (0)
-        if (dx_f32 && a->n_layers == 2) MLP_BWD_WIDE(float, 2);
-        else if (dx_f32) MLP_BWD_WIDE(float, 3);
-        else if (a->n_layers == 2) MLP_BWD_WIDE(bf16_t, 2);
-        else MLP_BWD_WIDE(bf16_t, 3);
-#undef MLP_BWD_WIDE
+        if (dx_f32 && a->n_layers == 2) launch_bwd_wide_mfma<float, 2>(p, st);
+        else if (dx_f32) launch_bwd_wide_mfma<float, 3>(p, st);
+        else if (a->n_layers == 2) launch_bwd_wide_mfma<bf16_t, 2>(p, st);
+        else launch_bwd_wide_mfma<bf16_t, 3>(p, st);
     } else if (a->mode == PAG_MLP_MFMA_BF16) {
         const int OB = (a->out_dim + 31) / 32;
         const size_t lds = (size_t)(64 * (OB * 32 + 8) + (a->n_layers == 3 ? 64 * RS : 0) + 64 * RS) * sizeof(bf16_t) + 4 * ST_BYTES;
-        if (out_f32 && dx_f32) MLP_BWD_NL(float, float);
-        else if (out_f32) MLP_BWD_NL(float, bf16_t);
-        else if (dx_f32) MLP_BWD_NL(bf16_t, float);
-        else MLP_BWD_NL(bf16_t, bf16_t);
+        if (out_f32 && dx_f32) launch_bwd_mfma<float, float>(p, a->n_layers, OB, lds, st);
+        else if (out_f32) launch_bwd_mfma<float, bf16_t>(p, a->n_layers, OB, lds, st);
+        else if (dx_f32) launch_bwd_mfma<bf16_t, float>(p, a->n_layers, OB, lds, st);
+        else launch_bwd_mfma<bf16_t, bf16_t>(p, a->n_layers, OB, lds, st);
     } else {
         const size_t lds = (size_t)(224 * PT + 64 * 64) * sizeof(float);
-        dim3 grid((unsigned)((M + PT - 1) / PT)), block(PT);
-        static bool attr_set = false;   // > 64 KiB of dynamic LDS must be opted into once per kernel
-        if (!attr_set) {
-            hipFuncSetAttribute((const void *)mlp_bwd_f32<float, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipFuncSetAttribute((const void *)mlp_bwd_f32<float, bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipFuncSetAttribute((const void *)mlp_bwd_f32<bf16_t, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipFuncSetAttribute((const void *)mlp_bwd_f32<bf16_t, bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_set = true;
-        }
-        if (out_f32 && dx_f32) hipLaunchKernelGGL((mlp_bwd_f32<float, float>), grid, block, lds, st, p, a->n_layers);
-        else if (out_f32) hipLaunchKernelGGL((mlp_bwd_f32<float, bf16_t>), grid, block, lds, st, p, a->n_layers);
-        else if (dx_f32) hipLaunchKernelGGL((mlp_bwd_f32<bf16_t, float>), grid, block, lds, st, p, a->n_layers);
-        else hipLaunchKernelGGL((mlp_bwd_f32<bf16_t, bf16_t>), grid, block, lds, st, p, a->n_layers);
+        const dim3 grid((unsigned)((M + PT - 1) / PT));
+        if (out_f32 && dx_f32) launch_bwd_f32<float, float>(p, a->n_layers, grid, lds, st);
+        else if (out_f32) launch_bwd_f32<float, bf16_t>(p, a->n_layers, grid, lds, st);
+        else if (dx_f32) launch_bwd_f32<bf16_t, float>(p, a->n_layers, grid, lds, st);
+        else launch_bwd_f32<bf16_t, bf16_t>(p, a->n_layers, grid, lds, st);
     }
     PAG_CHECK_LAUNCH("pag_mlp_bwd");
-    return PAG_OK;
-}
-
-static void wgrad_launch(const WgradBatch &b, int count, bool a1_f32, bool small, int n_blocks, size_t lds, hipStream_t st) {
-    const dim3 grid(n_blocks, count);
-    if (a1_f32) {
-        if (small) hipLaunchKernelGGL((mlp_wgrad_kernel<float, 2>), grid, dim3(256), lds, st, b);
-        else hipLaunchKernelGGL((mlp_wgrad_kernel<float, 6>), grid, dim3(256), lds, st, b);
-    } else {
-        if (small) hipLaunchKernelGGL((mlp_wgrad_kernel<bf16_t, 2>), grid, dim3(256), lds, st, b);
-        else hipLaunchKernelGGL((mlp_wgrad_kernel<bf16_t, 3, 8>), grid, dim3(512), lds, st, b);
-    }
-}
-
-extern "C" int pag_mlp_wgrad_blocks(int64_t M) {
-    int64_t chunks = (M + 63) / 64;
-    return (int)(chunks < 1024 ? (chunks > 0 ? chunks : 1) : 1024);
-}
-
-extern "C" int pag_mlp_wgrad(const void *dz, int dz_cols, int n_out, const void *a1, int a1_dtype, int a1_layout, int k1,
-                             const float *a2, int k2p, const int32_t *a2_index, int n_in, float *slabs, int n_blocks, int64_t M,
-                             void *stream) {
-    PAG_CHECK_ARG(M >= 0, "pag_mlp_wgrad: M < 0");
-    PAG_CHECK_ARG(n_out >= 1 && n_out <= 224 && dz_cols >= n_out, "pag_mlp_wgrad: n_out %d / dz_cols %d out of range", n_out, dz_cols);
-    PAG_CHECK_ARG(k1 > 0 && k1 % 8 == 0, "pag_mlp_wgrad: k1 %d must be a positive multiple of 8", k1);
-    PAG_CHECK_ARG(a2 == nullptr || (k2p > 0 && k2p % 8 == 0 && a2_index), "pag_mlp_wgrad: a2 needs k2p %% 8 == 0 and a2_index");
-    PAG_CHECK_ARG(n_in >= 1 && n_in <= 64 && n_in <= k1 + (a2 ? k2p : 0), "pag_mlp_wgrad: n_in %d out of range", n_in);
-    PAG_CHECK_ARG(a1_dtype == PAG_F32 || a1_dtype == PAG_BF16, "pag_mlp_wgrad: a1 dtype must be F32 or BF16");
-    PAG_CHECK_ARG(n_blocks >= 1, "pag_mlp_wgrad: n_blocks < 1");
-    if (M == 0) return PAG_OK;
-    PAG_CHECK_ARG(dz && a1 && slabs, "pag_mlp_wgrad: NULL dz/a1/slabs");
-    PAG_CHECK_ARG(a1_layout == PAG_LAYOUT_STRIDED || (a1_dtype == PAG_BF16 && k1 == 64 && n_in == 64 && a2 == nullptr),
-                  "pag_mlp_wgrad: XCD8 a1 needs bf16, k1 = n_in = 64 and no a2");
-    WgradParams p{(const bf16_t *)dz, dz_cols, n_out, a1, k1, a2, a2 ? k2p : 0, a2_index, n_in, slabs, M, a1_layout == PAG_LAYOUT_XCD8};
-    const int OB = (n_out + 31) / 32, IB = (n_in + 31) / 32;
-    const size_t lds = (size_t)(OB + IB) * 32 * WG_RS * sizeof(bf16_t);
-    const bool small = OB * (IB + 1) <= 8;      // fewer accumulators -> fewer VGPRs -> more resident workgroups
-    WgradBatch b{};
-    b.p[0] = p;
-    wgrad_launch(b, 1, a1_dtype == PAG_F32, small, n_blocks, lds, (hipStream_t)stream);
-    PAG_CHECK_LAUNCH("pag_mlp_wgrad");
-    return PAG_OK;
-}
-
-extern "C" int pag_mlp_wgrad_finish(const float *slabs, int n_blocks, int n_out, int n_in, int a1_layout, int a1_levels, int a1_feats,
-                                    float *dW, float *db, void *stream) {
-    PAG_CHECK_ARG(n_blocks >= 1 && n_out >= 1 && n_out <= 224 && n_in >= 1 && n_in <= 64, "pag_mlp_wgrad_finish: size out of range");
-    PAG_CHECK_ARG(slabs && dW && db, "pag_mlp_wgrad_finish: NULL slabs/dW/db");
-    const int grouped = a1_layout == PAG_LAYOUT_XCD8;
-    PAG_CHECK_ARG(!grouped || (a1_levels >= 1 && a1_feats >= 1 && a1_levels * a1_feats == n_in && ((a1_levels + 7) / 8) * a1_feats <= 8),
-                  "pag_mlp_wgrad_finish: XCD8 needs n_in = levels*feats");
-    FinishBatch fb{};
-    fb.p[0] = FinishParams{slabs, n_blocks, n_out, (n_out + 31) / 32 * 32, n_in, grouped ? a1_levels : 0, a1_feats, dW, db};
-    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(n_out, 1), dim3(WF_SPLITS * WG_SLAB_COLS), 0, (hipStream_t)stream, fb);
-    PAG_CHECK_LAUNCH("pag_mlp_wgrad_finish");
-    return PAG_OK;
-}
-
-// All weight gradients of one decoder: the layers that share a kernel variant (input dtype, narrow / wide) go into ONE slab
-// launch (grid.y = layer) and ONE finish launch sums every layer's slabs - 2-3 launches per decoder instead of 2 per layer.
-extern "C" int pag_mlp_wgrad_batch(const pag_wgrad_layer *layers, int n_layers, int64_t M, void *stream) {
-    PAG_CHECK_ARG(layers && n_layers >= 1 && n_layers <= WG_MAX_BATCH, "pag_mlp_wgrad_batch: n_layers %d not in [1,%d]", n_layers, WG_MAX_BATCH);
-    PAG_CHECK_ARG(M >= 1, "pag_mlp_wgrad_batch: M < 1 (callers zero the gradients of an empty batch themselves)");
-    hipStream_t st = (hipStream_t)stream;
-    bool done[WG_MAX_BATCH] = {};
-    FinishBatch fb{};
-    int max_out = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        const pag_wgrad_layer &y = layers[l];
-        PAG_CHECK_ARG(y.n_out >= 1 && y.n_out <= 224 && y.dz_cols >= y.n_out, "pag_mlp_wgrad_batch: layer %d n_out %d / dz_cols %d out of range", l, y.n_out, y.dz_cols);
-        PAG_CHECK_ARG(y.k1 > 0 && y.k1 % 8 == 0, "pag_mlp_wgrad_batch: layer %d k1 %d must be a positive multiple of 8", l, y.k1);
-        PAG_CHECK_ARG(y.a2 == nullptr || (y.k2p > 0 && y.k2p % 8 == 0 && y.a2_index), "pag_mlp_wgrad_batch: layer %d a2 needs k2p %% 8 == 0 and a2_index", l);
-        PAG_CHECK_ARG(y.n_in >= 1 && y.n_in <= 64 && y.n_in <= y.k1 + (y.a2 ? y.k2p : 0), "pag_mlp_wgrad_batch: layer %d n_in %d out of range", l, y.n_in);
-        PAG_CHECK_ARG(y.a1_dtype == PAG_F32 || y.a1_dtype == PAG_BF16, "pag_mlp_wgrad_batch: layer %d a1 dtype must be F32 or BF16", l);
-        PAG_CHECK_ARG(y.n_blocks >= 1 && y.dz && y.a1 && y.slabs && y.dW && y.db, "pag_mlp_wgrad_batch: layer %d NULL pointer or n_blocks < 1", l);
-        const bool grouped = y.a1_layout == PAG_LAYOUT_XCD8;
-        PAG_CHECK_ARG(!grouped || (y.a1_dtype == PAG_BF16 && y.k1 == 64 && y.n_in == 64 && y.a2 == nullptr && y.a1_levels >= 1 && y.a1_feats >= 1 &&
-                                   ((y.a1_levels + 7) / 8) * y.a1_feats <= 8),
-                      "pag_mlp_wgrad_batch: layer %d XCD8 a1 needs bf16, k1 = n_in = 64 (staged positions), levels*feats <= 64 and no a2", l);
-        // XCD8: the slab columns are the 64 staged positions, dW has levels*feats feature columns
-        fb.p[l] = FinishParams{y.slabs, y.n_blocks, y.n_out, (y.n_out + 31) / 32 * 32, grouped ? y.a1_levels * y.a1_feats : y.n_in,
-                               grouped ? y.a1_levels : 0, y.a1_feats, y.dW, y.db};
-        max_out = std::max(max_out, y.n_out);
-    }
-    for (int l = 0; l < n_layers; ++l) {
-        if (done[l]) continue;
-        const pag_wgrad_layer &y = layers[l];
-        const bool f32 = y.a1_dtype == PAG_F32;
-        const bool small = ((y.n_out + 31) / 32) * ((y.n_in + 31) / 32 + 1) <= 8;
-        WgradBatch b{};
-        int count = 0;
-        size_t lds = 0;
-        for (int k = l; k < n_layers; ++k) {
-            const pag_wgrad_layer &z = layers[k];
-            const int OB = (z.n_out + 31) / 32, IB = (z.n_in + 31) / 32;
-            if (done[k] || (z.a1_dtype == PAG_F32) != f32 || (OB * (IB + 1) <= 8) != small || z.n_blocks != y.n_blocks) continue;
-            b.p[count++] = WgradParams{(const bf16_t *)z.dz, z.dz_cols, z.n_out, z.a1, z.k1, z.a2, z.a2 ? z.k2p : 0, z.a2_index, z.n_in, z.slabs, M,
-                                       z.a1_layout == PAG_LAYOUT_XCD8};
-            lds = std::max(lds, (size_t)(OB + IB) * 32 * WG_RS * sizeof(bf16_t));
-            done[k] = true;
-        }
-        wgrad_launch(b, count, f32, small, y.n_blocks, lds, st);
-        PAG_CHECK_LAUNCH("pag_mlp_wgrad_batch (slabs)");
-    }
-    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(max_out, n_layers), dim3(WF_SPLITS * WG_SLAB_COLS), 0, st, fb);
-    PAG_CHECK_LAUNCH("pag_mlp_wgrad_batch (finish)");
-    return PAG_OK;
-}
-
-extern "C" int pag_affine_xcd8_fwd(const void *x, int64_t M, int x_levels, int x_feats, const float *W, const float *b, int n_out, int in_dim,
-                                   float *out, void *stream) {
-    PAG_CHECK_ARG(M >= 0, "pag_affine_xcd8_fwd: M < 0");
-    PAG_CHECK_ARG(n_out >= 1 && n_out <= AFF_MAX_OUT, "pag_affine_xcd8_fwd: n_out %d not in [1,%d]", n_out, AFF_MAX_OUT);
-    PAG_CHECK_ARG(x_feats >= 1 && ((x_levels + 7) / 8) * x_feats <= 8 && in_dim == x_levels * x_feats, "pag_affine_xcd8_fwd: in_dim %d != levels %d * feats %d (or more than 8 values per group)",
-                  in_dim, x_levels, x_feats);
-    if (M == 0) return PAG_OK;
-    PAG_CHECK_ARG(x && W && b && out, "pag_affine_xcd8_fwd: NULL input/output");
-    hipLaunchKernelGGL(affine_xcd8_fwd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t *)x, M, x_levels, x_feats, W, b,
-                       n_out, in_dim, out);
-    PAG_CHECK_LAUNCH("pag_affine_xcd8_fwd");
-    return PAG_OK;
-}
-
-extern "C" int pag_affine_xcd8_bwd_dx(const float *grad_out, int64_t M, int x_levels, int x_feats, const float *W, int n_out, int in_dim, void *dx,
-                                      void *stream) {
-    PAG_CHECK_ARG(M >= 0, "pag_affine_xcd8_bwd_dx: M < 0");
-    PAG_CHECK_ARG(n_out >= 1 && n_out <= AFF_MAX_OUT, "pag_affine_xcd8_bwd_dx: n_out %d not in [1,%d]", n_out, AFF_MAX_OUT);
-    PAG_CHECK_ARG(x_feats >= 1 && ((x_levels + 7) / 8) * x_feats <= 8 && in_dim == x_levels * x_feats, "pag_affine_xcd8_bwd_dx: in_dim %d != levels %d * feats %d (or more than 8 values per group)",
-                  in_dim, x_levels, x_feats);
-    if (M == 0) return PAG_OK;
-    PAG_CHECK_ARG(grad_out && W && dx, "pag_affine_xcd8_bwd_dx: NULL input/output");
-    hipLaunchKernelGGL(affine_xcd8_bwd_dx_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, grad_out, M, x_levels, x_feats, W, n_out, in_dim,
-                       (bf16_t *)dx);
-    PAG_CHECK_LAUNCH("pag_affine_xcd8_bwd_dx");
     return PAG_OK;
 }
 

@@ -1,0 +1,68 @@
+// Shared by the decoder translation units (mlp.hip, mlp_wgrad.hip, mlp_affine.hip; nothing else includes it): what more than one of them uses.
+// The transposed-MFMA scheme of the decoders is described at the top of mlp.hip.
+#pragma once
+#include "common.h"
+#include <algorithm>
+#include <type_traits>
+
+// What crosses translation units: a kernel is launched from the file that defines it (no relocatable device code), so the file that owns
+// a kernel other files need exports a host launcher for it
+namespace pagmlp {
+
+constexpr int WG_MAX_BATCH = 6;         // layers per weight-gradient launch (grid.y)
+constexpr int WG_SLAB_COLS = 96;        // floats per weight-gradient slab row: columns 0..63 dW, column 64 db
+
+struct FinishParams {
+    const float *slabs;
+    int n_blocks, n_out, rows_pad, n_in, grp_L, grp_F;
+    float *dW, *db;
+};
+struct FinishBatch {
+    FinishParams p[WG_MAX_BATCH];
+};
+// mlp.hip: wgrad_finish_kernel over layers 0 .. n_layers - 1 of `fb`, max_out = their largest n_out
+void launch_wgrad_finish(const FinishBatch &fb, int max_out, int n_layers, hipStream_t st);
+
+}  // namespace pagmlp
+
+namespace {
+using namespace pagmlp;
+
+typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
+typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ int rho(int q, int h) { return (q & 3) + 8 * (q >> 2) + 4 * h; }
+// staged position (8*g + e) of the XCD8 layout -> column level*F + f of the [M, L*F] feature row, or -1 (padding)
+// (a / d for the wave-uniform divisors of the staging loops: a shift when d is a power of two - the feature width and the pad sizes always
+// are - instead of the ~40-instruction software division; the loops below were bound by those: 25 k of a launch's clocks per workgroup)
+__device__ __forceinline__ int udiv_uniform(int a, int d) { return (d & (d - 1)) == 0 ? a >> (31 - __clz(d)) : a / d; }
+__device__ __forceinline__ int grp_col(int pos, int L, int F) {
+    const int g = pos >> 3, e = pos & 7;
+    const int j = udiv_uniform(e, F), f = e - j * F;
+    const int level = xcd8_level(g, j);
+    return (j < (L + 7) / 8 && level < L) ? level * F + f : -1;
+}
+__device__ __forceinline__ bf16x8 load8(const float *p) {
+    f32x4 a = *reinterpret_cast<const f32x4 *>(p);
+    f32x4 b = *reinterpret_cast<const f32x4 *>(p + 4);
+    bf16x8 r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        r[j] = (bf16_t)a[j];
+        r[j + 4] = (bf16_t)b[j];
+    }
+    return r;
+}
+__device__ __forceinline__ bf16x8 load8(const bf16_t *p) { return *reinterpret_cast<const bf16x8 *>(p); }
+
+__device__ __forceinline__ bf16x8 zero8() {
+    bf16x8 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = (bf16_t)0.0f;
+    return r;
+}
+
+
+}  // namespace

@@ -747,7 +747,7 @@ class _FusedMLP(torch.autograd.Function):
 
 
 DZ0_SLOTS = os.environ.get("PAG_DZ0_SLOTS", "1") != "0"      # A/B switch: per-(tile, ray) sums of dz_0 inside the colour backward (pag_mlp_bwd_args.dz0_slots)
-WGRAD_MAX_BATCH = 6      # WG_MAX_BATCH of csrc/mlp.hip
+WGRAD_MAX_BATCH = 6      # WG_MAX_BATCH of csrc/mlp_common.h
 WGRAD_FUSED = os.environ.get("PAG_NO_FUSED_WGRAD") is None      # narrow decoders: weight gradients inside pag_mlp_bwd (no dz tensors)
 
 
