@@ -710,6 +710,37 @@ int pag_confusion_matrix(const void *preds, int preds_dtype, const int64_t *pred
                          const int64_t *target_strides, const int64_t *shape, int C, int64_t *confmat, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Panoptic point-cloud map export (utils/render_map.py; main_interactive.py:109-129 `--save-map-only`): the reduction of rendered rays / dense lattice
+ * rows to the kept map points as an ORDERED APPEND behind a running device counter.  Kept rows land in row order behind *count (i64 [1], device),
+ * which the call advances by the number kept; a row whose slot is at or past `cap` is counted and not written, so an overflow shows in the counter
+ * and nothing is written out of bounds.  Output order and bits do not depend on how the rows are split over calls.  Three launches (four with the
+ * `argmax != 0` predicate), no host synchronisation, no float atomics, capturable in a graph.  n = 0 is a no-op; n <= 2^31.  Additive to ABI 14.
+ * Instance ids are torch.argmax's over inst f32 [n, I] (row i at i*inst_stride elements, 1 <= I <= 1024): the first index of the maximum, a NaN
+ * counting as the maximum; or they are copied from ids_in i64 [n] (give one of the two).
+ * ------------------------------------------------------------------------------------------ */
+
+/* Workspace of one call over n rows (0 for n outside (0, 2^31]); about 4 n bytes. */
+int64_t pag_map_workspace_bytes(int64_t n);
+
+/* render_points_at_depth :107-120 on one rendered chunk of n rays, global ray index ray0 + i: depth, alpha, density f32 [n] (the [n,1] buffers),
+ * hit u8 / bool [n], rgb f32 [n,3].  Kept iff density > min_density && alpha > min_alpha && hit && depth < depth_max && depth > depth_min (all
+ * strict).  point = sum_k (o_c - t + d_c depth)[k] R[k] (the arithmetic and op order of pag_pose_points; utils/outlier_rejection.py:89-97) with
+ * the camera cam[(ray0 + i) / rays_per_camera] (cam i32 [n_cam], rows of params f32 [C,9], clamped as in pag_pose_rays_fwd) and the camera-frame
+ * base ray (ray0 + i) % rays_per_camera of origins_c / dirs_c f32 [rays_per_camera,3] (the reference stacks the same base rays once per camera,
+ * :98).  -> points f32 [cap,3], color f32 [cap,3] (the rgb bits), ids_out i64 [cap]. */
+int pag_map_points(const float *params, int64_t C, const int32_t *cam, int64_t n_cam, int64_t rays_per_camera, const float *origins_c,
+                   const float *dirs_c, int64_t ray0, int64_t n, const float *depth, const float *alpha, const uint8_t *hit,
+                   const float *density, const float *rgb, const float *inst, int I, int64_t inst_stride, const int64_t *ids_in,
+                   float min_density, float min_alpha, float depth_min, float depth_max, float *points, float *color, int64_t *ids_out,
+                   int64_t cap, int64_t *count, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* get_dense_occupied_points :77-79 / generate_pc_map :160-165: rows of points_in f32 [n,3] kept iff value[i] > threshold (value f32 [n], strict)
+ * or, with value NULL, iff their instance id != 0.  -> points f32 [cap,3] and, with ids_out i64 [cap] not NULL and ids given, the kept rows' ids. */
+int pag_map_select(const float *points_in, int64_t n, const float *value, float threshold, const float *inst, int I, int64_t inst_stride,
+                   const int64_t *ids_in, float *points, int64_t *ids_out, int64_t cap, int64_t *count, void *workspace,
+                   int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-ray training loss of the rendered buffers (pc_nerf/trainer.py:443-446 rgb, :459-465 semantics,
  * loss/lin_assignment_things.py:80 instance term after the assignment) - one launch forward, one backward
  * ------------------------------------------------------------------------------------------ */

@@ -12,6 +12,8 @@
              utils/embedding.py, pc_nerf/clustering_nef.py
     metrics: PanopticQuality, panoptic_quality, clean_instances, MulticlassIoU (metrics.py) <- utils/metrics/panoptic_quality{,_func}.py,
              pc_nerf/trainer.py:670-673, :750-772 (validation)
+    map   : generate_pc_map_from_views, render_points_at_depth, map_points_from_buffers, generate_pc_map, get_dense_occupied_points,
+            pinhole_base_rays, save_map (map_export.py) <- utils/render_map.py, main_interactive.py:109-129 (--save-map-only)
     optim : Adam (torch.optim.Adam's interface on pag_adam_step) (optim.py) <- config_parser.py:667-673, trainer.py:583
 
 All compute goes through libpagnerf_hip.so (include/pagnerf_hip.h); there is no CPU fallback.
@@ -25,6 +27,8 @@ from .dd import PanopticDDensityNeF, PanopticDDensityPackedRFTracer    # noqa: F
 from .cluster import (ClusteringNeF, MeanShift, MeanShiftPanopticDDensityNeF, MeanShiftPanopticDeltaNeF,    # noqa: F401
                       MeanShiftPanopticNeF, estimate_bandwidth, mean_class_embedding)
 from .metrics import MulticlassIoU, PanopticQuality, clean_instances, panoptic_quality    # noqa: F401
+from .map_export import (MapAccumulator, generate_pc_map, generate_pc_map_from_views, get_dense_occupied_points,    # noqa: F401
+                         map_points_from_buffers, pinhole_base_rays, render_points_at_depth, save_map)
 from . import optim                                                # noqa: F401
 
 __version__ = "0.1.0"

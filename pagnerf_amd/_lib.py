@@ -164,6 +164,10 @@ _SIGS = {
     "pag_panoptic_clean_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "pag_panoptic_clean": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i64, ctypes.c_double, c_vp, c_i64, c_vp, c_vp]),
     "pag_confusion_matrix": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "pag_map_workspace_bytes": (c_i64, [c_i64]),
+    "pag_map_points": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp,
+                               c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "pag_map_select": (c_i32, [c_vp, c_i64, c_vp, c_f32, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "pag_mlp_dz0_slots_bytes": (c_i64, [c_i64, c_i64]),
     "pag_mlp_dz0_slots_sum": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pag_encode_bwd_rays_workspace_bytes": (c_i64, [c_i64, c_i64]),

@@ -38,7 +38,8 @@ SOURCES = {
     "supcon.hip": ["-ffp-contract=off"],     # the contrastive loss: the row statistics in the written op order
     "cluster.hip": ["-ffp-contract=off"],    # mean-shift clustering: the fp64 distances and sums in the written op order
     "panoptic.hip": ["-ffp-contract=off"],   # panoptic evaluation: the f32 IoU quotients and fp64 distances in the written op order
-    "sparse.hip": [],                         # the touched-rows exchange's mask / plan / pack / unpack passes: integer and copy work only
+    "map.hip": ["-ffp-contract=off"],        # map export: the unprojection in pose.hip's op order
+    "sparse.hip": [],                        # the touched-rows exchange's mask / plan / pack / unpack passes: integer and copy work only
 }
 
 

@@ -1776,3 +1776,84 @@ def render_loss(rgb=None, rgb_gt=None, rgb_weight=1.0, term_a=None, term_b=None,
         raise ValueError("render_loss needs at least one term")
     return _RenderLoss.apply(rgb, term_a.prob if term_a is not None else None, term_b.prob if term_b is not None else None,
                              rgb_gt, rgb_weight, term_a, term_b, eps)
+
+
+# ------------------------------------------------------------------------------------------- map export (csrc/map.hip)
+def _map_inst(name, n, inst, ids):
+    """-> (inst pointer, I, row stride, ids pointer, tensors to keep alive) for the instance-id arguments of pag_map_points / pag_map_select."""
+    if inst is not None and ids is not None:
+        raise RuntimeError("%s: give either inst or ids" % name)
+    if inst is not None:
+        if inst.dim() != 2 or inst.shape[0] != n:
+            raise RuntimeError("%s: inst must be [n, I], got %s" % (name, tuple(inst.shape)))
+        inst = inst.detach()
+        if inst.dtype != torch.float32:
+            inst = inst.float()
+        if (inst.shape[1] > 1 and inst.stride(1) != 1) or (n > 1 and inst.stride(0) < inst.shape[1]):
+            inst = inst.contiguous()
+        return inst.data_ptr(), inst.shape[1], (inst.stride(0) if n > 1 else inst.shape[1]), None, (inst,)
+    if ids is not None:
+        if ids.dtype != torch.int64 or ids.numel() != n:
+            raise RuntimeError("%s: ids must be int64 [n]" % name)
+        ids = ids.detach().reshape(-1).contiguous()
+        return None, 0, 0, ids.data_ptr(), (ids,)
+    return None, 0, 0, None, ()
+
+
+def _map_workspace(n, dev):
+    return torch.empty(max(int(L.load().pag_map_workspace_bytes(n)), 8), dtype=torch.uint8, device=dev)
+
+
+def map_points(params, cam, rays_per_camera, origins_c, dirs_c, ray0, depth, alpha, hit, density, rgb, points, color, ids_out, count, inst=None,
+               ids=None, min_density=40.0, min_alpha=0.9, depth_min=0.6, depth_max=0.8):
+    """utils/render_map.py:107-120 on one rendered chunk: the kept rays' world points, colours and instance ids appended in ray order to
+    points / color f32 [cap,3] and ids_out i64 [cap] behind the device counter `count` i64 [1] (pag_map_points; no host synchronisation)."""
+    _check_gpu(params, cam, origins_c, dirs_c, depth, alpha, hit, density, rgb, points, color, ids_out, count, inst, ids)
+    n = depth.numel()
+    if n == 0:
+        return
+    if alpha.numel() != n or hit.numel() != n or density.numel() != n or rgb.numel() != 3 * n:
+        raise RuntimeError("map_points: depth / alpha / hit / density [n] and rgb [n,3] must describe the same rays")
+    if cam.dtype != torch.int32 or params.dim() != 2 or params.shape[1] != 9 or origins_c.shape != dirs_c.shape or origins_c.shape != (rays_per_camera, 3):
+        raise RuntimeError("map_points: cam must be int32, params [C,9], base rays [rays_per_camera,3]")
+    if hit.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError("map_points: hit must be bool / uint8")
+    if points.dtype != torch.float32 or color.dtype != torch.float32 or ids_out.dtype != torch.int64 or count.dtype != torch.int64:
+        raise RuntimeError("map_points: points / color f32, ids_out / count int64")
+    cap = points.shape[0]
+    if color.shape[0] != cap or ids_out.shape[0] != cap or not (points.is_contiguous() and color.is_contiguous() and ids_out.is_contiguous()):
+        raise RuntimeError("map_points: points [cap,3], color [cap,3], ids_out [cap], contiguous")
+    f = lambda t: t.detach().reshape(-1).contiguous().float()                      # noqa: E731
+    prm, oc, dc = params.detach().contiguous().float(), origins_c.detach().contiguous().float(), dirs_c.detach().contiguous().float()
+    dep, alp, den, col, h = f(depth), f(alpha), f(density), f(rgb), hit.detach().reshape(-1).contiguous()
+    ip, I, stride, idp, keep = _map_inst("map_points", n, inst, ids)
+    if ip is None and idp is None:
+        raise RuntimeError("map_points: needs inst or ids")
+    cam = cam.contiguous()
+    ws = _map_workspace(n, dep.device)
+    _call("pag_map_points", prm.data_ptr(), prm.shape[0], cam.data_ptr(), cam.numel(), int(rays_per_camera), oc.data_ptr(), dc.data_ptr(), int(ray0), n,
+          dep.data_ptr(), alp.data_ptr(), h.data_ptr(), den.data_ptr(), col.data_ptr(), ip, I, stride, idp, float(min_density), float(min_alpha),
+          float(depth_min), float(depth_max), points.data_ptr(), color.data_ptr(), ids_out.data_ptr(), cap, count.data_ptr(), ws.data_ptr(), ws.numel(),
+          L.stream())
+
+
+def map_select(points_in, points, count, value=None, threshold=0.0, inst=None, ids=None, ids_out=None):
+    """utils/render_map.py:77-79 / :160-165: rows of points_in f32 [n,3] with value > threshold (or, without value, with instance id != 0)
+    appended in row order to points f32 [cap,3] (and their ids to ids_out i64 [cap]) behind the device counter (pag_map_select)."""
+    _check_gpu(points_in, points, count, value, inst, ids, ids_out)
+    n = points_in.shape[0]
+    if n == 0:
+        return
+    if points_in.dim() != 2 or points_in.shape[1] != 3 or (value is not None and value.numel() != n):
+        raise RuntimeError("map_select: points_in [n,3], value [n]")
+    if points.dtype != torch.float32 or count.dtype != torch.int64 or not points.is_contiguous() or (ids_out is not None and (
+            ids_out.dtype != torch.int64 or ids_out.shape[0] != points.shape[0] or not ids_out.is_contiguous())):
+        raise RuntimeError("map_select: points f32 [cap,3], ids_out int64 [cap], count int64 [1]")
+    pin = points_in.detach().contiguous().float()
+    val = value.detach().reshape(-1).contiguous().float() if value is not None else None
+    ip, I, stride, idp, keep = _map_inst("map_select", n, inst, ids)
+    if val is None and ip is None and idp is None:
+        raise RuntimeError("map_select: needs value, inst or ids")
+    ws = _map_workspace(n, pin.device)
+    _call("pag_map_select", pin.data_ptr(), n, val.data_ptr() if val is not None else None, float(threshold), ip, I, stride, idp, points.data_ptr(),
+          ids_out.data_ptr() if ids_out is not None else None, points.shape[0], count.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
