@@ -850,6 +850,42 @@ int pag_sparse_rows_pack(const float *grad, int L, int64_t T, int F, const uint3
 int pag_sparse_rows_unpack(const float *buf, int L, int64_t T, int F, const uint32_t *bits, const int32_t *word_prefix, const int32_t *caps, const int64_t *offs,
                            float *grad, void *stream);
 
+/* Semantic-NeRF decoder (pc_nerf/semantic_nerf.py:43-76, :188-224; additive, ABI 14): the whole network in one launch (mlp_deep.hip).
+ *   e = PE10(coords) (63 wide, SURVEY Appendix A2 order); trunk: 8 x (Linear + ReLU) at width 256, layer 0 reads e, layer 5 reads cat([e, h]) (e in the
+ *   first 63 columns), then lout 256 -> 256 without activation = feats; density = relu(Linear(256,1)(feats)); rgb = sigmoid(Linear(128,3)(relu(
+ *   Linear(319,128)(cat([feats, PE10(-ray_d)]))))); semantics = Linear(128,C)(relu(Linear(256,128)(feats))), raw logits.
+ * Rounding points: every Linear's input and weight are rounded to bf16 (round to nearest even), sums and biases are f32, sin / cos are the accurate ones.
+ * W[i] / b[i] are the f32 nn.Linear tensors ([out,in] row major): 0..7 trunk layers, 8 lout, 9 density, 10 / 11 colour layers[0] / lout, 12 / 13 semantics
+ * layers[0] / lout.  `channels` is a mask of PAG_DEEP_*; an output pointer is needed only for a requested channel; ray_d (f32 [M,3], per sample) only with
+ * PAG_DEEP_RGB.  save = 0: nothing but the outputs is written (validation render, prune).  save = 1 (training forward): every Linear's bf16 input is kept
+ * in the workspace for pag_deep_mlp_bwd; all three channels must then be requested.
+ *   pag_deep_mlp_supported        1 when the fused path takes (hidden, num_classes): hidden == 256, 1 <= num_classes <= 16
+ *   pag_deep_mlp_workspace_bytes  mode 0: forward with save = 0, 1: forward with save = 1, 2: backward (bwd_workspace); -1 on bad sizes
+ *   pag_deep_mlp_fwd              density f32 [M], rgb f32 [M,3], semantics f32 [M,C]
+ *   pag_deep_mlp_bwd              dW[i] / db[i] (f32, shapes of W[i] / b[i], overwritten) from the upstream gradients g_density [M], g_rgb [M,3],
+ *                                 g_semantics [M,C] (f32; NULL = zero), the forward's density / rgb outputs and its save = 1 workspace.  Gradient operands
+ *                                 (every layer's dz) are rounded to bf16 before both of their products; weight and bias gradients are per-workgroup
+ *                                 partial sums added in a fixed order by a finish pass (no atomics: two runs give the same bits).  No gradient with
+ *                                 respect to coords or ray_d.
+ * Bad sizes, NULL buffers and short workspaces are refused before any launch; M == 0 is a no-op (nothing is written). */
+enum { PAG_DEEP_DENSITY = 1, PAG_DEEP_RGB = 2, PAG_DEEP_SEMANTICS = 4 };
+typedef struct pag_deep_mlp_args {
+    const void *coords, *ray_d;
+    int hidden, num_classes, channels, save;
+    const void *W[14], *b[14];
+    void *density, *rgb, *semantics;
+    void *workspace;
+    int64_t workspace_bytes;
+    const void *g_density, *g_rgb, *g_semantics;
+    void *dW[14], *db[14];
+    void *bwd_workspace;
+    int64_t bwd_workspace_bytes;
+} pag_deep_mlp_args;
+int pag_deep_mlp_supported(int hidden, int num_classes);
+int64_t pag_deep_mlp_workspace_bytes(int64_t M, int hidden, int num_classes, int mode);
+int pag_deep_mlp_fwd(const pag_deep_mlp_args *args, int64_t M, void *stream);
+int pag_deep_mlp_bwd(const pag_deep_mlp_args *args, int64_t M, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

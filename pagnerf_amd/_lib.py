@@ -78,6 +78,15 @@ MlpBwdArgs._fields_ = [("grad_out", c_vp), ("out", c_vp), ("out_dtype", c_i32), 
                 ("pair", ctypes.POINTER(MlpBwdArgs)), ("dz0_slots", c_vp)]
 
 
+class DeepMlpArgs(ctypes.Structure):
+    """pag_deep_mlp_args (include/pagnerf_hip.h)."""
+    _fields_ = [("coords", c_vp), ("ray_d", c_vp), ("hidden", c_i32), ("num_classes", c_i32), ("channels", c_i32), ("save", c_i32),
+                ("W", c_vp * 14), ("b", c_vp * 14), ("density", c_vp), ("rgb", c_vp), ("semantics", c_vp),
+                ("workspace", c_vp), ("workspace_bytes", c_i64),
+                ("g_density", c_vp), ("g_rgb", c_vp), ("g_semantics", c_vp), ("dW", c_vp * 14), ("db", c_vp * 14),
+                ("bwd_workspace", c_vp), ("bwd_workspace_bytes", c_i64)]
+
+
 _SIGS = {
     "pag_abi_version": (c_i32, []),
     "pag_last_error_string": (ctypes.c_char_p, []),
@@ -175,6 +184,10 @@ _SIGS = {
                                          c_vp, c_vp, c_i64, c_i32, c_vp]),
     "pag_permuto_encode_bwd_rays": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_u32, c_fp, c_fp, c_fp, c_vp, c_vp, c_vp,
                                             c_i64, c_vp, c_vp, c_i64, c_i32, c_vp]),
+    "pag_deep_mlp_supported": (c_i32, [c_i32, c_i32]),
+    "pag_deep_mlp_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "pag_deep_mlp_fwd": (c_i32, [ctypes.POINTER(DeepMlpArgs), c_i64, c_vp]),
+    "pag_deep_mlp_bwd": (c_i32, [ctypes.POINTER(DeepMlpArgs), c_i64, c_vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -25,6 +25,7 @@ MLP = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 # encode / render reproduce the oracle's fp32 op order: no FMA contraction there
 SOURCES = {
     "mlp.hip": MLP,
+    "mlp_deep.hip": MLP,
     "encode.hip": ["-ffp-contract=off"],
     "mlp_wgrad.hip": MLP,
     "render.hip": ["-ffp-contract=off"],
