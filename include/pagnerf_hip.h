@@ -886,6 +886,37 @@ int64_t pag_deep_mlp_workspace_bytes(int64_t M, int hidden, int num_classes, int
 int pag_deep_mlp_fwd(const pag_deep_mlp_args *args, int64_t M, void *stream);
 int pag_deep_mlp_bwd(const pag_deep_mlp_args *args, int64_t M, void *stream);
 
+/* TensoRF vector-matrix grid (grids/tensorf.py::VMSplitFeatureVolume; additive, ABI 14): vm.hip.  f32 tables, f32 arithmetic.
+ * Tables are CHANNEL-LAST: plane i is f32 [R][R][C] (row = the pair's second coordinate, column = its first: matMode [[0,1],[0,2],[1,2]]), line i is
+ * f32 [R][C] along coordinate vecMode[i] = 2 - i; C = 16 for the density set, 48 for the appearance set; basis is the Linear(144, 27) weight [27][144]
+ * (column = plane * 48 + component).  Sampling is grid_sample's bilinear / align_corners / zero padding: pixel = ((c + 1) / 2) * (R - 1), taps outside
+ * the table contribute 0.
+ *   sigma[m] = sum_i sum_c plane_i,c(m) * line_i,c(m)          (density set)
+ *   app[m]   = basis . cat_i(plane_i(m) * line_i(m))           (appearance set; the 144-wide product stays on chip)
+ *   pag_vm_supported            1 for density_n_comp == 16, app_n_comp == 48, app_dim == 27, 2 <= res <= 2048; 0 otherwise
+ *   pag_vm_bwd_workspace_bytes  bytes of `workspace` pag_vm_bwd needs for M samples (the basis gradient's per-workgroup partial sums); -1 for M < 0
+ *   pag_vm_fwd                  xyz f32 [M,3] -> sigma f32 [M] and / or app f32 [M,27]; either output may be NULL (not both)
+ *   pag_vm_bwd                  g_sigma f32 [M] and / or g_app f32 [M,27] (NULL = zero, not both) -> the table gradients, ADDED with float atomics into
+ *                               g_* (same layouts as the tables; the caller zero-fills them; a set whose upstream gradient is NULL may have NULL
+ *                               gradient tables), and g_basis f32 [27][144], OVERWRITTEN from partial sums added in a fixed order (needed with g_app).
+ *                               The taps are recomputed from xyz.  A sample whose upstream gradients are all exactly zero writes nothing.  No gradient
+ *                               with respect to xyz (the reference detaches the coordinates).
+ * Bad sizes, NULL buffers and a short workspace are refused before any launch; M == 0 is a no-op (nothing is written). */
+typedef struct pag_vm_args {
+    const float *density_plane[3], *density_line[3], *app_plane[3], *app_line[3], *basis;
+    int density_n_comp, app_n_comp, app_dim, res;
+    const float *xyz;
+    float *sigma, *app;
+    const float *g_sigma, *g_app;
+    float *g_density_plane[3], *g_density_line[3], *g_app_plane[3], *g_app_line[3], *g_basis;
+    void *workspace;
+    int64_t workspace_bytes;
+} pag_vm_args;
+int pag_vm_supported(int density_n_comp, int app_n_comp, int app_dim, int res);
+int64_t pag_vm_bwd_workspace_bytes(int64_t M);
+int pag_vm_fwd(const pag_vm_args *args, int64_t M, void *stream);
+int pag_vm_bwd(const pag_vm_args *args, int64_t M, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,8 @@
     grid  : HashGridHIP, PermutoGridHIP           (grids.py)    <- grids/hash_grid_torch.py, grids/permuto_grid.py
     nef   : PanopticDeltaNeF, PanopticNeF         (nef.py)      <- pc_nerf/panoptic_delta_nef.py, pc_nerf/panoptic_nef.py
     semantic: SemanticNeF, Occtree (the Semantic-NeRF baseline) (semantic_nef.py) <- pc_nerf/semantic_nerf.py, grids/occtree.py
+    lifting : PanopticLiftingNeF, TensoRF, VMSplitFeatureVolume, MLPRenderFeature (the Panoptic Lifting baseline) (panoptic_lifting.py)
+              <- pc_nerf/panoptic_lifting.py, grids/tensorf.py
     tracer: PanopticPackedRFTracer                (tracer.py)   <- tracers/panoptic_packed_rf_tracer.py
     core  : Rays, RenderBuffer, Pipeline          (core.py)     <- wisp.core / wisp.models.Pipeline
     pose  : BAPipeline (learnable extrinsics)     (ba_pipeline.py) <- pc_nerf/ba_pipeline.py
@@ -24,6 +26,7 @@ from .grids import HashGridHIP, PermutoGridHIP                     # noqa: F401
 from .nef import PanopticDeltaNeF, PanopticNeF, BasicDecoder                    # noqa: F401
 from .tracer import PanopticPackedRFTracer                         # noqa: F401
 from .semantic_nef import Occtree, SemanticNeF                     # noqa: F401
+from .panoptic_lifting import MLPRenderFeature, PanopticLiftingNeF, TensoRF, VMSplitFeatureVolume    # noqa: F401
 from .ba_pipeline import BAPipeline                                # noqa: F401
 from .dd import PanopticDDensityNeF, PanopticDDensityPackedRFTracer    # noqa: F401
 from .cluster import (ClusteringNeF, MeanShift, MeanShiftPanopticDDensityNeF, MeanShiftPanopticDeltaNeF,    # noqa: F401

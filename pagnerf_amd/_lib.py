@@ -87,6 +87,15 @@ class DeepMlpArgs(ctypes.Structure):
                 ("bwd_workspace", c_vp), ("bwd_workspace_bytes", c_i64)]
 
 
+class VmArgs(ctypes.Structure):
+    """pag_vm_args (include/pagnerf_hip.h)."""
+    _fields_ = [("density_plane", c_vp * 3), ("density_line", c_vp * 3), ("app_plane", c_vp * 3), ("app_line", c_vp * 3), ("basis", c_vp),
+                ("density_n_comp", c_i32), ("app_n_comp", c_i32), ("app_dim", c_i32), ("res", c_i32),
+                ("xyz", c_vp), ("sigma", c_vp), ("app", c_vp), ("g_sigma", c_vp), ("g_app", c_vp),
+                ("g_density_plane", c_vp * 3), ("g_density_line", c_vp * 3), ("g_app_plane", c_vp * 3), ("g_app_line", c_vp * 3), ("g_basis", c_vp),
+                ("workspace", c_vp), ("workspace_bytes", c_i64)]
+
+
 _SIGS = {
     "pag_abi_version": (c_i32, []),
     "pag_last_error_string": (ctypes.c_char_p, []),
@@ -188,6 +197,10 @@ _SIGS = {
     "pag_deep_mlp_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
     "pag_deep_mlp_fwd": (c_i32, [ctypes.POINTER(DeepMlpArgs), c_i64, c_vp]),
     "pag_deep_mlp_bwd": (c_i32, [ctypes.POINTER(DeepMlpArgs), c_i64, c_vp]),
+    "pag_vm_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    "pag_vm_bwd_workspace_bytes": (c_i64, [c_i64]),
+    "pag_vm_fwd": (c_i32, [ctypes.POINTER(VmArgs), c_i64, c_vp]),
+    "pag_vm_bwd": (c_i32, [ctypes.POINTER(VmArgs), c_i64, c_vp]),
 }
 
 EXPORTS = tuple(_SIGS)

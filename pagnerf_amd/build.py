@@ -40,6 +40,7 @@ SOURCES = {
     "cluster.hip": ["-ffp-contract=off"],    # mean-shift clustering: the fp64 distances and sums in the written op order
     "panoptic.hip": ["-ffp-contract=off"],   # panoptic evaluation: the f32 IoU quotients and fp64 distances in the written op order
     "map.hip": ["-ffp-contract=off"],        # map export: the unprojection in pose.hip's op order
+    "vm.hip": ["-ffp-contract=off"],         # TensoRF vector-matrix grid: grid_sample's bilinear op order
     "sparse.hip": [],                        # the touched-rows exchange's mask / plan / pack / unpack passes: integer and copy work only
 }
 
