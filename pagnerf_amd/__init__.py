@@ -1,6 +1,7 @@
 """pagnerf_amd - MI355X-native hot path of PAg-NeRF behind the kaolin-wisp grid / nef / tracer API.
 
     grid  : HashGridHIP, PermutoGridHIP           (grids.py)    <- grids/hash_grid_torch.py, grids/permuto_grid.py
+            TriplanarGridHIP                      (triplanar.py) <- wisp TriplanarGrid (grid_type: 'TriplanarGrid'; third party, own spec)
     nef   : PanopticDeltaNeF, PanopticNeF         (nef.py)      <- pc_nerf/panoptic_delta_nef.py, pc_nerf/panoptic_nef.py
     semantic: SemanticNeF, Occtree (the Semantic-NeRF baseline) (semantic_nef.py) <- pc_nerf/semantic_nerf.py, grids/occtree.py
     lifting : PanopticLiftingNeF, TensoRF, VMSplitFeatureVolume, MLPRenderFeature (the Panoptic Lifting baseline) (panoptic_lifting.py)
@@ -23,6 +24,7 @@ All compute goes through libpagnerf_hip.so (include/pagnerf_hip.h); there is no 
 """
 from .core import Rays, RenderBuffer, Pipeline, batch_render       # noqa: F401
 from .grids import HashGridHIP, PermutoGridHIP                     # noqa: F401
+from .triplanar import TriplanarGridHIP                            # noqa: F401
 from .nef import PanopticDeltaNeF, PanopticNeF, BasicDecoder                    # noqa: F401
 from .tracer import PanopticPackedRFTracer                         # noqa: F401
 from .semantic_nef import Occtree, SemanticNeF                     # noqa: F401

@@ -24,6 +24,7 @@ _DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
 c_i64, c_i32, c_u32, c_f32, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_float, ctypes.c_void_p
 c_fp = ctypes.POINTER(ctypes.c_float)
+c_ip = ctypes.POINTER(ctypes.c_int)
 
 
 class HeadCompositeArgs(ctypes.Structure):
@@ -201,6 +202,9 @@ _SIGS = {
     "pag_vm_bwd_workspace_bytes": (c_i64, [c_i64]),
     "pag_vm_fwd": (c_i32, [ctypes.POINTER(VmArgs), c_i64, c_vp]),
     "pag_vm_bwd": (c_i32, [ctypes.POINTER(VmArgs), c_i64, c_vp]),
+    "pag_triplanar_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_ip, c_fp, c_vp, c_i32, c_i64, c_i64, c_vp]),
+    "pag_triplanar_bwd_tables": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_ip, c_fp, c_vp, c_vp]),
+    "pag_triplanar_bwd_xyz": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_ip, c_fp, c_vp, c_vp]),
 }
 
 EXPORTS = tuple(_SIGS)

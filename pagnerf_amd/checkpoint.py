@@ -8,12 +8,16 @@ What maps one to one (same module / parameter names): the four (five) decoders `
     `HashEmbedder.embeddings[i].weight` in grids/hash_grid_torch.py:61-65); they are located by SHAPE under the
     `nef.grid.` / `nef.delta_grid.` prefixes: one `[L, capacity, F]` tensor, or L tensors `[2^log2T, F]` in level order;
     a `[L, 3]` tensor is the permutohedral per-level shift;
+  * a tri-plane grid (wisp TriplanarGrid, third party: names and shapes recalled, PARITY UNPINNED) - `features.{i}.fmx|fmy|fmz` [1, F, R, R]
+    per level, copied into / written from the flat channel-last buffer (triplanar.py);
   * occupancy - wisp's OctreeAS buffers (`blas_octree`, grids/permuto_grid.py:33-38): kaolin's SPC octree is one byte per
     node in breadth-first order, bit i of a byte = child i present, children in Morton order i = 4x + 2y + z (recalled from
     the public kaolin documentation; third party, PARITY UNPINNED).  octree_to_bits() expands it into the dense bitfield
     the march kernels read.
 """
 import torch
+
+from .triplanar import TriplanarGridHIP
 
 
 def octree_to_bits(octree, level):
@@ -101,6 +105,15 @@ def load_reference_state_dict(pipeline, state_dict, strict_decoders=True):
                 continue
             prefix = "nef.%s." % name
             parts = _grid_tensors(sd, prefix)
+            if isinstance(grid, TriplanarGridHIP):                       # wisp TriplanarGrid: features.{i}.fmx|fmy|fmz [1,F,R,R]
+                keys = [["features.%d.%s" % (i, n) for n in ("fmx", "fmy", "fmz")] for i in range(grid.num_lods)]
+                if all(k in parts for level in keys for k in level):
+                    grid.set_planes([[parts[k] for k in level] for level in keys])
+                    used.update(prefix + k for level in keys for k in level)
+                if "blas_octree" in parts:
+                    grid.blas_init_bits(octree_to_bits(parts["blas_octree"], grid.blas_level).to(grid.blas_bits.device))
+                    used.update(prefix + k for k in parts if k.startswith("blas_"))
+                continue
             L, T, F = grid.tables.shape
             whole = [k for k, v in parts.items() if tuple(v.shape) == (L, T, F)]
             per_level = sorted([k for k, v in parts.items() if tuple(v.shape) == (T, F)],
@@ -172,7 +185,11 @@ def save_reference_state_dict(pipeline, permuto_names=("lattice_values", "random
             continue
         prefix = "nef.%s." % name
         tab = grid.tables.detach().float().cpu()
-        if isinstance(grid, PermutoGridHIP):
+        if isinstance(grid, TriplanarGridHIP):
+            for i, level in enumerate(grid.planes(tab)):
+                for n, t in zip(("fmx", "fmy", "fmz"), level):
+                    out[prefix + "features.%d.%s" % (i, n)] = t.contiguous().clone()
+        elif isinstance(grid, PermutoGridHIP):
             out[prefix + "embedder." + permuto_names[0]] = tab.clone()
             out[prefix + "embedder." + permuto_names[1]] = grid.random_shift_per_level.detach().float().cpu().clone()
         else:

@@ -131,6 +131,8 @@ class OccupancyBLAS(nn.Module):
 
 
 class _GridBase(OccupancyBLAS):
+    offers_xcd8 = True       # interpolate_scaled(layout="xcd8", addend=...) is available; a grid without it sends the nef down its ungrouped path
+
     def __init__(self, feature_dim, base_lod=2, num_lods=1, interpolation_type="linear", multiscale_type="cat",
                  feature_std=0.0, feature_bias=0.0, blas_level=7, table_dtype=torch.float32, **kwargs):
         super().__init__(blas_level)

@@ -23,9 +23,11 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import ops
 from .grids import HashGridHIP, PermutoGridHIP
+from .triplanar import TriplanarGridHIP
 
 _GRIDS = {"HashGridTorch": HashGridHIP, "HashGridTinyCudaNN": HashGridHIP, "HashGrid": HashGridHIP,
-          "HashGridHIP": HashGridHIP, "PermutoGrid": PermutoGridHIP, "PermutoGridHIP": PermutoGridHIP}
+          "HashGridHIP": HashGridHIP, "PermutoGrid": PermutoGridHIP, "PermutoGridHIP": PermutoGridHIP,
+          "TriplanarGrid": TriplanarGridHIP, "TriplanarGridHIP": TriplanarGridHIP}
 
 
 class BasicDecoder(nn.Module):
@@ -112,6 +114,9 @@ class PanopticDeltaNeF(nn.Module):
             gkw.setdefault("half_coords", True)       # grids/hash_grid_tinycudann.py:36 (custom_fwd cast_inputs=torch.half)
         self.grid = _GRIDS[grid_type](feature_dim, base_lod=base_lod, num_lods=num_lods,
                                       interpolation_type=interpolation_type, multiscale_type="cat", **gkw)
+        if not self.grid.offers_xcd8 and multiscale_type == "cat" and (num_lods * feature_dim) % 8:
+            # the ungrouped decoder path reads the strided features directly: the fused decoders take input widths that are multiples of 8
+            raise ValueError("%s: num_lods * feature_dim = %d must be a multiple of 8 with multiscale_type='cat'" % (grid_type, num_lods * feature_dim))
         self.lod_weights = torch.ones(num_lods * feature_dim)
         if panoptic_features_type in ("delta", "separate", None):
             self.delta_grid = copy.deepcopy(self.grid)
@@ -194,7 +199,8 @@ class PanopticDeltaNeF(nn.Module):
 
     def _grouped(self):
         """(levels, feats) when the bf16 path can use the XCD-grouped feature layout, else None."""
-        if self.precision == "bf16" and self.multiscale_type == "cat" and ops.xcd8_supported(self.num_lods, self.feature_dim):
+        if self.precision == "bf16" and self.multiscale_type == "cat" and getattr(self.grid, "offers_xcd8", True) \
+                and ops.xcd8_supported(self.num_lods, self.feature_dim):
             return (self.num_lods, self.feature_dim)
         return None
 
