@@ -938,6 +938,25 @@ int pag_triplanar_bwd_tables(const float *xyz, int64_t M, const void *grad_out, 
 int pag_triplanar_bwd_xyz(const float *xyz, int64_t M, const float *tables, const void *grad_out, int grad_dtype, int64_t stride_m, int64_t stride_c,
                           int n_levels, int n_feat, const int *res, const float *feat_scale, float *d_xyz, void *stream);
 
+/* Lattice total variation (loss/regularizers.py:41-54, the grid TV terms of pc_nerf/trainer.py:556-574; additive, ABI 14): regularizer.hip.
+ * `values` is channel-last and contiguous, viewed as [d0, d1, d2, C] (the lattice extents of the input padded with trailing 1s, then the channels), dtype
+ * PAG_F32 / PAG_F16 / PAG_BF16; every difference, product and partial sum is f32, the final combine f64, every element offset 64-bit.
+ *   out[0] = (1 / d0) * sum over the axes and over the points p with a +1 neighbour of phi(v[p + e_axis] - v[p]),   phi = |.| (power 1) or (.)^2 (power 2)
+ * - EVERY axis is divided by d0, the reference's `values.shape[0]` (:43, :47).  An axis of extent 1 contributes nothing.
+ *   grad[p] = (upstream[0] / d0) * sum over the axes of [phi'(v[p] - v[p - e]) - phi'(v[p + e] - v[p])], a face without a neighbour has no term;
+ *   phi'(t) = sign(t) with sign(0) = 0 (power 1), 2 t (power 2).  grad has the dtype of values (the f32 result rounded once); upstream is DEVICE f32 [1].
+ *   Every term is scaled by s = upstream[0] * (1 / d0) on its own and the terms are added in the order of the tensor-op form's backward (an axis's two
+ *   faces first, then the axes last to first), so that a half gradient is the form's f32 gradient rounded.
+ * Sums: f32 per thread, a fixed butterfly per wave, the waves in order, one partial per workgroup in `workspace` (pag_tv_workspace_bytes bytes, a function
+ * of the sizes only), then one workgroup adds the partials in f64 in a fixed order.  No floating-point atomics: the same input gives the same bits.
+ * 16-byte channel vectors are used when C is a multiple of 4 (f32) / 8 (f16, bf16) and the buffers are 16-byte aligned, single elements otherwise.
+ * Extents < 1, C outside [1, 2^24], more than 2^46 elements, a power other than 1 or 2, a bad dtype, NULL buffers and a short workspace are refused
+ * (PAG_ERR_ARG) before any launch; pag_tv_workspace_bytes returns 0 for sizes that would be refused. */
+int64_t pag_tv_workspace_bytes(int64_t d0, int64_t d1, int64_t d2, int64_t C);
+int pag_tv_fwd(const void *values, int dtype, int64_t d0, int64_t d1, int64_t d2, int64_t C, int power, void *workspace, int64_t workspace_bytes,
+               float *out, void *stream);
+int pag_tv_bwd(const void *values, int dtype, int64_t d0, int64_t d1, int64_t d2, int64_t C, int power, const float *upstream, void *grad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

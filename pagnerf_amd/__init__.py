@@ -18,6 +18,8 @@
              pc_nerf/trainer.py:670-673, :750-772 (validation)
     map   : generate_pc_map_from_views, render_points_at_depth, map_points_from_buffers, generate_pc_map, get_dense_occupied_points,
             pinhole_base_rays, save_map (map_export.py) <- utils/render_map.py, main_interactive.py:109-129 (--save-map-only)
+    regularizers: tv_loss, tv_l1_loss, tv_l2_loss, grid_tv_loss, grid_tv_l1_loss, grid_tv_l2_loss, step_tv_terms (regularizers.py)
+             <- loss/regularizers.py:41-70, pc_nerf/trainer.py:556-574 (the grid total-variation terms)
     optim : Adam (torch.optim.Adam's interface on pag_adam_step) (optim.py) <- config_parser.py:667-673, trainer.py:583
 
 All compute goes through libpagnerf_hip.so (include/pagnerf_hip.h); there is no CPU fallback.
@@ -36,6 +38,8 @@ from .cluster import (ClusteringNeF, MeanShift, MeanShiftPanopticDDensityNeF, Me
 from .metrics import MulticlassIoU, PanopticQuality, clean_instances, panoptic_quality    # noqa: F401
 from .map_export import (MapAccumulator, generate_pc_map, generate_pc_map_from_views, get_dense_occupied_points,    # noqa: F401
                          map_points_from_buffers, pinhole_base_rays, render_points_at_depth, save_map)
+from .regularizers import (grid_tv_l1_loss, grid_tv_l2_loss, grid_tv_loss, step_tv_terms, tv_l1_loss, tv_l2_loss,    # noqa: F401
+                           tv_loss)
 from . import optim                                                # noqa: F401
 
 __version__ = "0.1.0"

@@ -205,6 +205,9 @@ _SIGS = {
     "pag_triplanar_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_ip, c_fp, c_vp, c_i32, c_i64, c_i64, c_vp]),
     "pag_triplanar_bwd_tables": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_ip, c_fp, c_vp, c_vp]),
     "pag_triplanar_bwd_xyz": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_ip, c_fp, c_vp, c_vp]),
+    "pag_tv_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
+    "pag_tv_fwd": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp]),
+    "pag_tv_bwd": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -12,6 +12,9 @@ inst_weight 0.1 x pagnerf_amd.loss.SupConLoss(temperature 0.07, pn_ratio 0.5) on
 semantic terms; instance accuracy is then nearest-centroid: held-out rays take the id whose mean normalised training-ray embedding is
 closest in cosine (inst_acc), and - the configs' own route - mean-shift clusters of the training rays named by their majority id
 (inst_acc_mean_shift, n_clusters; pagnerf_amd.cluster.MeanShift).  The default (nll) keeps the per-ray NLL instance term.
+
+--grid-tvl1 / --grid-tvl2 / --delta-grid-tvl1 / --delta-grid-tvl2 W add the grid total-variation terms of pc_nerf/trainer.py:556-574 with those weights
+(pagnerf_amd.step_tv_terms; the YAMLs' commented-out value is 1e-7) on a (--tv-edge-num-samples + 1)^3 lattice; all 0 (the default) leaves the step as it was.
 """
 import argparse
 import json
@@ -54,10 +57,19 @@ def run(precision, a, dev):
     contrastive = a.inst_loss == "sup_contrastive"
     if contrastive:
         nef.inst_softmax = False                                     # best_contrast_delta.yaml: inst_softmax false
+    tv = dict(grid_tvl1_reg=a.grid_tvl1, grid_tvl2_reg=a.grid_tvl2, delta_grid_tvl1_reg=a.delta_grid_tvl1, delta_grid_tvl2_reg=a.delta_grid_tvl2,
+              tv_window_size=a.tv_window_size, tv_edge_num_samples=a.tv_edge_num_samples)
+    if not any(tv[k] > 0.0 for k in ("grid_tvl1_reg", "grid_tvl2_reg", "delta_grid_tvl1_reg", "delta_grid_tvl2_reg")):
+        tv = None
     gen = torch.Generator().manual_seed(123)
     for step in range(a.steps):
         rays, gt = scene_rays(a.rays, gen, dev)
-        loss = contrastive_step(nef, tracer, opt, rays, gt, chans) if contrastive else bench.train_step(nef, tracer, opt, rays, gt, chans, 1)
+        if contrastive:
+            loss = contrastive_step(nef, tracer, opt, rays, gt, chans, tv)
+        elif tv is not None:
+            loss = nll_tv_step(nef, tracer, opt, rays, gt, chans, tv)
+        else:
+            loss = bench.train_step(nef, tracer, opt, rays, gt, chans, 1)
     gen = torch.Generator().manual_seed(999)
     rays, gt = scene_rays(4 * a.rays, gen, dev)
     with torch.no_grad():
@@ -98,9 +110,23 @@ def run(precision, a, dev):
     return out
 
 
-def contrastive_step(nef, tracer, opt, rays, gt, channels):
+def nll_tv_step(nef, tracer, opt, rays, gt, channels, tv):
+    """bench.train_step's all-channel step (rgb L1 x 10, semantic NLL x 0.1, instance NLL x 1000) + the grid total-variation terms (trainer.py:556-574)."""
+    from pagnerf_amd import step_tv_terms
+    from pagnerf_amd.loss import render_loss, NllTerm
+    opt.zero_grad(set_to_none=True)
+    rb = tracer(nef, channels=channels, rays=rays, stage="train")
+    loss, _ = render_loss(rb.rgb, gt["rgb"], 10.0, NllTerm(rb.semantics, gt["sem"], weight=0.1), NllTerm(rb.inst_embedding, gt["inst"], weight=1000.0))
+    loss = loss + step_tv_terms(nef, **tv)
+    loss.backward()
+    opt.step()
+    return loss
+
+
+def contrastive_step(nef, tracer, opt, rays, gt, channels, tv=None):
     """rgb L1 (weight 10) + semantic NLL (0.1) as bench.train_step forms them, + inst_weight 0.1 x SupConLoss on the rays that hit
-    (pc_nerf/trainer.py:499-503 with best_contrast_delta.yaml's weights)."""
+    (pc_nerf/trainer.py:499-503 with best_contrast_delta.yaml's weights); tv: the grid total-variation terms' options (trainer.py:556-574) or None."""
+    from pagnerf_amd import step_tv_terms
     from pagnerf_amd.loss import render_loss, NllTerm, SupConLoss
     opt.zero_grad(set_to_none=True)
     rb = tracer(nef, channels=channels, rays=rays, stage="train")
@@ -108,6 +134,8 @@ def contrastive_step(nef, tracer, opt, rays, gt, channels):
     emb = rb.inst_embedding.reshape(1, -1, rb.inst_embedding.shape[-1])
     ids = gt["inst"].reshape(1, -1)
     loss = loss + 0.1 * SupConLoss(temperature=0.07, pn_ratio=0.5)(emb, ids, reduction="mean", anchor_mask=ids >= 0)
+    if tv is not None:
+        loss = loss + step_tv_terms(nef, **tv)
     loss.backward()
     opt.step()
     return loss
@@ -150,6 +178,11 @@ if __name__ == "__main__":
                          "PSNR of the HIP render against it, next to both renders' PSNR against the ground truth")
     ap.add_argument("--inst-loss", choices=("nll", "sup_contrastive"), default="nll",
                     help="instance term: per-ray NLL on the softmaxed head (default), or the supervised-contrastive loss on a raw embedding")
+    for flag in ("--grid-tvl1", "--grid-tvl2", "--delta-grid-tvl1", "--delta-grid-tvl2"):
+        ap.add_argument(flag, type=float, default=0.0, metavar="W",
+                        help="weight of the %s_reg term of pc_nerf/trainer.py:556-574 (0: the term is not formed)" % flag[2:].replace("-", "_"))
+    ap.add_argument("--tv-window-size", type=float, default=0.0001, help="tv_window_size (the YAMLs' 0.0001): enters only the lattice's random first vertex")
+    ap.add_argument("--tv-edge-num-samples", type=int, default=100, help="tv_edge_num_samples (the YAMLs' 100): the lattice has this + 1 points per edge")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     import __graft_entry__ as ge
