@@ -957,6 +957,39 @@ int pag_tv_fwd(const void *values, int dtype, int64_t d0, int64_t d1, int64_t d2
                float *out, void *stream);
 int pag_tv_bwd(const void *values, int dtype, int64_t d0, int64_t d1, int64_t d2, int64_t C, int power, const float *upstream, void *grad, void *stream);
 
+/* Ray sampling of a device-resident multiview dataset (datasets/transforms/ray_sampler.py:17-40, the per-image indexing and collation of
+ * datasets/multiview_dataset.py:177-192; additive, ABI 14): sample.hip.  One launch draws slot_count pixels without replacement for each of B views and
+ * gathers the pixels' rows of up to PAG_SAMPLE_MAX_MODES modes into the collated batch.
+ *   state   DEVICE int64 [2] = {seed, draw}, read by the kernel (a captured graph replays with the draw that is there at replay time)
+ *   views   DEVICE int32 [B], the view of each batch row; repeats allowed; a view outside [0, num_views) yields zero rows and ray_idx -1
+ *   pixel of output row (b, j) = slot slot_begin + j of the first min(k, n) entries of the keyed permutation of [0, n) with key (seed, draw, views[b]):
+ *           pagnerf_amd.dataset.sample_indices is the definition (6-round balanced Feistel network on the smallest even bit width >= max(2,
+ *           bit_length(n - 1)), murmur3-finaliser round function and key schedule, cycle-walked into [0, n); uint32 arithmetic only), reproduced exactly.
+ *           Slot j depends on (seed, draw, view, n, j) alone - not on k, the slice or the launch shape.
+ *   mode    src is [num_views, n, row] (per_view != 0) or [n, row] (shared); dst is [B, slot_count, row_bytes]; row_bytes counts a DESTINATION row.
+ *           PAG_SAMPLE_COPY copies row_bytes bytes (any dtype); PAG_SAMPLE_U8_TO_F32 reads row_bytes / 4 uint8 and writes (float)u / 255.0f
+ *           (IEEE division, torch's CPU `x.float() / 255`), so row_bytes must be a multiple of 4.  Rows move at the widest of 16 / 8 / 4 / 2 / 1 bytes that
+ *           divides row_bytes and both base addresses (pag_sample_copy_width returns it; 4 or 1 source bytes per step for a conversion; 0 = refused).
+ *   ray_idx int64 [B, slot_count] or NULL: the pixel.   cam_idx int32 [B * slot_count] or NULL: views[b] of the row, the per-ray camera row that
+ *           pc_nerf/ba_pipeline.py:85-92 in its per-ray form takes.
+ * Source offsets are 64-bit.  No atomics, no workspace.  Refused (PAG_ERR_ARG) before any launch: n outside [1, 2^30], k < 1, B outside [0, 65535],
+ * num_views < 1, more than PAG_SAMPLE_MAX_MODES modes, row_bytes outside [1, 2^20], an unknown conversion or one that does not fit row_bytes, slot_begin < 0,
+ * slot_count < 0 or slot_begin + slot_count > min(k, n), NULL pointers.  B == 0 or slot_count == 0 is a no-op.
+ * pag_sample_advance: state[1] += 1 as a one-thread launch; inside a captured step the sequence is sample, ..., advance. */
+#define PAG_SAMPLE_MAX_MODES 12
+enum { PAG_SAMPLE_COPY = 0, PAG_SAMPLE_U8_TO_F32 = 1 };
+typedef struct pag_sample_mode {
+    const void *src;
+    void *dst;
+    int64_t row_bytes;
+    int32_t per_view;
+    int32_t convert;
+} pag_sample_mode;
+int pag_sample_copy_width(const void *src, const void *dst, int64_t row_bytes, int convert);
+int pag_sample_batch(const int64_t *state, const int32_t *views, int B, int num_views, int64_t n, int64_t k, int64_t slot_begin, int64_t slot_count,
+                     const pag_sample_mode *modes, int n_modes, int64_t *ray_idx, int32_t *cam_idx, void *stream);
+int pag_sample_advance(int64_t *state, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

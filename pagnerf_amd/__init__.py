@@ -20,6 +20,8 @@
             pinhole_base_rays, save_map (map_export.py) <- utils/render_map.py, main_interactive.py:109-129 (--save-map-only)
     regularizers: tv_loss, tv_l1_loss, tv_l2_loss, grid_tv_loss, grid_tv_l1_loss, grid_tv_l2_loss, step_tv_terms (regularizers.py)
              <- loss/regularizers.py:41-70, pc_nerf/trainer.py:556-574 (the grid total-variation terms)
+    dataset: DeviceMultiviewDataset, BatchSampler, SampleRays, sample_indices, epoch_views (dataset.py)
+             <- datasets/multiview_dataset.py:120-192, datasets/transforms/ray_sampler.py:17-40, pc_nerf/trainer.py:216-219 (the step's inputs)
     optim : Adam (torch.optim.Adam's interface on pag_adam_step) (optim.py) <- config_parser.py:667-673, trainer.py:583
 
 All compute goes through libpagnerf_hip.so (include/pagnerf_hip.h); there is no CPU fallback.
@@ -40,6 +42,7 @@ from .map_export import (MapAccumulator, generate_pc_map, generate_pc_map_from_v
                          map_points_from_buffers, pinhole_base_rays, render_points_at_depth, save_map)
 from .regularizers import (grid_tv_l1_loss, grid_tv_l2_loss, grid_tv_loss, step_tv_terms, tv_l1_loss, tv_l2_loss,    # noqa: F401
                            tv_loss)
+from .dataset import BatchSampler, DeviceMultiviewDataset, SampleRays, epoch_views, sample_indices    # noqa: F401
 from . import optim                                                # noqa: F401
 
 __version__ = "0.1.0"

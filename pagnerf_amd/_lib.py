@@ -97,6 +97,14 @@ class VmArgs(ctypes.Structure):
                 ("workspace", c_vp), ("workspace_bytes", c_i64)]
 
 
+class SampleMode(ctypes.Structure):
+    """pag_sample_mode (include/pagnerf_hip.h)."""
+    _fields_ = [("src", c_vp), ("dst", c_vp), ("row_bytes", c_i64), ("per_view", c_i32), ("convert", c_i32)]
+
+
+SAMPLE_MAX_MODES = 12
+SAMPLE_COPY, SAMPLE_U8_TO_F32 = 0, 1
+
 _SIGS = {
     "pag_abi_version": (c_i32, []),
     "pag_last_error_string": (ctypes.c_char_p, []),
@@ -208,6 +216,9 @@ _SIGS = {
     "pag_tv_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     "pag_tv_fwd": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp]),
     "pag_tv_bwd": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "pag_sample_copy_width": (c_i32, [c_vp, c_vp, c_i64, c_i32]),
+    "pag_sample_batch": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(SampleMode), c_i32, c_vp, c_vp, c_vp]),
+    "pag_sample_advance": (c_i32, [c_vp, c_vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -43,6 +43,7 @@ SOURCES = {
     "vm.hip": ["-ffp-contract=off"],         # TensoRF vector-matrix grid: grid_sample's bilinear op order
     "triplanar.hip": ["-ffp-contract=off"],  # tri-plane grid: grid_sample's bilinear / reflection op order
     "sparse.hip": [],                        # the touched-rows exchange's mask / plan / pack / unpack passes: integer and copy work only
+    "sample.hip": [],                        # the dataset's ray sampling: keyed permutation and row gather, integer and copy work only
 }
 
 

@@ -1857,3 +1857,46 @@ def map_select(points_in, points, count, value=None, threshold=0.0, inst=None, i
     ws = _map_workspace(n, pin.device)
     _call("pag_map_select", pin.data_ptr(), n, val.data_ptr() if val is not None else None, float(threshold), ip, I, stride, idp, points.data_ptr(),
           ids_out.data_ptr() if ids_out is not None else None, points.shape[0], count.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
+
+
+def sample_copy_width(src_ptr, dst_ptr, row_bytes, convert=L.SAMPLE_COPY):
+    """Bytes per copy element pag_sample_batch uses for a mode with these base addresses and destination row size (16 / 8 / 4 / 2 / 1; for the uint8 -> f32
+    conversion 4 or 1 source bytes per step); 0 = the mode would be refused.  Host arithmetic only."""
+    return L.load().pag_sample_copy_width(src_ptr, dst_ptr, int(row_bytes), int(convert))
+
+
+def sample_mode_array(modes):
+    """[(src tensor, dst tensor, destination row bytes, per_view, convert)] -> ctypes array of pag_sample_mode."""
+    if len(modes) > L.SAMPLE_MAX_MODES:
+        raise RuntimeError("sample_batch: %d modes, at most %d per launch" % (len(modes), L.SAMPLE_MAX_MODES))
+    arr = (L.SampleMode * max(1, len(modes)))()
+    for a, (src, dst, row_bytes, per_view, convert) in zip(arr, modes):
+        _check_gpu(src, dst)
+        if not (src.is_contiguous() and dst.is_contiguous()):
+            raise RuntimeError("sample_batch: modes and outputs must be contiguous")
+        a.src, a.dst, a.row_bytes, a.per_view, a.convert = src.data_ptr(), dst.data_ptr(), int(row_bytes), int(bool(per_view)), int(convert)
+    return arr
+
+
+def sample_batch(state, views, num_views, n, k, slot_begin, slot_count, modes, ray_idx=None, cam_idx=None):
+    """datasets/transforms/ray_sampler.py:17-40 + the collation of datasets/multiview_dataset.py:177-192 as one launch (pag_sample_batch): for each of
+    the B views (device int32 [B]) slots [slot_begin, slot_begin + slot_count) of the keyed permutation of [0, n) under the device state int64 [2] =
+    {seed, draw}, and the rows of every mode at those pixels.  modes: a ctypes array from sample_mode_array (with its length) or the list it takes."""
+    _check_gpu(state, views, ray_idx, cam_idx)
+    if state.dtype != torch.int64 or state.numel() != 2 or views.dtype != torch.int32 or views.dim() != 1 or not views.is_contiguous():
+        raise RuntimeError("sample_batch: state int64 [2], views int32 [B]")
+    B = views.shape[0]
+    if (ray_idx is not None and (ray_idx.dtype != torch.int64 or ray_idx.numel() != B * slot_count or not ray_idx.is_contiguous())) or \
+            (cam_idx is not None and (cam_idx.dtype != torch.int32 or cam_idx.numel() != B * slot_count or not cam_idx.is_contiguous())):
+        raise RuntimeError("sample_batch: ray_idx int64 [B, slot_count], cam_idx int32 [B * slot_count]")
+    arr, n_modes = modes if isinstance(modes, tuple) else (sample_mode_array(modes), len(modes))
+    _call("pag_sample_batch", state.data_ptr(), views.data_ptr(), B, int(num_views), int(n), int(k), int(slot_begin), int(slot_count), arr, n_modes,
+          ray_idx.data_ptr() if ray_idx is not None else None, cam_idx.data_ptr() if cam_idx is not None else None, L.stream())
+
+
+def sample_advance(state):
+    """state[1] += 1 on the device (pag_sample_advance): the next draw, inside a captured graph too."""
+    _check_gpu(state)
+    if state.dtype != torch.int64 or state.numel() != 2:
+        raise RuntimeError("sample_advance: state int64 [2]")
+    _call("pag_sample_advance", state.data_ptr(), L.stream())

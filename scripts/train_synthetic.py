@@ -15,6 +15,11 @@ closest in cosine (inst_acc), and - the configs' own route - mean-shift clusters
 
 --grid-tvl1 / --grid-tvl2 / --delta-grid-tvl1 / --delta-grid-tvl2 W add the grid total-variation terms of pc_nerf/trainer.py:556-574 with those weights
 (pagnerf_amd.step_tv_terms; the YAMLs' commented-out value is 1e-7) on a (--tv-edge-num-samples + 1)^3 lattice; all 0 (the default) leaves the step as it was.
+
+--from-images V HxW trains from IMAGES instead of fresh random rays: the same closed form rendered into V images of H x W pixels from V fixed cameras,
+held in a pagnerf_amd.DeviceMultiviewDataset and dealt by pagnerf_amd.BatchSampler (--batch-images views per step, --rays / that many pixels of each,
+drawn without replacement by the sampling kernel) - the input side of pc_nerf/trainer.py:216-219 and :388-423.  --panoptic-epoch-start E keeps the
+trainer's schedule: rgb alone before epoch E.  Without the flag nothing changes.
 """
 import argparse
 import json
@@ -34,6 +39,14 @@ def scene_rays(n, gen, dev):
     o = torch.cat([(torch.rand(n, 2, generator=gen) - 0.5) * 1.2, torch.full((n, 1), 0.95)], 1)
     tgt = torch.cat([(torch.rand(n, 2, generator=gen) - 0.5) * 1.4, torch.full((n, 1), -0.2)], 1)
     d = torch.nn.functional.normalize(tgt - o, dim=-1)
+    rgb, sem, inst = scene_truth(o, d)
+    rays = pagnerf_amd.Rays(o.to(dev), d.to(dev), dist_min=0.0, dist_max=1.9)
+    return rays, dict(rgb=rgb.to(dev), sem=sem.to(dev), inst=inst.to(dev))
+
+
+def scene_truth(o, d):
+    """Closed-form ground truth of the rays (o, d) [n,3] on the CPU: colour [n,3], semantic class and instance id [n] (-100 where the ray misses)."""
+    n = o.shape[0]
     # sphere |p| = 0.5
     b = (o * d).sum(-1)
     c = (o * o).sum(-1) - 0.25
@@ -45,11 +58,59 @@ def scene_rays(n, gen, dev):
     sem = torch.where(hit, 1 + (p[:, 0] > 0).long() + 2 * (p[:, 1] > 0).long(), torch.full((n,), -100, dtype=torch.long))     # 1..4
     lon = torch.atan2(p[:, 1], p[:, 0])
     inst = torch.where(hit, 1 + ((lon + math.pi) / (2 * math.pi) * 12).long().clamp(0, 11), torch.full((n,), -100, dtype=torch.long))
-    rays = pagnerf_amd.Rays(o.to(dev), d.to(dev), dist_min=0.0, dist_max=1.9)
-    return rays, dict(rgb=rgb.to(dev), sem=sem.to(dev), inst=inst.to(dev))
+    return rgb, sem, inst
+
+
+def scene_images(V, H, W, dev):
+    """The scene as a dataset: V cameras on a circle of radius 0.45 at height 0.95 looking down, each pixel's ray through a regular H x W lattice of the
+    plane z = -0.2 (the plane scene_rays aims at); modes imgs [V,H,W,3], semantics / instance [V,H,W,1] int64, rays [V,H*W,3]."""
+    import pagnerf_amd
+    ang = torch.arange(V, dtype=torch.float32) * (2 * math.pi / V)
+    cam = torch.stack([0.45 * torch.cos(ang), 0.45 * torch.sin(ang), torch.full((V,), 0.95)], -1)                       # [V,3]
+    ys, xs = torch.meshgrid((torch.arange(H) + 0.5) / H - 0.5, (torch.arange(W) + 0.5) / W - 0.5, indexing="ij")
+    tgt = torch.stack([xs * 1.4, ys * 1.4, torch.full_like(xs, -0.2)], -1).reshape(1, H * W, 3)
+    o = cam[:, None, :].expand(V, H * W, 3).contiguous()
+    d = torch.nn.functional.normalize(tgt - o, dim=-1)
+    rgb, sem, inst = scene_truth(o.reshape(-1, 3), d.reshape(-1, 3))
+    data = dict(imgs=rgb.reshape(V, H, W, 3), semantics=sem.reshape(V, H, W, 1), instance=inst.reshape(V, H, W, 1),
+                rays=pagnerf_amd.Rays(o, d, dist_min=0.0, dist_max=1.9), filenames=["view_%03d" % v for v in range(V)])
+    return pagnerf_amd.DeviceMultiviewDataset(data, dev)
+
+
+def batch_to_step(batch):
+    """A collated batch of the sampler -> (rays [B*k], targets) as bench.train_step takes them (pc_nerf/trainer.py:396-422 flattens the same way)."""
+    import pagnerf_amd
+    r = batch["rays"]
+    rays = pagnerf_amd.Rays(r.origins.reshape(-1, 3), r.dirs.reshape(-1, 3), dist_min=r.dist_min, dist_max=r.dist_max)
+    return rays, dict(rgb=batch["imgs"].reshape(-1, 3), sem=batch["semantics"].reshape(-1), inst=batch["instance"].reshape(-1))
+
+
+def train_from_images(precision, a, dev, ds, steps, batch_images=None):
+    """`steps` steps of bench.train_step on batches of a BatchSampler over `ds` (whole batches only, so that every step has --rays rays).
+    a.panoptic_epoch_start (default 0): the epoch from which the semantic and instance terms are formed, as sem_epoch_start / inst_epoch_start of
+    pc_nerf/trainer.py:400-432 (both 601 in configs/bup20/best.yaml); earlier epochs render and supervise rgb alone.
+    -> (nef, tracer, the losses as one device tensor)."""
+    import pagnerf_amd
+    args = bench.parse(["--rays", str(a.rays), "--samples", str(a.samples), "--grid", a.grid, "--precision", precision, "--graphs", getattr(a, "graphs", "on")])
+    nef, tracer = bench.make_model(args, dev, seed=0), bench.make_tracer(args)
+    opt = bench.make_optimizer(nef)
+    start = int(getattr(a, "panoptic_epoch_start", 0))
+    B = min(batch_images or a.batch_images, ds.num_imgs)
+    sampler = pagnerf_amd.BatchSampler(ds, batch_size=B, num_samples=max(1, a.rays // B), seed=123, drop_last=True)
+    losses = []
+    while len(losses) < steps:
+        chans = ["rgb", "semantics", "inst_embedding"] if sampler.epoch >= start else ["rgb"]
+        for batch in sampler:
+            rays, gt = batch_to_step(batch)
+            losses.append(bench.train_step(nef, tracer, opt, rays, gt, chans, 1).detach())
+            if len(losses) == steps:
+                break
+    return nef, tracer, torch.stack(losses)
 
 
 def run(precision, a, dev):
+    if getattr(a, "from_images", None):
+        return run_from_images(precision, a, dev)
     args = bench.parse(["--rays", str(a.rays), "--samples", str(a.samples), "--grid", a.grid, "--precision", precision])
     nef, tracer = bench.make_model(args, dev, seed=0), bench.make_tracer(args)
     opt = bench.make_optimizer(nef)
@@ -108,6 +169,22 @@ def run(precision, a, dev):
     if contrastive:
         out.update(inst_acc_mean_shift=round(float((ms_pred == gt["inst"])[hit].float().mean()), 4), n_clusters=n_clusters)
     return out
+
+
+def run_from_images(precision, a, dev):
+    """--from-images: train through the dataset and its sampler, then score on the held-out random rays of the default path."""
+    import pagnerf_amd
+    V, (H, W) = int(a.from_images[0]), (int(x) for x in a.from_images[1].lower().split("x"))
+    ds = scene_images(V, H, W, dev)
+    nef, tracer, losses = train_from_images(precision, a, dev, ds, a.steps)
+    rays, gt = scene_rays(4 * a.rays, torch.Generator().manual_seed(999), dev)
+    with torch.no_grad():
+        rb = pagnerf_amd.batch_render(pagnerf_amd.Pipeline(nef, tracer), rays, channels=["rgb", "semantics", "inst_embedding"], render_batch=a.rays)
+    mse = float(((rb.rgb - gt["rgb"]) ** 2).mean())
+    hit = gt["inst"] >= 0
+    return dict(precision=precision, images=[V, H, W], dataset_bytes=ds.nbytes, first_loss=float(losses[0]), final_loss=float(losses[-1]),
+                psnr_db=round(-10 * math.log10(mse), 2), sem_acc=round(float((rb.semantics.argmax(-1) == gt["sem"])[gt["sem"] >= 0].float().mean()), 4),
+                inst_acc=round(float((rb.inst_embedding.argmax(-1) == gt["inst"])[hit].float().mean()), 4))
 
 
 def nll_tv_step(nef, tracer, opt, rays, gt, channels, tv):
@@ -183,7 +260,16 @@ if __name__ == "__main__":
                         help="weight of the %s_reg term of pc_nerf/trainer.py:556-574 (0: the term is not formed)" % flag[2:].replace("-", "_"))
     ap.add_argument("--tv-window-size", type=float, default=0.0001, help="tv_window_size (the YAMLs' 0.0001): enters only the lattice's random first vertex")
     ap.add_argument("--tv-edge-num-samples", type=int, default=100, help="tv_edge_num_samples (the YAMLs' 100): the lattice has this + 1 points per edge")
+    ap.add_argument("--from-images", nargs=2, metavar=("V", "HxW"), default=None,
+                    help="train from V rendered images of H x W pixels through DeviceMultiviewDataset + BatchSampler instead of fresh random rays")
+    ap.add_argument("--batch-images", type=int, default=None, help="--from-images: views per step (default 6, best.yaml's batch size)")
+    ap.add_argument("--panoptic-epoch-start", type=int, default=0, metavar="E",
+                    help="--from-images: epochs before E train rgb alone, as sem_epoch_start / inst_epoch_start do in the trainer (best.yaml: 601); 0 = all "
+                         "terms from the first step, like the default path")
     a = ap.parse_args()
+    if a.from_images is None and (a.batch_images is not None or a.panoptic_epoch_start):
+        ap.error("--batch-images and --panoptic-epoch-start belong to --from-images")
+    a.batch_images = 6 if a.batch_images is None else a.batch_images
     dev = torch.device("cuda:0")
     import __graft_entry__ as ge
     ge.build()
