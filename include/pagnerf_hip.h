@@ -709,6 +709,29 @@ int pag_panoptic_clean(const void *ids, int dtype, int64_t H, int64_t W, int64_t
 int pag_confusion_matrix(const void *preds, int preds_dtype, const int64_t *preds_strides, const void *target, int target_dtype,
                          const int64_t *target_strides, const int64_t *shape, int C, int64_t *confmat, void *stream);
 
+/* Workspace of pag_mask_ap_update (0 past the limits: 1 <= H*W <= 2^28, 1 <= max_detections <= 4096): two 8192-slot id tables and a dense
+ * [max_detections, 4096] count array, whatever the image size - nothing of it grows with ids * H * W. */
+int64_t pag_mask_ap_workspace_bytes(int64_t H, int64_t W, int max_detections);
+
+/* One image of the mask mAP of pc_nerf/trainer.py:674-675, :794-798, :839-843 (MeanAveragePrecision(iou_type="segm") with one class and every score
+ * 1.0), from label images instead of [K, H, W] mask stacks.  pred, pred_raw, target: [H, W] id images (int32 / int64 `*_dtype`, element (y, x) at
+ * y*stride_y + x*stride_x; never written).
+ * Detections: the distinct ids of pred_raw in ascending order without the smallest (mask_ids[1:], :753-755), the first max_detections of them; the
+ *   mask of one is the pixels of pred with its id (possibly none: :766-767 keeps zeroed masks).  With empty_detection_if_single_id, a pred_raw of
+ *   one distinct id gives one empty detection (:780-781).  Ground truths: the distinct ids of target without the smallest (gt_ids[1:], :791-792).
+ * IoU = double(i) / double(a_d + a_g - i) of the exact integer counts when i > 0, else 0.  Matching, per threshold of the host array thresholds
+ *   f64 [10] (passed to the launch by value), detections in order: the not yet matched ground truth of the largest IoU >= min(t, 1 - 1e-10), the
+ *   later one on a tie (COCOeval's greedy rule).
+ * slots i32 [max_detections] (device) receives one word per detection - bit 0 present, bit 1 + k matched at threshold k - and 0 in the slots past
+ * the last detection; *npig i64 (device) += the number of ground truths.  More than 4096 distinct ids in pred_raw or in target, the id INT64_MIN,
+ * or an id of pred that pred_raw lacks: the bit (1, 1, 2) is OR-ed into *state_flags i32 (device) and slots and npig are left untouched.
+ * Six launches, no host synchronisation, integer sums only (bitwise reproducible), every probe and id loop bounded by the table capacity. */
+int pag_mask_ap_update(const void *pred, int pred_dtype, int64_t pred_stride_y, int64_t pred_stride_x, const void *pred_raw, int raw_dtype,
+                       int64_t raw_stride_y, int64_t raw_stride_x, const void *target, int target_dtype, int64_t target_stride_y,
+                       int64_t target_stride_x, int64_t H, int64_t W, int max_detections, int empty_detection_if_single_id,
+                       const double *thresholds, void *workspace, int64_t workspace_bytes, int32_t *slots, int64_t *npig, int32_t *state_flags,
+                       void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Panoptic point-cloud map export (utils/render_map.py; main_interactive.py:109-129 `--save-map-only`): the reduction of rendered rays / dense lattice
  * rows to the kept map points as an ORDERED APPEND behind a running device counter.  Kept rows land in row order behind *count (i64 [1], device),

@@ -16,6 +16,8 @@
              utils/embedding.py, pc_nerf/clustering_nef.py
     metrics: PanopticQuality, panoptic_quality, clean_instances, MulticlassIoU (metrics.py) <- utils/metrics/panoptic_quality{,_func}.py,
              pc_nerf/trainer.py:670-673, :750-772 (validation)
+             MaskMeanAveragePrecision, PeakSignalNoiseRatio, ValidationMetrics (metrics.py) <- pc_nerf/trainer.py:651-941 (evaluate_metrics:
+             the mask mAP of :674-675 / :794-798, the PSNR of :677 / :708, and the validation row of :898-934)
     map   : generate_pc_map_from_views, render_points_at_depth, map_points_from_buffers, generate_pc_map, get_dense_occupied_points,
             pinhole_base_rays, save_map (map_export.py) <- utils/render_map.py, main_interactive.py:109-129 (--save-map-only)
     regularizers: tv_loss, tv_l1_loss, tv_l2_loss, grid_tv_loss, grid_tv_l1_loss, grid_tv_l2_loss, step_tv_terms (regularizers.py)
@@ -37,7 +39,8 @@ from .ba_pipeline import BAPipeline                                # noqa: F401
 from .dd import PanopticDDensityNeF, PanopticDDensityPackedRFTracer    # noqa: F401
 from .cluster import (ClusteringNeF, MeanShift, MeanShiftPanopticDDensityNeF, MeanShiftPanopticDeltaNeF,    # noqa: F401
                       MeanShiftPanopticNeF, estimate_bandwidth, mean_class_embedding)
-from .metrics import MulticlassIoU, PanopticQuality, clean_instances, panoptic_quality    # noqa: F401
+from .metrics import (MaskMeanAveragePrecision, MulticlassIoU, PanopticQuality, PeakSignalNoiseRatio, ValidationMetrics,    # noqa: F401
+                      clean_instances, panoptic_quality)
 from .map_export import (MapAccumulator, generate_pc_map, generate_pc_map_from_views, get_dense_occupied_points,    # noqa: F401
                          map_points_from_buffers, pinhole_base_rays, render_points_at_depth, save_map)
 from .regularizers import (grid_tv_l1_loss, grid_tv_l2_loss, grid_tv_loss, step_tv_terms, tv_l1_loss, tv_l2_loss,    # noqa: F401

@@ -191,6 +191,9 @@ _SIGS = {
     "pag_panoptic_clean_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "pag_panoptic_clean": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i64, ctypes.c_double, c_vp, c_i64, c_vp, c_vp]),
     "pag_confusion_matrix": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "pag_mask_ap_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "pag_mask_ap_update": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp,
+                                   c_i64, c_vp, c_vp, c_vp, c_vp]),
     "pag_map_workspace_bytes": (c_i64, [c_i64]),
     "pag_map_points": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp,
                                c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),

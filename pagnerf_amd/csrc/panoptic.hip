@@ -29,6 +29,11 @@
 //
 //   cm_kernel           confusion matrix [target, pred] of the semantic labels: LDS histogram per workgroup for C <= 64, wave-aggregated global
 //                       atomics above
+//
+//   ap_ids_kernel       mask mAP (trainer.py:794-798): per pixel, the ids of pred_raw and of target into two 8192-slot tables
+//   ap_rank_kernel      one workgroup per table: ids compacted and sorted ascending in LDS, rank = position - 1 per slot
+//   ap_pair_kernel      per pixel: (detection rank of the pred id, ground-truth rank of the target id) counted in a dense [max_det, 4096] array
+//   ap_match_kernel     one wave per IoU threshold: fp64 IoUs of exact integers, COCOeval's greedy matching, one slot word per detection
 #include "common.h"
 
 namespace {
@@ -619,6 +624,224 @@ inline unsigned pn_grid(int64_t n, int64_t per_block, unsigned max_blocks) {
     return (unsigned)(g < 1 ? 1 : g < max_blocks ? g : max_blocks);
 }
 
+// ================================================================================================ mask mean average precision
+// One image of MeanAveragePrecision(iou_type="segm") as the trainer feeds it (trainer.py:674-675, :794-798, :839-843): one class, every score 1, the
+// masks given as label images.  The masks of one label image are disjoint, so the per-id areas and the pairwise intersection counts of two label
+// images carry everything the [K, H, W] mask stacks do.  The id tables hold AP_CAP slots whatever the image size; more than AP_MAX_IDS distinct
+// ids on either side is flagged and the update dropped.
+constexpr uint32_t AP_CAP = 8192;             // slots of an id table: twice AP_MAX_IDS, so a legal image never fills it
+constexpr int AP_MAX_IDS = 4096;              // distinct ids per label image, the smallest included
+constexpr int AP_THRESHOLDS = 10;
+constexpr int AP_FLAG_IDS = 1;                // more than AP_MAX_IDS distinct ids, or the id INT64_MIN (its key is PN_EMPTY)
+constexpr int AP_FLAG_PRED_ID = 2;            // an id of pred that pred_raw lacks
+
+struct ApWs {
+    int32_t *flags;                  // [1] this call's flags
+    int32_t *n_raw, *n_tgt;          // [1] distinct ids of pred_raw / target
+    uint32_t *cr, *ct;               // [AP_CAP] pixels per id
+    int32_t *rr, *rt;                // [AP_CAP] per slot: position of the id in ascending order - 1 (the smallest id: -1)
+    uint32_t *area_g;                // [AP_MAX_IDS] ground-truth areas by rank
+    uint32_t *inter;                 // [max_det][AP_MAX_IDS] pixels of detection d (rank in pred_raw) with target column c = rank + 1 (0: the smallest
+                                     //                       target id, which is no ground truth); a row's sum is the detection's area in pred
+    unsigned long long *kr, *kt;     // [AP_CAP] id keys (cl_key) of pred_raw / target
+};
+
+__host__ inline int64_t ap_zero_bytes(int max_det) { return pn_align(256 + 4 * 4 * (int64_t)AP_CAP + 4 * (int64_t)AP_MAX_IDS * (1 + (int64_t)max_det)); }
+__host__ inline int64_t ap_ws_bytes(int max_det) { return ap_zero_bytes(max_det) + pn_align(2 * 8 * (int64_t)AP_CAP); }
+
+__host__ inline ApWs ap_ws(void *base, int max_det) {
+    unsigned char *p = reinterpret_cast<unsigned char *>(base);
+    ApWs w;
+    w.flags = reinterpret_cast<int32_t *>(p);
+    w.n_raw = w.flags + 1;
+    w.n_tgt = w.flags + 2;
+    w.cr = reinterpret_cast<uint32_t *>(p + 256);
+    w.ct = w.cr + AP_CAP;
+    w.rr = reinterpret_cast<int32_t *>(w.ct + AP_CAP);
+    w.rt = w.rr + AP_CAP;
+    w.area_g = reinterpret_cast<uint32_t *>(w.rt + AP_CAP);
+    w.inter = w.area_g + AP_MAX_IDS;
+    w.kr = reinterpret_cast<unsigned long long *>(p + ap_zero_bytes(max_det));
+    w.kt = w.kr + AP_CAP;
+    return w;
+}
+
+struct ApImg {
+    const void *ptr;
+    int dtype;
+    int64_t sy, sx;
+};
+
+struct ApThr {
+    double t[AP_THRESHOLDS];
+};
+
+// Pixel pass 1: the distinct ids of pred_raw and of target into their tables, with pixel counts.
+__global__ __launch_bounds__(256) void ap_ids_kernel(ApImg R, ApImg T, int64_t H, int64_t W, ApWs w) {
+    const int64_t N = H * W;
+    const int lane = __lane_id();
+    bool bad = false;
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); base < N; base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + lane;
+        const bool on = i < N;
+        long long vr = 0, vt = 0;
+        if (on) {
+            const int64_t y = i / W, x = i - y * W;
+            vr = pn_ld(R.ptr, R.dtype, y * R.sy + x * R.sx);
+            vt = pn_ld(T.ptr, T.dtype, y * T.sy + x * T.sx);
+            bad |= vr == INT64_MIN || vt == INT64_MIN;
+        }
+        pn_wave_insert_count(w.kr, w.cr, AP_CAP, cl_key(vr), on);
+        pn_wave_insert_count(w.kt, w.ct, AP_CAP, cl_key(vt), on);
+    }
+    if (bad) atomicOr(w.flags, AP_FLAG_IDS);
+}
+
+// Workgroup 0: pred_raw's table, workgroup 1: target's.  The ids are compacted into LDS and sorted ascending (cl_key keeps the order of the signed
+// ids); every slot gets rank = position - 1, and the target's areas are laid out by rank.
+__global__ __launch_bounds__(256) void ap_rank_kernel(ApWs w) {
+    __shared__ unsigned long long s_k[AP_MAX_IDS];
+    __shared__ int s_n;
+    const bool tgt = blockIdx.x == 1;
+    const unsigned long long *keys = tgt ? w.kt : w.kr;
+    const uint32_t *counts = tgt ? w.ct : w.cr;
+    int32_t *rank = tgt ? w.rt : w.rr;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    for (uint32_t s = threadIdx.x; s < AP_CAP; s += blockDim.x) {
+        const unsigned long long k = keys[s];
+        if (k == PN_EMPTY) continue;
+        const int i = atomicAdd(&s_n, 1);
+        if (i < AP_MAX_IDS) s_k[i] = k;
+    }
+    __syncthreads();
+    const int n = s_n;
+    if (n > AP_MAX_IDS) {                                          // the same for every thread
+        if (threadIdx.x == 0) atomicOr(w.flags, AP_FLAG_IDS);
+        return;
+    }
+    int n2 = 1;
+    while (n2 < n) n2 <<= 1;
+    for (int i = n + threadIdx.x; i < n2; i += blockDim.x) s_k[i] = PN_EMPTY;      // padding sorts last
+    __syncthreads();
+    for (int k = 2; k <= n2; k <<= 1)                              // bitonic sort; n2 <= AP_MAX_IDS bounds every loop
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < n2; i += blockDim.x) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const unsigned long long a = s_k[i], b = s_k[l];
+                    if ((a > b) == ((i & k) == 0)) {
+                        s_k[i] = b;
+                        s_k[l] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    for (int p = threadIdx.x; p < n; p += blockDim.x) {
+        const int64_t s = pn_find(keys, AP_CAP, s_k[p]);
+        if (s < 0) continue;
+        rank[s] = p - 1;
+        if (tgt && p >= 1) w.area_g[p - 1] = counts[s];
+    }
+    if (threadIdx.x == 0) *(tgt ? w.n_tgt : w.n_raw) = n;
+}
+
+// Pixel pass 2: the (detection, ground truth) counts.  The lanes of a wave that share (pred id, target id) elect a leader, which looks both ranks up
+// and adds the lane count once.
+__global__ __launch_bounds__(256) void ap_pair_kernel(ApImg P, ApImg T, int64_t H, int64_t W, int max_det, ApWs w) {
+    if (*w.flags & AP_FLAG_IDS) return;                            // set by an earlier launch: there are no ranks
+    const int64_t N = H * W;
+    const int lane = __lane_id();
+    bool missing = false;
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); base < N; base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + lane;
+        const bool on = i < N;
+        unsigned long long kp = 0, kt = 0;
+        if (on) {
+            const int64_t y = i / W, x = i - y * W;
+            kp = cl_key(pn_ld(P.ptr, P.dtype, y * P.sy + x * P.sx));
+            kt = cl_key(pn_ld(T.ptr, T.dtype, y * T.sy + x * T.sx));
+        }
+        unsigned long long pending = __ballot(on);
+        while (pending) {
+            const int leader = __ffsll((long long)pending) - 1;
+            const unsigned long long lp = __shfl(kp, leader), lt = __shfl(kt, leader);
+            const unsigned long long m = __ballot(on && kp == lp && kt == lt);
+            if (lane == leader) {
+                const int64_t sd = pn_find(w.kr, AP_CAP, lp), sg = pn_find(w.kt, AP_CAP, lt);
+                if (sd < 0) missing = true;
+                else if (sg >= 0) {
+                    const int d = w.rr[sd], c = w.rt[sg] + 1;
+                    if (d >= 0 && d < max_det && c >= 0 && c < AP_MAX_IDS) atomicAdd(&w.inter[(int64_t)d * AP_MAX_IDS + c], (uint32_t)__popcll(m));
+                }
+            }
+            pending &= ~m;
+        }
+    }
+    if (missing) atomicOr(w.flags, AP_FLAG_PRED_ID);
+}
+
+// One workgroup, one wave per IoU threshold.  Detections are visited in ascending id; the lanes of a wave go over the ground truths, lane l owning
+// g = l, l + 64, ... with their matched bits in one 64-bit register.  COCOeval's greedy rule: the unmatched ground truth of the largest IoU that is
+// >= min(t, 1 - 1e-10), the later one on a tie.
+__global__ __launch_bounds__(64 * AP_THRESHOLDS) void ap_match_kernel(ApWs w, int max_det, int empty_if_single, ApThr thr, int32_t *slots,
+                                                                      long long *npig, int32_t *state_flags) {
+    __shared__ uint32_t s_area[AP_MAX_IDS];
+    __shared__ uint32_t s_word[AP_MAX_IDS];
+    const int f = *w.flags;
+    if (f) {                                                       // slots and npig stay as they are
+        if (threadIdx.x == 0) *state_flags |= f;
+        return;
+    }
+    const int lane = __lane_id(), wave = threadIdx.x >> 6;
+    const int nr = *w.n_raw, G = *w.n_tgt - 1;
+    int D = nr - 1 < max_det ? nr - 1 : max_det;
+    if (empty_if_single && nr == 1) D = 1;                         // trainer.py:780-781: one all-zero mask
+    for (int d = wave; d < D; d += AP_THRESHOLDS) {
+        unsigned long long a = 0;
+        for (int c = lane; c <= G; c += 64) a += w.inter[(int64_t)d * AP_MAX_IDS + c];
+        a = wave_sum(a);
+        if (lane == 0) {
+            s_area[d] = (uint32_t)a;
+            s_word[d] = 1;
+        }
+    }
+    __syncthreads();
+    const double floor_t = thr.t[wave] < 1.0 - 1e-10 ? thr.t[wave] : 1.0 - 1e-10;
+    unsigned long long matched = 0;
+    for (int d = 0; d < D; ++d) {
+        const long long a_d = s_area[d];
+        double best = floor_t;
+        int m = -1;
+        if (a_d > 0)
+            for (int j = 0, g = lane; g < G; ++j, g += 64) {
+                if ((matched >> j) & 1) continue;
+                const long long i = w.inter[(int64_t)d * AP_MAX_IDS + g + 1];
+                if (i == 0) continue;
+                const double iou = (double)i / (double)(a_d + (long long)w.area_g[g] - i);
+                if (iou < best) continue;
+                best = iou;
+                m = g;
+            }
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ob = __shfl_xor(best, o);
+            const int om = __shfl_xor(m, o);
+            if (om >= 0 && (m < 0 || ob > best || (ob == best && om > m))) {
+                best = ob;
+                m = om;
+            }
+        }
+        if (m >= 0) {
+            if (lane == (m & 63)) matched |= 1ull << (m >> 6);
+            if (lane == 0) atomicOr(&s_word[d], 2u << wave);
+        }
+    }
+    __syncthreads();
+    for (int d = threadIdx.x; d < max_det; d += blockDim.x) slots[d] = d < D ? (int32_t)s_word[d] : 0;
+    if (threadIdx.x == 0) *npig += G;
+}
+
 }      // namespace
 
 extern "C" int64_t pag_panoptic_pq_workspace_bytes(int B, int64_t H, int64_t W, int n_cat) {
@@ -724,5 +947,43 @@ extern "C" int pag_confusion_matrix(const void *preds, int preds_dtype, const in
         hipLaunchKernelGGL(cm_kernel<false>, dim3(pn_grid(N, 256, 2048)), dim3(256), 0, st, P, T, shape[1], shape[2], shape[3], N, C,
                            (unsigned long long *)confmat);
     PAG_CHECK_LAUNCH("pag_confusion_matrix");
+    return PAG_OK;
+}
+
+extern "C" int64_t pag_mask_ap_workspace_bytes(int64_t H, int64_t W, int max_detections) {
+    if (H < 1 || W < 1 || H > PN_MAX_PIXELS || W > PN_MAX_PIXELS || H * W > PN_MAX_PIXELS || max_detections < 1 || max_detections > AP_MAX_IDS) return 0;
+    return ap_ws_bytes(max_detections);
+}
+
+extern "C" int pag_mask_ap_update(const void *pred, int pred_dtype, int64_t pred_stride_y, int64_t pred_stride_x, const void *pred_raw,
+                                  int raw_dtype, int64_t raw_stride_y, int64_t raw_stride_x, const void *target, int target_dtype,
+                                  int64_t target_stride_y, int64_t target_stride_x, int64_t H, int64_t W, int max_detections,
+                                  int empty_detection_if_single_id, const double *thresholds, void *workspace, int64_t workspace_bytes,
+                                  int32_t *slots, int64_t *npig, int32_t *state_flags, void *stream) {
+    PAG_CHECK_ARG(H >= 1 && W >= 1 && H <= PN_MAX_PIXELS && W <= PN_MAX_PIXELS && H * W <= PN_MAX_PIXELS && max_detections >= 1 &&
+                      max_detections <= AP_MAX_IDS,
+                  "pag_mask_ap_update: sizes (H %lld, W %lld, max_detections %d; 1 <= H*W <= 2^28, 1 <= max_detections <= %d)", (long long)H,
+                  (long long)W, max_detections, AP_MAX_IDS);
+    PAG_CHECK_ARG((pred_dtype == PAG_I32 || pred_dtype == PAG_I64) && (raw_dtype == PAG_I32 || raw_dtype == PAG_I64) &&
+                      (target_dtype == PAG_I32 || target_dtype == PAG_I64),
+                  "pag_mask_ap_update: dtypes %d / %d / %d (int32 or int64)", pred_dtype, raw_dtype, target_dtype);
+    PAG_CHECK_ARG(pred && pred_raw && target && thresholds && workspace && slots && npig && state_flags, "pag_mask_ap_update: NULL argument");
+    PAG_CHECK_ARG(workspace_bytes >= ap_ws_bytes(max_detections), "pag_mask_ap_update: workspace %lld < %lld bytes", (long long)workspace_bytes,
+                  (long long)ap_ws_bytes(max_detections));
+    hipStream_t st = (hipStream_t)stream;
+    const ApWs w = ap_ws(workspace, max_detections);
+    const int64_t N = H * W, zero_words = ap_zero_bytes(max_detections) / 8, key_words = 2 * (int64_t)AP_CAP;
+    const ApImg P{pred, pred_dtype, pred_stride_y, pred_stride_x}, R{pred_raw, raw_dtype, raw_stride_y, raw_stride_x},
+        T{target, target_dtype, target_stride_y, target_stride_x};
+    ApThr thr;
+    for (int k = 0; k < AP_THRESHOLDS; ++k) thr.t[k] = thresholds[k];
+    hipLaunchKernelGGL(pn_fill_kernel, dim3(pn_grid(zero_words, 256, 2048)), dim3(256), 0, st, (unsigned long long *)workspace, zero_words, 0ull);
+    hipLaunchKernelGGL(pn_fill_kernel, dim3(pn_grid(key_words, 256, 2048)), dim3(256), 0, st, w.kr, key_words, PN_EMPTY);
+    hipLaunchKernelGGL(ap_ids_kernel, dim3(pn_grid(N, 256, 2048)), dim3(256), 0, st, R, T, H, W, w);
+    hipLaunchKernelGGL(ap_rank_kernel, dim3(2), dim3(256), 0, st, w);
+    hipLaunchKernelGGL(ap_pair_kernel, dim3(pn_grid(N, 256, 2048)), dim3(256), 0, st, P, T, H, W, max_detections, w);
+    hipLaunchKernelGGL(ap_match_kernel, dim3(1), dim3(64 * AP_THRESHOLDS), 0, st, w, max_detections, empty_detection_if_single_id ? 1 : 0, thr, slots,
+                       (long long *)npig, state_flags);
+    PAG_CHECK_LAUNCH("pag_mask_ap_update");
     return PAG_OK;
 }

@@ -9,10 +9,16 @@ reference's check needs), so they can be captured in a graph; `compute()` reads 
 
 Inputs must be device tensors (the project has no CPU fallback) and are never modified.  Divergence: for B > 1 the reference adds the batch offsets of
 _make_instance_ids_batch_unique into the caller's preds and target in place; here the caller's tensors stay as they are.
+
+The other two figures of the reference's validation row (trainer.py:651-941 evaluate_metrics) and the row itself: MaskMeanAveragePrecision, the mask
+mAP of :674-675 / :794-798 from label images on pag_mask_ap_update (no [K, H, W] mask stack, no host run-length encoding); PeakSignalNoiseRatio
+(:677, :708) in tensor ops; ValidationMetrics, which feeds the five metrics one image at a time as :684-843 does and names the columns as :898-934.
 """
 import ctypes
+import math
 from collections.abc import Set
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -285,3 +291,305 @@ def iou_from_confmat(confmat):
     iou = tp.float() / denom.clamp(min=1).float()
     present = (denom > 0).float()
     return (iou * present).sum() / present.sum()
+
+
+# ------------------------------------------------------------------------------------------------- mask mAP
+AP_THRESHOLDS = np.linspace(0.5, 0.95, 10)
+AP_RECALLS = np.linspace(0.0, 1.0, 101)
+MAX_MASK_IDS = 4096
+_AP_FLAG_IDS = 1
+_AP_FLAG_PRED_ID = 2
+
+
+def _ap_from_slots(words, npig):
+    """(map, map_50, map_75) in fp64 from the slot words of every update in order and the ground-truth count: COCOeval's accumulate for one class,
+    every score equal (so the stable sort keeps the state order) and no ignored ground truth."""
+    if npig == 0:
+        return -1.0, -1.0, -1.0
+    words = np.asarray(words, dtype=np.int64)
+    words = words[(words & 1) != 0]
+    aps = []
+    for k in range(len(AP_THRESHOLDS)):
+        matched = ((words >> (1 + k)) & 1) != 0
+        tp = np.cumsum(matched).astype(np.float64)
+        fp = np.cumsum(~matched).astype(np.float64)
+        rc = tp / npig
+        pr = tp / (tp + fp + np.spacing(1))
+        pr = np.maximum.accumulate(pr[::-1])[::-1]              # non-increasing from the right
+        inds = np.searchsorted(rc, AP_RECALLS, side="left")
+        q = np.zeros(len(AP_RECALLS), np.float64)
+        ok = inds < len(pr)
+        q[ok] = pr[inds[ok]]
+        aps.append(np.mean(q))
+    return float(np.mean(aps)), float(aps[0]), float(aps[5])
+
+
+class MaskMeanAveragePrecision:
+    """The mask mAP of pc_nerf/trainer.py:674-675, :794-798, :839-843 (torchmetrics MeanAveragePrecision(iou_type="segm")) for the one way the trainer
+    uses it - a single class, every score 1.0 - with the masks given as label images, on pag_mask_ap_update (csrc/panoptic.hip).
+
+    MaskMeanAveragePrecision(max_detections=100); update(pred, target, pred_raw=None, empty_detection_if_single_id=False) with [H, W] int32 / int64
+    device tensors of any strides (never modified); compute() -> {'map', 'map_50', 'map_75'} f32 0-d tensors on the state's device; reset();
+    to(device) returns self.
+
+    The reference stacks one [K, H, W] mask per id (1.47 GB as int64 at 720 x 1280 with 200 ids) and hands the stack to pycocotools, which
+    run-length-encodes every mask on the host.  The masks of one label image are disjoint, so the areas and pairwise intersection counts of the two
+    label images carry the same information: two pixel passes and a matching kernel over a workspace that does not grow with the image, no host
+    synchronisation in update.
+
+    torchmetrics and pycocotools are third party and not installed where this was written: the definition below is recalled from COCOeval and is
+    this project's definition of record; parity is unpinned.
+    - Detections of one update: the distinct ids of pred_raw (default pred) in ascending order without the smallest (mask_ids[1:], :753-755), the
+      first max_detections of them (all scores tie and COCOeval's sort is stable).  The mask of a detection is the pixels of pred with its id: pred
+      is the cleaned image, clean_instances only moves pixels to the smallest id, and a detection that lost every pixel stays a detection of area
+      0 (:766-767 keeps zeroed masks).  empty_detection_if_single_id: a pred_raw of one distinct id gives one empty detection (:780-781).
+    - Ground truths: the distinct ids of target without the smallest, whatever it is - in a partly labelled frame that holds -1, the -1 is dropped
+      and 0 becomes a mask (gt_ids[1:], :791-792).  None is ignored, none is crowd.
+    - IoU = double(i) / double(a_d + a_g - i) of exact integer counts when i > 0, else 0.
+    - Matching, independently for each threshold of np.linspace(0.5, 0.95, 10), detections in order: the not yet matched ground truth of the
+      largest IoU >= min(t, 1 - 1e-10), the later one on a tie.
+    - State: max_detections int32 slot words per update in update order (bit 0 present, bit 1 + k matched at threshold k; 0 for a missing
+      detection), the int64 ground-truth count npig and an int32 flag word.  The slot buffer grows on the host by doubling.
+    - compute() reads the state back once and runs COCOeval's accumulate in numpy fp64: per threshold tp / fp cumulative sums over the present
+      detections, precision tp / (tp + fp + eps) made non-increasing from the right, sampled at the 101 recalls np.linspace(0, 1, 101) (0 past the
+      last recall), averaged; map is the mean over the thresholds, map_50 / map_75 thresholds 0 / 5; all -1 without a ground truth; rounded to
+      f32 last.  compute_fp64() gives the same three as Python floats before that rounding.
+    More than 4096 distinct ids in pred_raw or target, or an id of pred that pred_raw lacks, sets a device flag and drops that update; compute()
+    then raises ValueError.  H*W <= 2^28, max_detections <= 4096."""
+
+    def __init__(self, max_detections=100, **kwargs):
+        if int(max_detections) < 1 or int(max_detections) > MAX_MASK_IDS:
+            raise ValueError("max_detections %r not in [1, %d]" % (max_detections, MAX_MASK_IDS))
+        self.max_detections = int(max_detections)
+        self.slots = torch.zeros(4 * self.max_detections, dtype=torch.int32)
+        self.npig = torch.zeros(1, dtype=torch.int64)
+        self._flags = torch.zeros(1, dtype=torch.int32)
+        self.num_updates = 0
+        self._thresholds = (ctypes.c_double * len(AP_THRESHOLDS))(*AP_THRESHOLDS.tolist())
+
+    _STATE = ("slots", "npig", "_flags")
+
+    @property
+    def device(self):
+        return self.slots.device
+
+    def to(self, device):
+        for name in self._STATE:
+            setattr(self, name, getattr(self, name).to(device))
+        return self
+
+    def reset(self):
+        for name in self._STATE:
+            getattr(self, name).zero_()
+        self.num_updates = 0
+
+    def update(self, pred, target, pred_raw=None, empty_detection_if_single_id=False):
+        raw = pred if pred_raw is None else pred_raw
+        ops._check_gpu(pred, target, raw)
+        for t, what in ((pred, "pred"), (target, "target"), (raw, "pred_raw")):
+            if t.dim() != 2:
+                raise ValueError("%s must be an [H, W] id image, got %s" % (what, tuple(t.shape)))
+            if t.dtype not in _IDX:
+                raise TypeError("%s must be int32 or int64, got %s" % (what, t.dtype))
+            if t.shape != pred.shape or t.device != pred.device:
+                raise ValueError("%s %s on %s, pred %s on %s" % (what, tuple(t.shape), t.device, tuple(pred.shape), pred.device))
+        if self.device != pred.device:
+            self.to(pred.device)
+        H, W = pred.shape
+        if H * W == 0:
+            return
+        nbytes = int(L.load().pag_mask_ap_workspace_bytes(H, W, self.max_detections))
+        if nbytes == 0:
+            raise ValueError("MaskMeanAveragePrecision.update: %d pixels > 2^28" % (H * W))
+        md = self.max_detections
+        if (self.num_updates + 1) * md > self.slots.numel():
+            grown = torch.zeros(2 * self.slots.numel(), device=self.device, dtype=torch.int32)
+            grown[:self.slots.numel()] = self.slots
+            self.slots = grown
+        ws = torch.empty(nbytes, device=pred.device, dtype=torch.uint8)
+        ops._call("pag_mask_ap_update", pred.data_ptr(), _IDX[pred.dtype], pred.stride(0), pred.stride(1), raw.data_ptr(), _IDX[raw.dtype], raw.stride(0),
+                  raw.stride(1), target.data_ptr(), _IDX[target.dtype], target.stride(0), target.stride(1), H, W, md,
+                  int(bool(empty_detection_if_single_id)), self._thresholds, ws.data_ptr(), nbytes,
+                  self.slots.data_ptr() + 4 * self.num_updates * md, self.npig.data_ptr(), self._flags.data_ptr(), L.stream())
+        self.num_updates += 1
+
+    def compute_fp64(self):
+        flags = int(self._flags[0])
+        if flags & _AP_FLAG_IDS:
+            raise ValueError("MaskMeanAveragePrecision: an update had more than %d distinct ids (or the id -2^63)" % MAX_MASK_IDS)
+        if flags & _AP_FLAG_PRED_ID:
+            raise ValueError("MaskMeanAveragePrecision: pred held an id that pred_raw lacks")
+        words = self.slots[:self.num_updates * self.max_detections].cpu().numpy()
+        return dict(zip(("map", "map_50", "map_75"), _ap_from_slots(words, int(self.npig[0]))))
+
+    def compute(self):
+        return {k: torch.tensor(v, dtype=torch.float32, device=self.device) for k, v in self.compute_fp64().items()}
+
+
+# ------------------------------------------------------------------------------------------------- PSNR
+class PeakSignalNoiseRatio:
+    """torchmetrics.PeakSignalNoiseRatio() as pc_nerf/trainer.py:677, :708, :900 uses it (data_range=None), in tensor ops; recalled, parity unpinned.
+
+    States: sum_squared_error f64, total i64, min_target / max_target f32, both starting at 0.0 - so the range of all-positive images is max - 0.
+    update(preds, target): one shape, any strides (e.g. gts[..., :3]); a uint8 target is converted with dataset._u8_table; d = preds.float() -
+    target, squared in f32 and summed in f64; total += numel; min and max of target folded in; no host synchronisation.  compute(): with r =
+    max_target - min_target, (2 log r - log(sse / total)) * 10 / log 10, logarithms in f32, as an f32 0-d tensor.
+    Divergence: the reference accumulates the squared error in f32."""
+
+    def __init__(self, **kwargs):
+        self.sum_squared_error = torch.zeros((), dtype=torch.float64)
+        self.total = torch.zeros((), dtype=torch.int64)
+        self.min_target = torch.zeros((), dtype=torch.float32)
+        self.max_target = torch.zeros((), dtype=torch.float32)
+
+    _STATE = ("sum_squared_error", "total", "min_target", "max_target")
+
+    @property
+    def device(self):
+        return self.sum_squared_error.device
+
+    def to(self, device):
+        for name in self._STATE:
+            setattr(self, name, getattr(self, name).to(device))
+        return self
+
+    def reset(self):
+        for name in self._STATE:
+            getattr(self, name).zero_()
+
+    def update(self, preds, target):
+        if preds.shape != target.shape:
+            raise ValueError("preds %s and target %s must have the same shape" % (tuple(preds.shape), tuple(target.shape)))
+        if preds.device != target.device:
+            raise ValueError("preds on %s, target on %s" % (preds.device, target.device))
+        if target.numel() == 0:
+            return
+        if self.device != preds.device:
+            self.to(preds.device)
+        if target.dtype == torch.uint8:
+            from .dataset import _u8_table
+            target = _u8_table(target.device)[target.long()]
+        target = target.float()
+        d = preds.float() - target
+        self.sum_squared_error += (d * d).sum(dtype=torch.float64)
+        self.total += target.numel()
+        self.min_target = torch.minimum(self.min_target, target.min())
+        self.max_target = torch.maximum(self.max_target, target.max())
+
+    def compute(self):
+        r = self.max_target - self.min_target
+        mse = (self.sum_squared_error / self.total).float()
+        return (2.0 * torch.log(r) - torch.log(mse)) * (10.0 / math.log(10.0))
+
+
+# ------------------------------------------------------------------------------------------------- the validation row
+class ValidationMetrics:
+    """The metric half of PanopticTrainer.evaluate_metrics (pc_nerf/trainer.py:684-843, :898-934), one image per update: PSNR, semantic IoU,
+    panoptic quality and mask mAP of the render, and the same for the network predictions the dataset may carry (`_pred`).  Pictures, videos, the
+    pickles, the CSV row and TensorBoard are the caller's.
+
+    ValidationMetrics(num_classes, things_ids, stuff_ids, inst_num_dilations=-1, inst_outlier_rejection=False, predict_clusters=None) - the
+    defaults of config_parser.py:331, :401; predict_clusters is the contrastive NeFs' clustering (:738), else argmax.
+    update(rb, gts, sem_gts=None, inst_gts=None, sem_pred=None, inst_pred=None, labelled=None), rb a RenderBuffer reshaped to [H, W, .]:
+    - PSNR of rb.rgb[..., :3] against gts[..., :3], always (:708);
+    - with rb.semantics and sem_gts: semantics = argmax; the IoU is updated when the frame is labelled, and a second IoU from sem_pred (:715-729);
+    - with rb.inst_embedding and inst_gts: instances = predict_clusters(rb.inst_embedding) or argmax, inst_conf = max, then
+      clean_instances(instances, max(0, inst_num_dilations), inst_outlier_rejection, min_area=100) (:738-772); when both label images are
+      labelled, PanopticQuality(allow_unknown_preds_category=True) of (semantics, cleaned) against (sem_gts, inst_gts) and
+      MaskMeanAveragePrecision.update(cleaned, inst_gts, pred_raw=instances, empty_detection_if_single_id=True) (:784-798); with sem_pred and
+      inst_pred the `_pred` pair from them, without cleaning and without the empty detection (:808-843).
+    "Labelled" is the reference's `not torch.all(x == -1)`: labelled=(semantics, instances) from the caller (the dataset knows which frames carry
+    labels) makes update free of host synchronisation; labelled=None reads one two-element flag tensor back.
+    update returns {'semantics', 'instances', 'inst_conf'}: the label images and the confidence that save_preds pickles (:844-853), device tensors
+    (None where the channel or its labels were not given).
+    compute() -> Python floats under the reference's column names, quirks included: val/psnr, val/iou, val/map_, val/map_50_, val/map_75_,
+    val/{pq,rq,sq}_{all,things,stuff}; once a `_pred` input was seen also val/map__pred, val/map_50__pred, val/map_75__pred, val/iou_pred,
+    val/{pq,rq,sq}_{all,things,stuff}_pred, val/iou_gain and val/pq_things_gain (:908-934).
+    Divergence: the reference always emits the `_pred` columns and gains, from metrics that never saw an update."""
+
+    def __init__(self, num_classes, things_ids, stuff_ids, inst_num_dilations=-1, inst_outlier_rejection=False, predict_clusters=None):
+        things, stuff = set(int(c) for c in things_ids), set(int(c) for c in stuff_ids)
+        self.inst_num_dilations = int(inst_num_dilations)
+        self.inst_outlier_rejection = bool(inst_outlier_rejection)
+        self.predict_clusters = predict_clusters
+        self.psnr = PeakSignalNoiseRatio()
+        self.iou, self.iou_pred = MulticlassIoU(num_classes), MulticlassIoU(num_classes)
+        self.pq = PanopticQuality(things, stuff, allow_unknown_preds_category=True)
+        self.pq_pred = PanopticQuality(things, stuff, allow_unknown_preds_category=True)
+        self.map, self.map_pred = MaskMeanAveragePrecision(), MaskMeanAveragePrecision()
+        self.seen_pred = False
+
+    def _metrics(self):
+        return (self.psnr, self.iou, self.iou_pred, self.pq, self.pq_pred, self.map, self.map_pred)
+
+    def to(self, device):
+        for m in self._metrics():
+            m.to(device)
+        return self
+
+    def reset(self):
+        for m in self._metrics():
+            m.reset()
+        self.seen_pred = False
+
+    def update(self, rb, gts, sem_gts=None, inst_gts=None, sem_pred=None, inst_pred=None, labelled=None):
+        rgb, sem, emb = rb.rgb, getattr(rb, "semantics", None), getattr(rb, "inst_embedding", None)
+        ops._check_gpu(rgb, gts, sem, emb, sem_gts, inst_gts, sem_pred, inst_pred)
+        self.psnr.update(rgb[..., :3], gts[..., :3])
+        if labelled is not None:
+            sem_l, inst_l = bool(labelled[0]), bool(labelled[1])
+        else:
+            no = torch.zeros((), dtype=torch.bool, device=rgb.device)
+            sem_l, inst_l = torch.stack([no if x is None else (x != -1).any() for x in (sem_gts, inst_gts)]).tolist()
+        out = dict(semantics=None, instances=None, inst_conf=None)
+        semantics = None
+        if sem is not None and sem_gts is not None:
+            semantics = torch.argmax(sem, dim=-1)
+            out["semantics"] = semantics
+            if sem_l:
+                self.iou.update(semantics, sem_gts)
+            if sem_pred is not None:
+                self.seen_pred = True
+                if sem_l:
+                    self.iou_pred.update(sem_pred, sem_gts)
+        if emb is not None and inst_gts is not None:
+            instances = self.predict_clusters(emb) if self.predict_clusters is not None else torch.argmax(emb, dim=-1)
+            if instances.dtype not in _IDX:
+                instances = instances.long()
+            out["inst_conf"] = torch.max(emb, dim=-1)[0]
+            cleaned = clean_instances(instances, num_openings=max(0, self.inst_num_dilations), outlier_rejection=self.inst_outlier_rejection,
+                                      min_area=100)
+            out["instances"] = cleaned
+            both = sem_l and inst_l
+            if both and semantics is None:
+                raise ValueError("ValidationMetrics.update: the panoptic quality needs rb.semantics and sem_gts beside the instances")
+            gt_ids = inst_gts if inst_gts.dtype in _IDX else inst_gts.long()
+            if both:
+                labels = torch.stack((sem_gts.long(), gt_ids.long()))[None]
+                self.pq.update(torch.stack((semantics, cleaned.long()))[None], labels)
+                self.map.update(cleaned, gt_ids, pred_raw=instances, empty_detection_if_single_id=True)
+            if sem_pred is not None and inst_pred is not None:
+                self.seen_pred = True
+                if both:
+                    self.pq_pred.update(torch.stack((sem_pred.long(), inst_pred.long()))[None], labels)
+                    self.map_pred.update(inst_pred if inst_pred.dtype in _IDX else inst_pred.long(), gt_ids)
+        return out
+
+    def compute(self):
+        out = {"val/psnr": self.psnr.compute().item()}
+        suffixes = ("", "_pred") if self.seen_pred else ("",)
+        ious = [m.compute() for m in (self.iou, self.iou_pred)]
+        pqs = [m.compute() for m in (self.pq, self.pq_pred)]
+        if self.seen_pred:
+            out["val/iou_gain"] = (ious[0] - ious[1]).item()
+            out["val/pq_things_gain"] = (pqs[0]["things"]["pq"] - pqs[1]["things"]["pq"]).item()
+        for m, suffix in zip((self.map, self.map_pred), suffixes):
+            for metric, v in m.compute().items():
+                out["val/%s_%s" % (metric, suffix)] = v.item()
+        for v, suffix in zip(ious, suffixes):
+            out["val/iou%s" % suffix] = v.item()
+        for res, suffix in zip(pqs, suffixes):
+            for group in res:
+                for metric in ("pq", "rq", "sq"):
+                    out["val/%s_%s%s" % (metric, group, suffix)] = res[group][metric].item()
+        return out
