@@ -25,6 +25,9 @@
     dataset: DeviceMultiviewDataset, BatchSampler, SampleRays, sample_indices, epoch_views (dataset.py)
              <- datasets/multiview_dataset.py:120-192, datasets/transforms/ray_sampler.py:17-40, pc_nerf/trainer.py:216-219 (the step's inputs)
     optim : Adam (torch.optim.Adam's interface on pag_adam_step) (optim.py) <- config_parser.py:667-673, trainer.py:583
+    trainer: PanopticTrainer, LODAnneling (trainer.py) <- pc_nerf/trainer.py on wisp's BaseTrainer, utils/lod_anneling.py
+    config : load_config, register_class, build_from_config (config.py) <- config_parser.py:557-603, :679-781
+    train  : `python -m pagnerf_amd.train` (train.py) <- main_interactive.py, on datasets stored as .npz
 
 All compute goes through libpagnerf_hip.so (include/pagnerf_hip.h); there is no CPU fallback.
 """
@@ -47,5 +50,7 @@ from .regularizers import (grid_tv_l1_loss, grid_tv_l2_loss, grid_tv_loss, step_
                            tv_loss)
 from .dataset import BatchSampler, DeviceMultiviewDataset, SampleRays, epoch_views, sample_indices    # noqa: F401
 from . import optim                                                # noqa: F401
+from .trainer import LODAnneling, PanopticTrainer                  # noqa: F401
+from .config import build_from_config, load_config, register_class    # noqa: F401
 
 __version__ = "0.1.0"

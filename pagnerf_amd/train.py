@@ -1,0 +1,112 @@
+"""python -m pagnerf_amd.train --config YAML --dataset TRAIN.npz [--val-dataset VAL.npz] [--log-dir DIR] [--resume CKPT] [--valid-only]
+                              [--save-map PATH] [--set key=value ...]
+
+The native counterpart of the reference's main_interactive.py: a shipped YAML, a dataset that is already arrays, and the trainer of trainer.py.
+
+The .npz holds the arrays of the dict MultiviewDataset.init() leaves:
+
+    imgs [V,H,W,3] float32 and every further per-view mode (semantics, instance, semantics_pred, instance_pred, sem_conf, inst_conf ...) [V,H,W,C]
+    base_rays_origins, base_rays_dirs [H,W,3]   the camera-frame rays the views share (pose optimisation), base_rays_range [2] = (near, far)
+    rays_origins, rays_dirs [V,H,W,3]           world-frame rays per view, rays_range [2]                      (either pair, or both)
+    view_matrices [V,4,4]                        world -> camera, needed with optimize_extrinsics
+    num_classes, num_instances (scalars), things_ids, stuff_ids (int arrays)    the `semantic_info` lists
+    optional: scale (scalar), filenames [V]
+
+File-format loaders (BUP20, nerf_standard ...) are not part of this package.
+"""
+import argparse
+import logging
+import os
+import sys
+
+import numpy as np
+import torch
+
+RESERVED = ("base_rays_origins", "base_rays_dirs", "base_rays_range", "rays_origins", "rays_dirs", "rays_range", "view_matrices", "num_classes",
+            "num_instances", "things_ids", "stuff_ids", "scale", "filenames")
+
+
+def load_npz_dataset(path, device):
+    """The .npz of the module docstring -> DeviceMultiviewDataset with semantic_info / view_matrices / image_shape / filenames / scale attached."""
+    from .core import Rays
+    from .dataset import DeviceMultiviewDataset
+    z = np.load(os.path.expanduser(path), allow_pickle=False)
+    data = {k: torch.from_numpy(z[k]) for k in z.files if k not in RESERVED}
+    if "imgs" not in data:
+        raise ValueError("%s: no 'imgs' array" % path)
+    H, W = data["imgs"].shape[1:3]
+    for name in ("base_rays", "rays"):
+        if name + "_origins" in z.files:
+            lo, hi = (float(v) for v in z[name + "_range"]) if name + "_range" in z.files else (0.0, 6.0)
+            data[name] = Rays(torch.from_numpy(z[name + "_origins"]).float(), torch.from_numpy(z[name + "_dirs"]).float(), dist_min=lo, dist_max=hi)
+    ds = DeviceMultiviewDataset(data, device)
+    ds.image_shape = (int(H), int(W))
+    if "num_classes" in z.files:
+        ds.semantic_info = dict(num_classes=int(z["num_classes"]), num_instances=int(z["num_instances"]),
+                                things_ids=[int(v) for v in z["things_ids"]], stuff_ids=[int(v) for v in z["stuff_ids"]])
+    if "view_matrices" in z.files:
+        ds.view_matrices = torch.from_numpy(z["view_matrices"]).float()
+    if "scale" in z.files:
+        ds.scale = float(z["scale"])
+    if "filenames" in z.files:
+        ds.filenames = [str(v) for v in z["filenames"]]
+    return ds
+
+
+def save_map(trainer, dataset, path):
+    """--save-map: the panoptic point cloud of the trained field from the training views (map_export.generate_pc_map_from_views)."""
+    from . import map_export
+    from .core import Rays
+    leaf = {l.field: l.src for l in dataset._leaves if l.key == "base_rays"}
+    if not leaf or not hasattr(trainer.pipeline, "camera_extrinsics"):
+        raise ValueError("--save-map needs base_rays in the dataset and a BAPipeline (optimize_extrinsics)")
+    near, far = dataset._rays_range["base_rays"]
+    cloud = map_export.generate_pc_map_from_views(trainer.pipeline, Rays(leaf["origins"], leaf["dirs"], near, far),
+                                                  cam_ids=list(range(dataset.num_imgs)), render_batch=trainer.render_batch or 20000)
+    map_export.save_map(cloud, path)
+    return path
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m pagnerf_amd.train", description=__doc__.split("\n\n")[1])
+    ap.add_argument("--config", required=True, help="a YAML in the reference's layout (configs/bup20/*.yaml)")
+    ap.add_argument("--dataset", required=True, help="training views as .npz")
+    ap.add_argument("--val-dataset", help="validation views as .npz (needed with optimize_val_extrinsics and for validation)")
+    ap.add_argument("--log-dir", help="overrides the YAML's log_dir")
+    ap.add_argument("--resume", metavar="CKPT", help="continue the run of a PanopticTrainer checkpoint")
+    ap.add_argument("--valid-only", action="store_true", help="validate the (resumed / pretrained) model and exit")
+    ap.add_argument("--save-map", metavar="PATH", help="after training export the panoptic point cloud of the training views")
+    ap.add_argument("--set", action="append", default=[], metavar="key=value", help="override an option of the flattened namespace (repeatable)")
+    ap.add_argument("--device", default="cuda")
+    args = ap.parse_args(argv)
+
+    from . import config
+    cfg = config.load_config(args.config)
+    config.apply_overrides(cfg, args.set)
+    if args.log_dir:
+        cfg["log_dir"] = args.log_dir
+    if args.valid_only:
+        cfg["valid_only"] = True
+    logging.basicConfig(level=int(cfg.get("log_level") or logging.INFO), format="%(asctime)s|%(levelname)8s| %(message)s")
+    device = torch.device(args.device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())        # the dataset compares devices with their index
+    dataset = load_npz_dataset(args.dataset, device)
+    val_dataset = load_npz_dataset(args.val_dataset, device) if args.val_dataset else None
+    _, trainer = config.build_from_config(cfg, dataset, val_dataset, device=device)
+    if args.resume:
+        trainer.resume(args.resume)
+    if args.valid_only:
+        trainer.validate(trainer.epoch)
+        return 0
+    trainer.train()
+    trainer.save_checkpoint(os.path.join(trainer.log_dir, "model.pth"))
+    if val_dataset is not None and not (trainer.plan and trainer.plan["validate_after"]):      # the last epoch's own validation is not repeated
+        trainer.validate(trainer.epoch - 1)
+    if args.save_map:
+        save_map(trainer, dataset, args.save_map)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
