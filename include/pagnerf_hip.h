@@ -1013,6 +1013,56 @@ int pag_sample_batch(const int64_t *state, const int32_t *views, int B, int num_
                      const pag_sample_mode *modes, int n_modes, int64_t *ray_idx, int32_t *cam_idx, void *stream);
 int pag_sample_advance(int64_t *state, void *stream);
 
+/* Validation pictures (pc_nerf/trainer.py:710-829 and :855-896: the imgviz label_colormap / label2rgb / depth2rgb, torchvision masks_to_boxes /
+ * draw_bounding_boxes and 0.7-blend chain of evaluate_metrics, per image; additive, ABI 14): visualize.hip.  Two launches for one H x W image:
+ * pag_vis_stats, then pag_vis_paint, which writes every requested uint8 [H,W,3] picture once.  pagnerf_amd/visualize.py holds the tensor-op forms
+ * (`*_reference`) that define every picture bit for bit; the file is built without FMA contraction.
+ *   rgb      f32 (rgb_is_u8 == 0: the picture is trunc(clamp(x, 0, 1) * 255), NaN -> 0) or uint8 (taken as it is), rgb_stride elements per pixel (>= 3)
+ *   gt       f32, gt_stride floats per pixel;   depth f32 [H,W];   conf[2] f32 [H,W] (inst_conf, inst_conf_pred)
+ *   labels   PAG_VIS_L_*: int64 / int32 / uint8 (label_bytes 8 / 4 / 1) [H,W], NULL = absent
+ *   table    uint8 [256,3], the colour map of the depth and confidence pictures
+ *   out      PAG_VIS_*: the plane of each picture, NULL = not painted and not touched.  A requested picture whose inputs are absent is refused.
+ * Label colour: the PASCAL-VOC bit procedure on the id's low 24 bits (for j = 0..7: r |= bit0 << (7-j), g |= bit1 << (7-j), b |= bit2 << (7-j),
+ * id >>= 3); a negative id is black.  *_RGB of the semantic pictures: grey = rint(0.299f R + 0.587f G + 0.114f B) of the rgb picture,
+ * rint(blend_keep * grey + blend_alpha * colour).  Depth: t = (d - min) / (max - min) over the finite minimum / maximum, index min(255, floor(t * 256)),
+ * non-finite d black, max == min index 0; the confidences the same with the fixed range [conf_min, conf_max] and t clamped to [0, 1].
+ * INST_RGB / INST_PRED_RGB: the rgb picture, then the outline (box_width pixels inward, the highest id on top) of the inclusive pixel box of every id
+ * in [1, max_id] of labels[L_INST] / labels[L_INST_PRED] in the id's colour, then per channel where the label colour's channel is non-zero
+ * trunc(overlay_keep * base + overlay_alpha * colour).
+ * Workspace: int32, two halves of 4 + 8 * (max_id + 1) words each: {min key, max key, 0, 0}, then the box tables (x0, y0, x1, y1) of L_INST and
+ * L_INST_PRED.  The caller initialises BOTH halves once to {-1, 0, 0, 0} and (INT32_MAX, INT32_MAX, -1, -1) per id; pag_vis_stats reduces into half
+ * `phase` (LDS per workgroup, then integer min / max atomics: order-independent, the same input gives the same bits; an absent id keeps x0 > x1) -
+ * the depth range when `depth` is given, a box table when its label image is given - and pag_vis_paint reads half `phase` and re-initialises half
+ * `phase ^ 1`, so a caller that alternates `phase` never launches a fill.  Keys: the f32 bits made monotone (sign bit flipped / all bits flipped).
+ * Refused (PAG_ERR_ARG) before any launch: H, W < 1 or H * W * 3 >= 2^31, max_id outside [1, 1023], box_width < 1, a label_bytes other than 8 / 4 / 1,
+ * strides < 3, phase outside {0, 1}, a short or NULL workspace, a requested picture without its inputs. */
+#define PAG_VIS_PICTURES 15
+#define PAG_VIS_LABELS 6
+#define PAG_VIS_MAX_ID 1023
+enum { PAG_VIS_RGB = 0, PAG_VIS_GT, PAG_VIS_DEPTH, PAG_VIS_SEM, PAG_VIS_SEM_RGB, PAG_VIS_SEM_GT, PAG_VIS_SEM_PRED, PAG_VIS_SEM_PRED_RGB, PAG_VIS_INST,
+       PAG_VIS_INST_CONF, PAG_VIS_INST_RGB, PAG_VIS_INST_GT, PAG_VIS_INST_PRED, PAG_VIS_INST_PRED_RGB, PAG_VIS_INST_CONF_PRED };
+enum { PAG_VIS_L_SEM = 0, PAG_VIS_L_INST, PAG_VIS_L_SEM_GT, PAG_VIS_L_INST_GT, PAG_VIS_L_SEM_PRED, PAG_VIS_L_INST_PRED };
+typedef struct pag_vis_args {
+    int32_t H, W;
+    const void *rgb;
+    int32_t rgb_is_u8, rgb_stride;
+    const float *gt;
+    int32_t gt_stride, phase;
+    const float *depth;
+    const void *labels[PAG_VIS_LABELS];
+    int32_t label_bytes[PAG_VIS_LABELS];
+    const float *conf[2];
+    const unsigned char *table;
+    int32_t max_id, box_width;
+    float blend_keep, blend_alpha, overlay_keep, overlay_alpha, conf_min, conf_max;
+    int32_t *workspace;
+    int64_t workspace_bytes;
+    unsigned char *out[PAG_VIS_PICTURES];
+} pag_vis_args;
+int64_t pag_vis_workspace_bytes(int max_id);
+int pag_vis_stats(const pag_vis_args *args, void *stream);
+int pag_vis_paint(const pag_vis_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

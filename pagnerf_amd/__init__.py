@@ -24,6 +24,9 @@
              <- loss/regularizers.py:41-70, pc_nerf/trainer.py:556-574 (the grid total-variation terms)
     dataset: DeviceMultiviewDataset, BatchSampler, SampleRays, sample_indices, epoch_views (dataset.py)
              <- datasets/multiview_dataset.py:120-192, datasets/transforms/ray_sampler.py:17-40, pc_nerf/trainer.py:216-219 (the step's inputs)
+    visualize: ValidationPictures, label_colors, label2rgb, depth2rgb, instance_boxes, overlay_instances, write_png, read_png (visualize.py)
+             <- pc_nerf/trainer.py:710-829 (the pictures of evaluate_metrics: imgviz label_colormap / label2rgb / depth2rgb, torchvision
+             masks_to_boxes / draw_bounding_boxes, the 0.7 blend), :855-896 (the frames written per validation)
     optim : Adam (torch.optim.Adam's interface on pag_adam_step) (optim.py) <- config_parser.py:667-673, trainer.py:583
     trainer: PanopticTrainer, LODAnneling (trainer.py) <- pc_nerf/trainer.py on wisp's BaseTrainer, utils/lod_anneling.py
     config : load_config, register_class, build_from_config (config.py) <- config_parser.py:557-603, :679-781
@@ -49,6 +52,8 @@ from .map_export import (MapAccumulator, generate_pc_map, generate_pc_map_from_v
 from .regularizers import (grid_tv_l1_loss, grid_tv_l2_loss, grid_tv_loss, step_tv_terms, tv_l1_loss, tv_l2_loss,    # noqa: F401
                            tv_loss)
 from .dataset import BatchSampler, DeviceMultiviewDataset, SampleRays, epoch_views, sample_indices    # noqa: F401
+from .visualize import (ValidationPictures, depth2rgb, instance_boxes, label2rgb, label_colors, overlay_instances,    # noqa: F401
+                        read_png, write_png)
 from . import optim                                                # noqa: F401
 from .trainer import LODAnneling, PanopticTrainer                  # noqa: F401
 from .config import build_from_config, load_config, register_class    # noqa: F401

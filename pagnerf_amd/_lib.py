@@ -105,6 +105,17 @@ class SampleMode(ctypes.Structure):
 SAMPLE_MAX_MODES = 12
 SAMPLE_COPY, SAMPLE_U8_TO_F32 = 0, 1
 
+VIS_PICTURES, VIS_LABELS, VIS_MAX_ID = 15, 6, 1023
+
+
+class VisArgs(ctypes.Structure):
+    """pag_vis_args (include/pagnerf_hip.h): the validation pictures of pc_nerf/trainer.py:710-829, :855-896."""
+    _fields_ = [("H", c_i32), ("W", c_i32), ("rgb", c_vp), ("rgb_is_u8", c_i32), ("rgb_stride", c_i32), ("gt", c_vp), ("gt_stride", c_i32), ("phase", c_i32),
+                ("depth", c_vp), ("labels", c_vp * VIS_LABELS), ("label_bytes", c_i32 * VIS_LABELS), ("conf", c_vp * 2), ("table", c_vp),
+                ("max_id", c_i32), ("box_width", c_i32), ("blend_keep", c_f32), ("blend_alpha", c_f32), ("overlay_keep", c_f32), ("overlay_alpha", c_f32),
+                ("conf_min", c_f32), ("conf_max", c_f32), ("workspace", c_vp), ("workspace_bytes", c_i64), ("out", c_vp * VIS_PICTURES)]
+
+
 _SIGS = {
     "pag_abi_version": (c_i32, []),
     "pag_last_error_string": (ctypes.c_char_p, []),
@@ -222,6 +233,9 @@ _SIGS = {
     "pag_sample_copy_width": (c_i32, [c_vp, c_vp, c_i64, c_i32]),
     "pag_sample_batch": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(SampleMode), c_i32, c_vp, c_vp, c_vp]),
     "pag_sample_advance": (c_i32, [c_vp, c_vp]),
+    "pag_vis_workspace_bytes": (c_i64, [c_i32]),
+    "pag_vis_stats": (c_i32, [ctypes.POINTER(VisArgs), c_vp]),
+    "pag_vis_paint": (c_i32, [ctypes.POINTER(VisArgs), c_vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -44,6 +44,7 @@ SOURCES = {
     "triplanar.hip": ["-ffp-contract=off"],  # tri-plane grid: grid_sample's bilinear / reflection op order
     "sparse.hip": [],                        # the touched-rows exchange's mask / plan / pack / unpack passes: integer and copy work only
     "sample.hip": [],                        # the dataset's ray sampling: keyed permutation and row gather, integer and copy work only
+    "visualize.hip": ["-ffp-contract=off"],  # validation pictures: the blends and the colour-map index in the tensor-op forms' op order
 }
 
 

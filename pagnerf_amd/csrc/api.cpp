@@ -1,4 +1,5 @@
-// ABI version + thread-local error string.
+// ABI version + thread-local error string.  The entry points themselves live beside their kernels (the newest, additive within ABI 14:
+// pag_tv_* in regularizer.hip, pag_sample_* in sample.hip, pag_vis_* - the validation pictures of pc_nerf/trainer.py:710-829 - in visualize.hip).
 #include <stdarg.h>
 #include <stdio.h>
 #include "../../include/pagnerf_hip.h"

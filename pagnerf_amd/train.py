@@ -1,5 +1,5 @@
 """python -m pagnerf_amd.train --config YAML --dataset TRAIN.npz [--val-dataset VAL.npz] [--log-dir DIR] [--resume CKPT] [--valid-only]
-                              [--save-map PATH] [--set key=value ...]
+                              [--val-pictures] [--save-map PATH] [--set key=value ...]
 
 The native counterpart of the reference's main_interactive.py: a shipped YAML, a dataset that is already arrays, and the trainer of trainer.py.
 
@@ -75,6 +75,8 @@ def main(argv=None):
     ap.add_argument("--log-dir", help="overrides the YAML's log_dir")
     ap.add_argument("--resume", metavar="CKPT", help="continue the run of a PanopticTrainer checkpoint")
     ap.add_argument("--valid-only", action="store_true", help="validate the (resumed / pretrained) model and exit")
+    ap.add_argument("--val-pictures", action="store_true", help="validation writes its frames as PNG files under <log_dir>/val/epoch_<e>/ (with "
+                    "--valid-only --resume CKPT: render what was trained)")
     ap.add_argument("--save-map", metavar="PATH", help="after training export the panoptic point cloud of the training views")
     ap.add_argument("--set", action="append", default=[], metavar="key=value", help="override an option of the flattened namespace (repeatable)")
     ap.add_argument("--device", default="cuda")
@@ -87,6 +89,8 @@ def main(argv=None):
         cfg["log_dir"] = args.log_dir
     if args.valid_only:
         cfg["valid_only"] = True
+    if args.val_pictures:
+        cfg["val_pictures"] = True
     logging.basicConfig(level=int(cfg.get("log_level") or logging.INFO), format="%(asctime)s|%(levelname)8s| %(message)s")
     device = torch.device(args.device)
     if device.type == "cuda" and device.index is None:

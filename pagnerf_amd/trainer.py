@@ -139,7 +139,8 @@ class PanopticTrainer:
 
     dataset / val_dataset: DeviceMultiviewDatasets.  Beside their modes the trainer reads these attributes when present: `semantic_info` (dict with
     things_ids / stuff_ids / num_classes), `image_shape` (H, W) of the validation images, `filenames`, `labelled` (per view: (semantics, instances)
-    carry labels).  Additions of this build: `seed` (the samplers' stream), `use_graphs` (None: leave the tracer as it is)."""
+    carry labels).  Additions of this build: `seed` (the samplers' stream), `use_graphs` (None: leave the tracer as it is), `val_pictures`
+    (validate() writes the frames of num_val_frames_to_save / render_val_labels as PNG files; off by default)."""
 
     def __init__(self, pipeline, dataset, val_dataset=None, *, epochs=250, batch_size=512, num_rays_sampled_per_img=4096, lr=0.001, weight_decay=0,
                  grid_lr_weight=100.0, delta_grid_lr_weight=100.0, optimizer_type="adam", log_dir="_results/logs/runs/", exp_name=None,
@@ -154,7 +155,7 @@ class PanopticTrainer:
                  inst_num_dilations=-1, val_mip=None, num_clustering_samples=0, num_val_frames_to_save=0, render_val_labels=False,
                  dataset_num_workers=-1, optimize_val_extrinsics=False, val_extrinsics_start=0, val_extrinsics_end=-1, val_extrinsics_every=0,
                  prune_every=-1, prune_at_epoch=-1, prune_at_start=False, low_res_val=False, save_grid=False, save_preds=False, sem_softmax=False,
-                 voxel_raymarch_epoch_start=-1, samples_per_voxel=256, seed=0, use_graphs=None, **kwargs):
+                 voxel_raymarch_epoch_start=-1, samples_per_voxel=256, seed=0, use_graphs=None, val_pictures=False, **kwargs):
         self.pipeline, self.dataset, self.val_dataset = pipeline, dataset, val_dataset
         self.extra_args = kwargs
         self.num_epochs, self.batch_size, self.num_rays_sampled_per_img = int(epochs), int(batch_size), int(num_rays_sampled_per_img)
@@ -205,6 +206,8 @@ class PanopticTrainer:
         self.low_res_val, self.save_grid, self.save_preds, self.sem_softmax = low_res_val, save_grid, save_preds, sem_softmax
         self.voxel_raymarch_epoch_start, self.samples_per_voxel = voxel_raymarch_epoch_start, samples_per_voxel
         self.seed = int(seed)
+        self.val_pictures = bool(val_pictures)
+        self._pictures = self._picture_host = None
 
         tracer = getattr(pipeline, "tracer", None)
         nef = getattr(pipeline, "nef", None)
@@ -595,10 +598,33 @@ class PanopticTrainer:
         emb = rb.inst_embedding.float().reshape(V, labels.shape[1], -1)
         pipe.nef.train_clustering(torch.nn.functional.normalize(emb, dim=-1), labels)
 
+    def _write_pictures(self, pool, pending, slot, directory, idx, pics, stack):
+        """One device-to-host copy of a frame's picture stack into a reused pinned buffer (two of them alternate: a buffer is filled again only after
+        the PNG writers of its last frame have finished), then one write_png job per picture on `pool`."""
+        from .visualize import PICTURES, write_png
+        if self._picture_host is None or self._picture_host[0].shape[1:] != stack.shape[1:]:
+            self._picture_host = [torch.empty((len(PICTURES),) + tuple(stack.shape[1:]), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        for f in pending[slot]:
+            f.result()
+        host = self._picture_host[slot][:stack.shape[0]]
+        host.copy_(stack, non_blocking=True)
+        torch.cuda.current_stream(stack.device).synchronize()
+        arrays = host.numpy()
+        pending[slot] = [pool.submit(write_png, os.path.join(directory, "%d.png" % idx if name == "rgb" else "%d_%s.png" % (idx, name)), arrays[i])
+                         for i, name in enumerate(pics)]
+
     def validate(self, epoch=0):
-        """:943-999 without the pictures: clustering fit, every validation image rendered with batch_render under no_grad, ValidationMetrics per image,
-        one row appended to <log_dir>/metrics.csv (header once).  save_preds: the uint8 [2,H,W] (semantics, instances) pair and the instance confidence
-        of each frame as <log_dir>/panoptic/<name>.npy and <log_dir>/inst_conf/<name>.npy.  -> the metrics dict."""
+        """:943-999: clustering fit, every validation image rendered with batch_render under no_grad, ValidationMetrics per image, one row appended to
+        <log_dir>/metrics.csv (header once).  save_preds: the uint8 [2,H,W] (semantics, instances) pair and the instance confidence of each frame
+        as <log_dir>/panoptic/<name>.npy and <log_dir>/inst_conf/<name>.npy.  -> the metrics dict.
+
+        val_pictures: the frames that visualize.select_frame picks (:855-857: every num_val_frames_to_save-th, all of them when that is >= the
+        number of images, and with render_val_labels every frame that carries labels) are painted by ValidationPictures.render (two launches per
+        frame), copied to the host once and written to <log_dir>/val/epoch_<epoch>/ (:980) by at most 4 writer threads, which are joined before
+        validate() returns: <idx>.png, <idx>_gt, _sem, _sem_pred, _sem_gt, _inst, _inst_pred, _inst_gt under the reference's names (:859-879), and
+        the frames it only puts into its videos as <idx>_depth, _sem_rgb, _sem_pred_rgb, _inst_conf, _inst_conf_pred, _inst_rgb, _inst_pred_rgb -
+        each only when its inputs exist and its channel is active at this epoch.  No mp4 is written (there is no encoder here): the numbered frames are
+        the hand-over to one.  The metrics row, save_preds and the return value do not depend on val_pictures."""
         from .core import batch_render
         from .metrics import ValidationMetrics
         pipe, nef = self.pipeline, self.pipeline.nef
@@ -630,6 +656,15 @@ class PanopticTrainer:
             if not use_base and "rays" not in ds.modes:
                 raise ValueError("validate: the validation dataset has no world-frame `rays`, and the pipeline holds no cameras for its `base_rays` "
                                  "(they are appended only with optimize_val_extrinsics)")
+            pool = pic_dir = None
+            pending, frames_written = [[], []], 0
+            if self.val_pictures:
+                from concurrent.futures import ThreadPoolExecutor
+                from .visualize import ValidationPictures, select_frame
+                if self._pictures is None:
+                    self._pictures = ValidationPictures()
+                pic_dir = os.path.join(self.log_dir, "val", "epoch_%d" % epoch)
+                pool = ThreadPoolExecutor(max_workers=4)
             render_time = time.time()
             for idx in range(ds.num_imgs):
                 data = ds.gather([idx], every)
@@ -649,6 +684,22 @@ class PanopticTrainer:
                                      ("inst_conf", out["inst_conf"].float())):
                         os.makedirs(os.path.join(self.log_dir, sub), exist_ok=True)
                         np.save(os.path.join(self.log_dir, sub, name + ".npy"), arr.cpu().numpy())
+                if pool is not None and select_frame(idx, ds.num_imgs, self.num_val_frames_to_save, self.render_val_labels, flags[idx][0] or flags[idx][1]):
+                    os.makedirs(pic_dir, exist_ok=True)
+                    conf_pred = data["inst_conf"].reshape(H, W) if (use_inst and "inst_conf" in data) else None
+                    pics = self._pictures.render(
+                        rb, data["imgs"].reshape(H, W, -1), semantics=out["semantics"], instances=out["instances"],
+                        inst_conf=None if ev.predict_clusters is not None else out["inst_conf"],                # :737-742: no confidence beside clusters
+                        sem_gt=img(sem_key) if (use_sem and flags[idx][0]) else None,                            # :719-721
+                        inst_gt=img(inst_key) if (use_inst and flags[idx][0] and flags[idx][1]) else None,       # :784, :800
+                        sem_pred=img("semantics_pred") if use_sem else None, inst_pred=img("instance_pred") if use_inst else None,
+                        inst_conf_pred=conf_pred)
+                    self._write_pictures(pool, pending, frames_written % 2, pic_dir, idx, list(pics), self._pictures.stack)
+                    frames_written += 1
+            if pool is not None:
+                pool.shutdown(wait=True)
+                for f in pending[0] + pending[1]:
+                    f.result()
             metrics = ev.compute()
             render_time = time.time() - render_time
         metrics["epoch"] = epoch
