@@ -1063,6 +1063,33 @@ int64_t pag_vis_workspace_bytes(int max_id);
 int pag_vis_stats(const pag_vis_args *args, void *stream);
 int pag_vis_paint(const pag_vis_args *args, void *stream);
 
+/* View preparation of a NeRF-standard dataset (datasets/formats/nerf_standard.py:57-60 img_as_float32 + resize_mip, :239-267 the per-view ray grid,
+ * :269-282 masks and the alpha composite; datasets/formats/bup20.py:203-229 the nearest label resample; additive, ABI 14): prepare.hip.
+ * pagnerf_amd/formats.py holds the tensor-op forms (`prepare_views_reference`, `prepare_labels_reference`, `rays_reference`) that define the results.
+ *   src      DEVICE uint8 [B, H0, W0, C0], C0 = 3 or 4: the decoded frames of a chunk.  f = 2^mip must divide H0 and W0; h = H0 / f, w = W0 / f.
+ *   imgs     f32 [V, h, w, 3]: per channel (float)S / (float)(255 f f), S the integer sum of the f x f block, one IEEE division; with C0 = 4 composited
+ *            onto the background with a = the fourth channel: PAG_BG_WHITE clamp((v * a) + (1 - a), 0, 1), PAG_BG_BLACK clamp(v - (1 - a), 0, 1), three
+ *            roundings in that order (built without FMA contraction): bit for bit the definition.
+ *   masks    uint8 [V, h, w, 1]: a > 0.5 (1 with C0 = 3)
+ *   origins  f32 [V, h, w, 3]: c2w[v][:, 3], a copy.    c2w: DEVICE f32 [V, 3, 4], camera -> world, indexed by the DESTINATION view
+ *   dirs     f32 [V, h, w, 3]: normalise(R d_cam), R = c2w[v][:, :3], d_cam = ((x + 0.5 - w/2 - x0) / fx, -(y + 0.5 - h/2 - y0) / fy, -1)
+ * Chunk view b is written to view view_offset + b of every destination; any subset of the four outputs may be NULL (not written; src is needed for imgs /
+ * masks only, c2w for origins / dirs only).  One launch; a thread per output pixel, an RGBA pixel read as one word (8- and 16-byte vectors along a block
+ * row where f and the address of src allow), RGB and sources that are not word-aligned by bytes; the destinations need their dtype's alignment only.
+ * No atomics, no workspace.  Refused (PAG_ERR_ARG) before any launch: mip outside [0, 8], B outside
+ * [0, 65535], C0 other than 3 / 4, sizes < 1 or not divisible by f, more than 2^30 output pixels, view_offset < 0 or view_offset + B > V, an unknown
+ * background, a NULL src / c2w that a requested output needs, a zero or NaN focal length with dirs.  B == 0 or no output is a no-op.
+ * pag_prepare_labels: all label planes of a chunk in one launch: dst[view_offset + b][y][x] = src[b][y f][x f] for each plane (src DEVICE uint8
+ * [B, H0, W0], dst int64 [V, h, w, 1]); at most PAG_PREPARE_MAX_PLANES planes, the same size checks, NULL planes refused. */
+#define PAG_PREPARE_MAX_PLANES 8
+typedef struct pag_label_plane {
+    const void *src;
+    int64_t *dst;
+} pag_label_plane;
+int pag_prepare_views(const void *src, int B, int H0, int W0, int C0, int mip, int bg, const float *c2w, float fx, float fy, float x0, float y0,
+                      int64_t view_offset, int64_t V, float *imgs, unsigned char *masks, float *origins, float *dirs, void *stream);
+int pag_prepare_labels(const pag_label_plane *planes, int n_planes, int B, int H0, int W0, int mip, int64_t view_offset, int64_t V, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

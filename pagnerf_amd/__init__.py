@@ -30,7 +30,9 @@
     optim : Adam (torch.optim.Adam's interface on pag_adam_step) (optim.py) <- config_parser.py:667-673, trainer.py:583
     trainer: PanopticTrainer, LODAnneling (trainer.py) <- pc_nerf/trainer.py on wisp's BaseTrainer, utils/lod_anneling.py
     config : load_config, register_class, build_from_config (config.py) <- config_parser.py:557-603, :679-781
-    train  : `python -m pagnerf_amd.train` (train.py) <- main_interactive.py, on datasets stored as .npz
+    train  : `python -m pagnerf_amd.train` (train.py) <- main_interactive.py, on a NeRF-standard folder or arrays stored as .npz
+    formats: load_nerf_standard, standard_cameras, decode_image, prepare_views_reference, prepare_labels_reference (formats.py)
+             <- datasets/formats/nerf_standard.py, the label resample of datasets/formats/bup20.py:203-229 (`python -m pagnerf_amd.formats`: folder -> .npz)
 
 All compute goes through libpagnerf_hip.so (include/pagnerf_hip.h); there is no CPU fallback.
 """
@@ -54,6 +56,8 @@ from .regularizers import (grid_tv_l1_loss, grid_tv_l2_loss, grid_tv_loss, step_
 from .dataset import BatchSampler, DeviceMultiviewDataset, SampleRays, epoch_views, sample_indices    # noqa: F401
 from .visualize import (ValidationPictures, depth2rgb, instance_boxes, label2rgb, label_colors, overlay_instances,    # noqa: F401
                         read_png, write_png)
+from .formats import (decode_image, load_nerf_standard, prepare_labels_reference, prepare_views_reference,    # noqa: F401
+                      standard_cameras)
 from . import optim                                                # noqa: F401
 from .trainer import LODAnneling, PanopticTrainer                  # noqa: F401
 from .config import build_from_config, load_config, register_class    # noqa: F401

@@ -105,6 +105,13 @@ class SampleMode(ctypes.Structure):
 SAMPLE_MAX_MODES = 12
 SAMPLE_COPY, SAMPLE_U8_TO_F32 = 0, 1
 
+class LabelPlane(ctypes.Structure):
+    """pag_label_plane (include/pagnerf_hip.h)."""
+    _fields_ = [("src", c_vp), ("dst", c_vp)]
+
+
+PREPARE_MAX_PLANES = 8
+
 VIS_PICTURES, VIS_LABELS, VIS_MAX_ID = 15, 6, 1023
 
 
@@ -236,6 +243,8 @@ _SIGS = {
     "pag_vis_workspace_bytes": (c_i64, [c_i32]),
     "pag_vis_stats": (c_i32, [ctypes.POINTER(VisArgs), c_vp]),
     "pag_vis_paint": (c_i32, [ctypes.POINTER(VisArgs), c_vp]),
+    "pag_prepare_views": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_f32, c_f32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pag_prepare_labels": (c_i32, [ctypes.POINTER(LabelPlane), c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp]),
 }
 
 EXPORTS = tuple(_SIGS)

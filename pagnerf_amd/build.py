@@ -45,6 +45,7 @@ SOURCES = {
     "sparse.hip": [],                        # the touched-rows exchange's mask / plan / pack / unpack passes: integer and copy work only
     "sample.hip": [],                        # the dataset's ray sampling: keyed permutation and row gather, integer and copy work only
     "visualize.hip": ["-ffp-contract=off"],  # validation pictures: the blends and the colour-map index in the tensor-op forms' op order
+    "prepare.hip": ["-ffp-contract=off"],    # dataset view preparation: the alpha composite in the tensor-op form's op order (three roundings)
 }
 
 

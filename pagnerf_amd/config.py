@@ -24,7 +24,7 @@ _LOGGED_IGNORED = set()
 _BUILDER_KEYS = frozenset({"nef_type", "tracer_type", "trainer_type", "grid_type", "optimize_extrinsics", "optimize_val_extrinsics", "pretrained",
                            "model_format", "tree_type", "base_lod", "num_lods", "max_grid_res", "valid_only", "ray_max_travel", "num_classes",
                            "num_instances", "anchor_frame_idxs", "pose_opt_only_frame_idxs", "log_level", "config", "delta_capacity_log_2", "min_distance", "max_distance",
-                           "raymarch_type", "num_steps"})
+                           "raymarch_type", "num_steps", "mip", "bg_color", "dataset_num_workers"})      # the last three: train.load_dataset
 
 
 def register_class(cls, name=None):

@@ -25,15 +25,15 @@ from . import ops
 from .core import Rays
 
 
-def pinhole_base_rays(width, height, focal_x, focal_y, x0=0.0, y0=0.0, mip=0, device=None):
+def pinhole_base_rays(width, height, focal_x, focal_y, x0=0.0, y0=0.0, mip=0, device=None, dtype=torch.float32):
     """Camera-frame rays of one image at `mip` (:83-98: size // 2^mip, intrinsics / 2^mip, pixel centres, identity extrinsics) -> Rays [h*w], row-major
     (y slow).  wisp's generate_centered_pixel_coords / generate_pinhole_rays are third party (RECALLED from the public wisp / kaolin sources, PARITY
     UNPINNED):  px = x + 0.5, py = y + 0.5;  dir = normalise(((px - w/2 - x0) / fx, -(py - h/2 - y0) / fy, -1));  origin = 0.
-    Every export below also takes ready-made base rays, so nothing pinned depends on this helper."""
+    Every export below also takes ready-made base rays, so nothing pinned depends on this helper.  dtype: the precision it is evaluated in."""
     f = 2 ** mip
     w, h = int(width // f), int(height // f)
     fx, fy, cx, cy = focal_x / f, focal_y / f, x0 / f, y0 / f
-    py, px = torch.meshgrid(torch.arange(h, dtype=torch.float32, device=device) + 0.5, torch.arange(w, dtype=torch.float32, device=device) + 0.5,
+    py, px = torch.meshgrid(torch.arange(h, dtype=dtype, device=device) + 0.5, torch.arange(w, dtype=dtype, device=device) + 0.5,
                             indexing="ij")
     d = torch.stack(((px - w / 2.0 - cx) / fx, -(py - h / 2.0 - cy) / fy, -torch.ones_like(px)), -1).reshape(-1, 3)
     d = d / torch.linalg.norm(d, dim=-1, keepdim=True)

@@ -1900,3 +1900,87 @@ def sample_advance(state):
     if state.dtype != torch.int64 or state.numel() != 2:
         raise RuntimeError("sample_advance: state int64 [2]")
     _call("pag_sample_advance", state.data_ptr(), L.stream())
+
+
+def _prepare_sizes(name, src, mip, planes_dims):
+    mip = int(mip)
+    if not 0 <= mip <= 8:
+        raise RuntimeError("%s: mip %d not in [0, 8]" % (name, mip))
+    if src.dtype != torch.uint8 or src.dim() != planes_dims or not src.is_contiguous():
+        raise RuntimeError("%s: the source is a contiguous uint8 tensor of %d axes, got %s %s" % (name, planes_dims, src.dtype, tuple(src.shape)))
+    B, H0, W0 = src.shape[:3]
+    f = 1 << mip
+    if H0 % f or W0 % f:
+        raise RuntimeError("%s: source size %d x %d is not divisible by 2^mip = %d" % (name, H0, W0, f))
+    return mip, B, H0, W0, H0 // f, W0 // f
+
+
+def _prepare_dst(name, what, t, dtype, V, h, w, C, view_offset, B):
+    if t is None:
+        return V
+    _check_gpu(t)
+    if t.dtype != dtype or t.dim() != 4 or tuple(t.shape[1:]) != (h, w, C) or not t.is_contiguous():
+        raise RuntimeError("%s: %s is a contiguous %s [V, %d, %d, %d], got %s %s" % (name, what, dtype, h, w, C, t.dtype, tuple(t.shape)))
+    if V is not None and t.shape[0] != V:
+        raise RuntimeError("%s: %s holds %d views, the other outputs %d" % (name, what, t.shape[0], V))
+    if view_offset < 0 or view_offset + B > t.shape[0]:
+        raise RuntimeError("%s: views [%d, %d) outside %s's [0, %d)" % (name, view_offset, view_offset + B, what, t.shape[0]))
+    return t.shape[0]
+
+
+def prepare_views(src_u8, mip, bg_color, view_offset=0, imgs=None, masks=None, origins=None, dirs=None, c2w=None, intrinsics=None):
+    """datasets/formats/nerf_standard.py:57-60 and :239-282 for the decoded frames of a chunk, as one launch (pag_prepare_views): src_u8 uint8
+    [B, H0, W0, 3 or 4] on the GPU -> views [view_offset, view_offset + B) of the requested outputs, each the whole dataset's tensor: imgs f32 [V, h, w, 3],
+    masks bool (or uint8) [V, h, w, 1], origins / dirs f32 [V, h, w, 3].  The rays need c2w f32 [V, 3, 4] (of the DESTINATION views) and
+    intrinsics = (fx, fy, x0, y0) at the output size.  pagnerf_amd.formats holds the definition."""
+    name = "prepare_views"
+    _check_gpu(src_u8, c2w)
+    view_offset = int(view_offset)
+    mip, B, H0, W0, h, w = _prepare_sizes(name, src_u8, mip, 4)
+    C0 = src_u8.shape[3]
+    if C0 not in (3, 4):
+        raise RuntimeError("%s: %d source channels, 3 or 4 expected" % (name, C0))
+    if bg_color not in ("white", "black"):
+        raise RuntimeError("%s: bg_color %r is neither 'white' nor 'black'" % (name, bg_color))
+    if masks is not None and masks.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError("%s: masks is bool or uint8, got %s" % (name, masks.dtype))
+    V = _prepare_dst(name, "imgs", imgs, torch.float32, None, h, w, 3, view_offset, B)
+    V = _prepare_dst(name, "masks", masks, masks.dtype if masks is not None else None, V, h, w, 1, view_offset, B)
+    V = _prepare_dst(name, "origins", origins, torch.float32, V, h, w, 3, view_offset, B)
+    V = _prepare_dst(name, "dirs", dirs, torch.float32, V, h, w, 3, view_offset, B)
+    if V is None:
+        return
+    fx = fy = x0 = y0 = 0.0
+    if origins is not None or dirs is not None:
+        if c2w is None or c2w.dtype != torch.float32 or tuple(c2w.shape) != (V, 3, 4) or not c2w.is_contiguous():
+            raise RuntimeError("%s: the rays need c2w, a contiguous f32 [%d, 3, 4]" % (name, V))
+        if dirs is not None:
+            if intrinsics is None or len(intrinsics) != 4:
+                raise RuntimeError("%s: dirs needs intrinsics = (fx, fy, x0, y0)" % name)
+            fx, fy, x0, y0 = (float(v) for v in intrinsics)
+    p = lambda t: t.data_ptr() if t is not None else None
+    _call("pag_prepare_views", src_u8.data_ptr(), B, H0, W0, C0, mip, L.BG_WHITE if bg_color == "white" else L.BG_BLACK, p(c2w), fx, fy, x0, y0, view_offset, V,
+          p(imgs), p(masks), p(origins), p(dirs), L.stream())
+
+
+def prepare_labels(planes, mip, view_offset=0):
+    """datasets/formats/bup20.py:203-229 (nearest resample at an integer factor) for every label plane of a chunk in one launch (pag_prepare_labels):
+    planes = [(src uint8 [B, H0, W0], dst int64 [V, h, w, 1])] on the GPU; dst[view_offset + b, y, x] = src[b, y * 2^mip, x * 2^mip]."""
+    name = "prepare_labels"
+    view_offset = int(view_offset)
+    if len(planes) > L.PREPARE_MAX_PLANES:
+        raise RuntimeError("%s: %d planes, at most %d per launch" % (name, len(planes), L.PREPARE_MAX_PLANES))
+    if not planes:
+        return
+    arr = (L.LabelPlane * len(planes))()
+    size, V = None, None
+    for a, (src, dst) in zip(arr, planes):
+        _check_gpu(src, dst)
+        mip, B, H0, W0, h, w = _prepare_sizes(name, src, mip, 3)
+        if size is not None and (B, H0, W0) != size:
+            raise RuntimeError("%s: planes of different sizes, %s and %s" % (name, size, (B, H0, W0)))
+        size = (B, H0, W0)
+        V = _prepare_dst(name, "a destination", dst, torch.int64, V, h, w, 1, view_offset, B)
+        a.src, a.dst = src.data_ptr(), dst.data_ptr()
+    B, H0, W0 = size
+    _call("pag_prepare_labels", arr, len(planes), B, H0, W0, mip, view_offset, V, L.stream())

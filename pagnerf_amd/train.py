@@ -1,9 +1,11 @@
-"""python -m pagnerf_amd.train --config YAML --dataset TRAIN.npz [--val-dataset VAL.npz] [--log-dir DIR] [--resume CKPT] [--valid-only]
+"""python -m pagnerf_amd.train --config YAML --dataset TRAIN.npz|DIR [--val-dataset VAL.npz|DIR] [--log-dir DIR] [--resume CKPT] [--valid-only]
                               [--val-pictures] [--save-map PATH] [--set key=value ...]
 
-The native counterpart of the reference's main_interactive.py: a shipped YAML, a dataset that is already arrays, and the trainer of trainer.py.
+The native counterpart of the reference's main_interactive.py: a shipped YAML, a dataset, and the trainer of trainer.py.
 
-The .npz holds the arrays of the dict MultiviewDataset.init() leaves:
+A dataset is a NeRF-standard folder (transforms*.json and image files; formats.load_nerf_standard with the YAML's `mip`, `bg_color` and
+`dataset_num_workers`, split 'train' for --dataset and 'val' for --val-dataset; without --val-dataset the folder's own 'val' split when it has one), or
+an .npz of arrays (python -m pagnerf_amd.formats writes one from a folder).  The .npz holds the arrays of the dict MultiviewDataset.init() leaves:
 
     imgs [V,H,W,3] float32 and every further per-view mode (semantics, instance, semantics_pred, instance_pred, sem_conf, inst_conf ...) [V,H,W,C]
     base_rays_origins, base_rays_dirs [H,W,3]   the camera-frame rays the views share (pose optimisation), base_rays_range [2] = (near, far)
@@ -12,7 +14,7 @@ The .npz holds the arrays of the dict MultiviewDataset.init() leaves (INTEGRATIO
     num_classes, num_instances (scalars), things_ids, stuff_ids (int arrays)    the `semantic_info` lists
     optional: scale (scalar), filenames [V]
 
-File-format loaders (BUP20, nerf_standard ...) are not part of this package.
+The NeRF-standard loader, with this package's label extension, is formats.py; BUP20's own loader (agrobot_base.py) is not part of this package.
 """
 import argparse
 import logging
@@ -53,6 +55,17 @@ def load_npz_dataset(path, device):
     return ds
 
 
+def load_dataset(path, split, cfg, device):
+    """--dataset / --val-dataset: a folder goes to formats.load_nerf_standard (split `split`; mip, bg_color and dataset_num_workers from the YAML
+    namespace), anything else to load_npz_dataset."""
+    path = os.path.expanduser(path)
+    if not os.path.isdir(path):
+        return load_npz_dataset(path, device)
+    from .formats import load_nerf_standard
+    return load_nerf_standard(path, split=split, mip=int(cfg.get("mip") or 0), bg_color=cfg.get("bg_color") or "white", device=device,
+                              num_workers=int(cfg.get("dataset_num_workers") or 0))
+
+
 def save_map(trainer, dataset, path):
     """--save-map: the panoptic point cloud of the trained field from the training views (map_export.generate_pc_map_from_views)."""
     from . import map_export
@@ -70,8 +83,9 @@ def save_map(trainer, dataset, path):
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m pagnerf_amd.train", description=__doc__.split("\n\n")[1])
     ap.add_argument("--config", required=True, help="a YAML in the reference's layout (configs/bup20/*.yaml)")
-    ap.add_argument("--dataset", required=True, help="training views as .npz")
-    ap.add_argument("--val-dataset", help="validation views as .npz (needed with optimize_val_extrinsics and for validation)")
+    ap.add_argument("--dataset", required=True, help="training views: a NeRF-standard folder or an .npz")
+    ap.add_argument("--val-dataset", help="validation views: a NeRF-standard folder or an .npz (needed with optimize_val_extrinsics and for validation; default: the "
+                    "'val' split of a --dataset folder that has one)")
     ap.add_argument("--log-dir", help="overrides the YAML's log_dir")
     ap.add_argument("--resume", metavar="CKPT", help="continue the run of a PanopticTrainer checkpoint")
     ap.add_argument("--valid-only", action="store_true", help="validate the (resumed / pretrained) model and exit")
@@ -95,8 +109,12 @@ def main(argv=None):
     device = torch.device(args.device)
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())        # the dataset compares devices with their index
-    dataset = load_npz_dataset(args.dataset, device)
-    val_dataset = load_npz_dataset(args.val_dataset, device) if args.val_dataset else None
+    dataset = load_dataset(args.dataset, "train", cfg, device)
+    val_root = args.val_dataset
+    if not val_root and os.path.isdir(os.path.expanduser(args.dataset)):
+        from .formats import transforms_files
+        val_root = args.dataset if "val" in transforms_files(args.dataset) else None
+    val_dataset = load_dataset(val_root, "val", cfg, device) if val_root else None
     _, trainer = config.build_from_config(cfg, dataset, val_dataset, device=device)
     if args.resume:
         trainer.resume(args.resume)
