@@ -154,10 +154,9 @@ def _marched_samples(dev, n_rays, steps, seed=1):
     return samples.reshape(-1, 3).contiguous(), ridx
 
 
-@pytest.mark.parametrize("upsampled", [False, True])
-def test_real_shapes_against_the_tensor_op_path(gpu_device, upsampled):
-    """16 / 48 components at R = 128 (and upsampled to 144), about 2 x 10^5 samples marched along real rays, a third of them with zero upstream
-    gradients: kernels against the nef's tensor-op path, the project's elementwise tolerances."""
+def _real_shapes(gpu_device, upsampled, n_rays, m_min, m_max):
+    """Ray-ordered samples of n_rays marched rays, every third ray with zero upstream gradients: kernels against the nef's tensor-op path, the
+    project's elementwise tolerances."""
     import pagnerf_amd
     torch.manual_seed(3)
     grid = pagnerf_amd.TensoRF(blas_level=4).to(gpu_device)
@@ -165,9 +164,10 @@ def test_real_shapes_against_the_tensor_op_path(gpu_device, upsampled):
         grid.step_upsample_vm_grid()
     f = grid.features
     assert f.res == (144 if upsampled else 128)
-    x, ridx = _marched_samples(gpu_device, 480, 512)
+    x, ridx = _marched_samples(gpu_device, n_rays, 512)
     M = x.shape[0]
-    assert 150_000 <= M <= 250_000, M
+    print("%d rays: %d samples, %d backward chunks" % (n_rays, M, (M + 255) // 256))
+    assert m_min <= M <= m_max, M
     gs, ga = torch.randn(M, device=gpu_device), torch.randn(M, H.APP, device=gpu_device)
     dead = (ridx % 3 == 0)
     gs[dead], ga[dead] = 0.0, 0.0
@@ -184,6 +184,20 @@ def test_real_shapes_against_the_tensor_op_path(gpu_device, upsampled):
         print("%-18s rel-L2 %.3e" % (n, H.rel_l2(got[n].cpu().numpy(), want[n].cpu().numpy())))
     for n in want:
         _close(got[n], want[n], 2e-4, 2e-5, n)
+
+
+@pytest.mark.parametrize("upsampled", [False, True])
+def test_real_shapes_against_the_tensor_op_path(gpu_device, upsampled):
+    """16 / 48 components at R = 128 (and upsampled to 144), about 2 x 10^5 samples marched along real rays, a third of them with zero upstream
+    gradients: kernels against the nef's tensor-op path, the project's elementwise tolerances."""
+    _real_shapes(gpu_device, upsampled, 480, 150_000, 250_000)
+
+
+def test_real_shapes_past_the_backward_stride(gpu_device):
+    """The backward launches at most 1024 workgroups that stride over 256-sample chunks, so a workgroup takes a second chunk - and carries the tap
+    sums of the cell it was in from one chunk into the next - only with more than 1024 x 256 samples: more marched rays than above, same ray
+    order, same dead-ray pattern, same gates."""
+    _real_shapes(gpu_device, False, 840, 1024 * 256 + 256 + 1, 450_000)
 
 
 def test_bf16_decoders_stay_within_the_bf16_tolerance(gpu_device, g16):

@@ -152,6 +152,55 @@ def rel_l2(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
 
 
+# The launch-regime cases of tests/test_gpu_semantic_nef_regimes.py: key -> (samples, classes, channels with an upstream gradient).  Their noise floors
+# are stored in g15b_semantic_regimes.npz (tests/golden/make_golden_semantic_regimes.py); weights, inputs and upstream gradients come from the seeds.
+CHANNELS = ("density", "rgb", "semantics")
+M_SLICES, M_PERSIST = 2049, 256 * 256 + 256 + 33
+REGIME_CASES = {
+    "m2049": (M_SLICES, 6, CHANNELS),
+    "m65825": (M_PERSIST, 6, CHANNELS),
+    "c1": (M_SLICES, 1, CHANNELS),
+    "c16": (M_SLICES, 16, CHANNELS),
+    "only_density": (M_SLICES, 6, ("density",)),
+    "only_rgb": (M_SLICES, 6, ("rgb",)),
+    "only_semantics": (M_SLICES, 6, ("semantics",)),
+}
+NEAR_ZERO = 0.02
+
+
+def regime_case(key, seed=SEED):
+    """-> (weights, coords, dirs, upstream, plain) of a case for one weight seed: `plain` is the fp32 restatement's outputs, the density upstream is
+    zeroed where its |density_pre| < NEAR_ZERO (a ReLU flip there would move a whole term), channels without an upstream gradient hold zeros."""
+    M, C, chans = REGIME_CASES[key]
+    w = make_weights(seed, classes=C)
+    x, d = make_inputs(n=M)
+    with torch.no_grad():
+        plain = {k: v.numpy() for k, v in restate({k: torch.from_numpy(v) for k, v in w.items()}, torch.from_numpy(x), torch.from_numpy(d)).items()}
+    up = make_upstream(seed, n=M, classes=C)
+    up["density"][np.abs(plain["density_pre"]) < NEAR_ZERO] = 0.0
+    for c in CHANNELS:
+        if c not in chans:
+            up[c] = np.zeros_like(up[c])
+    return w, x, d, up, plain
+
+
+def wgrad_split(M, C=CLASSES):
+    """(tiles, tile pairs, slices, pairs per slice) of the weight-gradient pass for M samples.  The slice count is read off the library's backward
+    workspace size (one slab set per slice, 2656 bf16 of dz per sample padded to 256 samples: DESIGN 4.16), so a change of the kernel's constants
+    shows here; the 32-sample tile and the pair are the MFMA shape."""
+    import __graft_entry__ as ge
+    ge.build()
+    from pagnerf_amd import _lib as L
+    ws = lambda m: int(L.load().pag_deep_mlp_workspace_bytes(m, 256, C, 2))                    # noqa: E731
+    pad = lambda m: (m + 255) // 256 * 256                                                     # noqa: E731
+    unit = ws(65) - ws(64)                      # 2 -> 3 tiles is 1 -> 2 pairs at the same padded size: one more slab set
+    extra = ws(M) - ws(1) - (pad(M) - 256) * 2656 * 2
+    assert unit > 0 and extra % unit == 0, (unit, extra)
+    ntile = (M + 31) // 32
+    npair, n_split = (ntile + 1) // 2, 1 + extra // unit
+    return ntile, npair, n_split, -(-npair // n_split)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------ tests
 @pytest.fixture(scope="module")
 def g15():
@@ -397,3 +446,35 @@ def test_rgb_needs_one_direction_per_batch_entry():
         a = nef(channels={"density", "semantics"}, coords=x, ray_d=d[:2])      # unused, so its shape does not matter
         b = nef(channels={"density", "semantics"}, coords=x, ray_d=None)
     assert torch.equal(a["density"], b["density"]) and torch.equal(a["semantics"], b["semantics"])
+
+
+def test_regime_floors_hold_every_case_channel_and_parameter():
+    """g15b_semantic_regimes.npz (floors only): every case of REGIME_CASES with its sizes, a floor per output channel and one per parameter of
+    param_shapes(classes=C)."""
+    g = golden("g15b_semantic_regimes.npz")
+    assert sorted(str(k) for k in g["cases"]) == sorted(REGIME_CASES)
+    for key, (M, C, chans) in REGIME_CASES.items():
+        assert int(g[key + "_M"]) == M and int(g[key + "_C"]) == C, key
+        for c in ("feats",) + CHANNELS:
+            assert 0.0 < float(g[key + "_floor_" + c]) < 1e-2, (key, c)
+        names = [str(n) for n in g[key + "_grad_names"]]
+        assert names == sorted(n for n in param_shapes(classes=C) if not n.endswith("bands")), key
+        floors = g[key + "_grad_floors"]
+        assert floors.shape == (len(names),) and np.isfinite(floors).all() and (floors >= 0).all() and floors.max() < 5e-2, key
+        for n, f in zip(names, floors):                  # a head without an upstream gradient has a gradient of exactly zero: no floor
+            head = {"decoder_density": "density", "decoder_color": "rgb", "decoder_semantics": "semantics"}.get(n.split(".")[0])
+            if head is not None and head not in chans:
+                assert f == 0.0, (key, n, f)
+            elif n.endswith("weight"):
+                assert f > 0.0, (key, n, f)
+
+
+def test_regime_sizes_sit_in_the_launch_regimes_they_are_named_for():
+    """2049 samples: an odd tile count whose last tile holds one sample, two tile pairs per weight-gradient slice, and slices with nothing to do;
+    65 825 samples: more 256-sample batches than the 256 workgroups of the persistent kernels, and a short last slice."""
+    ntile, npair, n_split, per = wgrad_split(M_SLICES)
+    assert ntile % 2 == 1 and M_SLICES % 32 == 1 and per >= 2 and per * (n_split - 1) >= npair and npair % per != 0, (ntile, npair, n_split, per)
+    ntile, npair, n_split, per = wgrad_split(M_PERSIST)
+    assert per >= 2 and npair % per != 0 and per * (n_split - 1) < npair, (ntile, npair, n_split, per)
+    assert (M_PERSIST + 255) // 256 > 256 and M_PERSIST % 256 == 33
+    assert wgrad_split(2048)[3] == 1                    # the sizes of tests/test_gpu_semantic_nef.py: at most one pair per slice
