@@ -21,13 +21,14 @@
 //
 // FP32 path (PAG_MLP_FP32): one lane per sample, fp32 FMA chains in k order with the weights
 // broadcast from LDS - the parity path (tolerance 1e-5 against the fp32 oracle).
+//
+// Dynamic LDS: a kernel takes its regions from its layout struct in mlp_lds.h (lds_at<T>(smem, L.region)) and its launcher passes the same
+// struct's `bytes` - a region is added there, once.  mlp_fwd_mfma and head_composite_fwd_kernel are the exceptions (mlp_lds.h says why): their
+// carve-up is still a chain that has to be kept in step with FwdLds / HeadCompLds by hand.
 #include "mlp_common.h"
+#include "mlp_lds.h"
 
 namespace {
-
-constexpr int WIDE_BWD_WAVES = 8;      // waves per workgroup of mlp_bwd_wide_mfma (8 or 16; one workgroup per CU)
-constexpr int RS = 72;          // LDS row stride (bf16 elements) of a 64-wide weight row: 144 B
-constexpr int HID = 64;
 
 __device__ __forceinline__ int swap23(int a) { return (a & ~12) | ((a & 4) << 1) | ((a & 8) >> 1); }
 struct FwdParams {
@@ -260,8 +261,6 @@ __device__ __forceinline__ void raw_to_block(const V (&raw)[4], f32x16 &acc) {
 // GRBM_GUI_ACTIVE).  Row-major [M,64] bf16 tiles (32 rows = 4 KiB contiguous) and 32-column blocks of the wide
 // [M,W] tensors therefore go through a wave-private LDS buffer: global side = fully coalesced 16-byte-per-lane
 // accesses, register side = ds_read/ds_write_b64 in accumulator layout.
-constexpr int ST_RS = 72;                         // staging row stride in bf16 (144 B: conflict-light for b64 and b128)
-constexpr int ST_BYTES = 32 * ST_RS * 2;          // 4608 B per wave
 
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -463,7 +462,6 @@ __device__ __forceinline__ void wt_chain_pinned(const bf16_t *Wt, int stride, co
 // 16 rows, one chunk column) land in 16 different bank pairs, and the 4 rows of a transposed block use 4 different chunk
 // groups, so neither access pattern has bank conflicts (the 32-lane ds_read_b64 of a whole column is 2-way).
 typedef short i16x4 __attribute__((ext_vector_type(4)));
-constexpr int TW_ELEMS = 32 * 64;
 __device__ __forceinline__ int tw_f(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 __device__ __forceinline__ int tw_off(int row, int chunk) { return row * 64 + ((chunk ^ tw_f(row)) << 2); }
 // row-major global pieces (tile64_fetch: piece `it` of a lane = row it*8 + lane/8, channels 8*(lane%8)..+7)
@@ -549,6 +547,7 @@ template <typename X1T, typename OutT, int NL, int OBMAX>
 __global__ __launch_bounds__(256, (OBMAX > 2 ? FWD_WAVES_WIDE : FWD_WAVES_NARROW)) void mlp_fwd_mfma(FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int OB = (p.out_dim + 31) / 32;
+    // FwdLds(NL, OB), written as a chain: with the run-time OB, absolute offsets compile to different code (see mlp_lds.h)
     bf16_t *W0s = reinterpret_cast<bf16_t *>(smem);                  // [64][RS] natural k
     bf16_t *W1s = W0s + 64 * RS;                                     // [64][RS] permuted k (NL == 3)
     bf16_t *WLs = W1s + (NL == 3 ? 64 * RS : 0);                     // [OB*32][RS] permuted k
@@ -834,13 +833,12 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_fast(FwdParams p) {
     constexpr bool GRP = KIND != 1;
     constexpr int NKS0 = GRP ? 4 : 3;
     constexpr float LOG2E = 1.4426950408889634f;
-    bf16_t *W0s = reinterpret_cast<bf16_t *>(smem);                  // [64][RS] natural k
-    bf16_t *W1s = W0s + 64 * RS;                                     // [64][RS] permuted k (NL == 3)
-    bf16_t *WLs = W1s + (NL == 3 ? 64 * RS : 0);                     // [32][RS] permuted k
-    float *b0s = reinterpret_cast<float *>(WLs + 32 * RS);
-    float *b1s = b0s + 64;
-    float *bLs = b1s + 64;
-    bf16_t *stg = reinterpret_cast<bf16_t *>(bLs + 32) + (threadIdx.x >> 6) * (ST_BYTES / 2);      // wave-private staging tile
+    constexpr FwdLds L(NL, 1);
+    bf16_t *W0s = lds_at<bf16_t>(smem, L.W0);                        // [64][RS] natural k
+    bf16_t *W1s = lds_at<bf16_t>(smem, L.W1);                        // [64][RS] permuted k (NL == 3)
+    bf16_t *WLs = lds_at<bf16_t>(smem, L.WL);                        // [32][RS] permuted k
+    float *b0s = lds_at<float>(smem, L.b0), *b1s = lds_at<float>(smem, L.b1), *bLs = lds_at<float>(smem, L.bL);
+    bf16_t *stg = lds_at<bf16_t>(smem, L.stg) + (threadIdx.x >> 6) * (L.stg_stride / 2);      // wave-private staging tile
     stage_weight(W0s, RS, 64, 64, p.W[0], HID, p.in_dim, false, p.grp_L, p.grp_F);
     if (NL == 3) stage_weight(W1s, RS, 64, 64, p.W[1], HID, HID, true);
     stage_weight(WLs, RS, 32, 64, p.W[NL - 1], p.out_dim, HID, true);
@@ -970,16 +968,11 @@ constexpr int CD_WAVES = 2;      // waves per SIMD asked of the compiler (146 VG
 __global__ __launch_bounds__(256, CD_WAVES) void mlp_fwd_density_colour(FwdParams pd, FwdParams pc) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr float LOG2E = 1.4426950408889634f;
-    bf16_t *W0d = reinterpret_cast<bf16_t *>(smem);                  // density: [64][RS] natural k, [32][RS] permuted k
-    bf16_t *WLd = W0d + 64 * RS;
-    bf16_t *W0c = WLd + 32 * RS;                                     // colour: [64][RS] natural k, [64][RS] permuted k, [32][RS] permuted k
-    bf16_t *W1c = W0c + 64 * RS;
-    bf16_t *WLc = W1c + 64 * RS;
-    float *b0d = reinterpret_cast<float *>(WLc + 32 * RS);
-    float *bLd = b0d + 64;
-    float *b0c = bLd + 32;
-    float *b1c = b0c + 64;
-    float *bLc = b1c + 64;
+    constexpr DensityColourLds L{};
+    bf16_t *W0d = lds_at<bf16_t>(smem, L.W0d), *WLd = lds_at<bf16_t>(smem, L.WLd);      // density: [64][RS] natural k, [32][RS] permuted k
+    bf16_t *W0c = lds_at<bf16_t>(smem, L.W0c), *W1c = lds_at<bf16_t>(smem, L.W1c), *WLc = lds_at<bf16_t>(smem, L.WLc);      // colour: [64][RS] natural k, [64][RS] permuted k, [32][RS] permuted k
+    float *b0d = lds_at<float>(smem, L.b0d), *bLd = lds_at<float>(smem, L.bLd);
+    float *b0c = lds_at<float>(smem, L.b0c), *b1c = lds_at<float>(smem, L.b1c), *bLc = lds_at<float>(smem, L.bLc);
     stage_weight(W0d, RS, 64, 64, pd.W[0], HID, pd.in_dim, false, pd.grp_L, pd.grp_F);
     stage_weight(WLd, RS, 32, 64, pd.W[1], pd.out_dim, HID, true);
     stage_weight(W0c, RS, 64, 64, pc.W[0], HID, pc.in_dim, false);
@@ -1084,23 +1077,20 @@ __global__ __launch_bounds__(256, CD_WAVES) void mlp_fwd_density_colour(FwdParam
 // features) is evaluated on the tile while it is in registers - its own launch was one more 268 MB read of the features.  The weights
 // of both decoders then take 66 KiB: 8 waves share them (512 threads, one workgroup per CU) instead of two 4-wave workgroups.
 constexpr int WIDE_FWD_PAIR_THREADS = 1024;
+constexpr int wide_fwd_waves(bool pair) { return (pair ? WIDE_FWD_PAIR_THREADS : 256) / 64; }
 template <bool SAVE0, bool PAIR>
 __global__ __launch_bounds__(PAIR ? WIDE_FWD_PAIR_THREADS : 256, PAIR ? 1 : 2) void mlp_fwd_wide_stats(FwdParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int OB = 7;
     constexpr float LOG2E = 1.4426950408889634f;
     const int NW = blockDim.x >> 6;
-    bf16_t *W0s = reinterpret_cast<bf16_t *>(smem);
-    bf16_t *W1s = W0s + 64 * RS;
-    bf16_t *WLs = W1s + 64 * RS;                                     // [OB*32][RS] permuted k
-    bf16_t *W0s2 = WLs + OB * 32 * RS;                               // PAIR: [64][RS] natural k, [32][RS] permuted k
-    bf16_t *WLs2 = W0s2 + (PAIR ? 64 * RS : 0);
-    float *b0s = reinterpret_cast<float *>(WLs2 + (PAIR ? 32 * RS : 0));
-    float *b1s = b0s + 64;
-    float *bLs = b1s + 64;
-    float *b0s2 = bLs + OB * 32;
-    float *bLs2 = b0s2 + (PAIR ? 64 : 0);
-    bf16_t *stg = reinterpret_cast<bf16_t *>(bLs2 + (PAIR ? 32 : 0)) + (threadIdx.x >> 6) * (ST_BYTES / 2);
+    constexpr FwdLds L(3, OB, wide_fwd_waves(PAIR), PAIR);
+    bf16_t *W0s = lds_at<bf16_t>(smem, L.W0), *W1s = lds_at<bf16_t>(smem, L.W1);
+    bf16_t *WLs = lds_at<bf16_t>(smem, L.WL);                        // [OB*32][RS] permuted k
+    bf16_t *W0s2 = lds_at<bf16_t>(smem, L.W0p), *WLs2 = lds_at<bf16_t>(smem, L.WLp);      // PAIR: [64][RS] natural k, [32][RS] permuted k
+    float *b0s = lds_at<float>(smem, L.b0), *b1s = lds_at<float>(smem, L.b1), *bLs = lds_at<float>(smem, L.bL);
+    float *b0s2 = lds_at<float>(smem, L.b0p), *bLs2 = lds_at<float>(smem, L.bLp);
+    bf16_t *stg = lds_at<bf16_t>(smem, L.stg) + (threadIdx.x >> 6) * (L.stg_stride / 2);
     stage_weight(W0s, RS, 64, 64, p.W[0], HID, p.in_dim, false, p.grp_L, p.grp_F);
     stage_weight(W1s, RS, 64, 64, p.W[1], HID, HID, true);
     stage_weight(WLs, RS, OB * 32, 64, p.W[2], p.out_dim, HID, true);
@@ -1222,14 +1212,15 @@ template <typename OutT, typename DxT, int NL, int OBMAX>
 __global__ __launch_bounds__(256, (OBMAX == 2 ? 1 : BWD_WAVES)) void mlp_bwd_mfma(BwdParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int OB = (p.out_dim + 31) / 32;
-    const int RSL = OB * 32 + 8;
-    bf16_t *WLt = reinterpret_cast<bf16_t *>(smem);              // [64 in][RSL]  k = output channel (permuted)
-    bf16_t *W1t = WLt + 64 * RSL;                                // [64][RS]      (NL == 3)
-    bf16_t *W0t = W1t + (NL == 3 ? 64 * RS : 0);                 // [64 in-feature rows][RS]
+    const BwdLds L(NL, OB);
+    const int RSL = L.rsl;
+    bf16_t *WLt = lds_at<bf16_t>(smem, L.WLt);                   // [64 in][RSL]  k = output channel (permuted)
+    bf16_t *W1t = lds_at<bf16_t>(smem, L.W1t);                   // [64][RS]      (NL == 3)
+    bf16_t *W0t = lds_at<bf16_t>(smem, L.W0t);                   // [64 in-feature rows][RS]
     stage_weight_t(WLt, RSL, 64, OB * 32, p.W[NL - 1], p.out_dim, HID);
     if (NL == 3) stage_weight_t(W1t, RS, 64, 64, p.W[1], HID, HID);
     if (p.dx1) stage_weight_t(W0t, RS, 64, 64, p.W[0], HID, p.in_dim, p.grp_L, p.grp_F);
-    bf16_t *stg = W0t + 64 * RS + (threadIdx.x >> 6) * (ST_BYTES / 2);      // wave-private staging tile
+    bf16_t *stg = lds_at<bf16_t>(smem, L.stg) + (threadIdx.x >> 6) * (L.stg_stride / 2);      // wave-private staging tile
     __syncthreads();
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1599,27 +1590,27 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void mlp_bwd_fused(BwdParams p) {
     static_assert(OBL == 1 || KIND == 0, "a 64-wide output layer exists for the dense-gradient form only");
     constexpr bool GRP = KIND != 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int RSL = OBL * 32 + 8;
-    bf16_t *WLt = reinterpret_cast<bf16_t *>(smem);              // [64 in][RSL]  k = output channel (permuted)
-    bf16_t *W1t = WLt + 64 * RSL;                                // [64][RS]      (NL == 3)
-    bf16_t *W0t = W1t + (NL == 3 ? 64 * RS : 0);                 // [64 in-feature rows][RS]
+    constexpr FusedLds L(NL, OBL, DZ0);
+    constexpr int RSL = L.rsl;
+    bf16_t *WLt = lds_at<bf16_t>(smem, L.WLt);                   // [64 in][RSL]  k = output channel (permuted)
+    bf16_t *W1t = lds_at<bf16_t>(smem, L.W1t);                   // [64][RS]      (NL == 3)
+    bf16_t *W0t = lds_at<bf16_t>(smem, L.W0t);                   // [64 in-feature rows][RS]
     stage_weight_t(WLt, RSL, 64, OBL * 32, p.W[NL - 1], p.out_dim, HID);
     // (W_1 and W_0 are staged below, both images from one pass each)
     // the forward's own images of the hidden layers: their activations are RECOMPUTED here (8 - 16 MFMAs per tile on idle matrix
     // cores, same fragments and instruction sequence as mlp_fwd_mfma: bit-identical) instead of being written by the forward and
     // read back - 268 MB each way per hidden layer at M = 2.1 M, in kernels that run at the HBM rate
-    bf16_t *W0s = W0t + 64 * RS;                                 // [64][RS] natural k
-    bf16_t *W1s = W0s + 64 * RS;                                 // [64][RS] permuted k (NL == 3)
-    float *b0s = reinterpret_cast<float *>(W1s + (NL == 3 ? 64 * RS : 0));
-    float *b1s = b0s + 64;
+    bf16_t *W0s = lds_at<bf16_t>(smem, L.W0s);                   // [64][RS] natural k
+    bf16_t *W1s = lds_at<bf16_t>(smem, L.W1s);                   // [64][RS] permuted k (NL == 3)
+    float *b0s = lds_at<float>(smem, L.b0), *b1s = lds_at<float>(smem, L.b1);
     stage_weight_both(W0s, RS, false, W0t, RS, 64, 64, p.W[0], HID, p.in_dim, p.grp_L, p.grp_F);
     if (NL == 3) stage_weight_both(W1s, RS, true, W1t, RS, 64, 64, p.W[1], HID, HID);
     for (int e = threadIdx.x; e < 64; e += blockDim.x) {
         b0s[e] = p.b[0][e];
         b1s[e] = NL == 3 ? p.b[1][e] : 0.0f;
     }
-    bf16_t *Tx = reinterpret_cast<bf16_t *>(b1s + 64) + (threadIdx.x >> 6) * ((NL + 1) * TW_ELEMS);      // wave-private swizzled tiles
-    bf16_t *Th0 = Tx + TW_ELEMS, *Th1 = Th0 + (NL == 3 ? TW_ELEMS : 0), *Tz = Th1 + TW_ELEMS;
+    const int wtile = (threadIdx.x >> 6) * L.tile_stride;      // wave-private swizzled tiles
+    bf16_t *Tx = lds_at<bf16_t>(smem, L.Tx + wtile), *Th0 = lds_at<bf16_t>(smem, L.Th0 + wtile), *Th1 = lds_at<bf16_t>(smem, L.Th1 + wtile), *Tz = lds_at<bf16_t>(smem, L.Tz + wtile);
     __syncthreads();
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1647,7 +1638,7 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void mlp_bwd_fused(BwdParams p) {
     };
 
     // DZ0 == 2: wave-private scratch behind the tiles - the local ray number of each of the tile's 32 samples and the ray of each local number
-    int *lray_s = reinterpret_cast<int *>(reinterpret_cast<bf16_t *>(b1s + 64) + 4 * ((NL + 1) * TW_ELEMS)) + (threadIdx.x >> 6) * 64, *rid_s = lray_s + 32;
+    int *lray_s = lds_at<int>(smem, L.rays) + (threadIdx.x >> 6) * (L.rays_stride / 4), *rid_s = lray_s + 32;
     int ray_c = 0;             // x2 row (= ray) of this lane's sample in the CURRENT tile (DZ0 == 2)
     unsigned heads_c = 0u;     // bit s: sample s of the current tile starts a new ray
     auto note_rays = [&](int ray_here) __attribute__((always_inline)) {      // called at the top of a tile, before its first wave_lds_sync
@@ -2063,15 +2054,14 @@ struct PairParams {
 __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
     const BwdParams &pi = pp.i, &ps = pp.s;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int RSLI = 72, RSLS = 40;
-    bf16_t *WLtI = reinterpret_cast<bf16_t *>(smem);             // [64][72]  k = the 64 outputs of .i's upper layer (permuted)
-    bf16_t *W0tI = WLtI + 64 * RSLI;                             // [64 input positions][RS]
-    bf16_t *W0sI = W0tI + 64 * RS;                               // [64][RS] natural k (forward recompute)
-    bf16_t *WLtS = W0sI + 64 * RS;                               // [64][40]
-    bf16_t *W0tS = WLtS + 64 * RSLS;
-    bf16_t *W0sS = W0tS + 64 * RS;
-    float *b0I = reinterpret_cast<float *>(W0sS + 64 * RS);
-    float *b0S = b0I + 64;
+    constexpr PairLds L{};
+    constexpr int RSLI = L.rslI, RSLS = L.rslS;
+    bf16_t *WLtI = lds_at<bf16_t>(smem, L.WLtI);                 // [64][72]  k = the 64 outputs of .i's upper layer (permuted)
+    bf16_t *W0tI = lds_at<bf16_t>(smem, L.W0tI);                 // [64 input positions][RS]
+    bf16_t *W0sI = lds_at<bf16_t>(smem, L.W0sI);                 // [64][RS] natural k (forward recompute)
+    bf16_t *WLtS = lds_at<bf16_t>(smem, L.WLtS);                 // [64][40]
+    bf16_t *W0tS = lds_at<bf16_t>(smem, L.W0tS), *W0sS = lds_at<bf16_t>(smem, L.W0sS);
+    float *b0I = lds_at<float>(smem, L.b0I), *b0S = lds_at<float>(smem, L.b0S);
     stage_weight_t(WLtI, RSLI, 64, 64, pi.W[1], pi.out_dim, HID);
     stage_weight_both(W0sI, RS, false, W0tI, RS, 64, 64, pi.W[0], HID, pi.in_dim, pi.grp_L, pi.grp_F);
     stage_weight_t(WLtS, RSLS, 64, 32, ps.W[1], ps.out_dim, HID);
@@ -2080,8 +2070,8 @@ __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
         b0I[e] = pi.b[0][e];
         b0S[e] = ps.b[0][e];
     }
-    bf16_t *Tx = reinterpret_cast<bf16_t *>(b0S + 64) + (threadIdx.x >> 6) * (4 * TW_ELEMS);      // wave-private swizzled tiles
-    bf16_t *ThI = Tx + TW_ELEMS, *ThS = ThI + TW_ELEMS, *Tz = ThS + TW_ELEMS;
+    const int wtile = (threadIdx.x >> 6) * L.tile_stride;      // wave-private swizzled tiles
+    bf16_t *Tx = lds_at<bf16_t>(smem, L.Tx + wtile), *ThI = lds_at<bf16_t>(smem, L.ThI + wtile), *ThS = lds_at<bf16_t>(smem, L.ThS + wtile), *Tz = lds_at<bf16_t>(smem, L.Tz + wtile);
     __syncthreads();
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -2417,22 +2407,21 @@ __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
 // OB + 1 = 8 waves per workgroup, one workgroup per CU: two waves per SIMD.  0.43 ms; per-wave barrier waits (in-kernel clocks: profiles/README.md, round 3): the
 // block waves that share a SIMD with another block wave wait 4-30 %, the helper 5 % - the roles are balanced, what is left is the
 // issue time of two waves per SIMD.
-constexpr int WR_RS = 256;         // floats per staged gradient row
-constexpr int WB_RMAX = 4;         // rays whose gradient rows are staged per tile; tiles spanning more read their rows from global
 template <int OB>
 __global__ __launch_bounds__((OB + 1) * 64) void mlp_bwd_wide_blocks(BwdParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int RSL = OB * 32 + 8;
+    constexpr WideBlocksLds L(OB);
+    constexpr int RSL = L.rsl;
     constexpr float LOG2E = 1.4426950408889634f;
-    bf16_t *WLt = reinterpret_cast<bf16_t *>(smem);              // [64 hidden][RSL]   k = output channel (permuted)
-    bf16_t *WLs = WLt + 64 * RSL;                                // [OB*32 channels][RS] permuted k (forward layout)
-    float *bLs = reinterpret_cast<float *>(WLs + OB * 32 * RS);  // [OB*32]
-    bf16_t *Th = reinterpret_cast<bf16_t *>(bLs + OB * 32);      // [4][tile]  activations, ring over tiles
-    bf16_t *Tp = Th + 4 * TW_ELEMS;                              // helper's transpose buffer for the hidden-gradient store
-    bf16_t *TzAll = Tp + TW_ELEMS;                               // [OB][tile] dz block of each block wave (block 0 of its tile)
-    float *grow = reinterpret_cast<float *>(TzAll + OB * TW_ELEMS);      // [2][WB_RMAX][WR_RS]
-    float *dotbuf = grow + 2 * WB_RMAX * WR_RS;                  // [2][OB][64]
-    bf16x8 *zbuf = reinterpret_cast<bf16x8 *>(dotbuf + 2 * OB * 64);     // [2][OB][2][64]
+    bf16_t *WLt = lds_at<bf16_t>(smem, L.WLt);                   // [64 hidden][RSL]   k = output channel (permuted)
+    bf16_t *WLs = lds_at<bf16_t>(smem, L.WLs);                   // [OB*32 channels][RS] permuted k (forward layout)
+    float *bLs = lds_at<float>(smem, L.bL);                      // [OB*32]
+    bf16_t *Th = lds_at<bf16_t>(smem, L.Th);                     // [4][tile]  activations, ring over tiles
+    bf16_t *Tp = lds_at<bf16_t>(smem, L.Tp);                     // helper's transpose buffer for the hidden-gradient store
+    bf16_t *TzAll = lds_at<bf16_t>(smem, L.Tz);                  // [OB][tile] dz block of each block wave (block 0 of its tile)
+    float *grow = lds_at<float>(smem, L.grow);                   // [2][WB_RMAX][WR_RS]
+    float *dotbuf = lds_at<float>(smem, L.dot);                  // [2][OB][64]
+    bf16x8 *zbuf = lds_at<bf16x8>(smem, L.zbuf);                 // [2][OB][2][64]
     stage_weight_both(WLs, RS, true, WLt, RSL, OB * 32, 64, p.W[0], p.out_dim, HID);
     for (int e = threadIdx.x; e < OB * 32; e += blockDim.x) bLs[e] = e < p.out_dim ? p.b_last[e] : -1e30f;      // padding channels: p = exp2(-huge) = 0
     for (int e = threadIdx.x; e < 2 * OB * 64; e += blockDim.x) dotbuf[e] = 0.0f;
@@ -2448,7 +2437,7 @@ __global__ __launch_bounds__((OB + 1) * 64) void mlp_bwd_wide_blocks(BwdParams p
     bf16_t *dzh = reinterpret_cast<bf16_t *>(p.dz[0]);
     const bool is_block = wave < OB;
     const int ob = is_block ? wave : 0;
-    bf16_t *Tz = TzAll + ob * TW_ELEMS;
+    bf16_t *Tz = TzAll + ob * (L.Tz_stride / 2);
     auto row_of = [&](int64_t tile) __attribute__((always_inline)) { return min(min(tile, ntiles - 1) * 32 + r, M - 1); };
     // The helper wave stages through registers: loads are issued a whole iteration before the LDS writes that consume them.  Its wave
     // shares a SIMD with a block wave, so every VALU instruction it saves is issue time for both: all its global traffic goes through
@@ -2744,15 +2733,16 @@ template <typename DxT, int NL, int NW>
 __global__ __launch_bounds__(NW * 64) void mlp_bwd_wide_mfma(BwdParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int OB = (p.out_dim + 31) / 32;
-    const int RSL = OB * 32 + 8;
-    bf16_t *WLt = reinterpret_cast<bf16_t *>(smem);              // [64 hidden][RSL]   k = output channel (permuted)
-    bf16_t *WLs = WLt + 64 * RSL;                                // [OB*32 channels][RS] permuted k (forward layout)
-    bf16_t *W1t = WLs + OB * 32 * RS;                            // [64][RS]      (NL == 3)
-    bf16_t *W0t = W1t + (NL == 3 ? 64 * RS : 0);                 // [64 in-feature rows][RS]
-    float *bLs = reinterpret_cast<float *>(W0t + 64 * RS);       // [OB*32]
-    bf16_t *stg = reinterpret_cast<bf16_t *>(bLs + OB * 32) + (threadIdx.x >> 6) * (ST_BYTES / 2);
-    float *grow = reinterpret_cast<float *>(reinterpret_cast<bf16_t *>(bLs + OB * 32) + NW * (ST_BYTES / 2)) +
-                  (threadIdx.x >> 6) * (OB * 32);              // wave-private copy of the tile's upstream gradient row [OB*32]
+    const WideMfmaLds L(NL, OB, NW);
+    const int RSL = L.rsl;
+    bf16_t *WLt = lds_at<bf16_t>(smem, L.WLt);                   // [64 hidden][RSL]   k = output channel (permuted)
+    bf16_t *WLs = WLt + (L.WLs - L.WLt) / 2;                     // [OB*32 channels][RS] permuted k (forward layout)
+    bf16_t *W1t = WLs + (L.W1t - L.WLs) / 2;                     // [64][RS]      (NL == 3)
+    bf16_t *W0t = W1t + (L.W0t - L.W1t) / 2;                     // [64 in-feature rows][RS]
+    float *bLs = reinterpret_cast<float *>(W0t + (L.bL - L.W0t) / 2);      // [OB*32]
+    bf16_t *stg = reinterpret_cast<bf16_t *>(bLs + (L.stg - L.bL) / 4) + (threadIdx.x >> 6) * (L.stg_stride / 2);
+    float *grow = reinterpret_cast<float *>(reinterpret_cast<bf16_t *>(bLs + (L.stg - L.bL) / 4) + (L.grow - L.stg) / 2) +
+                  (threadIdx.x >> 6) * (L.grow_stride / 4);      // wave-private copy of the tile's upstream gradient row [OB*32]
     stage_weight_t(WLt, RSL, 64, OB * 32, p.W[NL - 1], p.out_dim, HID);
     stage_weight(WLs, RS, OB * 32, 64, p.W[NL - 1], p.out_dim, HID, true);
     if (NL == 3) stage_weight_t(W1t, RS, 64, 64, p.W[1], HID, HID);
@@ -3030,6 +3020,7 @@ template <int OBT>
 __global__ __launch_bounds__(256, 2) void head_composite_fwd_kernel(HeadCompParams p) {      // two waves per SIMD: 256 registers
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int OB = OBT ? OBT : (p.out_dim + 31) / 32;
+    // HeadCompLds(OB), written as a chain: with the run-time OB, absolute offsets compile to different code (see mlp_lds.h)
     bf16_t *WLs = reinterpret_cast<bf16_t *>(smem);                  // [OB*32][RS] permuted k (forward layout)
     float *bLs = reinterpret_cast<float *>(WLs + OB * 32 * RS);      // [OB*32]
     float *red = bLs + OB * 32;                                      // [4][OB*32]
@@ -3166,18 +3157,14 @@ __global__ __launch_bounds__(256, 1) void head_fwd_once_kernel(FwdParams p, Head
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int OB = 7;
     constexpr float LOG2E = 1.4426950408889634f;
-    bf16_t *W0s = reinterpret_cast<bf16_t *>(smem);
-    bf16_t *W1s = W0s + 64 * RS;
-    bf16_t *WLs = W1s + 64 * RS;                                     // [OB*32][RS] permuted k
-    bf16_t *W0s2 = WLs + OB * 32 * RS;                               // PAIR: [64][RS] natural k, [32][RS] permuted k
-    bf16_t *WLs2 = W0s2 + (PAIR ? 64 * RS : 0);
-    float *b0s = reinterpret_cast<float *>(WLs2 + (PAIR ? 32 * RS : 0));
-    float *b1s = b0s + 64;
-    float *bLs = b1s + 64;
-    float *b0s2 = bLs + OB * 32;
-    float *bLs2 = b0s2 + (PAIR ? 64 : 0);
-    float *red = bLs2 + (PAIR ? 32 : 0);                             // [4][OB*32]
-    bf16_t *stg = reinterpret_cast<bf16_t *>(red + 4 * OB * 32) + (threadIdx.x >> 6) * (ST_BYTES / 2);
+    constexpr FwdLds L(3, OB, 4, PAIR, true);
+    bf16_t *W0s = lds_at<bf16_t>(smem, L.W0), *W1s = lds_at<bf16_t>(smem, L.W1);
+    bf16_t *WLs = lds_at<bf16_t>(smem, L.WL);                        // [OB*32][RS] permuted k
+    bf16_t *W0s2 = lds_at<bf16_t>(smem, L.W0p), *WLs2 = lds_at<bf16_t>(smem, L.WLp);      // PAIR: [64][RS] natural k, [32][RS] permuted k
+    float *b0s = lds_at<float>(smem, L.b0), *b1s = lds_at<float>(smem, L.b1), *bLs = lds_at<float>(smem, L.bL);
+    float *b0s2 = lds_at<float>(smem, L.b0p), *bLs2 = lds_at<float>(smem, L.bLp);
+    float *red = lds_at<float>(smem, L.red);                         // [4][OB*32]
+    bf16_t *stg = lds_at<bf16_t>(smem, L.stg) + (threadIdx.x >> 6) * (L.stg_stride / 2);
     stage_weight(W0s, RS, 64, 64, p.W[0], HID, p.in_dim, false, p.grp_L, p.grp_F);
     stage_weight(W1s, RS, 64, 64, p.W[1], HID, HID, true);
     stage_weight(WLs, RS, OB * 32, 64, p.W[2], p.out_dim, HID, true);
@@ -3374,7 +3361,6 @@ __global__ __launch_bounds__(256, 1) void head_fwd_once_kernel(FwdParams p, Head
 // ------------------------------------------------------------------------------------ FP32 parity path
 // One lane per sample.  Weights transposed in LDS ([k][j]) so the 64 outputs of a layer are 16
 // broadcast ds_read_b128; the per-sample activation column lives in LDS ([k][lane]).
-constexpr int PT = 128;   // threads per block on this path
 
 __device__ void stage_f32_t(float *dst, const float *W, int n_out, int n_in, int out_pad) {   // dst[k][out_pad]
     for (int e = threadIdx.x; e < n_in * out_pad; e += blockDim.x) {
@@ -3386,8 +3372,9 @@ __device__ void stage_f32_t(float *dst, const float *W, int n_out, int n_in, int
 template <typename X1T, typename OutT>
 __global__ __launch_bounds__(PT) void mlp_fwd_f32(FwdParams p, int n_layers) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float *xs = reinterpret_cast<float *>(smem);          // [64][PT] activation columns
-    float *wt = xs + 64 * PT;                             // current layer's W^T [k][out_pad]
+    constexpr F32Lds L(64);
+    float *xs = lds_at<float>(smem, L.cols);              // [64][PT] activation columns
+    float *wt = lds_at<float>(smem, L.wt);                // current layer's W^T [k][out_pad]
     const int t = threadIdx.x;
     const int64_t m = (int64_t)blockIdx.x * PT + t;
     const bool live = m < p.M;
@@ -3461,8 +3448,9 @@ __device__ void stage_f32_n(float *dst, const float *W, int row0, int rows, int 
 template <typename OutT, typename DxT>
 __global__ __launch_bounds__(PT) void mlp_bwd_f32(BwdParams p, int n_layers) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float *zs = reinterpret_cast<float *>(smem);          // [224][PT] dz column of the current layer
-    float *wt = zs + 224 * PT;                            // [64 rows j][64 k]
+    constexpr F32Lds L(224);
+    float *zs = lds_at<float>(smem, L.cols);              // [224][PT] dz column of the current layer
+    float *wt = lds_at<float>(smem, L.wt);                // [64 rows j][64 k]
     const int t = threadIdx.x;
     const int64_t m = (int64_t)blockIdx.x * PT + t;
     const bool live = m < p.M;
@@ -3535,7 +3523,6 @@ inline unsigned mlp_grid(int64_t M) {
 }
 
 // Kernels that ask for more than 64 KiB of dynamic LDS opt in once per kernel and process (gfx950 has 160 KiB per workgroup)
-constexpr int LDS_MAX_BYTES = 160 * 1024;
 template <auto Kernel>
 void raise_lds_limit(int bytes = LDS_MAX_BYTES) {
     static const hipError_t once = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
@@ -3559,70 +3546,93 @@ void set_pair_head(FwdParams &p, const pag_mlp_fwd_args *b) {
 }
 
 template <typename X1T, typename OutT, int NL>
-void launch_fwd_mfma_nl(const FwdParams &p, int OB, size_t lds, hipStream_t st) {
+void launch_fwd_mfma_nl(const FwdParams &p, hipStream_t st) {
     const dim3 grid(mlp_grid(p.M)), block(256);
+    const int OB = (p.out_dim + 31) / 32;
+    const size_t lds = FwdLds(NL, OB).bytes;
     if (OB <= 1) hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 1>), grid, block, lds, st, p);
     else if (OB <= 2) hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 2>), grid, block, lds, st, p);
     else if (OB <= 4) hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 4>), grid, block, lds, st, p);
     else hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 7>), grid, block, lds, st, p);
 }
 template <typename X1T, typename OutT>
-void launch_fwd_mfma(const FwdParams &p, int n_layers, int OB, size_t lds, hipStream_t st) {
-    if (n_layers == 2) launch_fwd_mfma_nl<X1T, OutT, 2>(p, OB, lds, st);
-    else launch_fwd_mfma_nl<X1T, OutT, 3>(p, OB, lds, st);
+void launch_fwd_mfma(const FwdParams &p, int n_layers, hipStream_t st) {
+    if (n_layers == 2) launch_fwd_mfma_nl<X1T, OutT, 2>(p, st);
+    else launch_fwd_mfma_nl<X1T, OutT, 3>(p, st);
+}
+
+constexpr int FAST_FWD_GRID_CAP = 768;      // three workgroups per CU are resident: one round, tiles grid-strided (1536 ran two rounds with a ragged second: colour forward 63 -> 57 us)
+template <int KIND>
+void launch_fwd_fast(const FwdParams &p, int n_layers, bool save, hipStream_t st) {
+    const dim3 grid(std::min<unsigned>(mlp_grid(p.M), FAST_FWD_GRID_CAP)), block(256);
+    const size_t lds = FwdLds(n_layers, 1).bytes;
+    if (n_layers == 2 && save) hipLaunchKernelGGL((mlp_fwd_fast<2, KIND, true>), grid, block, lds, st, p);
+    else if (n_layers == 2) hipLaunchKernelGGL((mlp_fwd_fast<2, KIND, false>), grid, block, lds, st, p);
+    else if (save) hipLaunchKernelGGL((mlp_fwd_fast<3, KIND, true>), grid, block, lds, st, p);
+    else hipLaunchKernelGGL((mlp_fwd_fast<3, KIND, false>), grid, block, lds, st, p);
+}
+template <bool SAVE0, bool PAIR>
+void launch_fwd_wide_stats(const FwdParams &p, unsigned grid, hipStream_t st) {
+    constexpr int NW = wide_fwd_waves(PAIR);
+    raise_lds_limit<mlp_fwd_wide_stats<SAVE0, PAIR>>();
+    hipLaunchKernelGGL((mlp_fwd_wide_stats<SAVE0, PAIR>), dim3(grid), dim3(NW * 64), FwdLds(3, OB_MAX, NW, PAIR).bytes, st, p);
+}
+template <bool PAIR>
+void launch_head_fwd_once(const FwdParams &p, const HeadCompParams &c, unsigned grid, hipStream_t st) {
+    raise_lds_limit<head_fwd_once_kernel<PAIR>>();
+    hipLaunchKernelGGL((head_fwd_once_kernel<PAIR>), dim3(grid), dim3(256), FwdLds(3, OB_MAX, 4, PAIR, true).bytes, st, p, c);
 }
 
 template <typename OutT, typename DxT, int NL>
-void launch_bwd_mfma_nl(const BwdParams &p, int OB, size_t lds, hipStream_t st) {
+void launch_bwd_mfma_nl(const BwdParams &p, hipStream_t st) {
     const dim3 grid(mlp_grid(p.M)), block(256);
+    const int OB = (p.out_dim + 31) / 32;
+    const size_t lds = BwdLds(NL, OB).bytes;
     if (OB <= 1) hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 1>), grid, block, lds, st, p);
     else if (OB <= 2) hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 2>), grid, block, lds, st, p);
     else if (OB <= 4) hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 4>), grid, block, lds, st, p);
     else hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 7>), grid, block, lds, st, p);
 }
 template <typename OutT, typename DxT>
-void launch_bwd_mfma(const BwdParams &p, int n_layers, int OB, size_t lds, hipStream_t st) {
-    if (n_layers == 2) launch_bwd_mfma_nl<OutT, DxT, 2>(p, OB, lds, st);
-    else launch_bwd_mfma_nl<OutT, DxT, 3>(p, OB, lds, st);
+void launch_bwd_mfma(const BwdParams &p, int n_layers, hipStream_t st) {
+    if (n_layers == 2) launch_bwd_mfma_nl<OutT, DxT, 2>(p, st);
+    else launch_bwd_mfma_nl<OutT, DxT, 3>(p, st);
 }
 
 template <typename OutT, typename DxT>
-void launch_bwd_f32(const BwdParams &p, int n_layers, dim3 grid, size_t lds, hipStream_t st) {
-    raise_lds_limit<mlp_bwd_f32<OutT, DxT>>((int)lds);      // 128 KiB
-    hipLaunchKernelGGL((mlp_bwd_f32<OutT, DxT>), grid, dim3(PT), lds, st, p, n_layers);
+void launch_bwd_f32(const BwdParams &p, int n_layers, hipStream_t st) {
+    constexpr F32Lds L(224);      // 128 KiB
+    raise_lds_limit<mlp_bwd_f32<OutT, DxT>>(L.bytes);
+    hipLaunchKernelGGL((mlp_bwd_f32<OutT, DxT>), dim3((unsigned)((p.M + PT - 1) / PT)), dim3(PT), L.bytes, st, p, n_layers);
 }
 
 template <int NL, int KIND, bool DXACC, int OBL = 1, int DZ0 = 0>
-void launch_bwd_fused(const BwdParams &p, unsigned grid, size_t lds, hipStream_t st) {
+void launch_bwd_fused(const BwdParams &p, unsigned grid, hipStream_t st) {
     raise_lds_limit<mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>>();
-    hipLaunchKernelGGL((mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>), dim3(grid), dim3(256), lds, st, p);
+    hipLaunchKernelGGL((mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>), dim3(grid), dim3(256), FusedLds(NL, OBL, DZ0).bytes, st, p);
 }
 template <int NL>
-void launch_bwd_fused_kind(const BwdParams &p, int kind, bool acc, int dz0, unsigned grid, size_t lds, hipStream_t st) {
-    if (kind == 0) launch_bwd_fused<NL, 0, false>(p, grid, lds, st);
-    else if (kind == 1 && dz0 == 2) launch_bwd_fused<NL, 1, false, 1, 2>(p, grid, lds + 4 * 64 * sizeof(int), st);
-    else if (kind == 1 && dz0 == 1) launch_bwd_fused<NL, 1, false, 1, 1>(p, grid, lds, st);
-    else if (kind == 1) launch_bwd_fused<NL, 1, false>(p, grid, lds, st);
-    else if (acc) launch_bwd_fused<NL, 2, true>(p, grid, lds, st);
-    else launch_bwd_fused<NL, 2, false>(p, grid, lds, st);
+void launch_bwd_fused_kind(const BwdParams &p, int kind, bool acc, int dz0, unsigned grid, hipStream_t st) {
+    if (kind == 0) launch_bwd_fused<NL, 0, false>(p, grid, st);
+    else if (kind == 1 && dz0 == 2) launch_bwd_fused<NL, 1, false, 1, 2>(p, grid, st);
+    else if (kind == 1 && dz0 == 1) launch_bwd_fused<NL, 1, false, 1, 1>(p, grid, st);
+    else if (kind == 1) launch_bwd_fused<NL, 1, false>(p, grid, st);
+    else if (acc) launch_bwd_fused<NL, 2, true>(p, grid, st);
+    else launch_bwd_fused<NL, 2, false>(p, grid, st);
 }
 
 // stage A of the fused wide-head backward
 void launch_bwd_wide_blocks(const BwdParams &p, unsigned grid, hipStream_t st) {
     constexpr int OBW = 7;
-    const size_t lds = (size_t)(64 * (OBW * 32 + 8) + OBW * 32 * RS) * sizeof(bf16_t) + (size_t)OBW * 32 * sizeof(float) +
-                       (size_t)(5 + OBW) * TW_ELEMS * sizeof(bf16_t) + (size_t)2 * WB_RMAX * WR_RS * sizeof(float) +
-                       (size_t)2 * OBW * 64 * sizeof(float) + (size_t)2 * OBW * 2 * 64 * 16;
     raise_lds_limit<mlp_bwd_wide_blocks<OBW>>();
-    hipLaunchKernelGGL((mlp_bwd_wide_blocks<OBW>), dim3(grid), dim3((OBW + 1) * 64), lds, st, p);
+    hipLaunchKernelGGL((mlp_bwd_wide_blocks<OBW>), dim3(grid), dim3((OBW + 1) * 64), WideBlocksLds(OBW).bytes, st, p);
 }
 
 template <typename DxT, int NL>
 void launch_bwd_wide_mfma(const BwdParams &p, hipStream_t st) {
     constexpr int NW = WIDE_BWD_WAVES;
     const int OB = (p.out_dim + 31) / 32;
-    const size_t lds = (size_t)(64 * (OB * 32 + 8) + OB * 32 * RS + (NL == 3 ? 64 * RS : 0) + 64 * RS) * sizeof(bf16_t) +
-                       (size_t)OB * 32 * sizeof(float) + (size_t)NW * ST_BYTES + (size_t)NW * OB * 32 * sizeof(float);
+    const size_t lds = WideMfmaLds(NL, OB, NW).bytes;
     const int64_t tiles = (p.M + 31) / 32;
     const unsigned grid = (unsigned)std::min<int64_t>((tiles + NW - 1) / NW, 256);      // one workgroup per CU, tiles grid-strided
     raise_lds_limit<mlp_bwd_wide_mfma<DxT, NL, NW>>();
@@ -3641,7 +3651,6 @@ extern "C" int pag_mlp_fwd_pair_supported(const pag_mlp_fwd_args *a, const pag_m
     return wide && narrow ? 1 : 0;
 }
 
-constexpr int FAST_FWD_GRID_CAP = 768;      // three workgroups per CU are resident: one round, tiles grid-strided (1536 ran two rounds with a ragged second: colour forward 63 -> 57 us)
 extern "C" int pag_mlp_fwd_producer_supported(const pag_mlp_fwd_args *a, const pag_mlp_fwd_args *d, int64_t M) {
     if (!a || !d || M < 1 || M > PAG_MLP_FUSED_WIDE_MAX_M) return 0;
     const bool density = d->mode == PAG_MLP_MFMA_BF16 && d->x1_dtype == PAG_BF16 && d->x1_layout == PAG_LAYOUT_XCD8 && d->k1 == 64 && !d->x2 && d->n_layers == 2 &&
@@ -3740,36 +3749,22 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
                 c.per_wave = ((hc->n_samples > 0 && hc->n_samples < 160 * hc->P) || hc->P >= HC_PER_WAVE_P) ? 1 : 0;
                 constexpr int HEAD_ONCE_GRID = 256;
                 const unsigned grid = (unsigned)std::min<int64_t>(c.per_wave ? (hc->P + 3) / 4 : hc->P, HEAD_ONCE_GRID);
-                if (a->pair) {
-                    const size_t lds = (size_t)(128 + 224 + 96) * RS * sizeof(bf16_t) + (size_t)(128 + 224 + 96 + 4 * 224) * sizeof(float) + 4 * ST_BYTES;
-                    raise_lds_limit<head_fwd_once_kernel<true>>();
-                    hipLaunchKernelGGL((head_fwd_once_kernel<true>), dim3(grid), dim3(256), lds, st, p, c);
-                } else {
-                    const size_t lds = (size_t)(128 + 224) * RS * sizeof(bf16_t) + (size_t)(128 + 224 + 4 * 224) * sizeof(float) + 4 * ST_BYTES;
-                    raise_lds_limit<head_fwd_once_kernel<false>>();
-                    hipLaunchKernelGGL((head_fwd_once_kernel<false>), dim3(grid), dim3(256), lds, st, p, c);
-                }
+                if (a->pair) launch_head_fwd_once<true>(p, c, grid, st);
+                else launch_head_fwd_once<false>(p, c, grid, st);
                 PAG_CHECK_LAUNCH("pag_mlp_fwd (wide head, decoder + per-ray sum)");
                 return PAG_OK;
             }
             if (a->pair) {
-                constexpr int NWP = WIDE_FWD_PAIR_THREADS / 64;      // waves per workgroup (one workgroup per CU shares the 66 KiB of weights)
-                const size_t lds = (size_t)(128 + 224 + 96) * RS * sizeof(bf16_t) + (128 + 224 + 96) * sizeof(float) + NWP * ST_BYTES;
+                constexpr int NWP = wide_fwd_waves(true);      // waves per workgroup (one workgroup per CU shares the 66 KiB of weights)
                 // one workgroup per CU is all that fits (LDS): a grid of 1.5 x 256 ran a full round and a half-empty one (220 us, of which
                 // the second round's 110 us kept 128 CUs idle: profiles/README.md, round 4 timelines) - at most ONE round, tiles grid-strided
                 constexpr int WIDE_FWD_PAIR_GRID = 256;
                 const unsigned grid = std::min<unsigned>((mlp_grid(M) * 4 + NWP - 1) / NWP, WIDE_FWD_PAIR_GRID);
-                raise_lds_limit<mlp_fwd_wide_stats<false, true>>();
-                hipLaunchKernelGGL((mlp_fwd_wide_stats<false, true>), dim3(grid), dim3(WIDE_FWD_PAIR_THREADS), lds, st, p);
+                launch_fwd_wide_stats<false, true>(p, grid, st);
+            } else if (a->hidden_save[0]) {
+                launch_fwd_wide_stats<true, false>(p, mlp_grid(M), st);
             } else {
-                const size_t lds = (size_t)(128 + 224) * RS * sizeof(bf16_t) + (128 + 224) * sizeof(float) + 4 * ST_BYTES;
-                if (a->hidden_save[0]) {
-                    raise_lds_limit<mlp_fwd_wide_stats<true, false>>();
-                    hipLaunchKernelGGL((mlp_fwd_wide_stats<true, false>), dim3(mlp_grid(M)), dim3(256), lds, st, p);
-                } else {
-                    raise_lds_limit<mlp_fwd_wide_stats<false, false>>();
-                    hipLaunchKernelGGL((mlp_fwd_wide_stats<false, false>), dim3(mlp_grid(M)), dim3(256), lds, st, p);
-                }
+                launch_fwd_wide_stats<false, false>(p, mlp_grid(M), st);
             }
             PAG_CHECK_LAUNCH("pag_mlp_fwd (wide head statistics)");
             return PAG_OK;
@@ -3798,24 +3793,14 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
             pd.hsave[0] = pd.hsave[1] = nullptr;
             pd.grp_L = d->x1_levels;
             pd.grp_F = d->x1_feats;
-            const size_t lds = (size_t)(64 + 32 + 64 + 64 + 32) * RS * sizeof(bf16_t) + (64 + 32 + 64 + 64 + 32) * sizeof(float);
-            hipLaunchKernelGGL(mlp_fwd_density_colour, dim3(std::min<unsigned>(mlp_grid(M), FAST_FWD_GRID_CAP)), dim3(256), lds, st, pd, p);
+            hipLaunchKernelGGL(mlp_fwd_density_colour, dim3(std::min<unsigned>(mlp_grid(M), FAST_FWD_GRID_CAP)), dim3(256), DensityColourLds{}.bytes, st, pd, p);
             PAG_CHECK_LAUNCH("pag_mlp_fwd (density + colour)");
             return PAG_OK;
         }
         if (kind >= 0 && (save_all || save_none)) {
-            const size_t lds = (size_t)(64 + (a->n_layers == 3 ? 64 : 0) + 32) * RS * sizeof(bf16_t) + (128 + 32) * sizeof(float) + 4 * ST_BYTES;
-#define FWD_FAST(NL_, K_, S_) hipLaunchKernelGGL((mlp_fwd_fast<NL_, K_, S_>), dim3(std::min<unsigned>(mlp_grid(M), FAST_FWD_GRID_CAP)), dim3(256), lds, st, p)
-#define FWD_FAST_K(K_)                                                        \
-    do {                                                                      \
-        if (a->n_layers == 2) { if (save_all) FWD_FAST(2, K_, true); else FWD_FAST(2, K_, false); } \
-        else { if (save_all) FWD_FAST(3, K_, true); else FWD_FAST(3, K_, false); }                 \
-    } while (0)
-            if (kind == 0) FWD_FAST_K(0);
-            else if (kind == 1) FWD_FAST_K(1);
-            else FWD_FAST_K(2);
-#undef FWD_FAST_K
-#undef FWD_FAST
+            if (kind == 0) launch_fwd_fast<0>(p, a->n_layers, save_all, st);
+            else if (kind == 1) launch_fwd_fast<1>(p, a->n_layers, save_all, st);
+            else launch_fwd_fast<2>(p, a->n_layers, save_all, st);
             PAG_CHECK_LAUNCH("pag_mlp_fwd (straight-line)");
             return PAG_OK;
         }
@@ -3824,14 +3809,12 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
     PAG_CHECK_ARG(!a->x1_producer, "pag_mlp_fwd: x1_producer rides only in the straight-line colour launch (pag_mlp_fwd_producer_supported)");
     PAG_CHECK_ARG(!a->pair, "pag_mlp_fwd: pair rides only in the straight-line wide-head launch (M <= %lld)", (long long)PAG_MLP_FUSED_WIDE_MAX_M);
     if (a->mode == PAG_MLP_MFMA_BF16) {
-        const int OB = (a->out_dim + 31) / 32;
-        const size_t lds = (size_t)(64 + (a->n_layers == 3 ? 64 : 0) + OB * 32) * RS * sizeof(bf16_t) + (128 + OB * 32) * sizeof(float) + 4 * ST_BYTES;
-        if (a->x1_dtype == PAG_F32 && a->out_dtype == PAG_F32) launch_fwd_mfma<float, float>(p, a->n_layers, OB, lds, st);
-        else if (a->x1_dtype == PAG_F32) launch_fwd_mfma<float, bf16_t>(p, a->n_layers, OB, lds, st);
-        else if (a->out_dtype == PAG_F32) launch_fwd_mfma<bf16_t, float>(p, a->n_layers, OB, lds, st);
-        else launch_fwd_mfma<bf16_t, bf16_t>(p, a->n_layers, OB, lds, st);
+        if (a->x1_dtype == PAG_F32 && a->out_dtype == PAG_F32) launch_fwd_mfma<float, float>(p, a->n_layers, st);
+        else if (a->x1_dtype == PAG_F32) launch_fwd_mfma<float, bf16_t>(p, a->n_layers, st);
+        else if (a->out_dtype == PAG_F32) launch_fwd_mfma<bf16_t, float>(p, a->n_layers, st);
+        else launch_fwd_mfma<bf16_t, bf16_t>(p, a->n_layers, st);
     } else {
-        const size_t lds = (size_t)(64 * PT + 64 * 64) * sizeof(float);
+        const size_t lds = F32Lds(64).bytes;
         dim3 grid((unsigned)((M + PT - 1) / PT)), block(PT);
         if (a->x1_dtype == PAG_F32 && a->out_dtype == PAG_F32)
             hipLaunchKernelGGL((mlp_fwd_f32<float, float>), grid, block, lds, st, p, a->n_layers);
@@ -4091,17 +4074,15 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
         int n_fin = 3;
         if (b) {
             // the companion head runs in the same launch as the layers below the wide head: one read of the input, one write of the summed gradient
-            const size_t ldsP = (size_t)(64 * 72 * 5 + 64 * 40) * sizeof(bf16_t) + 128 * sizeof(float) + (size_t)4 * 4 * TW_ELEMS * sizeof(bf16_t);
             raise_lds_limit<mlp_bwd_pair>();
             PairParams pp{pb, ps};
-            hipLaunchKernelGGL(mlp_bwd_pair, dim3(grid), dim3(256), ldsP, st, pp);
+            hipLaunchKernelGGL(mlp_bwd_pair, dim3(grid), dim3(256), PairLds{}.bytes, st, pp);
             PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, layers below the wide head + companion head)");
             fb.p[3] = FinishParams{slabS0, (int)grid, HID, 64, b->in_dim, p.grp_L, p.grp_F, b->dW[0], b->db[0]};
             fb.p[4] = FinishParams{slabS1, (int)grid, b->out_dim, 32, HID, 0, 0, b->dW[1], b->db[1]};
             n_fin = 5;
         } else {
-            const size_t ldsB = (size_t)(64 * (64 + 8) + 2 * 64 * RS) * sizeof(bf16_t) + 128 * sizeof(float) + (size_t)4 * 3 * TW_ELEMS * sizeof(bf16_t);
-            launch_bwd_fused<2, 0, false, 2>(pb, grid, ldsB, st);
+            launch_bwd_fused<2, 0, false, 2>(pb, grid, st);
             PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, layers below the wide head)");
         }
         launch_wgrad_finish(fb, a->out_dim, n_fin, st);
@@ -4116,14 +4097,12 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
             p.slabs[l] = ws;
             ws += (int64_t)grid * (l + 1 < a->n_layers ? 64 : 32) * WG_SLAB_COLS;
         }
-        const size_t lds = (size_t)(64 * (32 + 8) + 2 * (a->n_layers == 3 ? 64 * RS : 0) + 2 * 64 * RS) * sizeof(bf16_t) + 128 * sizeof(float) +
-                           (size_t)4 * (a->n_layers + 1) * TW_ELEMS * sizeof(bf16_t);
         p.dz[0] = kind == 1 ? a->dz[0] : nullptr;
         p.dz0_slots = kind == 1 ? a->dz0_slots : nullptr;
         // colour-like with the per-ray input's gradient requested: dz_0 is written as well (1) or, samples packed ray by ray, summed per (tile, ray) (2)
         const int dz0 = kind != 1 ? 0 : (a->dz0_slots ? 2 : (a->dz[0] ? 1 : 0));
-        if (a->n_layers == 2) launch_bwd_fused_kind<2>(p, kind, a->dx1_accumulate != 0, dz0, grid, lds, st);
-        else launch_bwd_fused_kind<3>(p, kind, a->dx1_accumulate != 0, dz0, grid, lds, st);
+        if (a->n_layers == 2) launch_bwd_fused_kind<2>(p, kind, a->dx1_accumulate != 0, dz0, grid, st);
+        else launch_bwd_fused_kind<3>(p, kind, a->dx1_accumulate != 0, dz0, grid, st);
         PAG_CHECK_LAUNCH("pag_mlp_bwd (fused)");
         FinishBatch fb{};
         int max_out = 0;
@@ -4145,19 +4124,15 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
         else if (a->n_layers == 2) launch_bwd_wide_mfma<bf16_t, 2>(p, st);
         else launch_bwd_wide_mfma<bf16_t, 3>(p, st);
     } else if (a->mode == PAG_MLP_MFMA_BF16) {
-        const int OB = (a->out_dim + 31) / 32;
-        const size_t lds = (size_t)(64 * (OB * 32 + 8) + (a->n_layers == 3 ? 64 * RS : 0) + 64 * RS) * sizeof(bf16_t) + 4 * ST_BYTES;
-        if (out_f32 && dx_f32) launch_bwd_mfma<float, float>(p, a->n_layers, OB, lds, st);
-        else if (out_f32) launch_bwd_mfma<float, bf16_t>(p, a->n_layers, OB, lds, st);
-        else if (dx_f32) launch_bwd_mfma<bf16_t, float>(p, a->n_layers, OB, lds, st);
-        else launch_bwd_mfma<bf16_t, bf16_t>(p, a->n_layers, OB, lds, st);
+        if (out_f32 && dx_f32) launch_bwd_mfma<float, float>(p, a->n_layers, st);
+        else if (out_f32) launch_bwd_mfma<float, bf16_t>(p, a->n_layers, st);
+        else if (dx_f32) launch_bwd_mfma<bf16_t, float>(p, a->n_layers, st);
+        else launch_bwd_mfma<bf16_t, bf16_t>(p, a->n_layers, st);
     } else {
-        const size_t lds = (size_t)(224 * PT + 64 * 64) * sizeof(float);
-        const dim3 grid((unsigned)((M + PT - 1) / PT));
-        if (out_f32 && dx_f32) launch_bwd_f32<float, float>(p, a->n_layers, grid, lds, st);
-        else if (out_f32) launch_bwd_f32<float, bf16_t>(p, a->n_layers, grid, lds, st);
-        else if (dx_f32) launch_bwd_f32<bf16_t, float>(p, a->n_layers, grid, lds, st);
-        else launch_bwd_f32<bf16_t, bf16_t>(p, a->n_layers, grid, lds, st);
+        if (out_f32 && dx_f32) launch_bwd_f32<float, float>(p, a->n_layers, st);
+        else if (out_f32) launch_bwd_f32<float, bf16_t>(p, a->n_layers, st);
+        else if (dx_f32) launch_bwd_f32<bf16_t, float>(p, a->n_layers, st);
+        else launch_bwd_f32<bf16_t, bf16_t>(p, a->n_layers, st);
     }
     PAG_CHECK_LAUNCH("pag_mlp_bwd");
     return PAG_OK;
@@ -4201,7 +4176,7 @@ extern "C" int pag_head_composite_fwd(const int64_t *pack_start, const int32_t *
     // waves sharing a pack each pay it
     p.per_wave = ((samples_hint > 0 && samples_hint < 160 * P) || P >= HC_PER_WAVE_P) ? 1 : 0;
     const int OB = (out_dim + 31) / 32;
-    const size_t lds = (size_t)OB * 32 * RS * sizeof(bf16_t) + (size_t)5 * OB * 32 * sizeof(float) + 4 * ST_BYTES;
+    const size_t lds = HeadCompLds(OB).bytes;
     constexpr int HC_GRID = 512;
     const unsigned grid = (unsigned)std::min<int64_t>(p.per_wave ? (P + 3) / 4 : P, HC_GRID);
     if (OB == 7) hipLaunchKernelGGL(head_composite_fwd_kernel<7>, dim3(grid), dim3(256), lds, (hipStream_t)stream, p);

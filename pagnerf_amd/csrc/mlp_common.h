@@ -33,6 +33,10 @@ typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// a region of the dynamic LDS segment at a byte offset taken from the kernel's layout (mlp_lds.h)
+template <typename T>
+__device__ __forceinline__ T *lds_at(unsigned char *smem, int byte_offset) { return reinterpret_cast<T *>(smem) + byte_offset / (int)sizeof(T); }
+
 __device__ __forceinline__ int rho(int q, int h) { return (q & 3) + 8 * (q >> 2) + 4 * h; }
 // staged position (8*g + e) of the XCD8 layout -> column level*F + f of the [M, L*F] feature row, or -1 (padding)
 // (a / d for the wave-uniform divisors of the staging loops: a shift when d is a power of two - the feature width and the pad sizes always

@@ -2,6 +2,7 @@
 // wrote; wgrad_finish_kernel, which sums them, stays in mlp.hip beside the fused backward kernels whose slabs it sums as well, and is reached
 // through pagmlp::launch_wgrad_finish.
 #include "mlp_common.h"
+#include "mlp_lds.h"
 
 namespace {
 
@@ -30,7 +31,6 @@ struct WgradParams {
 struct WgradBatch {
     WgradParams p[WG_MAX_BATCH];
 };
-constexpr int WG_RS = 72;       // LDS row stride (bf16) of the transposed tiles: 64 samples + 8 pad
 
 template <typename A1T, int APW /* accumulator blocks per wave */, int NWV = 4 /* waves per workgroup */>
 // narrow variant (APW 2, 4 waves): asking for 5 waves per SIMD keeps every accumulator in VGPRs (no AGPR copies) under 102
@@ -41,8 +41,9 @@ __global__ __launch_bounds__(NWV * 64, (APW == 2 ? 5 : (APW == 3 ? 4 : 1))) void
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int OB = (p.n_out + 31) / 32;
     const int IB = (p.n_in + 31) / 32;                 // 1 or 2
-    bf16_t *Zt = reinterpret_cast<bf16_t *>(smem);      // [OB*32][WG_RS]
-    bf16_t *At = Zt + OB * 32 * WG_RS;                  // [IB*32][WG_RS]
+    const WgradLds L(OB, IB);
+    bf16_t *Zt = lds_at<bf16_t>(smem, L.Zt);            // [OB*32][WG_RS]
+    bf16_t *At = lds_at<bf16_t>(smem, L.At);            // [IB*32][WG_RS]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int npairs = OB * (IB + 1);
@@ -219,7 +220,7 @@ extern "C" int pag_mlp_wgrad(const void *dz, int dz_cols, int n_out, const void 
                   "pag_mlp_wgrad: XCD8 a1 needs bf16, k1 = n_in = 64 and no a2");
     WgradParams p{(const bf16_t *)dz, dz_cols, n_out, a1, k1, a2, a2 ? k2p : 0, a2_index, n_in, slabs, M, a1_layout == PAG_LAYOUT_XCD8};
     const int OB = (n_out + 31) / 32, IB = (n_in + 31) / 32;
-    const size_t lds = (size_t)(OB + IB) * 32 * WG_RS * sizeof(bf16_t);
+    const size_t lds = WgradLds(OB, IB).bytes;
     const bool small = OB * (IB + 1) <= 8;      // fewer accumulators -> fewer VGPRs -> more resident workgroups
     WgradBatch b{};
     b.p[0] = p;
@@ -282,7 +283,7 @@ extern "C" int pag_mlp_wgrad_batch(const pag_wgrad_layer *layers, int n_layers, 
             if (done[k] || (z.a1_dtype == PAG_F32) != f32 || (OB * (IB + 1) <= 8) != small || z.n_blocks != y.n_blocks) continue;
             b.p[count++] = WgradParams{(const bf16_t *)z.dz, z.dz_cols, z.n_out, z.a1, z.k1, z.a2, z.a2 ? z.k2p : 0, z.a2_index, z.n_in, z.slabs, M,
                                        z.a1_layout == PAG_LAYOUT_XCD8};
-            lds = std::max(lds, (size_t)(OB + IB) * 32 * WG_RS * sizeof(bf16_t));
+            lds = std::max<size_t>(lds, WgradLds(OB, IB).bytes);      // the launch's layers share a workgroup size: the largest layout
             done[k] = true;
         }
         wgrad_launch(b, count, f32, small, y.n_blocks, lds, st);

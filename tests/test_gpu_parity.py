@@ -1135,6 +1135,61 @@ def test_straight_line_forward_kernels(gpu_device):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("case", ["saved", "fused", "dz0_rows", "dz0_slots"])
+def test_two_layer_colour_decoder_against_fp32_mode(gpu_device, case):
+    """The TWO-layer colour-like decoder (bf16 x1 [M,16] + per-ray x2, sigmoid, density column) - the instantiations of the dedicated kernels that
+    the nef's three-layer colour decoder never selects: mlp_fwd_fast<2, 1, SAVE = true> (`saved`: the backward takes the generic kernels and the
+    separate weight gradients) and mlp_bwd_fused<2, 1, false, 1, DZ0> with DZ0 = 0 (`fused`), 1 (`dz0_rows`: d x2 from the dz_0 tensor) and 2
+    (`dz0_slots`: d x2 from per-(tile, ray) sums).  M = 161: five full 32-row tiles and one row - all four waves work, one wave takes a second tile,
+    the last tile is ragged.  Against the same call in PAG_MLP_FP32 mode on bf16-representable operands, under the bounds
+    test_fused_mlp_forward_backward sets for the colour shape on the bf16 path: 2e-2 on the output, 2e-2 relative L2 on every gradient."""
+    ops, L = _ops()
+    dev = gpu_device
+    rs = np.random.RandomState(41)
+    M, N = 161, 7
+    ridx = torch.from_numpy(np.sort(np.concatenate([np.arange(N), rs.randint(0, N, size=M - N)])).astype(np.int32)).to(dev)      # every ray has a sample
+    counts = torch.bincount(ridx.long(), minlength=N)
+    packs = (torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0)]), ops._ray_iota(N, dev))      # one pack per ray: the form the slots need
+    W, b = _rand_mlp(rs, (43, 64, 3))
+    W = [w.bfloat16().float() for w in W]
+    x1v = torch.from_numpy(rs.standard_normal(size=(M, 16)).astype(np.float32)).to(dev).bfloat16()
+    x2v = torch.zeros(N, 32, device=dev)
+    x2v[:, :27] = torch.from_numpy(rs.standard_normal(size=(N, 27)).astype(np.float32)).to(dev).bfloat16().float()
+    g_rgb = torch.from_numpy(rs.standard_normal(size=(M, 3)).astype(np.float32)).to(dev)
+    g_sig = torch.from_numpy(rs.standard_normal(size=(M,)).astype(np.float32)).to(dev)
+    want_dx2 = case in ("dz0_rows", "dz0_slots")
+
+    def run(mode):
+        Wg = [w.to(dev).requires_grad_(True) for w in W]
+        bg = [v.to(dev).requires_grad_(True) for v in b]
+        x1 = x1v.clone().requires_grad_(True)
+        x2 = x2v.clone().requires_grad_(want_dx2)
+        rgb, sigma = ops.colour_and_density(x1, Wg, bg, x2, ridx, 43, out_act=L.ACT_SIGMOID, mode=mode, out_dtype=torch.float32,
+                                            x2_packs=packs if case == "dz0_slots" else None)
+        ((rgb * g_rgb).sum() + (sigma * g_sig).sum()).backward()
+        torch.cuda.synchronize()
+        grads = [t.grad.float() for t in Wg + bg + [x1]] + ([x2.grad[:, :27]] if want_dx2 else [])
+        return rgb.detach(), sigma.detach(), grads
+
+    fused_was, slots_was = ops.WGRAD_FUSED, ops.DZ0_SLOTS
+    try:
+        ops.WGRAD_FUSED = case != "saved"
+        ops.DZ0_SLOTS = case == "dz0_slots"
+        rgb, sigma, grads = run(L.MLP_MFMA_BF16)
+    finally:
+        ops.WGRAD_FUSED, ops.DZ0_SLOTS = fused_was, slots_was
+    rgb32, sigma32, grads32 = run(L.MLP_FP32)
+    assert torch.equal(sigma, sigma32)
+    err = float((rgb - rgb32).abs().max())
+    print("%s: max |rgb - fp32| %.3g" % (case, err))
+    assert err < 2e-2
+    for k, (u, v) in enumerate(zip(grads, grads32)):
+        e = _rel_l2(u, v)
+        print("%s: gradient %d rel L2 %.3g" % (case, k, e))
+        assert float(v.abs().sum()) > 0 and e < 2e-2, (case, k, e)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("option", ["pos_encoding", "position", "separate", "appearance", "sum"])
 def test_nef_panoptic_feature_types_and_multiscale_sum(gpu_device, option):
     """The nef options outside best.yaml (pc_nerf/panoptic_delta_nef.py:172-173, :210-234; decoder input widths panoptic_nef.py:78-105):
