@@ -126,16 +126,6 @@ class VisArgs(ctypes.Structure):
 _SIGS = {
     "pag_abi_version": (c_i32, []),
     "pag_last_error_string": (ctypes.c_char_p, []),
-    "pag_hash_encode_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_fp, c_fp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp]),
-    "pag_hash_encode_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_fp, c_fp, c_vp, c_vp, c_i64, c_i32, c_vp]),
-    "pag_hash_encode_bwd_set": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_fp, c_fp, c_vp, c_vp, c_i64, c_i32, c_vp]),
-    "pag_permuto_encode_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_u32, c_fp, c_fp, c_fp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp]),
-    "pag_permuto_encode_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_u32, c_fp, c_fp, c_fp, c_vp, c_vp, c_i64, c_i32, c_vp]),
-    "pag_permuto_encode_bwd_set": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_u32, c_fp, c_fp, c_fp, c_vp, c_vp, c_i64, c_i32, c_vp]),
-    "pag_hash_encode_bwd_xyz": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_fp, c_fp, c_vp, c_vp, c_i64, c_i32, c_vp]),
-    "pag_permuto_encode_bwd_xyz": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_u32, c_fp, c_fp, c_fp, c_vp, c_vp, c_i64, c_i32, c_vp]),
-    "pag_hash_encode_fwd_add": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_fp, c_fp, c_vp, c_vp, c_i32, c_vp]),
-    "pag_permuto_encode_fwd_add": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_u32, c_fp, c_fp, c_fp, c_vp, c_vp, c_i32, c_vp]),
     "pag_encode_bwd_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32, c_i64]),
     "pag_mlp_fwd": (c_i32, [ctypes.POINTER(MlpFwdArgs), c_i64, c_vp]),
     "pag_mlp_fwd_pair_supported": (c_i32, [ctypes.POINTER(MlpFwdArgs), ctypes.POINTER(MlpFwdArgs)]),
@@ -219,10 +209,6 @@ _SIGS = {
     "pag_mlp_dz0_slots_bytes": (c_i64, [c_i64, c_i64]),
     "pag_mlp_dz0_slots_sum": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pag_encode_bwd_rays_workspace_bytes": (c_i64, [c_i64, c_i64]),
-    "pag_hash_encode_bwd_rays": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_fp, c_fp, c_vp, c_vp, c_vp, c_i64,
-                                         c_vp, c_vp, c_i64, c_i32, c_vp]),
-    "pag_permuto_encode_bwd_rays": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_u32, c_fp, c_fp, c_fp, c_vp, c_vp, c_vp,
-                                            c_i64, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "pag_deep_mlp_supported": (c_i32, [c_i32, c_i32]),
     "pag_deep_mlp_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
     "pag_deep_mlp_fwd": (c_i32, [ctypes.POINTER(DeepMlpArgs), c_i64, c_vp]),
@@ -246,6 +232,23 @@ _SIGS = {
     "pag_prepare_views": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_f32, c_f32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pag_prepare_labels": (c_i32, [ctypes.POINTER(LabelPlane), c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp]),
 }
+
+# The twelve grid-encoder entry points, pag_{hash,permuto}_encode_{fwd,fwd_add,bwd,bwd_set,bwd_xyz,bwd_rays}: the operation's leading arguments, the
+# kind-specific middle (ops._EncodeSpec.mid() supplies its values in this order), the operation's trailing arguments.
+_ENC_MID = {"hash": [c_i32, c_fp, c_fp],                    # log2_T, resolutions_host, feat_scale_host
+            "permuto": [c_u32, c_fp, c_fp, c_fp]}           # capacity, scale_factor_host, shift_host, feat_scale_host
+_ENC_FWD = [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32]         # xyz, M, tables, table_dtype, n_levels, n_feat
+_ENC_BWD = [c_vp, c_i64, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32]                  # xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, n_levels, n_feat
+_ENC_XYZ = [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32]     # xyz, M, tables, table_dtype, then as _ENC_BWD from grad_out on
+_ENC_OPS = {
+    "fwd": (_ENC_FWD, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp]),                   # out, out_dtype, out_stride_m, out_stride_c, layout, flags, stream
+    "fwd_add": (_ENC_FWD, [c_vp, c_vp, c_i32, c_vp]),                                     # addend, out, flags, stream
+    "bwd": (_ENC_BWD, [c_vp, c_vp, c_i64, c_i32, c_vp]),                                  # grad_tables, workspace, workspace_bytes, flags, stream
+    "bwd_set": (_ENC_BWD, [c_vp, c_vp, c_i64, c_i32, c_vp]),
+    "bwd_xyz": (_ENC_XYZ, [c_vp, c_vp, c_i64, c_i32, c_vp]),                              # d_xyz, workspace, workspace_bytes, flags, stream
+    "bwd_rays": (_ENC_XYZ, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp]),    # ridx, depths, pack_start, N, out, workspace, workspace_bytes, flags, stream
+}
+_SIGS.update({"pag_%s_encode_%s" % (kind, op): (c_i32, head + mid + tail) for op, (head, tail) in _ENC_OPS.items() for kind, mid in _ENC_MID.items()})
 
 EXPORTS = tuple(_SIGS)
 _lib = None

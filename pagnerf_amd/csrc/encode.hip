@@ -1023,12 +1023,26 @@ inline BinPlan bin_plan(int64_t M, int L, int F, int NV, int64_t rows) {
     return b;
 }
 
+// One call of a grid encoder entry point as its fill function (fill_hash / fill_permuto below) leaves it: the kernels' parameter blocks - the one of
+// the other kind stays zero - and what the launchers need of the encoder's shape.
+struct EncodeCall {
+    const char *name;            // the exported entry point, for messages
+    int kind;                    // 0 hash, 1 permuto
+    int n_levels, n_feat;
+    int n_vertices;              // per sample and level: 8 (hash), 4 (permuto)
+    int lpx;                     // levels per XCD group: ceil(n_levels / 8)
+    int64_t rows;                // table rows per level
+    HashParams hp{};
+    PermutoParams pp{};
+};
+
 template <int KIND>
-int launch_binned(const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t sm, int64_t sc, int grouped, int L, int F,
-                  int64_t rows, const HashParams &hp, const PermutoParams &pp, float *gtab, void *workspace,
-                  int64_t workspace_bytes, hipStream_t st, const char *name, bool overwrite = false) {
+int launch_binned(const EncodeCall &ec, const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t sm, int64_t sc, int grouped,
+                  float *gtab, void *workspace, int64_t workspace_bytes, hipStream_t st, bool overwrite) {
     constexpr int NV = KIND == 0 ? 8 : 4;
-    const BinPlan b = bin_plan(M, L, F, NV, rows);
+    const int L = ec.n_levels, F = ec.n_feat;
+    const char *name = ec.name;
+    const BinPlan b = bin_plan(M, L, F, NV, ec.rows);
     PAG_CHECK_ARG(workspace_bytes >= b.total, "%s: workspace %lld B < required %lld B", name, (long long)workspace_bytes, (long long)b.total);
     PAG_CHECK_ARG(b.NS <= NS_MAX, "%s: table too large for the binned backward (%d slices > %d)", name, b.NS, NS_MAX);
     PAG_CHECK_ARG(F == 2 || F == 4 || F == 1, "%s: n_feat", name);
@@ -1045,14 +1059,14 @@ int launch_binned(const float *xyz, int64_t M, const void *grad_out, int grad_dt
     const size_t lds = ((size_t)1 << b.shift) * F * sizeof(unsigned long long);
     const int lpx = grouped ? (L + 7) / 8 : 1;
 #define BIN_LAUNCH1(GT, F_, LPX_)                                                                                       \
-    hipLaunchKernelGGL((bin_kernel<KIND, GT, F_, LPX_, (sizeof(GT) == 2 && F_ == 2)>), g1, dim3(tile_samples(NV)), 0, st, xyz, M, (const GT *)grad_out, sm, sc, grouped, hp, pp, lay)
+    hipLaunchKernelGGL((bin_kernel<KIND, GT, F_, LPX_, (sizeof(GT) == 2 && F_ == 2)>), g1, dim3(tile_samples(NV)), 0, st, xyz, M, (const GT *)grad_out, sm, sc, grouped, ec.hp, ec.pp, lay)
 #define BIN_LAUNCH(GT, F_)                                                                                              \
     do {                                                                                                                \
         if (lpx == 1) BIN_LAUNCH1(GT, F_, 1);                                                                           \
         else if (lpx == 2) BIN_LAUNCH1(GT, F_, 2);                                                                      \
         else if (lpx == 3) BIN_LAUNCH1(GT, F_, 3);                                                                      \
         else BIN_LAUNCH1(GT, F_, 4);                                                                                    \
-        hipLaunchKernelGGL((reduce_kernel<F_, NV, (sizeof(GT) == 2 && F_ == 2)>), g2, dim3(1024), lds, st, lay, rows, gtab, overwrite ? 1 : 0); \
+        hipLaunchKernelGGL((reduce_kernel<F_, NV, (sizeof(GT) == 2 && F_ == 2)>), g2, dim3(1024), lds, st, lay, ec.rows, gtab, overwrite ? 1 : 0); \
     } while (0)
     if (grad_dtype == PAG_F32) {
         if (F == 2) BIN_LAUNCH(float, 2);
@@ -1070,7 +1084,7 @@ int launch_binned(const float *xyz, int64_t M, const void *grad_out, int grad_dt
 
 inline unsigned encode_grid(int64_t M) { return (unsigned)(((M + ENC_FWD_THREADS - 1) / ENC_FWD_THREADS) * 8); }
 
-// ---- dispatch helpers: (table dtype, out dtype, F, LPX) -> kernel instantiation
+// ---- dispatch helpers: (table dtype, out / grad dtype, F, LPX) -> kernel instantiation
 #define PAG_DISPATCH_F_LPX(F_, LPX_, CALL)                 \
     if (n_feat == F_ && lpx == LPX_) {                     \
         constexpr int F = F_;                              \
@@ -1092,376 +1106,230 @@ inline unsigned encode_grid(int64_t M) { return (unsigned)(((M + ENC_FWD_THREADS
     PAG_DISPATCH_F_LPX(1, 3, CALL)      \
     PAG_DISPATCH_F_LPX(1, 4, CALL)
 
-int check_common(const char *name, const void *xyz, int64_t M, int n_levels, int n_feat) {
+// The (table dtype, out / grad dtype) ladder: fn(Type<TableT>, Type<OtherT>) for a checked pair of dtype codes (tables F32 | F16, the other operand
+// F32 | BF16).  fn is a generic lambda, so what it launches may depend on the types (`if constexpr`) without instantiating the other branch.
+template <typename T>
+struct Type {
+    using type = T;
+};
+template <typename Fn>
+void dispatch_types(int table_dtype, int other_dtype, Fn &&fn) {
+    if (table_dtype == PAG_F32 && other_dtype == PAG_F32) fn(Type<float>(), Type<float>());
+    else if (table_dtype == PAG_F32) fn(Type<float>(), Type<bf16_t>());
+    else if (other_dtype == PAG_F32) fn(Type<__half>(), Type<float>());
+    else fn(Type<__half>(), Type<bf16_t>());
+}
+
+// ---- the two fill functions: an entry point's kind-specific arguments -> EncodeCall, with the checks every operation shares
+int fill_common(EncodeCall &ec, const char *name, int kind, const void *xyz, int64_t M, int n_levels, int n_feat) {
     PAG_CHECK_ARG(M >= 0, "%s: M < 0", name);
     PAG_CHECK_ARG(M == 0 || xyz != nullptr, "%s: xyz is NULL", name);
     PAG_CHECK_ARG(n_levels >= 1 && n_levels <= PAG_MAX_LEVELS, "%s: n_levels %d not in [1,%d]", name, n_levels, PAG_MAX_LEVELS);
     PAG_CHECK_ARG(n_feat == 1 || n_feat == 2 || n_feat == 4, "%s: n_feat %d not in {1,2,4}", name, n_feat);
     PAG_CHECK_ARG(n_levels * n_feat <= PAG_MAX_FEATS, "%s: n_levels*n_feat %d > %d", name, n_levels * n_feat, PAG_MAX_FEATS);
+    ec.name = name;
+    ec.kind = kind;
+    ec.n_levels = n_levels;
+    ec.n_feat = n_feat;
+    ec.n_vertices = kind == 0 ? 8 : 4;
+    ec.lpx = (n_levels + 7) / 8;
+    return PAG_OK;
+}
+
+int fill_hash(EncodeCall &ec, const char *name, const void *xyz, int64_t M, int n_levels, int n_feat, int log2_T, const float *resolutions_host,
+              const float *feat_scale_host, int flags) {
+    if (int rc = fill_common(ec, name, 0, xyz, M, n_levels, n_feat)) return rc;
+    PAG_CHECK_ARG(log2_T >= 1 && log2_T <= 30, "%s: log2_T %d not in [1,30]", name, log2_T);
+    PAG_CHECK_ARG(resolutions_host, "%s: resolutions_host is NULL", name);
+    ec.rows = (int64_t)1 << log2_T;
+    HashParams &p = ec.hp;
+    p.L = n_levels;
+    p.log2T = log2_T;
+    p.has_scale = feat_scale_host != nullptr;
+    p.half_coords = (flags & PAG_ENC_HALF_COORDS) ? 1 : 0;
+    for (int l = 0; l < n_levels; ++l) p.res[l] = resolutions_host[l];
+    for (int c = 0; c < n_levels * n_feat; ++c) p.scale[c] = feat_scale_host ? feat_scale_host[c] : 1.0f;
+    return PAG_OK;
+}
+
+int fill_permuto(EncodeCall &ec, const char *name, const void *xyz, int64_t M, int n_levels, int n_feat, uint32_t capacity,
+                 const float *scale_factor_host, const float *shift_host, const float *feat_scale_host, int flags) {
+    if (int rc = fill_common(ec, name, 1, xyz, M, n_levels, n_feat)) return rc;
+    PAG_CHECK_ARG(capacity >= 1, "%s: capacity is 0", name);
+    PAG_CHECK_ARG(scale_factor_host && shift_host, "%s: NULL scale_factor/shift", name);
+    ec.rows = (int64_t)capacity;
+    PermutoParams &p = ec.pp;
+    p.L = n_levels;
+    p.half_coords = (flags & PAG_ENC_HALF_COORDS) ? 1 : 0;
+    p.capacity = capacity;
+    p.pow2mask = (capacity & (capacity - 1)) == 0 ? capacity - 1 : 0;       // capacity 1: mask 0
+    p.has_scale = feat_scale_host != nullptr;
+    for (int l = 0; l < n_levels; ++l)
+        for (int a = 0; a < 3; ++a) {
+            p.sf[l][a] = scale_factor_host[l * 3 + a];
+            p.shift[l][a] = shift_host[l * 3 + a];
+        }
+    for (int c = 0; c < n_levels * n_feat; ++c) p.scale[c] = feat_scale_host ? feat_scale_host[c] : 1.0f;
+    return PAG_OK;
+}
+
+// ---- one implementation per operation.  The checks that do not depend on the encoder kind sit here, once: dtypes, layout, the XCD8 constraint
+// (bf16 operand, ceil(L/8)*F <= 8 elements per piece), NULL buffers, workspace presence and size.
+bool xcd8_fits(const EncodeCall &ec, int dtype) { return dtype == PAG_BF16 && ec.lpx * ec.n_feat <= 8; }
+
+// Forward; addend (XCD8 only): out = bf16(addend + bf16(features)).
+template <int KIND>
+int encode_fwd(EncodeCall &ec, const float *xyz, int64_t M, const void *tables, int table_dtype, void *out, int out_dtype, int64_t out_stride_m,
+               int64_t out_stride_c, int layout, const void *addend_p, void *stream) {
+    PAG_CHECK_ARG(table_dtype == PAG_F32 || table_dtype == PAG_F16, "%s: table dtype must be F32 or F16", ec.name);
+    PAG_CHECK_ARG(out_dtype == PAG_F32 || out_dtype == PAG_BF16, "%s: out dtype must be F32 or BF16", ec.name);
+    PAG_CHECK_ARG(layout == PAG_LAYOUT_STRIDED || (layout == PAG_LAYOUT_XCD8 && xcd8_fits(ec, out_dtype)),
+                  "%s: XCD8 layout needs bf16 output and ceil(L/8)*F <= 8", ec.name);
+    if (M == 0) return PAG_OK;
+    PAG_CHECK_ARG(tables && out, "%s: NULL tables/out", ec.name);
+    ec.hp.pair_loads = (reinterpret_cast<uintptr_t>(tables) & 15) == 0 && ec.hp.log2T >= 1;
+    const bf16_t *addend = (const bf16_t *)addend_p;
+    const int grouped = layout == PAG_LAYOUT_XCD8, n_feat = ec.n_feat, lpx = ec.lpx;
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
+    bool launched = false;
+    dispatch_types(table_dtype, out_dtype, [&](auto table_t, auto out_t) {
+        using TT = typename decltype(table_t)::type;
+        using OT = typename decltype(out_t)::type;
+        if constexpr (KIND == 0) {
+            PAG_DISPATCH_ALL((hash_fwd_kernel<TT, OT, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const TT *)tables, ec.hp, (OT *)out, out_stride_m, out_stride_c, grouped, addend)))
+        } else {
+            if constexpr (sizeof(OT) == 2) {          // the addend form exists for bf16 output only (XCD8)
+                if (addend) {
+                    PAG_DISPATCH_ALL((permuto_fwd_add_kernel<TT, OT, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const TT *)tables, ec.pp, (OT *)out, out_stride_m, out_stride_c, grouped, addend)))
+                    return;
+                }
+            }
+            PAG_DISPATCH_ALL((permuto_fwd_kernel<TT, OT, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const TT *)tables, ec.pp, (OT *)out, out_stride_m, out_stride_c, grouped)))
+        }
+    });
+    PAG_CHECK_ARG(launched, "%s: unsupported (n_feat=%d, n_levels=%d)", ec.name, n_feat, ec.n_levels);
+    PAG_CHECK_LAUNCH(ec.name);
+    return PAG_OK;
+}
+
+// Table gradient.  Accumulates into grad_tables (the caller zeroes it) or, with `overwrite`, writes every row: no zero fill of the 50 MB table before
+// the call and no read of it in the reduce pass.  With a workspace the binned algorithm (the only one that overwrites, and the only one that reads
+// the XCD8 layout), without one fp32 global atomics per vertex.
+template <int KIND>
+int encode_bwd(const EncodeCall &ec, bool overwrite, const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t g_stride_m,
+               int64_t g_stride_c, int layout, float *grad_tables, void *workspace, int64_t workspace_bytes, void *stream) {
+    PAG_CHECK_ARG(!overwrite || workspace, "%s: the overwriting form needs the binned algorithm (a workspace)", ec.name);
+    PAG_CHECK_ARG(grad_dtype == PAG_F32 || grad_dtype == PAG_BF16, "%s: grad dtype must be F32 or BF16", ec.name);
+    const int grouped = layout == PAG_LAYOUT_XCD8;
+    PAG_CHECK_ARG(!grouped || (workspace && xcd8_fits(ec, grad_dtype)), "%s: XCD8 layout needs bf16 gradients, a workspace and ceil(L/8)*F <= 8", ec.name);
+    if (M == 0) return PAG_OK;
+    PAG_CHECK_ARG(grad_out && grad_tables, "%s: NULL grad_out/grad_tables", ec.name);
+    hipStream_t st = (hipStream_t)stream;
+    if (workspace) {
+        if (int rc = launch_binned<KIND>(ec, xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, grouped, grad_tables, workspace, workspace_bytes, st, overwrite)) return rc;
+        PAG_CHECK_LAUNCH(ec.name);
+        return PAG_OK;
+    }
+    const int n_feat = ec.n_feat, lpx = ec.lpx;
+    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
+    bool launched = false;
+    dispatch_types(PAG_F32 /* no table operand */, grad_dtype, [&](auto, auto grad_t) {
+        using GT = typename decltype(grad_t)::type;
+        if constexpr (KIND == 0) {
+            PAG_DISPATCH_ALL((hash_bwd_kernel<GT, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const GT *)grad_out, g_stride_m, g_stride_c, ec.hp, grad_tables)))
+        } else {
+            PAG_DISPATCH_ALL((permuto_bwd_kernel<GT, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const GT *)grad_out, g_stride_m, g_stride_c, ec.pp, grad_tables)))
+        }
+    });
+    PAG_CHECK_ARG(launched, "%s: unsupported (n_feat=%d, n_levels=%d)", ec.name, n_feat, ec.n_levels);
+    PAG_CHECK_LAUNCH(ec.name);
+    return PAG_OK;
+}
+
+struct RaysArgs {            // the per-ray form of the position gradient
+    const int32_t *ridx;
+    const float *depths;
+    const int64_t *pack_start;
+    int64_t N;
+};
+int64_t rays_slot_rows(int64_t M, int64_t N) { return (M + 63) / 64 + N; }
+
+// Position gradient: d_xyz f32 [M,3] per sample or, with `rays`, reduced per ray inside the gather pass (see xyz_grad_rays_kernel): d_xyz = f32 [N,6]
+// (d origin | d dir), zero-filled when there are no samples.
+template <int KIND>
+int encode_bwd_xyz(const EncodeCall &ec, const float *xyz, int64_t M, const void *tables, int table_dtype, const void *grad_out, int grad_dtype,
+                   int64_t g_stride_m, int64_t g_stride_c, int layout, float *d_xyz, void *workspace, int64_t workspace_bytes, void *stream,
+                   const RaysArgs *rays = nullptr) {
+    hipStream_t st = (hipStream_t)stream;
+    if (rays) {
+        PAG_CHECK_ARG(rays->N >= 1, "%s: N %lld < 1", ec.name, (long long)rays->N);
+        PAG_CHECK_ARG(M == 0 || (rays->ridx && rays->depths && rays->pack_start), "%s: NULL ridx / depths / pack_start", ec.name);
+        if (M == 0) return hipMemsetAsync(d_xyz, 0, (size_t)rays->N * 6 * sizeof(float), st) == hipSuccess ? PAG_OK : PAG_ERR_LAUNCH;
+    }
+    PAG_CHECK_ARG(table_dtype == PAG_F32 || table_dtype == PAG_F16, "%s: table dtype must be F32 or F16", ec.name);
+    PAG_CHECK_ARG(grad_dtype == PAG_F32 || grad_dtype == PAG_BF16, "%s: grad dtype must be F32 or BF16", ec.name);
+    const int grouped = layout == PAG_LAYOUT_XCD8;
+    PAG_CHECK_ARG(!grouped || xcd8_fits(ec, grad_dtype), "%s: XCD8 layout needs bf16 gradients and ceil(L/8)*F <= 8", ec.name);
+    if (M == 0) return PAG_OK;
+    PAG_CHECK_ARG(tables && grad_out && d_xyz && workspace, "%s: NULL tables/grad_out/d_xyz/workspace", ec.name);
+    const int64_t slot_rows = rays ? rays_slot_rows(M, rays->N) : 0;
+    if (rays) PAG_CHECK_ARG(workspace_bytes >= 8 * slot_rows * 6 * (int64_t)sizeof(float), "%s: workspace smaller than 8 * (ceil(M / 64) + N) * 6 floats", ec.name);
+    else PAG_CHECK_ARG(workspace_bytes >= (int64_t)8 * M * 3 * (int64_t)sizeof(float), "%s: workspace smaller than 8*M*3 floats", ec.name);
+    float *part = (float *)workspace;          // one plane per XCD group: [8][M][3], or 6-float slots [8][slot_rows][6]
+    const int groups = ec.n_levels < 8 ? ec.n_levels : 8, n_feat = ec.n_feat, lpx = ec.lpx;
+    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
+    bool launched = false;
+    dispatch_types(table_dtype, grad_dtype, [&](auto table_t, auto grad_t) {
+        using TT = typename decltype(table_t)::type;
+        using GT = typename decltype(grad_t)::type;
+        if (rays) {
+            PAG_DISPATCH_ALL((xyz_grad_rays_kernel<KIND, TT, GT, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const TT *)tables, (const GT *)grad_out, g_stride_m, g_stride_c, grouped, ec.hp, ec.pp, rays->ridx, rays->depths, part, slot_rows)))
+        } else {
+            PAG_DISPATCH_ALL((xyz_grad_kernel<KIND, TT, GT, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const TT *)tables, (const GT *)grad_out, g_stride_m, g_stride_c, grouped, ec.hp, ec.pp, part)))
+        }
+    });
+    PAG_CHECK_ARG(launched, "%s: unsupported (n_feat=%d, n_levels=%d)", ec.name, n_feat, ec.n_levels);
+    if (rays) {
+        ray_slots_sum_kernel<<<dim3((unsigned)((rays->N + 3) / 4)), dim3(256), 0, st>>>(rays->pack_start, rays->N, part, slot_rows, groups, d_xyz);
+    } else {
+        const int64_t n = M * 3;
+        xyz_grad_sum_kernel<<<dim3((unsigned)((((n % 4 == 0) ? n / 4 : n) + 255) / 256)), dim3(256), 0, st>>>(part, n, groups, d_xyz);
+    }
+    PAG_CHECK_LAUNCH(ec.name);
     return PAG_OK;
 }
 
 }  // namespace
 
-static int hash_encode_fwd_impl(const float *xyz, int64_t M, const void *tables, int table_dtype, int n_levels,
-                                int n_feat, int log2_T, const float *resolutions_host, const float *feat_scale_host,
-                                void *out, int out_dtype, int64_t out_stride_m, int64_t out_stride_c, int layout,
-                                const void *addend_p, int flags, void *stream) {
-    const bf16_t *addend = (const bf16_t *)addend_p;
-    PAG_CHECK_ARG(!addend || layout == PAG_LAYOUT_XCD8, "pag_hash_encode_fwd_add: the addend needs the XCD8 layout");
-    int rc = check_common("pag_hash_encode_fwd", xyz, M, n_levels, n_feat);
-    if (rc) return rc;
-    PAG_CHECK_ARG(log2_T >= 1 && log2_T <= 30, "pag_hash_encode_fwd: log2_T %d not in [1,30]", log2_T);
-    PAG_CHECK_ARG(resolutions_host, "pag_hash_encode_fwd: resolutions_host is NULL");
-    PAG_CHECK_ARG(table_dtype == PAG_F32 || table_dtype == PAG_F16, "pag_hash_encode_fwd: table dtype must be F32 or F16");
-    PAG_CHECK_ARG(out_dtype == PAG_F32 || out_dtype == PAG_BF16, "pag_hash_encode_fwd: out dtype must be F32 or BF16");
-    PAG_CHECK_ARG(layout == PAG_LAYOUT_STRIDED || (layout == PAG_LAYOUT_XCD8 && out_dtype == PAG_BF16 && ((n_levels + 7) / 8) * n_feat <= 8),
-                  "pag_hash_encode_fwd: XCD8 layout needs bf16 output and ceil(L/8)*F <= 8");
-    const int grouped = layout == PAG_LAYOUT_XCD8;
-    if (M == 0) return PAG_OK;
-    PAG_CHECK_ARG(tables && out, "pag_hash_encode_fwd: NULL tables/out");
-    HashParams p;
-    p.L = n_levels;
-    p.log2T = log2_T;
-    p.has_scale = feat_scale_host != nullptr;
-    p.pair_loads = (reinterpret_cast<uintptr_t>(tables) & 15) == 0 && log2_T >= 1;
-    p.half_coords = (flags & PAG_ENC_HALF_COORDS) ? 1 : 0;
-    for (int l = 0; l < n_levels; ++l) p.res[l] = resolutions_host[l];
-    for (int c = 0; c < n_levels * n_feat; ++c) p.scale[c] = feat_scale_host ? feat_scale_host[c] : 1.0f;
-    const int lpx = (n_levels + 7) / 8;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
-    bool launched = false;
-    if (table_dtype == PAG_F32 && out_dtype == PAG_F32) {
-        PAG_DISPATCH_ALL((hash_fwd_kernel<float, float, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const float *)tables, p, (float *)out, out_stride_m, out_stride_c, grouped, addend)))
-    } else if (table_dtype == PAG_F32 && out_dtype == PAG_BF16) {
-        PAG_DISPATCH_ALL((hash_fwd_kernel<float, bf16_t, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const float *)tables, p, (bf16_t *)out, out_stride_m, out_stride_c, grouped, addend)))
-    } else if (table_dtype == PAG_F16 && out_dtype == PAG_F32) {
-        PAG_DISPATCH_ALL((hash_fwd_kernel<__half, float, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const __half *)tables, p, (float *)out, out_stride_m, out_stride_c, grouped, addend)))
-    } else {
-        PAG_DISPATCH_ALL((hash_fwd_kernel<__half, bf16_t, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const __half *)tables, p, (bf16_t *)out, out_stride_m, out_stride_c, grouped, addend)))
-    }
-    PAG_CHECK_ARG(launched, "pag_hash_encode_fwd: unsupported (n_feat=%d, n_levels=%d)", n_feat, n_levels);
-    PAG_CHECK_LAUNCH("pag_hash_encode_fwd");
-    return PAG_OK;
+// ---- the exported entry points (include/pagnerf_hip.h): fill, then call
+extern "C" int pag_hash_encode_fwd(const float *xyz, int64_t M, const void *tables, int table_dtype, int n_levels, int n_feat, int log2_T,
+                                   const float *resolutions_host, const float *feat_scale_host, void *out, int out_dtype, int64_t out_stride_m, int64_t out_stride_c,
+                                   int layout, int flags, void *stream) {
+    EncodeCall ec;
+    if (int rc = fill_hash(ec, "pag_hash_encode_fwd", xyz, M, n_levels, n_feat, log2_T, resolutions_host, feat_scale_host, flags)) return rc;
+    return encode_fwd<0>(ec, xyz, M, tables, table_dtype, out, out_dtype, out_stride_m, out_stride_c, layout, nullptr, stream);
+}
+extern "C" int pag_permuto_encode_fwd(const float *xyz, int64_t M, const void *tables, int table_dtype, int n_levels, int n_feat, uint32_t capacity,
+                                      const float *scale_factor_host, const float *shift_host, const float *feat_scale_host, void *out, int out_dtype,
+                                      int64_t out_stride_m, int64_t out_stride_c, int layout, int flags, void *stream) {
+    EncodeCall ec;
+    if (int rc = fill_permuto(ec, "pag_permuto_encode_fwd", xyz, M, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host, flags)) return rc;
+    return encode_fwd<1>(ec, xyz, M, tables, table_dtype, out, out_dtype, out_stride_m, out_stride_c, layout, nullptr, stream);
 }
 
-extern "C" int pag_hash_encode_fwd(const float *xyz, int64_t M, const void *tables, int table_dtype, int n_levels,
-                                   int n_feat, int log2_T, const float *resolutions_host, const float *feat_scale_host,
-                                   void *out, int out_dtype, int64_t out_stride_m, int64_t out_stride_c, int layout, int flags, void *stream) {
-    return hash_encode_fwd_impl(xyz, M, tables, table_dtype, n_levels, n_feat, log2_T, resolutions_host, feat_scale_host, out, out_dtype,
-                                out_stride_m, out_stride_c, layout, nullptr, flags, stream);
+extern "C" int pag_hash_encode_fwd_add(const float *xyz, int64_t M, const void *tables, int table_dtype, int n_levels, int n_feat, int log2_T,
+                                       const float *resolutions_host, const float *feat_scale_host, const void *addend, void *out, int flags, void *stream) {
+    EncodeCall ec;
+    if (int rc = fill_hash(ec, "pag_hash_encode_fwd_add", xyz, M, n_levels, n_feat, log2_T, resolutions_host, feat_scale_host, flags)) return rc;
+    return encode_fwd<0>(ec, xyz, M, tables, table_dtype, out, PAG_BF16, 0, 0, PAG_LAYOUT_XCD8, addend, stream);
 }
-
-extern "C" int pag_hash_encode_fwd_add(const float *xyz, int64_t M, const void *tables, int table_dtype, int n_levels,
-                                       int n_feat, int log2_T, const float *resolutions_host, const float *feat_scale_host,
-                                       const void *addend, void *out, int flags, void *stream) {
-    return hash_encode_fwd_impl(xyz, M, tables, table_dtype, n_levels, n_feat, log2_T, resolutions_host, feat_scale_host, out, PAG_BF16, 0,
-                                0, PAG_LAYOUT_XCD8, addend, flags, stream);
-}
-
-static int hash_encode_bwd_impl(bool overwrite, const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t g_stride_m,
-                                int64_t g_stride_c, int layout, int n_levels, int n_feat, int log2_T, const float *resolutions_host,
-                                const float *feat_scale_host, float *grad_tables, void *workspace,
-                                int64_t workspace_bytes, int flags, void *stream) {
-    int rc = check_common("pag_hash_encode_bwd", xyz, M, n_levels, n_feat);
-    if (rc) return rc;
-    PAG_CHECK_ARG(!overwrite || workspace, "pag_hash_encode_bwd_set: the overwriting form needs the binned algorithm (a workspace)");
-    PAG_CHECK_ARG(log2_T >= 1 && log2_T <= 30, "pag_hash_encode_bwd: log2_T %d not in [1,30]", log2_T);
-    PAG_CHECK_ARG(resolutions_host, "pag_hash_encode_bwd: resolutions_host is NULL");
-    PAG_CHECK_ARG(grad_dtype == PAG_F32 || grad_dtype == PAG_BF16, "pag_hash_encode_bwd: grad dtype must be F32 or BF16");
-    const int grouped = layout == PAG_LAYOUT_XCD8;
-    PAG_CHECK_ARG(!grouped || (workspace && grad_dtype == PAG_BF16 && ((n_levels + 7) / 8) * n_feat <= 8),
-                  "pag_hash_encode_bwd: XCD8 layout needs bf16 gradients, a workspace and ceil(L/8)*F <= 8");
-    if (M == 0) return PAG_OK;
-    PAG_CHECK_ARG(grad_out && grad_tables, "pag_hash_encode_bwd: NULL grad_out/grad_tables");
-    HashParams p;
-    p.L = n_levels;
-    p.log2T = log2_T;
-    p.has_scale = feat_scale_host != nullptr;
-    p.half_coords = (flags & PAG_ENC_HALF_COORDS) ? 1 : 0;
-    for (int l = 0; l < n_levels; ++l) p.res[l] = resolutions_host[l];
-    for (int c = 0; c < n_levels * n_feat; ++c) p.scale[c] = feat_scale_host ? feat_scale_host[c] : 1.0f;
-    const int lpx = (n_levels + 7) / 8;
-    hipStream_t st = (hipStream_t)stream;
-    if (workspace) {
-        PermutoParams unused{};
-        int r2 = launch_binned<0>(xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, grouped, n_levels, n_feat, (int64_t)1 << log2_T, p,
-                                  unused, grad_tables, workspace, workspace_bytes, st, "pag_hash_encode_bwd", overwrite);
-        if (r2) return r2;
-        PAG_CHECK_LAUNCH("pag_hash_encode_bwd");
-        return PAG_OK;
-    }
-    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
-    bool launched = false;
-    if (grad_dtype == PAG_F32) {
-        PAG_DISPATCH_ALL((hash_bwd_kernel<float, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const float *)grad_out, g_stride_m, g_stride_c, p, grad_tables)))
-    } else {
-        PAG_DISPATCH_ALL((hash_bwd_kernel<bf16_t, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const bf16_t *)grad_out, g_stride_m, g_stride_c, p, grad_tables)))
-    }
-    PAG_CHECK_ARG(launched, "pag_hash_encode_bwd: unsupported (n_feat=%d, n_levels=%d)", n_feat, n_levels);
-    PAG_CHECK_LAUNCH("pag_hash_encode_bwd");
-    return PAG_OK;
-}
-
-static int fill_permuto(PermutoParams &p, int n_levels, int n_feat, uint32_t capacity, const float *sf, const float *sh,
-                        const float *scale, int flags) {
-    p.L = n_levels;
-    p.half_coords = (flags & PAG_ENC_HALF_COORDS) ? 1 : 0;
-    p.capacity = capacity;
-    p.pow2mask = (capacity & (capacity - 1)) == 0 ? capacity - 1 : 0;
-    if (capacity == 1) p.pow2mask = 0;
-    p.has_scale = scale != nullptr;
-    for (int l = 0; l < n_levels; ++l)
-        for (int a = 0; a < 3; ++a) {
-            p.sf[l][a] = sf[l * 3 + a];
-            p.shift[l][a] = sh[l * 3 + a];
-        }
-    for (int c = 0; c < n_levels * n_feat; ++c) p.scale[c] = scale ? scale[c] : 1.0f;
-    return 0;
-}
-
-static int permuto_encode_fwd_impl(const float *xyz, int64_t M, const void *tables, int table_dtype, int n_levels,
-                                   int n_feat, uint32_t capacity, const float *scale_factor_host, const float *shift_host,
-                                   const float *feat_scale_host, void *out, int out_dtype, int64_t out_stride_m,
-                                   int64_t out_stride_c, int layout, const void *addend_p, int flags, void *stream) {
-    const bf16_t *addend = (const bf16_t *)addend_p;
-    PAG_CHECK_ARG(!addend || layout == PAG_LAYOUT_XCD8, "pag_permuto_encode_fwd_add: the addend needs the XCD8 layout");
-    int rc = check_common("pag_permuto_encode_fwd", xyz, M, n_levels, n_feat);
-    if (rc) return rc;
-    PAG_CHECK_ARG(capacity >= 1, "pag_permuto_encode_fwd: capacity is 0");
-    PAG_CHECK_ARG(scale_factor_host && shift_host, "pag_permuto_encode_fwd: NULL scale_factor/shift");
-    PAG_CHECK_ARG(table_dtype == PAG_F32 || table_dtype == PAG_F16, "pag_permuto_encode_fwd: table dtype must be F32 or F16");
-    PAG_CHECK_ARG(out_dtype == PAG_F32 || out_dtype == PAG_BF16, "pag_permuto_encode_fwd: out dtype must be F32 or BF16");
-    PAG_CHECK_ARG(layout == PAG_LAYOUT_STRIDED || (layout == PAG_LAYOUT_XCD8 && out_dtype == PAG_BF16 && ((n_levels + 7) / 8) * n_feat <= 8),
-                  "pag_permuto_encode_fwd: XCD8 layout needs bf16 output and ceil(L/8)*F <= 8");
-    const int grouped = layout == PAG_LAYOUT_XCD8;
-    if (M == 0) return PAG_OK;
-    PAG_CHECK_ARG(tables && out, "pag_permuto_encode_fwd: NULL tables/out");
-    PermutoParams p;
-    fill_permuto(p, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host, flags);
-    const int lpx = (n_levels + 7) / 8;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
-    bool launched = false;
-#define PFWD(TT, OT)                                                                                                                 \
-    PAG_DISPATCH_ALL((permuto_fwd_kernel<TT, OT, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const TT *)tables, p, (OT *)out, out_stride_m, \
-                                                                                   out_stride_c, grouped)))
-#define PFWD_ADD(TT, OT)                                                                                                             \
-    PAG_DISPATCH_ALL((permuto_fwd_add_kernel<TT, OT, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const TT *)tables, p, (OT *)out, out_stride_m, \
-                                                                                       out_stride_c, grouped, addend)))
-    if (table_dtype == PAG_F32 && out_dtype == PAG_F32) {
-        PFWD(float, float)
-    } else if (table_dtype == PAG_F32 && out_dtype == PAG_BF16) {
-        if (addend) { PFWD_ADD(float, bf16_t) } else { PFWD(float, bf16_t) }
-    } else if (table_dtype == PAG_F16 && out_dtype == PAG_F32) {
-        PFWD(__half, float)
-    } else {
-        if (addend) { PFWD_ADD(__half, bf16_t) } else { PFWD(__half, bf16_t) }
-    }
-#undef PFWD
-#undef PFWD_ADD
-    PAG_CHECK_ARG(launched, "pag_permuto_encode_fwd: unsupported (n_feat=%d, n_levels=%d)", n_feat, n_levels);
-    PAG_CHECK_LAUNCH("pag_permuto_encode_fwd");
-    return PAG_OK;
-}
-
-extern "C" int pag_permuto_encode_fwd(const float *xyz, int64_t M, const void *tables, int table_dtype, int n_levels,
-                                      int n_feat, uint32_t capacity, const float *scale_factor_host, const float *shift_host,
-                                      const float *feat_scale_host, void *out, int out_dtype, int64_t out_stride_m,
-                                      int64_t out_stride_c, int layout, int flags, void *stream) {
-    return permuto_encode_fwd_impl(xyz, M, tables, table_dtype, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host,
-                                   out, out_dtype, out_stride_m, out_stride_c, layout, nullptr, flags, stream);
-}
-
-extern "C" int pag_permuto_encode_fwd_add(const float *xyz, int64_t M, const void *tables, int table_dtype, int n_levels,
-                                          int n_feat, uint32_t capacity, const float *scale_factor_host, const float *shift_host,
-                                          const float *feat_scale_host, const void *addend, void *out, int flags, void *stream) {
-    return permuto_encode_fwd_impl(xyz, M, tables, table_dtype, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host,
-                                   out, PAG_BF16, 0, 0, PAG_LAYOUT_XCD8, addend, flags, stream);
-}
-
-static int permuto_encode_bwd_impl(bool overwrite, const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t g_stride_m,
-                                   int64_t g_stride_c, int layout, int n_levels, int n_feat, uint32_t capacity,
-                                   const float *scale_factor_host, const float *shift_host, const float *feat_scale_host,
-                                   float *grad_tables, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
-    int rc = check_common("pag_permuto_encode_bwd", xyz, M, n_levels, n_feat);
-    if (rc) return rc;
-    PAG_CHECK_ARG(!overwrite || workspace, "pag_permuto_encode_bwd_set: the overwriting form needs the binned algorithm (a workspace)");
-    PAG_CHECK_ARG(capacity >= 1, "pag_permuto_encode_bwd: capacity is 0");
-    PAG_CHECK_ARG(scale_factor_host && shift_host, "pag_permuto_encode_bwd: NULL scale_factor/shift");
-    PAG_CHECK_ARG(grad_dtype == PAG_F32 || grad_dtype == PAG_BF16, "pag_permuto_encode_bwd: grad dtype must be F32 or BF16");
-    const int grouped = layout == PAG_LAYOUT_XCD8;
-    PAG_CHECK_ARG(!grouped || (workspace && grad_dtype == PAG_BF16 && ((n_levels + 7) / 8) * n_feat <= 8),
-                  "pag_permuto_encode_bwd: XCD8 layout needs bf16 gradients, a workspace and ceil(L/8)*F <= 8");
-    if (M == 0) return PAG_OK;
-    PAG_CHECK_ARG(grad_out && grad_tables, "pag_permuto_encode_bwd: NULL grad_out/grad_tables");
-    PermutoParams p;
-    fill_permuto(p, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host, flags);
-    const int lpx = (n_levels + 7) / 8;
-    hipStream_t st = (hipStream_t)stream;
-    if (workspace) {
-        HashParams unused{};
-        int r2 = launch_binned<1>(xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, grouped, n_levels, n_feat, (int64_t)capacity, unused,
-                                  p, grad_tables, workspace, workspace_bytes, st, "pag_permuto_encode_bwd", overwrite);
-        if (r2) return r2;
-        PAG_CHECK_LAUNCH("pag_permuto_encode_bwd");
-        return PAG_OK;
-    }
-    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
-    bool launched = false;
-    if (grad_dtype == PAG_F32) {
-        PAG_DISPATCH_ALL((permuto_bwd_kernel<float, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const float *)grad_out, g_stride_m, g_stride_c, p, grad_tables)))
-    } else {
-        PAG_DISPATCH_ALL((permuto_bwd_kernel<bf16_t, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const bf16_t *)grad_out, g_stride_m, g_stride_c, p, grad_tables)))
-    }
-    PAG_CHECK_ARG(launched, "pag_permuto_encode_bwd: unsupported (n_feat=%d, n_levels=%d)", n_feat, n_levels);
-    PAG_CHECK_LAUNCH("pag_permuto_encode_bwd");
-    return PAG_OK;
-}
-
-struct RaysArgs {            // per-ray reduction of the position gradient (launch_xyz_grad): NULL ridx = the per-sample form
-    const int32_t *ridx = nullptr;
-    const float *depths = nullptr;
-    const int64_t *pack_start = nullptr;
-    int64_t N = 0;
-};
-static int64_t rays_slot_rows(int64_t M, int64_t N) { return (M + 63) / 64 + N; }
-
-template <int KIND>
-static int launch_xyz_grad(const char *name, const float *xyz, int64_t M, const void *tables, int table_dtype, const void *grad_out,
-                           int grad_dtype, int64_t sm, int64_t sc, int layout, int n_levels, int n_feat, const HashParams &hp,
-                           const PermutoParams &pp, float *d_xyz, void *workspace, int64_t workspace_bytes, hipStream_t st, const RaysArgs &ra = RaysArgs()) {
-    PAG_CHECK_ARG(table_dtype == PAG_F32 || table_dtype == PAG_F16, "%s: table dtype must be F32 or F16", name);
-    PAG_CHECK_ARG(grad_dtype == PAG_F32 || grad_dtype == PAG_BF16, "%s: grad dtype must be F32 or BF16", name);
-    const int grouped = layout == PAG_LAYOUT_XCD8;
-    PAG_CHECK_ARG(!grouped || (grad_dtype == PAG_BF16 && ((n_levels + 7) / 8) * n_feat <= 8),
-                  "%s: XCD8 layout needs bf16 gradients and ceil(L/8)*F <= 8", name);
-    if (M == 0) return PAG_OK;
-    PAG_CHECK_ARG(tables && grad_out && d_xyz && workspace, "%s: NULL tables/grad_out/d_xyz/workspace", name);
-    const int groups = n_levels < 8 ? n_levels : 8;
-    const int lpx = (n_levels + 7) / 8;
-    dim3 grid(encode_grid(M)), block(ENC_FWD_THREADS);
-    bool launched = false;
-    if (ra.ridx) {       // reduced per ray inside the pass: d_xyz = out f32 [N,6] (d origin | d dir)
-        PAG_CHECK_ARG(ra.depths && ra.pack_start && ra.N >= 1, "%s: per-ray form needs ridx, depths, pack_start and N >= 1", name);
-        const int64_t rows_ = rays_slot_rows(M, ra.N);
-        PAG_CHECK_ARG(workspace_bytes >= 8 * rows_ * 6 * (int64_t)sizeof(float), "%s: workspace smaller than 8 * (ceil(M / 64) + N) * 6 floats", name);
-        float *slots = (float *)workspace;
-#define PAG_XR(TT, GT) PAG_DISPATCH_ALL((xyz_grad_rays_kernel<KIND, TT, GT, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const TT *)tables, (const GT *)grad_out, sm, sc, grouped, hp, pp, ra.ridx, ra.depths, slots, rows_)))
-        if (table_dtype == PAG_F32 && grad_dtype == PAG_F32) { PAG_XR(float, float) }
-        else if (table_dtype == PAG_F32 && grad_dtype == PAG_BF16) { PAG_XR(float, bf16_t) }
-        else if (table_dtype == PAG_F16 && grad_dtype == PAG_F32) { PAG_XR(__half, float) }
-        else { PAG_XR(__half, bf16_t) }
-#undef PAG_XR
-        PAG_CHECK_ARG(launched, "%s: unsupported (n_feat=%d, n_levels=%d)", name, n_feat, n_levels);
-        ray_slots_sum_kernel<<<dim3((unsigned)((ra.N + 3) / 4)), dim3(256), 0, st>>>(ra.pack_start, ra.N, slots, rows_, groups, d_xyz);
-        PAG_CHECK_LAUNCH(name);
-        return PAG_OK;
-    }
-    PAG_CHECK_ARG(workspace_bytes >= (int64_t)8 * M * 3 * (int64_t)sizeof(float), "%s: workspace smaller than 8*M*3 floats", name);
-    float *part = (float *)workspace;
-    if (table_dtype == PAG_F32 && grad_dtype == PAG_F32) {
-        PAG_DISPATCH_ALL((xyz_grad_kernel<KIND, float, float, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const float *)tables, (const float *)grad_out, sm, sc, grouped, hp, pp, part)))
-    } else if (table_dtype == PAG_F32 && grad_dtype == PAG_BF16) {
-        PAG_DISPATCH_ALL((xyz_grad_kernel<KIND, float, bf16_t, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const float *)tables, (const bf16_t *)grad_out, sm, sc, grouped, hp, pp, part)))
-    } else if (table_dtype == PAG_F16 && grad_dtype == PAG_F32) {
-        PAG_DISPATCH_ALL((xyz_grad_kernel<KIND, __half, float, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const __half *)tables, (const float *)grad_out, sm, sc, grouped, hp, pp, part)))
-    } else {
-        PAG_DISPATCH_ALL((xyz_grad_kernel<KIND, __half, bf16_t, F, LPX><<<grid, block, 0, st>>>(xyz, M, (const __half *)tables, (const bf16_t *)grad_out, sm, sc, grouped, hp, pp, part)))
-    }
-    PAG_CHECK_ARG(launched, "%s: unsupported (n_feat=%d, n_levels=%d)", name, n_feat, n_levels);
-    const int64_t n = M * 3;
-    xyz_grad_sum_kernel<<<dim3((unsigned)((((n % 4 == 0) ? n / 4 : n) + 255) / 256)), dim3(256), 0, st>>>(part, n, groups, d_xyz);
-    PAG_CHECK_LAUNCH(name);
-    return PAG_OK;
-}
-
-extern "C" int pag_hash_encode_bwd_xyz(const float *xyz, int64_t M, const void *tables, int table_dtype, const void *grad_out,
-                                       int grad_dtype, int64_t g_stride_m, int64_t g_stride_c, int layout, int n_levels, int n_feat,
-                                       int log2_T, const float *resolutions_host, const float *feat_scale_host, float *d_xyz,
-                                       void *workspace, int64_t workspace_bytes, int flags, void *stream) {
-    int rc = check_common("pag_hash_encode_bwd_xyz", xyz, M, n_levels, n_feat);
-    if (rc) return rc;
-    PAG_CHECK_ARG(log2_T >= 1 && log2_T <= 30, "pag_hash_encode_bwd_xyz: log2_T %d not in [1,30]", log2_T);
-    PAG_CHECK_ARG(resolutions_host, "pag_hash_encode_bwd_xyz: resolutions_host is NULL");
-    HashParams p;
-    p.L = n_levels;
-    p.log2T = log2_T;
-    p.has_scale = feat_scale_host != nullptr;
-    p.half_coords = (flags & PAG_ENC_HALF_COORDS) ? 1 : 0;
-    for (int l = 0; l < n_levels; ++l) p.res[l] = resolutions_host[l];
-    for (int c = 0; c < n_levels * n_feat; ++c) p.scale[c] = feat_scale_host ? feat_scale_host[c] : 1.0f;
-    PermutoParams unused{};
-    return launch_xyz_grad<0>("pag_hash_encode_bwd_xyz", xyz, M, tables, table_dtype, grad_out, grad_dtype, g_stride_m, g_stride_c, layout,
-                              n_levels, n_feat, p, unused, d_xyz, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-extern "C" int pag_permuto_encode_bwd_xyz(const float *xyz, int64_t M, const void *tables, int table_dtype, const void *grad_out,
-                                          int grad_dtype, int64_t g_stride_m, int64_t g_stride_c, int layout, int n_levels,
-                                          int n_feat, uint32_t capacity, const float *scale_factor_host, const float *shift_host,
-                                          const float *feat_scale_host, float *d_xyz, void *workspace, int64_t workspace_bytes,
+extern "C" int pag_permuto_encode_fwd_add(const float *xyz, int64_t M, const void *tables, int table_dtype, int n_levels, int n_feat, uint32_t capacity,
+                                          const float *scale_factor_host, const float *shift_host, const float *feat_scale_host, const void *addend, void *out,
                                           int flags, void *stream) {
-    int rc = check_common("pag_permuto_encode_bwd_xyz", xyz, M, n_levels, n_feat);
-    if (rc) return rc;
-    PAG_CHECK_ARG(capacity >= 1, "pag_permuto_encode_bwd_xyz: capacity is 0");
-    PAG_CHECK_ARG(scale_factor_host && shift_host, "pag_permuto_encode_bwd_xyz: NULL scale_factor/shift");
-    PermutoParams p;
-    fill_permuto(p, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host, flags);
-    HashParams unused{};
-    return launch_xyz_grad<1>("pag_permuto_encode_bwd_xyz", xyz, M, tables, table_dtype, grad_out, grad_dtype, g_stride_m, g_stride_c,
-                              layout, n_levels, n_feat, unused, p, d_xyz, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-// Position gradient reduced per ray (d origin | d dir, f32 [N,6]) in the gather pass itself: see xyz_grad_rays_kernel.
-extern "C" int64_t pag_encode_bwd_rays_workspace_bytes(int64_t M, int64_t N) {
-    return (M > 0 && N > 0) ? 8 * rays_slot_rows(M, N) * 6 * (int64_t)sizeof(float) : 0;
-}
-static int rays_check(const char *name, const int32_t *ridx, const float *depths, const int64_t *pack_start, int64_t N, int64_t M) {
-    PAG_CHECK_ARG(N >= 1, "%s: N %lld < 1", name, (long long)N);
-    PAG_CHECK_ARG(M == 0 || (ridx && depths && pack_start), "%s: NULL ridx / depths / pack_start", name);
-    return PAG_OK;
-}
-extern "C" int pag_hash_encode_bwd_rays(const float *xyz, int64_t M, const void *tables, int table_dtype, const void *grad_out, int grad_dtype,
-                                        int64_t g_stride_m, int64_t g_stride_c, int layout, int n_levels, int n_feat, int log2_T,
-                                        const float *resolutions_host, const float *feat_scale_host, const int32_t *ridx, const float *depths,
-                                        const int64_t *pack_start, int64_t N, float *out, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
-    int rc = check_common("pag_hash_encode_bwd_rays", xyz, M, n_levels, n_feat);
-    if (rc) return rc;
-    rc = rays_check("pag_hash_encode_bwd_rays", ridx, depths, pack_start, N, M);
-    if (rc) return rc;
-    PAG_CHECK_ARG(log2_T >= 1 && log2_T <= 30, "pag_hash_encode_bwd_rays: log2_T %d not in [1,30]", log2_T);
-    PAG_CHECK_ARG(resolutions_host, "pag_hash_encode_bwd_rays: resolutions_host is NULL");
-    HashParams p;
-    p.L = n_levels;
-    p.log2T = log2_T;
-    p.has_scale = feat_scale_host != nullptr;
-    p.half_coords = (flags & PAG_ENC_HALF_COORDS) ? 1 : 0;
-    for (int l = 0; l < n_levels; ++l) p.res[l] = resolutions_host[l];
-    for (int c = 0; c < n_levels * n_feat; ++c) p.scale[c] = feat_scale_host ? feat_scale_host[c] : 1.0f;
-    PermutoParams unused{};
-    RaysArgs ra{ridx, depths, pack_start, N};
-    if (M == 0) return hipMemsetAsync(out, 0, (size_t)N * 6 * sizeof(float), (hipStream_t)stream) == hipSuccess ? PAG_OK : PAG_ERR_LAUNCH;
-    return launch_xyz_grad<0>("pag_hash_encode_bwd_rays", xyz, M, tables, table_dtype, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, n_levels, n_feat,
-                              p, unused, out, workspace, workspace_bytes, (hipStream_t)stream, ra);
-}
-extern "C" int pag_permuto_encode_bwd_rays(const float *xyz, int64_t M, const void *tables, int table_dtype, const void *grad_out, int grad_dtype,
-                                           int64_t g_stride_m, int64_t g_stride_c, int layout, int n_levels, int n_feat, uint32_t capacity,
-                                           const float *scale_factor_host, const float *shift_host, const float *feat_scale_host, const int32_t *ridx,
-                                           const float *depths, const int64_t *pack_start, int64_t N, float *out, void *workspace, int64_t workspace_bytes,
-                                           int flags, void *stream) {
-    int rc = check_common("pag_permuto_encode_bwd_rays", xyz, M, n_levels, n_feat);
-    if (rc) return rc;
-    rc = rays_check("pag_permuto_encode_bwd_rays", ridx, depths, pack_start, N, M);
-    if (rc) return rc;
-    PAG_CHECK_ARG(capacity >= 1 && scale_factor_host && shift_host, "pag_permuto_encode_bwd_rays: capacity 0 or NULL scale_factor / shift");
-    PermutoParams p;
-    fill_permuto(p, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host, flags);
-    HashParams unused{};
-    RaysArgs ra{ridx, depths, pack_start, N};
-    if (M == 0) return hipMemsetAsync(out, 0, (size_t)N * 6 * sizeof(float), (hipStream_t)stream) == hipSuccess ? PAG_OK : PAG_ERR_LAUNCH;
-    return launch_xyz_grad<1>("pag_permuto_encode_bwd_rays", xyz, M, tables, table_dtype, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, n_levels, n_feat,
-                              unused, p, out, workspace, workspace_bytes, (hipStream_t)stream, ra);
+    EncodeCall ec;
+    if (int rc = fill_permuto(ec, "pag_permuto_encode_fwd_add", xyz, M, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host, flags)) return rc;
+    return encode_fwd<1>(ec, xyz, M, tables, table_dtype, out, PAG_BF16, 0, 0, PAG_LAYOUT_XCD8, addend, stream);
 }
 
 extern "C" int64_t pag_encode_bwd_workspace_bytes(int64_t M, int n_levels, int n_feat, int n_vertices, int64_t rows_per_level) {
@@ -1469,31 +1337,69 @@ extern "C" int64_t pag_encode_bwd_workspace_bytes(int64_t M, int n_levels, int n
     return bin_plan(M, n_levels, n_feat, n_vertices, rows_per_level).total;
 }
 
-// Exported forms: *_bwd ACCUMULATES into grad_tables (caller zeroes it); *_bwd_set OVERWRITES every row (binned algorithm only) -
-// no zero fill of the 50 MB table before the call and no read of it in the reduce pass.
-extern "C" int pag_hash_encode_bwd(const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t g_stride_m,
-                                   int64_t g_stride_c, int layout, int n_levels, int n_feat, int log2_T, const float *resolutions_host,
-                                   const float *feat_scale_host, float *grad_tables, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
-    return hash_encode_bwd_impl(false, xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, n_levels, n_feat, log2_T, resolutions_host,
-                                feat_scale_host, grad_tables, workspace, workspace_bytes, flags, stream);
+extern "C" int pag_hash_encode_bwd(const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t g_stride_m, int64_t g_stride_c, int layout, int n_levels,
+                                   int n_feat, int log2_T, const float *resolutions_host, const float *feat_scale_host, float *grad_tables, void *workspace,
+                                   int64_t workspace_bytes, int flags, void *stream) {
+    EncodeCall ec;
+    if (int rc = fill_hash(ec, "pag_hash_encode_bwd", xyz, M, n_levels, n_feat, log2_T, resolutions_host, feat_scale_host, flags)) return rc;
+    return encode_bwd<0>(ec, false, xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, grad_tables, workspace, workspace_bytes, stream);
 }
-extern "C" int pag_hash_encode_bwd_set(const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t g_stride_m,
+extern "C" int pag_hash_encode_bwd_set(const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t g_stride_m, int64_t g_stride_c, int layout,
+                                       int n_levels, int n_feat, int log2_T, const float *resolutions_host, const float *feat_scale_host, float *grad_tables,
+                                       void *workspace, int64_t workspace_bytes, int flags, void *stream) {
+    EncodeCall ec;
+    if (int rc = fill_hash(ec, "pag_hash_encode_bwd_set", xyz, M, n_levels, n_feat, log2_T, resolutions_host, feat_scale_host, flags)) return rc;
+    return encode_bwd<0>(ec, true, xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, grad_tables, workspace, workspace_bytes, stream);
+}
+extern "C" int pag_permuto_encode_bwd(const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t g_stride_m, int64_t g_stride_c, int layout,
+                                      int n_levels, int n_feat, uint32_t capacity, const float *scale_factor_host, const float *shift_host,
+                                      const float *feat_scale_host, float *grad_tables, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
+    EncodeCall ec;
+    if (int rc = fill_permuto(ec, "pag_permuto_encode_bwd", xyz, M, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host, flags)) return rc;
+    return encode_bwd<1>(ec, false, xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, grad_tables, workspace, workspace_bytes, stream);
+}
+extern "C" int pag_permuto_encode_bwd_set(const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t g_stride_m, int64_t g_stride_c, int layout,
+                                          int n_levels, int n_feat, uint32_t capacity, const float *scale_factor_host, const float *shift_host,
+                                          const float *feat_scale_host, float *grad_tables, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
+    EncodeCall ec;
+    if (int rc = fill_permuto(ec, "pag_permuto_encode_bwd_set", xyz, M, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host, flags)) return rc;
+    return encode_bwd<1>(ec, true, xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, grad_tables, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pag_hash_encode_bwd_xyz(const float *xyz, int64_t M, const void *tables, int table_dtype, const void *grad_out, int grad_dtype, int64_t g_stride_m,
                                        int64_t g_stride_c, int layout, int n_levels, int n_feat, int log2_T, const float *resolutions_host,
-                                       const float *feat_scale_host, float *grad_tables, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
-    return hash_encode_bwd_impl(true, xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, n_levels, n_feat, log2_T, resolutions_host,
-                                feat_scale_host, grad_tables, workspace, workspace_bytes, flags, stream);
+                                       const float *feat_scale_host, float *d_xyz, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
+    EncodeCall ec;
+    if (int rc = fill_hash(ec, "pag_hash_encode_bwd_xyz", xyz, M, n_levels, n_feat, log2_T, resolutions_host, feat_scale_host, flags)) return rc;
+    return encode_bwd_xyz<0>(ec, xyz, M, tables, table_dtype, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, d_xyz, workspace, workspace_bytes, stream);
 }
-extern "C" int pag_permuto_encode_bwd(const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t g_stride_m,
-                                      int64_t g_stride_c, int layout, int n_levels, int n_feat, uint32_t capacity,
-                                      const float *scale_factor_host, const float *shift_host, const float *feat_scale_host,
-                                      float *grad_tables, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
-    return permuto_encode_bwd_impl(false, xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, n_levels, n_feat, capacity, scale_factor_host,
-                                   shift_host, feat_scale_host, grad_tables, workspace, workspace_bytes, flags, stream);
+extern "C" int pag_permuto_encode_bwd_xyz(const float *xyz, int64_t M, const void *tables, int table_dtype, const void *grad_out, int grad_dtype, int64_t g_stride_m,
+                                          int64_t g_stride_c, int layout, int n_levels, int n_feat, uint32_t capacity, const float *scale_factor_host,
+                                          const float *shift_host, const float *feat_scale_host, float *d_xyz, void *workspace, int64_t workspace_bytes, int flags,
+                                          void *stream) {
+    EncodeCall ec;
+    if (int rc = fill_permuto(ec, "pag_permuto_encode_bwd_xyz", xyz, M, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host, flags)) return rc;
+    return encode_bwd_xyz<1>(ec, xyz, M, tables, table_dtype, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, d_xyz, workspace, workspace_bytes, stream);
 }
-extern "C" int pag_permuto_encode_bwd_set(const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t g_stride_m,
-                                          int64_t g_stride_c, int layout, int n_levels, int n_feat, uint32_t capacity,
-                                          const float *scale_factor_host, const float *shift_host, const float *feat_scale_host,
-                                          float *grad_tables, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
-    return permuto_encode_bwd_impl(true, xyz, M, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, n_levels, n_feat, capacity, scale_factor_host,
-                                   shift_host, feat_scale_host, grad_tables, workspace, workspace_bytes, flags, stream);
+
+extern "C" int64_t pag_encode_bwd_rays_workspace_bytes(int64_t M, int64_t N) {
+    return (M > 0 && N > 0) ? 8 * rays_slot_rows(M, N) * 6 * (int64_t)sizeof(float) : 0;
+}
+extern "C" int pag_hash_encode_bwd_rays(const float *xyz, int64_t M, const void *tables, int table_dtype, const void *grad_out, int grad_dtype, int64_t g_stride_m,
+                                        int64_t g_stride_c, int layout, int n_levels, int n_feat, int log2_T, const float *resolutions_host,
+                                        const float *feat_scale_host, const int32_t *ridx, const float *depths, const int64_t *pack_start, int64_t N, float *out,
+                                        void *workspace, int64_t workspace_bytes, int flags, void *stream) {
+    EncodeCall ec;
+    if (int rc = fill_hash(ec, "pag_hash_encode_bwd_rays", xyz, M, n_levels, n_feat, log2_T, resolutions_host, feat_scale_host, flags)) return rc;
+    const RaysArgs rays{ridx, depths, pack_start, N};
+    return encode_bwd_xyz<0>(ec, xyz, M, tables, table_dtype, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, out, workspace, workspace_bytes, stream, &rays);
+}
+extern "C" int pag_permuto_encode_bwd_rays(const float *xyz, int64_t M, const void *tables, int table_dtype, const void *grad_out, int grad_dtype, int64_t g_stride_m,
+                                           int64_t g_stride_c, int layout, int n_levels, int n_feat, uint32_t capacity, const float *scale_factor_host,
+                                           const float *shift_host, const float *feat_scale_host, const int32_t *ridx, const float *depths, const int64_t *pack_start,
+                                           int64_t N, float *out, void *workspace, int64_t workspace_bytes, int flags, void *stream) {
+    EncodeCall ec;
+    if (int rc = fill_permuto(ec, "pag_permuto_encode_bwd_rays", xyz, M, n_levels, n_feat, capacity, scale_factor_host, shift_host, feat_scale_host, flags)) return rc;
+    const RaysArgs rays{ridx, depths, pack_start, N};
+    return encode_bwd_xyz<1>(ec, xyz, M, tables, table_dtype, grad_out, grad_dtype, g_stride_m, g_stride_c, layout, out, workspace, workspace_bytes, stream, &rays);
 }

@@ -76,15 +76,21 @@ class _EncodeSpec:
 
     def _bind(self):
         kw = self.kw
+        self.flags = L.ENC_HALF_COORDS if kw["half_coords"] else 0
         if self.kind == "hash":
             self.log2_T = kw["log2_T"]
             self.res = L.host_floats(kw["resolutions"])
-            self.flags = L.ENC_HALF_COORDS if kw["half_coords"] else 0
+            self.vertices, self._mid = 8, (self.log2_T, self.res)
         else:
             self.capacity = kw["capacity"]
             self.sf = L.host_floats(kw["scale_factor"])
             self.shift = L.host_floats(kw["shift"])
-            self.flags = L.ENC_HALF_COORDS if kw["half_coords"] else 0
+            self.vertices, self._mid = 4, (self.capacity, self.sf, self.shift)
+
+    def mid(self, feat_scale):
+        """The kind-specific middle of every pag_<kind>_encode_* argument list (_lib._ENC_MID): hash log2_T, resolutions, feat_scale; permuto capacity,
+        scale_factor, shift, feat_scale."""
+        return self._mid + (L.host_floats(feat_scale),)
 
     def __getstate__(self):
         return dict(kind=self.kind, L=self.L, F=self.F, kw=self.kw)
@@ -123,91 +129,93 @@ def _layout_args(t):
     return t.stride(0), t.stride(1), L.LAYOUT_STRIDED
 
 
+def _encode_call(op, spec, feat_scale, flags, head, tail):
+    """pag_<kind>_encode_<op>(*head, the spec's middle, *tail, flags, stream); flags None = as the spec says."""
+    _call("pag_%s_encode_%s" % (spec.kind, op), *head, *spec.mid(feat_scale), *tail, spec.flags if flags is None else flags, L.stream())
+
+
 def _encode_fwd(spec, xyz, tables, feat_scale, out, addend=None, flags=None):
-    M = xyz.shape[0]
-    flags = spec.flags if flags is None else flags
-    fs = L.host_floats(feat_scale)
+    head = (L.ptr(xyz), xyz.shape[0], L.ptr(tables), L.dtype_code(tables), spec.L, spec.F)
     sm, sc, lay = _layout_args(out)
     if addend is not None:                    # out = bf16(addend + bf16(features)), XCD8 layout only
         assert lay == L.LAYOUT_XCD8 and addend.shape == out.shape and addend.dtype == torch.bfloat16 and addend.is_contiguous()
-        if spec.kind == "hash":
-            _call("pag_hash_encode_fwd_add", L.ptr(xyz), M, L.ptr(tables), L.dtype_code(tables), spec.L, spec.F, spec.log2_T, spec.res, fs,
-                  L.ptr(addend), out.data_ptr(), flags, L.stream())
-        else:
-            _call("pag_permuto_encode_fwd_add", L.ptr(xyz), M, L.ptr(tables), L.dtype_code(tables), spec.L, spec.F, spec.capacity, spec.sf,
-                  spec.shift, fs, L.ptr(addend), out.data_ptr(), flags, L.stream())
-        return
-    if spec.kind == "hash":
-        _call("pag_hash_encode_fwd", L.ptr(xyz), M, L.ptr(tables), L.dtype_code(tables), spec.L, spec.F, spec.log2_T,
-              spec.res, fs, out.data_ptr(), L.dtype_code(out), sm, sc, lay, flags, L.stream())
+        _encode_call("fwd_add", spec, feat_scale, flags, head, (L.ptr(addend), out.data_ptr()))
     else:
-        _call("pag_permuto_encode_fwd", L.ptr(xyz), M, L.ptr(tables), L.dtype_code(tables), spec.L, spec.F, spec.capacity,
-              spec.sf, spec.shift, fs, out.data_ptr(), L.dtype_code(out), sm, sc, lay, flags, L.stream())
+        _encode_call("fwd", spec, feat_scale, flags, head, (out.data_ptr(), L.dtype_code(out), sm, sc, lay))
 
-
-_DTYPE_CODE = {torch.float32: L.F32, torch.float16: L.F16, torch.bfloat16: L.BF16}
 
 BWD_ALGO = "binned"     # "binned": atomic-free two-pass scatter (default); "atomic": per-vertex fp32 global atomics
 
 
 def _encode_bwd(spec, xyz, grad_out, feat_scale, grad_tables, overwrite=False, flags=None):
     """overwrite: grad_tables is uninitialised memory that the binned reduce pass fills completely (pag_*_encode_bwd_set)."""
-    lib = L.load()
-    flags = spec.flags if flags is None else flags
     M = xyz.shape[0]
-    fs = L.host_floats(feat_scale)
     sm, sc, lay = _layout_args(grad_out)
     ws, ws_ptr, ws_bytes = None, None, 0
     if BWD_ALGO == "binned" or lay == L.LAYOUT_XCD8:
-        ws_bytes = lib.pag_encode_bwd_workspace_bytes(M, spec.L, spec.F, 8 if spec.kind == "hash" else 4, spec.rows())
+        ws_bytes = L.load().pag_encode_bwd_workspace_bytes(M, spec.L, spec.F, spec.vertices, spec.rows())
         ws = torch.empty(ws_bytes, device=xyz.device, dtype=torch.uint8)
         ws_ptr = ws.data_ptr()
     assert not overwrite or ws_ptr is not None
-    suffix = "_set" if overwrite else ""
-    if spec.kind == "hash":
-        _call("pag_hash_encode_bwd" + suffix, L.ptr(xyz), M, grad_out.data_ptr(), L.dtype_code(grad_out), sm, sc, lay, spec.L, spec.F,
-              spec.log2_T, spec.res, fs, L.ptr(grad_tables), ws_ptr, ws_bytes, flags, L.stream())
-    else:
-        _call("pag_permuto_encode_bwd" + suffix, L.ptr(xyz), M, grad_out.data_ptr(), L.dtype_code(grad_out), sm, sc, lay, spec.L, spec.F,
-              spec.capacity, spec.sf, spec.shift, fs, L.ptr(grad_tables), ws_ptr, ws_bytes, flags, L.stream())
+    _encode_call("bwd_set" if overwrite else "bwd", spec, feat_scale, flags,
+                 (L.ptr(xyz), M, grad_out.data_ptr(), L.dtype_code(grad_out), sm, sc, lay, spec.L, spec.F), (L.ptr(grad_tables), ws_ptr, ws_bytes))
 
 
-def _encode_bwd_xyz(spec, xyz, tables, grad_out, feat_scale, flags=None):
-    """d loss / d xyz f32 [M,3] (pose optimisation: ba_pipeline.py:85-92)."""
+def _encode_bwd_xyz(spec, xyz, tables, grad_out, feat_scale, flags=None, rays=None):
+    """d loss / d xyz f32 [M,3] (pose optimisation: ba_pipeline.py:85-92) or, with rays = (ridx, depths, pack_start, N), reduced per ray inside the
+    gather pass: f32 [N,6] (d origin | d dir)."""
     M = xyz.shape[0]
-    flags = spec.flags if flags is None else flags
-    fs = L.host_floats(feat_scale)
     sm, sc, lay = _layout_args(grad_out)
-    d_xyz, ws = torch.empty(M, 3, device=xyz.device), torch.empty(8 * M * 3, device=xyz.device)
-    if spec.kind == "hash":
-        _call("pag_hash_encode_bwd_xyz", L.ptr(xyz), M, L.ptr(tables), L.dtype_code(tables), grad_out.data_ptr(), L.dtype_code(grad_out),
-              sm, sc, lay, spec.L, spec.F, spec.log2_T, spec.res, fs, L.ptr(d_xyz), L.ptr(ws), ws.numel() * 4, flags, L.stream())
+    head = (L.ptr(xyz), M, L.ptr(tables), L.dtype_code(tables), grad_out.data_ptr(), L.dtype_code(grad_out), sm, sc, lay, spec.L, spec.F)
+    if rays is None:
+        out, ws = torch.empty(M, 3, device=xyz.device), torch.empty(8 * M * 3, device=xyz.device)
+        _encode_call("bwd_xyz", spec, feat_scale, flags, head, (L.ptr(out), L.ptr(ws), ws.numel() * 4))
     else:
-        _call("pag_permuto_encode_bwd_xyz", L.ptr(xyz), M, L.ptr(tables), L.dtype_code(tables), grad_out.data_ptr(),
-              L.dtype_code(grad_out), sm, sc, lay, spec.L, spec.F, spec.capacity, spec.sf, spec.shift, fs, L.ptr(d_xyz), L.ptr(ws),
-              ws.numel() * 4, flags, L.stream())
-    return d_xyz
+        ridx, depths, pack_start, N = rays
+        out = torch.empty(N, 6, device=xyz.device)
+        ws_bytes = L.load().pag_encode_bwd_rays_workspace_bytes(max(M, 1), N)
+        ws = torch.empty(ws_bytes // 4, device=xyz.device)
+        _encode_call("bwd_rays", spec, feat_scale, flags, head, (L.ptr(ridx), L.ptr(depths), L.ptr(pack_start), N, L.ptr(out), L.ptr(ws), ws_bytes))
+    return out
+
+
+def _encode_forward(xyz, tables, spec, feat_scale, out_dtype, feature_major, addend, flags):
+    """What the forward of both autograd nodes does: shape check, output allocation, launch -> (xyz as f32 contiguous, the tables contiguous, features)."""
+    xyz = xyz.detach().contiguous().float()
+    M, C = xyz.shape[0], spec.L * spec.F
+    if tables.shape != (spec.L, spec.rows(), spec.F):
+        raise RuntimeError("tables shape %s does not match the encoder spec %s" % (tuple(tables.shape), (spec.L, spec.rows(), spec.F)))
+    if feature_major == "xcd8":
+        out = torch.empty(8, M, 8, device=xyz.device, dtype=torch.bfloat16)
+    elif feature_major:
+        out = torch.empty(C, M, device=xyz.device, dtype=out_dtype).t()
+    else:
+        out = torch.empty(M, C, device=xyz.device, dtype=out_dtype)
+    tc = tables.detach().contiguous()
+    if M:
+        _encode_fwd(spec, xyz, tc, feat_scale, out, addend.detach() if addend is not None else None, flags=flags)
+    return xyz, tc, out
+
+
+def _table_grad(ctx, xyz, g):
+    """The table gradient of both autograd nodes, in the tables' dtype."""
+    M = xyz.shape[0]
+    if M and (BWD_ALGO == "binned" or g.dim() == 3):       # the reduce pass writes every row: no zero fill, no read-modify-write
+        gt = torch.empty(ctx.tshape, device=xyz.device, dtype=torch.float32)
+        _encode_bwd(ctx.spec, xyz, g, ctx.feat_scale, gt, overwrite=True, flags=ctx.flags)
+    else:
+        gt = torch.zeros(ctx.tshape, device=xyz.device, dtype=torch.float32)
+        if M:
+            _encode_bwd(ctx.spec, xyz, g, ctx.feat_scale, gt, flags=ctx.flags)
+    return gt.to(ctx.tdtype)
 
 
 class _Encode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, tables, spec, feat_scale, out_dtype, feature_major, addend=None, flags=None):
         _check_gpu(xyz, tables)
-        ctx.flags = flags
-        xyz = xyz.detach().contiguous().float()
-        M, C = xyz.shape[0], spec.L * spec.F
-        if tables.shape != (spec.L, spec.rows(), spec.F):
-            raise RuntimeError("tables shape %s does not match the encoder spec %s" % (tuple(tables.shape), (spec.L, spec.rows(), spec.F)))
-        if feature_major == "xcd8":
-            out = torch.empty(8, M, 8, device=xyz.device, dtype=torch.bfloat16)
-        elif feature_major:
-            out = torch.empty(C, M, device=xyz.device, dtype=out_dtype).t()
-        else:
-            out = torch.empty(M, C, device=xyz.device, dtype=out_dtype)
-        tc = tables.detach().contiguous()
-        if M:
-            _encode_fwd(spec, xyz, tc, feat_scale, out, addend.detach() if addend is not None else None, flags=flags)
-        ctx.spec, ctx.feat_scale = spec, feat_scale
+        xyz, tc, out = _encode_forward(xyz, tables, spec, feat_scale, out_dtype, feature_major, addend, flags)
+        ctx.spec, ctx.feat_scale, ctx.flags = spec, feat_scale, flags
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(xyz, tc)           # d/d xyz needs the table rows again
         else:
@@ -218,23 +226,14 @@ class _Encode(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         xyz = ctx.saved_tensors[0]
-        need_t, need_x = ctx.needs_input_grad[1], ctx.needs_input_grad[0]
         gt = d_xyz = None
         if g.dtype not in (torch.float32, torch.bfloat16):
             g = g.float()
         if g.dim() == 3:
             g = g.contiguous()
-        if need_t:
-            binned = BWD_ALGO == "binned" or g.dim() == 3
-            if xyz.shape[0] and binned:       # the reduce pass writes every row: no zero fill, no read-modify-write
-                gt = torch.empty(ctx.tshape, device=xyz.device, dtype=torch.float32)
-                _encode_bwd(ctx.spec, xyz, g, ctx.feat_scale, gt, overwrite=True, flags=ctx.flags)
-            else:
-                gt = torch.zeros(ctx.tshape, device=xyz.device, dtype=torch.float32)
-                if xyz.shape[0]:
-                    _encode_bwd(ctx.spec, xyz, g, ctx.feat_scale, gt, flags=ctx.flags)
-            gt = gt.to(ctx.tdtype)
-        if need_x:
+        if ctx.needs_input_grad[1]:
+            gt = _table_grad(ctx, xyz, g)
+        if ctx.needs_input_grad[0]:
             d_xyz = _encode_bwd_xyz(ctx.spec, xyz, ctx.saved_tensors[1], g, ctx.feat_scale, flags=ctx.flags) if xyz.shape[0] \
                 else torch.zeros_like(xyz)
         return d_xyz, gt, None, None, None, None, None, None
@@ -253,14 +252,7 @@ class _EncodeRays(torch.autograd.Function):
     @staticmethod
     def forward(ctx, origins, dirs, xyz, tables, spec, feat_scale, out_dtype, xcd8, flags, depths, pack_start, ridx):
         _check_gpu(xyz, tables, depths, pack_start, ridx)
-        xyz = xyz.detach().contiguous().float()
-        M, C = xyz.shape[0], spec.L * spec.F
-        if tables.shape != (spec.L, spec.rows(), spec.F):
-            raise RuntimeError("tables shape %s does not match the encoder spec %s" % (tuple(tables.shape), (spec.L, spec.rows(), spec.F)))
-        out = torch.empty(8, M, 8, device=xyz.device, dtype=torch.bfloat16) if xcd8 else torch.empty(M, C, device=xyz.device, dtype=out_dtype)
-        tc = tables.detach().contiguous()
-        if M:
-            _encode_fwd(spec, xyz, tc, feat_scale, out, None, flags=flags)
+        xyz, tc, out = _encode_forward(xyz, tables, spec, feat_scale, out_dtype, "xcd8" if xcd8 else False, None, flags)
         ctx.spec, ctx.feat_scale, ctx.flags, ctx.N = spec, feat_scale, flags, origins.shape[0]
         ctx.save_for_backward(xyz, tc, depths.detach().reshape(-1).float().contiguous(), pack_start, ridx.detach().reshape(-1).contiguous())
         ctx.tshape, ctx.tdtype = tables.shape, tables.dtype
@@ -269,35 +261,14 @@ class _EncodeRays(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         xyz, tc, depths, pack_start, ridx = ctx.saved_tensors
-        spec, N, M, dev = ctx.spec, ctx.N, ctx.saved_tensors[0].shape[0], ctx.saved_tensors[0].device
         if g.dtype not in (torch.float32, torch.bfloat16):
             g = g.float()
         g = g.contiguous()
         gt = d_o = d_d = None
         if ctx.needs_input_grad[3]:
-            if M and (BWD_ALGO == "binned" or g.dim() == 3):
-                gt = torch.empty(ctx.tshape, device=dev, dtype=torch.float32)
-                _encode_bwd(spec, xyz, g, ctx.feat_scale, gt, overwrite=True, flags=ctx.flags)
-            else:
-                gt = torch.zeros(ctx.tshape, device=dev, dtype=torch.float32)
-                if M:
-                    _encode_bwd(spec, xyz, g, ctx.feat_scale, gt, flags=ctx.flags)
-            gt = gt.to(ctx.tdtype)
+            gt = _table_grad(ctx, xyz, g)
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            out = torch.empty(N, 6, device=dev)
-            lib = L.load()
-            ws_bytes = lib.pag_encode_bwd_rays_workspace_bytes(max(M, 1), N)
-            ws = torch.empty(ws_bytes // 4, device=dev)
-            flags = spec.flags if ctx.flags is None else ctx.flags
-            fs = L.host_floats(ctx.feat_scale)
-            sm, sc, lay = _layout_args(g)
-            tail = (L.ptr(ridx), L.ptr(depths), L.ptr(pack_start), N, L.ptr(out), L.ptr(ws), ws_bytes, flags, L.stream())
-            if spec.kind == "hash":
-                _call("pag_hash_encode_bwd_rays", L.ptr(xyz), M, L.ptr(tc), L.dtype_code(tc), g.data_ptr(), L.dtype_code(g), sm, sc, lay, spec.L, spec.F, spec.log2_T,
-                      spec.res, fs, *tail)
-            else:
-                _call("pag_permuto_encode_bwd_rays", L.ptr(xyz), M, L.ptr(tc), L.dtype_code(tc), g.data_ptr(), L.dtype_code(g), sm, sc, lay, spec.L, spec.F, spec.capacity,
-                      spec.sf, spec.shift, fs, *tail)
+            out = _encode_bwd_xyz(ctx.spec, xyz, tc, g, ctx.feat_scale, flags=ctx.flags, rays=(ridx, depths, pack_start, ctx.N))
             d_o, d_d = out[:, :3], out[:, 3:]
         return d_o, d_d, None, gt, None, None, None, None, None, None, None, None
 
@@ -511,7 +482,7 @@ class _FusedMLP(torch.autograd.Function):
         bc = [b.detach().contiguous().float() for b in bs]
         for i in range(n_layers):
             a.W[i], a.b[i] = L.ptr(Wc[i]), L.ptr(bc[i])
-        a.out_act, a.out, a.out_dtype, a.mode = out_act, L.ptr(out), _DTYPE_CODE[out_dtype], mode
+        a.out_act, a.out, a.out_dtype, a.mode = out_act, L.ptr(out), L._DT[out_dtype], mode
         for i, h in enumerate(hidden):
             a.hidden_save[i] = L.ptr(h)
         # wide softmax heads: per-sample (max*log2e, 1/sum) lets the backward rebuild the probabilities from the saved
@@ -614,7 +585,7 @@ class _FusedMLP(torch.autograd.Function):
             if len(rank1) > 3:
                 g_ray_scale = rank1[3].float()            # named: stays alive past the launch
                 a.g_ray_scale = L.ptr(g_ray_scale)
-        a.out, a.out_dtype, a.out_act = L.ptr(out), _DTYPE_CODE[out_dtype], out_act
+        a.out, a.out_dtype, a.out_act = L.ptr(out), L._DT[out_dtype], out_act
         a.k1, a.in_dim, a.n_layers, a.out_dim = k1, in_dim, n_layers, out_dim
         if grouped is not None:
             a.x1_layout, a.x1_levels, a.x1_feats = L.LAYOUT_XCD8, grouped[0], grouped[1]

@@ -134,6 +134,90 @@ def test_argument_validation_without_gpu(lib):
     assert lib.pag_adam_step(0, None, None, None, None, None, 1e-3, 0.9, 0.999, 1e-15, 0.0, 1, None) == 0                  # nothing to do
 
 
+# The twelve grid-encoder entry points as (operation, kind): argument names in the header's order = operation head + kind middle + operation tail
+_ENC_HEAD = {"fwd": "xyz M tables table_dtype L F", "bwd": "xyz M grad grad_dtype sm sc layout L F",
+             "bwd_xyz": "xyz M tables table_dtype grad grad_dtype sm sc layout L F"}
+_ENC_HEAD.update(fwd_add=_ENC_HEAD["fwd"], bwd_set=_ENC_HEAD["bwd"], bwd_rays=_ENC_HEAD["bwd_xyz"])
+_ENC_MID = {"hash": "log2_T res fs", "permuto": "capacity sf shift fs"}
+_ENC_TAIL = {"fwd": "out out_dtype sm sc layout flags stream", "fwd_add": "addend out flags stream", "bwd": "grad_tables ws ws_bytes flags stream",
+             "bwd_xyz": "d_xyz ws ws_bytes flags stream", "bwd_rays": "ridx depths pack_start N d_xyz ws ws_bytes flags stream"}
+_ENC_TAIL["bwd_set"] = _ENC_TAIL["bwd"]
+_BWD, _XYZ, _RAYS, _GRADS = ("bwd", "bwd_set"), ("bwd_xyz", "bwd_rays"), ("bwd_rays",), ("bwd", "bwd_set", "bwd_xyz", "bwd_rays")
+_XCD8 = 1
+# (what is wrong, operations it is tried on (None: every one that has the arguments), arguments that differ from a valid call, {M: return code}).
+# The return codes are the ones the library gave before the host layer was folded onto one code path; 0 at M == 0 next to -1 at M == 5 = the
+# argument is only looked at behind the "nothing to do" return.  Every M == 5 row is refused before a launch: its non-NULL pointers are never read.
+_ENC_ROWS = [
+    ("nothing wrong, no samples", None, {}, {0: 0}),
+    ("M < 0", None, {}, {-1: -1}),
+    ("NULL xyz", None, {"xyz": None}, {0: 0, 5: -1}),
+    ("n_levels 0", None, {"L": 0}, {0: -1, 5: -1}),
+    ("n_levels PAG_MAX_LEVELS + 1", None, {"L": 33}, {0: -1, 5: -1}),
+    ("n_feat 3", None, {"F": 3}, {0: -1, 5: -1}),
+    ("n_levels * n_feat > PAG_MAX_FEATS", None, {"L": 32, "F": 4}, {0: -1, 5: -1}),
+    ("log2_T 0", None, {"log2_T": 0}, {0: -1, 5: -1}),
+    ("log2_T 31", None, {"log2_T": 31}, {0: -1, 5: -1}),
+    ("NULL resolutions", None, {"res": None}, {0: -1, 5: -1}),
+    ("capacity 0", None, {"capacity": 0}, {0: -1, 5: -1}),
+    ("NULL scale_factor", None, {"sf": None}, {0: -1, 5: -1}),
+    ("NULL shift", None, {"shift": None}, {0: -1, 5: -1}),
+    ("table dtype BF16", None, {"table_dtype": 2}, {0: -1, 5: -1}),
+    ("out dtype F16", None, {"out_dtype": 1}, {0: -1, 5: -1}),
+    ("grad dtype F16", None, {"grad_dtype": 1}, {0: -1, 5: -1}),
+    ("XCD8 with f32 output", ("fwd",), {"layout": _XCD8, "out_dtype": 0}, {0: -1, 5: -1}),
+    ("XCD8 with f32 gradient", _GRADS, {"layout": _XCD8, "grad_dtype": 0}, {0: -1, 5: -1}),
+    # ceil(L/8) * F > 8 (with F in {1, 2, 4} that takes L * F > PAG_MAX_FEATS as well: the call is refused, whichever check comes first)
+    ("XCD8 with ceil(L/8)*F > 8", ("fwd",), {"layout": _XCD8, "out_dtype": 2, "L": 17, "F": 4}, {0: -1, 5: -1}),
+    ("XCD8 with ceil(L/8)*F > 8", ("fwd_add",), {"L": 17, "F": 4}, {0: -1, 5: -1}),
+    ("XCD8 with ceil(L/8)*F > 8", _GRADS, {"layout": _XCD8, "grad_dtype": 2, "L": 17, "F": 4}, {0: -1, 5: -1}),
+    ("_bwd_set without a workspace", ("bwd_set",), {"ws": None, "ws_bytes": 0}, {0: -1, 5: -1}),
+    ("XCD8 table gradient without a workspace", _BWD, {"layout": _XCD8, "grad_dtype": 2, "ws": None, "ws_bytes": 0}, {0: -1, 5: -1}),
+    ("binned table gradient with a workspace of 8 bytes", _BWD, {"ws_bytes": 8}, {0: 0, 5: -1}),
+    ("position gradient with a workspace of 8 bytes", _XYZ, {"ws_bytes": 8}, {0: 0, 5: -1}),
+    ("position gradient without a workspace", _XYZ, {"ws": None}, {0: 0, 5: -1}),
+    ("no rays", _RAYS, {"N": 0}, {0: -1, 5: -1}),
+    ("NULL ridx", _RAYS, {"ridx": None}, {5: -1}),
+    ("NULL depths", _RAYS, {"depths": None}, {5: -1}),
+    ("NULL pack_start", _RAYS, {"pack_start": None}, {5: -1}),
+    ("NULL tables", None, {"tables": None}, {0: 0, 5: -1}),
+    ("NULL out", ("fwd", "fwd_add"), {"out": None}, {0: 0, 5: -1}),
+    ("NULL grad_out", None, {"grad": None}, {0: 0, 5: -1}),
+    ("NULL grad_tables", None, {"grad_tables": None}, {0: 0, 5: -1}),
+    ("NULL d_xyz", None, {"d_xyz": None}, {0: 0, 5: -1}),
+]
+
+
+def test_encoder_entry_points_validate_without_gpu(lib):
+    """pag_{hash,permuto}_encode_{fwd,fwd_add,bwd,bwd_set,bwd_xyz,bwd_rays}: every argument check of the shared host layer, on each of the twelve entry
+    points it applies to, with the return code it has had since the entry point exists - and on which side of the M == 0 return the check sits."""
+    floats = (ctypes.c_float * 96)(*([16.0] * 96))
+    one = ctypes.c_void_p(16)          # a non-NULL pointer value; the call is refused before it is ever dereferenced
+    valid = dict(xyz=one, tables=one, table_dtype=0, grad=one, grad_dtype=0, out=one, out_dtype=0, sm=8, sc=1, layout=0, L=4, F=2, log2_T=10, res=floats,
+                 capacity=1024, sf=floats, shift=floats, fs=None, addend=one, grad_tables=one, d_xyz=one, ws=one, ws_bytes=1 << 40, ridx=one, depths=one,
+                 pack_start=one, N=3, flags=0, stream=None)
+    calls = 0
+    for op in _ENC_HEAD:
+        for kind in _ENC_MID:
+            names = (_ENC_HEAD[op] + " " + _ENC_MID[kind] + " " + _ENC_TAIL[op]).split()
+            fn = getattr(lib, "pag_%s_encode_%s" % (kind, op))
+            assert len(names) == len(fn.argtypes), (kind, op)
+            for what, ops_, bad, codes in _ENC_ROWS:
+                if (ops_ is not None and op not in ops_) or not set(bad) <= set(names):
+                    continue
+                for M, rc in codes.items():
+                    # the per-ray form zero-fills its result when M == 0 (device work: tests/test_gpu_edges.py::test_empty_inputs_everywhere) - unless
+                    # one of the checks in front of that refuses the call, and those are the rows that name this form alone
+                    if op == "bwd_rays" and M == 0 and ops_ != _RAYS:
+                        continue
+                    args = dict(valid, M=M)
+                    if M <= 0:         # no samples: no buffers either (the workspace stays: its presence selects the algorithm)
+                        args.update({k: None for k, v in valid.items() if v is one and k != "ws"})
+                    args.update(bad)
+                    assert fn(*[args[n] for n in names]) == rc, (kind, op, what, M, lib.pag_last_error_string())
+                    calls += 1
+    assert calls == 362        # no row of the table fell through the filters
+
+
 def test_product_path_refuses_cpu_tensors():
     from pagnerf_amd import ops
     spec = ops.hash_spec([16.0, 32.0], 8, 2)

@@ -406,6 +406,55 @@ def test_position_gradient_reduced_per_ray_in_the_gather_pass(gpu_device, mode, 
     np.testing.assert_allclose(d1.cpu().numpy(), d0.cpu().numpy(), rtol=2e-4, atol=2e-5 * float(d0.abs().max()))
 
 
+@pytest.mark.parametrize("layout", ["xcd8", None])
+def test_hash_position_gradient_reduced_per_ray_in_the_gather_pass(gpu_device, layout):
+    """pag_hash_encode_bwd_rays against the per-sample form (pag_hash_encode_bwd_xyz + pag_ray_sample_grad), as the permuto test above: a 16-level F = 2
+    hash grid (2^12 rows per level), packed samples from the ray march with ragged rays, a ray without samples and M % 64 != 0; the bf16 XCD8 and the
+    strided f32 layout.  Same table gradient bit for bit; origin / direction gradients to fp32 summation order."""
+    import pagnerf_amd
+    from pagnerf_amd import ops
+    dev = gpu_device
+    N, S, level = 300, 40, 5
+    gen = torch.Generator().manual_seed(0)
+    g = pagnerf_amd.HashGridHIP(2, codebook_bitwidth=12, blas_level=level)
+    g.init_from_resolutions(g.level_resolutions(16.0, 512.0, 16), exact=True)
+    g.tables.data = torch.randn(16, 2 ** 12, 2, generator=gen) * 0.3
+    g = g.to(dev)
+    o = (torch.rand(N, 3, generator=gen) - 0.5) * 0.6
+    o[7] = 5.0                                              # a ray that misses the volume: no samples
+    d = torch.nn.functional.normalize(torch.randn(N, 3, generator=gen), dim=-1)
+    g.blas_init(torch.rand(2 ** level, 2 ** level, 2 ** level, generator=gen).reshape(-1) > 0.35)
+    jitter = torch.rand(N, S, generator=gen).to(dev)
+    w = None
+    res = {}
+    for fused in (True, False):
+        ops.RAYS_FUSED = fused
+        try:
+            oo, dd = o.to(dev).requires_grad_(True), d.to(dev).requires_grad_(True)
+            out = g.raymarch(pagnerf_amd.Rays(oo, dd, dist_min=0.0, dist_max=2.0), level=None, num_samples=S, raymarch_type="ray", jitter=jitter)
+            samples = out[2]
+            assert hasattr(samples, "_pag_rays") and samples.requires_grad
+            M = samples.reshape(-1, 3).shape[0]
+            g.tables.grad = None
+            feats = g.interpolate_scaled(samples, None, out_dtype=torch.bfloat16 if layout else torch.float32, layout=layout)
+            assert (type(feats.grad_fn).__name__ == "_EncodeRaysBackward") == fused
+            if w is None:
+                w = torch.randn(feats.shape, generator=torch.Generator().manual_seed(3)).to(dev)
+            (feats.float() * w).sum().backward()
+            res[fused] = (oo.grad.clone(), dd.grad.clone(), g.tables.grad.clone(), M)
+        finally:
+            ops.RAYS_FUSED = True
+    (o1, d1, t1, M1), (o0, d0, t0, M0) = res[True], res[False]
+    assert M1 == M0 and M1 % 64 != 0 and float(o0[7].abs().sum()) == 0.0 and float(o1[7].abs().sum()) == 0.0
+    assert torch.equal(t1, t0) and float(t0.abs().sum()) > 0
+    assert float(o0.abs().sum()) > 0 and float(d0.abs().sum()) > 0
+    for name, got, want in (("origins", o1, o0), ("dirs", d1, d0)):
+        worst = float(((got - want).abs() / (2e-5 * want.abs().max() + 2e-4 * want.abs())).max())
+        print("hash per-ray position gradient, %s, layout %s: M %d, worst |diff| / tolerance %.3f" % (name, layout, M1, worst))
+    np.testing.assert_allclose(o1.cpu().numpy(), o0.cpu().numpy(), rtol=2e-4, atol=2e-5 * float(o0.abs().max()))
+    np.testing.assert_allclose(d1.cpu().numpy(), d0.cpu().numpy(), rtol=2e-4, atol=2e-5 * float(d0.abs().max()))
+
+
 @pytest.mark.parametrize("mode", ["ray", "voxel"])
 def test_view_embedding_gradient_from_per_tile_ray_sums(gpu_device, mode):
     """pag_mlp_bwd_args.dz0_slots: the colour decoder's backward sums dz_0 per (32-sample tile, ray) on the matrix cores and pag_mlp_dz0_slots_sum adds a

@@ -730,6 +730,20 @@ def test_encode_position_gradients(gpu_device):
     np.testing.assert_allclose(x.grad.cpu().numpy(), g["dx"], rtol=1e-4, atol=2e-3)        # |dx| ~ 1e2..1e3 at res 512
     np.testing.assert_allclose(tab.grad.cpu().numpy(), g["dtables"], rtol=1e-4, atol=1e-4)
 
+    def xcd8_gradient(go, Lv, F):
+        """go f32 [M, Lv*F] -> (the same gradient as the bf16 [8, M, 8] XCD-grouped tensor, its bf16-rounded values back in [M, Lv*F])."""
+        cols, M = ops.xcd8_columns(Lv, F), go.shape[0]
+        gg = torch.zeros(64, M)
+        for p, c in enumerate(cols):
+            if c >= 0:
+                gg[p] = torch.from_numpy(go[:, c])
+        gg = gg.reshape(8, 8, M).permute(0, 2, 1).contiguous().bfloat16()
+        gob = np.zeros_like(go)
+        for p, c in enumerate(cols):
+            if c >= 0:
+                gob[:, c] = gg[p // 8, :, p % 8].float().numpy()
+        return gg, gob
+
     rs = np.random.RandomState(12)
     for M, Lv, cap in ((3000, 24, 4099), (777, 5, 256)):
         F = 2
@@ -748,19 +762,26 @@ def test_encode_position_gradients(gpu_device):
         if ops.xcd8_supported(Lv, F):
             x2 = torch.from_numpy(xs).to(dev).requires_grad_(True)
             o = ops.encode(x2, t, spec, torch.from_numpy(scale), layout="xcd8")
-            cols = ops.xcd8_columns(Lv, F)
-            gg = torch.zeros(64, M)
-            for p, c in enumerate(cols):
-                if c >= 0:
-                    gg[p] = torch.from_numpy(go[:, c])
-            gg = gg.reshape(8, 8, M).permute(0, 2, 1).contiguous().bfloat16()
+            gg, gob = xcd8_gradient(go, Lv, F)
             o.backward(gg.to(dev))
-            gob = np.zeros_like(go)
-            for p, c in enumerate(cols):
-                if c >= 0:
-                    gob[:, c] = gg[p // 8, :, p % 8].float().numpy()
             ref2 = op.permuto_encode_bwd_xyz(xs, tb, gob * scale[None], shifts, sf)
             assert _rel_l2(x2.grad.cpu(), torch.from_numpy(ref2)) < 1e-5, (M, Lv)
+
+    # the hash encoder's position gradient in the XCD8 layout (two bands of 8 levels), against autograd through the oracle's forward
+    from oracle import hash_encode as oh
+    M, Lv, F, log2T = 777, 16, 2, 12
+    res = oh.level_resolutions(16.0, 512.0, Lv)
+    xs = rs.uniform(-1, 1, size=(M, 3)).astype(np.float32)
+    tb = rs.standard_normal(size=(Lv, 2 ** log2T, F)).astype(np.float32)
+    go = rs.standard_normal(size=(M, Lv * F)).astype(np.float32)
+    scale = rs.uniform(0.5, 1.5, size=Lv * F).astype(np.float32)
+    x2 = torch.from_numpy(xs).to(dev).requires_grad_(True)
+    o = ops.encode(x2, torch.from_numpy(tb).to(dev), ops.hash_spec(res, log2T, F), torch.from_numpy(scale), layout="xcd8")
+    gg, gob = xcd8_gradient(go, Lv, F)
+    o.backward(gg.to(dev))
+    ref3 = oh.hash_encode_bwd_xyz(torch.from_numpy(xs), torch.from_numpy(tb), torch.from_numpy(gob * scale[None]), res, log2T)
+    print("hash position gradient, XCD8 layout: rel l2 %.3e" % _rel_l2(x2.grad.cpu(), ref3))
+    assert _rel_l2(x2.grad.cpu(), ref3) < 1e-5
 
 
 def _look_at_views(C, gen):
