@@ -909,6 +909,62 @@ int64_t pag_deep_mlp_workspace_bytes(int64_t M, int hidden, int num_classes, int
 int pag_deep_mlp_fwd(const pag_deep_mlp_args *args, int64_t M, void *stream);
 int pag_deep_mlp_bwd(const pag_deep_mlp_args *args, int64_t M, void *stream);
 
+/* 128-wide decoders (additive, ABI 14; mlp_h128.hip): one wisp BasicDecoder at hidden width 128 per call - decoder_density / decoder_color /
+ * decoder_semantics / decoder_inst of pc_nerf/panoptic_nef.py:114-164 with hidden_dim / sem_hidden_dim / inst_hidden_dim = 128 (config_parser.py:149's
+ * default, main_hp_tunning.py:84-87's grid).  n_hidden (1 .. 3) Linear + ReLU layers of width `hidden` = 128, then lout: W[i] / b[i] are the f32 nn.Linear
+ * tensors of layers[i] (i < n_hidden) and lout (i = n_hidden); out_dim <= 224, in_dim <= 64.  bf16 operands, f32 accumulate on the matrix cores: the
+ * layer-0 input, every weight and every hidden activation are rounded to bf16 (round to nearest even), sums, biases and the output activation are f32.
+ *   x1        PAG_LAYOUT_XCD8: the encoders' bf16 [8][M][8] tensor of x1_levels x x1_feats features (k1 = 64, in_dim = levels * feats, no x2), or
+ *             PAG_LAYOUT_STRIDED: [M, k1] row-major, bf16 or f32, k1 % 8 == 0
+ *   x2        f32 [R, k2p] or NULL, k2p % 8 == 0, rows gathered per sample through x2_index i32 [M]; k1 + k2p <= 64; input columns >= in_dim are ignored
+ *   out       [M, out_dim] row-major, f32 or bf16, after out_act (PAG_ACT_*)
+ *   workspace NULL (nothing but `out` is written: validation, prune) or pag_mlp128_workspace_bytes(M, n_hidden, out_dim, 1) bytes, 256-B aligned: the
+ *             layer-0 input and every hidden layer's post-ReLU output, bf16, kept for pag_mlp128_bwd.  Plane layout ("native"): samples are padded to
+ *             Mp = ceil(M / 256) * 256; the plane of columns [c0, c0 + 32 nb) starts at bf16 element Mp * c0 and holds, per 32-sample tile t and 32-column
+ *             block blk, 64 x 4 chunks of 4 values: chunk (g, lane) = columns 32 blk + 8 g + 4 (lane >> 5) + 0..3 of sample 32 t + (lane & 31), at element
+ *             ((t * nb + blk) * 4 + g) * 256 + 4 lane.  Planes: the input (64 positions) at column 0, h_l at 64 + 128 l.
+ * pag_mlp128_bwd: data and weight gradients.  grad_out [M, out_dim] in out's dtype, `out` the forward's output (sigmoid / softmax).  Writes
+ *   bwd_workspace  pag_mlp128_workspace_bytes(M, n_hidden, out_dim, 2) bytes: first the pre-activation gradients dz_l as bf16 native planes (dz_l at column
+ *             128 l, the output layer's after them) - dz_0, the first plane, is what the caller sums per ray for the gradient of x2 -, then the weight
+ *             gradients' partial sums
+ *   dx1       NULL or the gradient of x1 in x1's form: bf16 [8][M][8] with padding positions zero (dx1_accumulate = 1: added to what is there), or
+ *             [M, k1] (dx1_dtype bf16 / f32), columns >= in_dim zero
+ *   dW[i], db[i]   f32, shapes of W[i] / b[i], overwritten: per-workgroup partial sums added in a fixed order by a finish launch (no atomics: two runs give
+ *             the same bits)
+ * pag_mlp128_workspace_bytes(M, n_hidden, out_dim, mode), with Mp as above, ob = 1 (out_dim <= 32), 4 (<= 128) or 7, align = round up to 256:
+ *   mode 0 (forward, nothing saved)  0
+ *   mode 1 (forward, saving)         align(Mp * (64 + 128 n_hidden) * 2)
+ *   mode 2 (backward)                align(Mp * (128 n_hidden + 32 ob) * 2) + align(128 * (128 n_hidden + 32 ob) * 129 * 4)
+ *   -1 for M < 0, M > PAG_MLP128_MAX_M or an unsupported shape; 0 for M == 0.
+ * pag_mlp128_supported: 1 when (n_hidden, hidden, in_dim, out_dim) is a shape these kernels take.
+ * The forward launches min(ceil(M / 256), 256) workgroups of 256 samples each and grid-strides.  Every sample offset is 64-bit; M above PAG_MLP128_MAX_M is
+ * refused (PAG_ERR_ARG).  Bad sizes, NULL buffers and short workspaces are refused before any launch, the message naming the field; M == 0 is a no-op. */
+#define PAG_MLP128_MAX_M ((int64_t)1 << 26)
+typedef struct pag_mlp128_fwd_args {
+    const void *x1; int x1_dtype; int k1;
+    int x1_layout; int x1_levels; int x1_feats;
+    const float *x2; int k2p; const int32_t *x2_index;
+    int in_dim; int n_hidden; int hidden; int out_dim;
+    const float *W[4]; const float *b[4];
+    int out_act;
+    void *out; int out_dtype;
+    void *workspace; int64_t workspace_bytes;
+} pag_mlp128_fwd_args;
+typedef struct pag_mlp128_bwd_args {
+    const void *grad_out; const void *out; int out_dtype; int out_act;
+    int k1; int k2p; int in_dim; int n_hidden; int hidden; int out_dim;
+    int x1_layout; int x1_levels; int x1_feats;
+    const float *W[4];
+    const void *workspace; int64_t workspace_bytes;       /* the forward's */
+    void *bwd_workspace; int64_t bwd_workspace_bytes;
+    void *dx1; int dx1_dtype; int dx1_accumulate;
+    float *dW[4]; float *db[4];
+} pag_mlp128_bwd_args;
+int pag_mlp128_supported(int n_hidden, int hidden, int in_dim, int out_dim);
+int64_t pag_mlp128_workspace_bytes(int64_t M, int n_hidden, int out_dim, int mode);
+int pag_mlp128_fwd(const pag_mlp128_fwd_args *args, int64_t M, void *stream);
+int pag_mlp128_bwd(const pag_mlp128_bwd_args *args, int64_t M, void *stream);
+
 /* TensoRF vector-matrix grid (grids/tensorf.py::VMSplitFeatureVolume; additive, ABI 14): vm.hip.  f32 tables, f32 arithmetic.
  * Tables are CHANNEL-LAST: plane i is f32 [R][R][C] (row = the pair's second coordinate, column = its first: matMode [[0,1],[0,2],[1,2]]), line i is
  * f32 [R][C] along coordinate vecMode[i] = 2 - i; C = 16 for the density set, 48 for the appearance set; basis is the Linear(144, 27) weight [27][144]

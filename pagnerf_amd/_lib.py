@@ -88,6 +88,28 @@ class DeepMlpArgs(ctypes.Structure):
                 ("bwd_workspace", c_vp), ("bwd_workspace_bytes", c_i64)]
 
 
+MLP128_MAX_M = 1 << 26              # PAG_MLP128_MAX_M
+MLP128_BATCH, MLP128_MAX_GRID = 256, 256      # samples per workgroup batch, workgroups per launch (the forward / backward grid-stride beyond their product)
+
+
+class Mlp128FwdArgs(ctypes.Structure):
+    """pag_mlp128_fwd_args (include/pagnerf_hip.h)."""
+    _fields_ = [("x1", c_vp), ("x1_dtype", c_i32), ("k1", c_i32), ("x1_layout", c_i32), ("x1_levels", c_i32), ("x1_feats", c_i32),
+                ("x2", c_vp), ("k2p", c_i32), ("x2_index", c_vp),
+                ("in_dim", c_i32), ("n_hidden", c_i32), ("hidden", c_i32), ("out_dim", c_i32),
+                ("W", c_vp * 4), ("b", c_vp * 4), ("out_act", c_i32), ("out", c_vp), ("out_dtype", c_i32),
+                ("workspace", c_vp), ("workspace_bytes", c_i64)]
+
+
+class Mlp128BwdArgs(ctypes.Structure):
+    """pag_mlp128_bwd_args (include/pagnerf_hip.h)."""
+    _fields_ = [("grad_out", c_vp), ("out", c_vp), ("out_dtype", c_i32), ("out_act", c_i32),
+                ("k1", c_i32), ("k2p", c_i32), ("in_dim", c_i32), ("n_hidden", c_i32), ("hidden", c_i32), ("out_dim", c_i32),
+                ("x1_layout", c_i32), ("x1_levels", c_i32), ("x1_feats", c_i32),
+                ("W", c_vp * 4), ("workspace", c_vp), ("workspace_bytes", c_i64), ("bwd_workspace", c_vp), ("bwd_workspace_bytes", c_i64),
+                ("dx1", c_vp), ("dx1_dtype", c_i32), ("dx1_accumulate", c_i32), ("dW", c_vp * 4), ("db", c_vp * 4)]
+
+
 class VmArgs(ctypes.Structure):
     """pag_vm_args (include/pagnerf_hip.h)."""
     _fields_ = [("density_plane", c_vp * 3), ("density_line", c_vp * 3), ("app_plane", c_vp * 3), ("app_line", c_vp * 3), ("basis", c_vp),
@@ -213,6 +235,10 @@ _SIGS = {
     "pag_deep_mlp_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
     "pag_deep_mlp_fwd": (c_i32, [ctypes.POINTER(DeepMlpArgs), c_i64, c_vp]),
     "pag_deep_mlp_bwd": (c_i32, [ctypes.POINTER(DeepMlpArgs), c_i64, c_vp]),
+    "pag_mlp128_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    "pag_mlp128_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "pag_mlp128_fwd": (c_i32, [ctypes.POINTER(Mlp128FwdArgs), c_i64, c_vp]),
+    "pag_mlp128_bwd": (c_i32, [ctypes.POINTER(Mlp128BwdArgs), c_i64, c_vp]),
     "pag_vm_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "pag_vm_bwd_workspace_bytes": (c_i64, [c_i64]),
     "pag_vm_fwd": (c_i32, [ctypes.POINTER(VmArgs), c_i64, c_vp]),

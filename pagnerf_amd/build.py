@@ -26,6 +26,7 @@ MLP = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 SOURCES = {
     "mlp.hip": MLP,
     "mlp_deep.hip": MLP,
+    "mlp_h128.hip": MLP,
     "encode.hip": ["-ffp-contract=off"],
     "mlp_wgrad.hip": MLP,
     "render.hip": ["-ffp-contract=off"],

@@ -1,4 +1,4 @@
-// Shared by the decoder translation units (mlp.hip, mlp_wgrad.hip, mlp_affine.hip, mlp_deep.hip; nothing else includes it): what more than one of them uses.
+// Shared by the decoder translation units (mlp.hip, mlp_wgrad.hip, mlp_affine.hip, mlp_deep.hip, mlp_h128.hip; nothing else includes it): what more than one of them uses.
 // The transposed-MFMA scheme of the decoders is described at the top of mlp.hip.
 #pragma once
 #include "common.h"

@@ -31,14 +31,17 @@ _GRIDS = {"HashGridTorch": HashGridHIP, "HashGridTinyCudaNN": HashGridHIP, "Hash
 
 
 class BasicDecoder(nn.Module):
-    """wisp BasicDecoder's parameter layout (layers[i], lout) with a fused forward."""
+    """wisp BasicDecoder's parameter layout (layers[i], lout) with a fused forward: the 64-wide family (pag_mlp_fwd, best.yaml) or the
+    128-wide one (pag_mlp128_fwd: config_parser.py:149's default width, the other half of main_hp_tunning.py:84-87's grid)."""
 
     def __init__(self, input_dim, output_dim, num_layers=1, hidden_dim=64, bias=True):
         super().__init__()
-        if hidden_dim != 64 or num_layers not in (1, 2):
-            raise NotImplementedError("fused decoder supports hidden_dim=64 and 1-2 hidden layers (best.yaml); got %d x %d"
+        if hidden_dim not in (64, 128) or num_layers not in ((1, 2) if hidden_dim == 64 else (1, 2, 3)):
+            raise NotImplementedError("fused decoders support hidden_dim=64 (1-2 hidden layers) and hidden_dim=128 (1-3 hidden layers); got %d x %d"
                                       % (num_layers, hidden_dim))
-        self.input_dim, self.output_dim = input_dim, output_dim
+        if hidden_dim == 128 and (input_dim > 64 or output_dim > 224 or not bias):
+            raise NotImplementedError("128-wide fused decoder: input_dim <= 64, output_dim <= 224, with biases; got %d -> %d" % (input_dim, output_dim))
+        self.input_dim, self.output_dim, self.hidden_dim = input_dim, output_dim, hidden_dim
         self.layers = nn.ModuleList([nn.Linear(input_dim if i == 0 else hidden_dim, hidden_dim, bias=bias)
                                      for i in range(num_layers)])
         self.lout = nn.Linear(hidden_dim, output_dim, bias=bias)
@@ -50,6 +53,18 @@ class BasicDecoder(nn.Module):
     def forward(self, x1, x2=None, x2_index=None, out_act=L.ACT_NONE, mode=L.MLP_MFMA_BF16, out_dtype=torch.float32,
                 x1_grouped=None, x2_packs=None):
         W, b = self.weights()
+        if self.hidden_dim == 128:
+            if mode == L.MLP_MFMA_BF16 and x1.is_cuda:
+                return ops.fused_mlp128(x1, W, b, x2=x2, x2_index=x2_index, in_dim=self.input_dim, out_act=out_act, mode=mode,
+                                        out_dtype=out_dtype, x1_grouped=x1_grouped, x2_packs=x2_packs)
+            # precision='fp32' and CPU tensors: the parity path at this width is the definition itself
+            if x1_grouped is not None:
+                raise NotImplementedError("the tensor-op form of the 128-wide decoder reads strided features")
+            n1 = min(x1.shape[1], self.input_dim)
+            x = x1[:, :n1].float()
+            if self.input_dim > n1:
+                x = torch.cat([x, x2[x2_index.long(), :self.input_dim - n1].float()], -1)
+            return ops.wide_mlp_reference(x, W, b, out_act).to(out_dtype)
         return ops.fused_mlp(x1, W, b, x2=x2, x2_index=x2_index, in_dim=self.input_dim, out_act=out_act, mode=mode,
                              out_dtype=out_dtype, x1_grouped=x1_grouped, x2_packs=x2_packs)
 
@@ -276,7 +291,9 @@ class PanopticDeltaNeF(nn.Module):
         self._feat_cache = (coords, feats if self._heads_read_live_features() else feats.detach())
         grp = self._grouped()
         # with the colour decoder to follow, the density decoder's launch is parked and rides in the colour decoder's (ops.decoder_hold)
-        hold = ops.decoder_hold(feats) if (ops.CD_FUSED and "rgb" in compute_channels and feats.is_cuda) else None
+        # (128-wide density / colour decoders run as two plain nodes: the 64-wide family's cross-decoder fusions do not exist at that width)
+        wide = self.decoder_density.hidden_dim == 128 or self.decoder_color.hidden_dim == 128
+        hold = ops.decoder_hold(feats) if (ops.CD_FUSED and "rgb" in compute_channels and feats.is_cuda and not wide) else None
         # everything between decoder_hold() and flush_hold() sits in ONE try / finally: whatever raises in between (the density decoder, the view
         # embedding, the colour decoder before it took the parked launch), the launch is issued or forgotten and no later trace can inherit it
         try:
@@ -286,11 +303,16 @@ class PanopticDeltaNeF(nn.Module):
                 if num_samples != 1 and ridx is None:                                  # one direction per pack entry -> per sample
                     ray_d = ray_d[:, None].repeat(1, num_samples, 1).reshape(-1, 3)
                 pe, index = self._view_embedding(ray_d, ridx, ray_dirs)
-                W, b = self.decoder_color.weights()
-                # colour decoder and the density column of its input as one node (ops._ColourDensity)
-                rgb, sigma = ops.colour_and_density(density_feats, W, b, pe, index, self.decoder_color.input_dim, out_act=L.ACT_SIGMOID,
-                                                    mode=mode, x2_packs=ray_packs if ridx is not None else None, producer=hold)
-                density = sigma.reshape(batch, num_samples, 1)
+                if wide:
+                    rgb = self.decoder_color(density_feats, x2=pe, x2_index=index, out_act=L.ACT_SIGMOID, mode=mode,
+                                             x2_packs=ray_packs if ridx is not None else None)
+                    density = torch.relu(density_feats[:, 0:1].float()).reshape(batch, num_samples, 1)   # :188
+                else:
+                    W, b = self.decoder_color.weights()
+                    # colour decoder and the density column of its input as one node (ops._ColourDensity)
+                    rgb, sigma = ops.colour_and_density(density_feats, W, b, pe, index, self.decoder_color.input_dim, out_act=L.ACT_SIGMOID,
+                                                        mode=mode, x2_packs=ray_packs if ridx is not None else None, producer=hold)
+                    density = sigma.reshape(batch, num_samples, 1)
                 out["rgb"] = rgb.reshape(batch, num_samples, 3)
             else:
                 density = torch.relu(density_feats[:, 0:1].float()).reshape(batch, num_samples, 1)   # :188
@@ -356,9 +378,15 @@ class PanopticDeltaNeF(nn.Module):
             pad = self._wide_pad = (torch.eye(64, device=W[0].device), torch.zeros(64, device=W[0].device))
         return [W[0], pad[0], W[1]], [b[0], pad[1], b[1]]
 
+    def _wide_head_requested(self, channels):
+        """Is a requested panoptic head 128 wide?  The decoder + compositing nodes (ops.head_composite*) exist for the 64-wide family only.  The
+        choice made here: ONE 128-wide head among the requested ones sends ALL of them down the tracer's decoder -> composite_feats route (a
+        64-wide semantic head next to a 128-wide instance head is then evaluated unfused too - same arithmetic, one code path to keep right)."""
+        return any(dec.hidden_dim == 128 for ch, dec in (("semantics", self.decoder_semantics), ("inst_embedding", self.decoder_inst)) if ch in channels)
+
     def can_fuse_panoptic(self, channels):
         """True when the semantic / instance heads can run as decoder + compositing in one autograd node."""
-        if self.precision != "bf16" or self._pan_grouped() is None:
+        if self.precision != "bf16" or self._pan_grouped() is None or self._wide_head_requested(channels):
             return False
         ok = True
         if "semantics" in channels:
@@ -489,7 +517,7 @@ class PanopticNeF(PanopticDeltaNeF):
         return out
 
     def can_fuse_panoptic(self, channels):
-        if self.precision != "bf16" or self._grouped() is None:
+        if self.precision != "bf16" or self._grouped() is None or self._wide_head_requested(channels):
             return False
         ok = True
         if "semantics" in channels:

@@ -842,6 +842,150 @@ def fused_mlp(x1, weights, biases, x2=None, x2_index=None, in_dim=None, out_act=
     return out
 
 
+# ----------------------------------------------------------------------------- 128-wide decoders
+def wide_mlp_reference(x, W, b, out_act=L.ACT_NONE, round_bf16=False):
+    """The DEFINITION of the 128-wide decoders (pag_mlp128_fwd) in tensor ops, on any device: Linear + ReLU ... Linear [+ sigmoid / softmax].
+    round_bf16: the input, the weights and the hidden activations are rounded to bf16 straight-through (the kernels' rounding points; sums,
+    biases and the output activation stay f32) - at width 128 this is also the precision='fp32' / CPU path of nef.BasicDecoder."""
+    def r(t):
+        return t + (t.detach().bfloat16().to(t.dtype) - t.detach()) if round_bf16 else t
+    h = r(x)
+    for i in range(len(W)):
+        h = torch.nn.functional.linear(h, r(W[i]), None if b[i] is None else b[i])
+        if i + 1 < len(W):
+            h = r(torch.relu(h))
+    if out_act == L.ACT_SIGMOID:
+        h = torch.sigmoid(h)
+    elif out_act == L.ACT_SOFTMAX:
+        h = torch.softmax(h, -1)
+    return h
+
+
+def _native_plane(ws, col0, width, M):
+    """Columns [col0, col0 + width) of a pag_mlp128 workspace (uint8 tensor of "native" bf16 planes, include/pagnerf_hip.h) as a bf16 [M, width] tensor."""
+    Mp = (M + L.MLP128_BATCH - 1) // L.MLP128_BATCH * L.MLP128_BATCH
+    p = ws.view(torch.bfloat16)[Mp * col0:Mp * (col0 + width)].view(Mp // 32, width // 32, 4, 2, 32, 4)     # tile, block, g, lane half, sample, value
+    return p.permute(0, 4, 1, 2, 3, 5).reshape(Mp, width)[:M]
+
+
+class _FusedMLP128(torch.autograd.Function):
+    """One BasicDecoder at hidden width 128 (pag_mlp128_fwd / pag_mlp128_bwd): no host read of device data, no shape that depends on device
+    data, every buffer from torch's allocator - a captured step replays it."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, x2_index, in_dim, out_act, out_dtype, grouped, *wb):
+        _check_gpu(x1, x2, x2_index, *wb)
+        n_hidden = len(wb) // 2 - 1
+        Ws, bs = wb[:n_hidden + 1], wb[n_hidden + 1:]
+        if any(v is None for v in bs):
+            raise NotImplementedError("fused_mlp128 needs biases")
+        if grouped is not None:
+            M, k1 = x1.shape[1], 64
+        else:
+            M, k1 = x1.shape
+        x1 = x1.detach()
+        if not x1.is_contiguous():
+            x1 = x1.contiguous()
+        if x1.dtype not in (torch.float32, torch.bfloat16):
+            x1 = x1.float()
+        out_dim = Ws[-1].shape[0]
+        need_grad = _OUTER_GRAD and bool(any(ctx.needs_input_grad))
+        out = torch.empty(M, out_dim, device=x1.device, dtype=out_dtype)
+        a = L.Mlp128FwdArgs()
+        a.x1, a.x1_dtype, a.k1 = L.ptr(x1), L.dtype_code(x1), k1
+        if grouped is not None:
+            a.x1_layout, a.x1_levels, a.x1_feats = L.LAYOUT_XCD8, grouped[0], grouped[1]
+        if x2 is not None:
+            x2 = x2.detach().contiguous().float()
+            x2_index = x2_index.detach().contiguous()
+            if x2_index.dtype != torch.int32:
+                x2_index = x2_index.int()
+            a.x2, a.k2p, a.x2_index = L.ptr(x2), x2.shape[1], L.ptr(x2_index)
+        a.in_dim, a.n_hidden, a.hidden, a.out_dim = in_dim, n_hidden, Ws[0].shape[0], out_dim
+        Wc = [w.detach().contiguous().float() for w in Ws]
+        bc = [b.detach().contiguous().float() for b in bs]
+        for i in range(n_hidden + 1):
+            a.W[i], a.b[i] = L.ptr(Wc[i]), L.ptr(bc[i])
+        a.out_act, a.out, a.out_dtype = out_act, L.ptr(out), L._DT[out_dtype]
+        ws = None
+        if need_grad and M:          # under torch.no_grad() nothing is saved and no workspace is asked for
+            nbytes = L.load().pag_mlp128_workspace_bytes(M, n_hidden, out_dim, 1)
+            L.check(min(nbytes, 0), "pag_mlp128_workspace_bytes")
+            ws = torch.empty(nbytes, device=x1.device, dtype=torch.uint8)
+            a.workspace, a.workspace_bytes = L.ptr(ws), nbytes
+        if M:
+            _call("pag_mlp128_fwd", ctypes.byref(a), M, L.stream())
+        ctx.cfg = (in_dim, out_act, n_hidden, k1, grouped, M, out_dtype, tuple(x1.shape), x1.dtype)
+        ctx.x2_packs = None
+        ctx.save_for_backward(x2, x2_index, out, ws, *Wc)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return _FusedMLP128._backward_impl(ctx, g)
+
+    @staticmethod
+    def _backward_impl(ctx, g, dx1_into=None):
+        """dx1_into: an XCD8 gradient tensor of another decoder on the same input - this one's d x1 is added to it in place."""
+        in_dim, out_act, n_hidden, k1, grouped, M, out_dtype, x1_shape, x1_dtype = ctx.cfg
+        x2, x2_index, out, ws = ctx.saved_tensors[:4]
+        Wc = list(ctx.saved_tensors[4:])
+        dev, out_dim = out.device, out.shape[1]
+        need_dx = ctx.needs_input_grad[0]
+        need_dx2 = ctx.needs_input_grad[1] and x2 is not None
+        dx1 = (dx1_into if dx1_into is not None else torch.empty(x1_shape, device=dev, dtype=x1_dtype)) if need_dx else None
+        gW = [torch.empty_like(w) for w in Wc]
+        gb = [torch.empty(w.shape[0], device=dev) for w in Wc]
+        dx2 = torch.zeros_like(x2) if need_dx2 else None
+        if M == 0:
+            for t in gW + gb:
+                t.zero_()
+            return (dx1, dx2, None, None, None, None, None, *gW, *gb)
+        g = g.contiguous().to(out_dtype)       # grad_out travels in the output's dtype
+        a = L.Mlp128BwdArgs()
+        a.grad_out, a.out, a.out_dtype, a.out_act = L.ptr(g), L.ptr(out), L._DT[out_dtype], out_act
+        a.k1, a.k2p, a.in_dim, a.n_hidden, a.hidden, a.out_dim = k1, (x2.shape[1] if x2 is not None else 0), in_dim, n_hidden, Wc[0].shape[0], out_dim
+        if grouped is not None:
+            a.x1_layout, a.x1_levels, a.x1_feats = L.LAYOUT_XCD8, grouped[0], grouped[1]
+        nbytes = L.load().pag_mlp128_workspace_bytes(M, n_hidden, out_dim, 2)
+        L.check(min(nbytes, 0), "pag_mlp128_workspace_bytes")
+        bws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        a.workspace, a.workspace_bytes, a.bwd_workspace, a.bwd_workspace_bytes = L.ptr(ws), ws.numel(), L.ptr(bws), nbytes
+        a.dx1, a.dx1_dtype = L.ptr(dx1), (L.dtype_code(dx1) if need_dx else 0)
+        a.dx1_accumulate = 1 if (need_dx and dx1_into is not None) else 0
+        for i in range(n_hidden + 1):
+            a.W[i], a.dW[i], a.db[i] = L.ptr(Wc[i]), L.ptr(gW[i]), L.ptr(gb[i])
+        _call("pag_mlp128_bwd", ctypes.byref(a), M, L.stream())
+        if need_dx2:
+            # d x2[r] = (sum of dz_0 over the samples that gathered row r) @ W_0[:, k1:] - the per-ray view embedding's gradient (pose
+            # optimisation); dz_0 is the first plane of the backward workspace.  Not a hot path at this width: a segmented sum and one small matmul.
+            # With x2_packs (the tracer's calls) the sum is the segmented-sum launch, in a fixed order; without them it is index_add_, whose float
+            # atomics make d x2 - and only d x2: d x1, dW and db never pass through an atomic - differ in the last bits from run to run
+            dz0 = _native_plane(bws, 0, 128, M)
+            R = x2.shape[0]
+            if ctx.x2_packs is not None:                 # rows gathered pack by pack: one segmented-sum launch (deterministic)
+                pack_start, ray_of_pack = ctx.x2_packs
+                seg = composite_feats(dz0.contiguous(), torch.ones(M, device=dev), torch.ones(R, device=dev), pack_start, ray_of_pack, R)
+            else:
+                seg = torch.zeros(R, 128, device=dev).index_add_(0, x2_index.long(), dz0.float())
+            dx2[:, :in_dim - k1] = seg.float() @ Wc[0][:, k1:in_dim].bfloat16().float()          # the weights as the kernels round them
+        return (dx1, dx2, None, None, None, None, None, *gW, *gb)
+
+
+def fused_mlp128(x1, weights, biases, x2=None, x2_index=None, in_dim=None, out_act=L.ACT_NONE, mode=L.MLP_MFMA_BF16,
+                 out_dtype=torch.float32, x1_grouped=None, x2_packs=None):
+    """fused_mlp at hidden width 128: 1 - 3 Linear + ReLU layers, then lout [+ sigmoid / softmax], in one launch (pag_mlp128_fwd).  Same arguments
+    as fused_mlp; bf16 operands on the matrix cores only (the precision='fp32' path at this width is wide_mlp_reference)."""
+    if mode != L.MLP_MFMA_BF16:
+        raise NotImplementedError("fused_mlp128 runs in MLP_MFMA_BF16 mode; the fp32 form at width 128 is ops.wide_mlp_reference")
+    if in_dim is None:
+        in_dim = weights[0].shape[1]
+    out = _apply_decoder(_FusedMLP128, x1, x2, x2_index, int(in_dim), out_act, out_dtype, x1_grouped, *weights, *biases)
+    if x2_packs is not None and x2 is not None and x2.requires_grad and out.grad_fn is not None:
+        out.grad_fn.x2_packs = x2_packs      # (pack_start, ray_of_pack): x2_index is constant inside each pack (d/d x2 only)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ ray march
 def raymarch_ray(origins, dirs, dist_min, dist_max, num_samples, jitter=None, occupancy_bits=None, blas_level=7, want_ridx64=False):
     """'ray'-mode march + occupancy filter + pack.  Returns
