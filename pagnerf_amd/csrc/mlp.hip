@@ -592,6 +592,13 @@ __global__ __launch_bounds__(256, (OBMAX > 2 ? FWD_WAVES_WIDE : FWD_WAVES_NARROW
                 xf[s] = load8(p.x2 + (int64_t)ray * p.k2p + (f0 - p.k1));
             else
                 xf[s] = zero8();
+            // columns at or beyond in_dim are absent, whatever they hold: a NaN there must not meet its zero weight (the group of 8 that
+            // straddles in_dim and those behind it; XCD8 has in_dim = levels * feats, its padding positions are the encoders' zeros)
+            if (!p.grp_L && f0 + 8 > p.in_dim) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (f0 + j >= p.in_dim) xf[s][j] = (bf16_t)0.0f;
+            }
         }
     };
     const int64_t tile_step = (int64_t)gridDim.x * 4;
