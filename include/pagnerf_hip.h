@@ -1146,6 +1146,72 @@ int pag_prepare_views(const void *src, int B, int H0, int W0, int C0, int mip, i
                       int64_t view_offset, int64_t V, float *imgs, unsigned char *masks, float *origins, float *dirs, void *stream);
 int pag_prepare_labels(const pag_label_plane *planes, int n_planes, int B, int H0, int W0, int mip, int64_t view_offset, int64_t V, void *stream);
 
+/* The BUP20 loader's device work (datasets/formats/bup20.py:189-234 on agrobot_base.py:442-461 the depth filter of the detector's instance masks and
+ * :524-547 the label planes from COCO annotations; additive, ABI 14): bup20.hip.  pagnerf_amd/bup20.py holds the tensor-op / NumPy forms that define the
+ * results (`polygon_keys_reference`, `coco_labels_reference`, `pred_stats_reference`, `prepare_frames_reference`) and builds the tables (`coco_tables`);
+ * every output is bit for bit the definition.
+ *
+ * Ground-truth labels.  All tables are DEVICE int32 arrays for the B frames of a chunk (n_* are host numbers):
+ *   verts [n_verts, 2]        the rounded vertices trunc(5 v + 0.5) of every polygon part, ring not closed
+ *   part_vert_begin [n_parts+1]   a part's vertices; an RLE part has none
+ *   point_begin [n_verts+1]   prefix sums of the per-edge boundary point counts max(|dX|, |dY|) + 1 (edge e starts at vertex e)
+ *   part_key_begin [n_parts+1]    a part's slice of `keys`: an upper bound of its key count (polygon) or its count (RLE)
+ *   part_key_count [n_parts]  keys in the slice: written per polygon part, given for an RLE part, whose keys are in `keys` already
+ *   ann_part_begin [n_anns+1], ann_label [n_anns]    an annotation's parts and its class index
+ *   ann_cover [n_anns]        H0 W0 for an annotation known to cover the image, else 0; the counting pass adds the covered pixels of the annotations
+ *                             in cand [n_cand] (so one pag_coco_labels call per set of tables)
+ *   frame_ann_begin [B+1], frame_labelled [B]        a frame's annotations; a frame with frame_labelled 0 becomes -1 everywhere
+ *   max_part_keys             the largest polygon part's key bound, computed by the host from the vertices
+ * pag_coco_keys: one workgroup per polygon part walks its boundary points (a lane per consecutive pair, the points from their edge's closed form with
+ * one fp64 line each), keeps the pairs that cross a pixel column, and sorts the part's keys X H0 + Y in LDS.  pag_coco_labels: a thread per output pixel
+ * (y, x) of the h x w = H0 / 2^mip x W0 / 2^mip plane reads source pixel (y 2^mip, x 2^mip): covered by a part iff the number of its keys <= x H0 + y is
+ * odd, by an annotation iff by any of its parts; semantics = min(max_label, sum of the covering annotations' labels, starting again from zero at an
+ * annotation that covers all H0 W0 pixels), instance = 1 + the index within the frame of the last covering annotation, else 0; int64 [V, h, w, 1] each,
+ * written at view view_offset + b, either may be NULL.  With n_cand > 0 a counting launch precedes it (integer atomics, one per wave).
+ * Refused (PAG_ERR_ARG) before any launch: max_part_keys above PAG_COCO_MAX_PART_KEYS (that image takes the tensor-op form), (W0 + 1) H0 >= 2^31, B or
+ * n_cand outside [0, 65535], negative counts, NULL tables that a count says are read, mip outside [0, 8], sizes not divisible by 2^mip, views outside
+ * [0, V). */
+#define PAG_COCO_MAX_PART_KEYS 4096
+typedef struct pag_coco_tables {
+    const int32_t *verts, *part_vert_begin, *point_begin, *part_key_begin;
+    int32_t *part_key_count, *keys;
+    const int32_t *ann_part_begin, *ann_label;
+    int32_t *ann_cover;
+    const int32_t *cand, *frame_ann_begin, *frame_labelled;
+    int32_t n_verts, n_parts, n_anns, n_cand, B, max_part_keys;
+} pag_coco_tables;
+int pag_coco_keys(const pag_coco_tables *tables, int H0, int W0, void *stream);
+int pag_coco_labels(const pag_coco_tables *tables, int H0, int W0, int mip, int max_label, int64_t view_offset, int64_t V, int64_t *semantics,
+                    int64_t *instance, void *stream);
+/* pag_bup20_pred_stats: counts int32 [B, n_ids, 2], ZEROED by the caller, += per view and instance id (pixels, pixels whose depth d = (float)raw * 0.001f
+ * has 0 < d <= max_depth); inst DEVICE int32 [B, H0, W0] with ids in [0, n_ids), depth DEVICE uint16 [B, H0, W0].  Integer atomics (a workgroup
+ * histogram in LDS up to 2048 ids).  Refused: B outside [0, 65535], H0 W0 outside [1, 2^24), n_ids outside [1, 2^24], max_depth <= 0, NULL buffers.
+ * pag_bup20_prepare: one launch per chunk, a thread per output pixel, every destination may be NULL, chunk view b goes to view view_offset + b:
+ *   kept(id) = 2 valid > total from counts (NULL: everything is kept); inst' = inst if kept else 0; sem' = 0 where inst' = 0 (with counts only)
+ *   semantics_pred, instance_pred int64 [V, h, w, 1]: sem', inst' at source pixel (y f, x f), f = 2^mip
+ *   imgs f32 [V, h, w, 3], depths, sem_conf_out, inst_conf_out f32 [V, h, w, 1]: f = 1 the source value, else ((0.25 a + 0.25 b) + 0.25 c) + 0.25 d of
+ *   the source pixels at offsets f/2 - 1 and f/2 in each axis (a top-left, b top-right, c bottom-left, d bottom-right), fp32, not contracted; an image
+ *   value is (float)u8 / 255f, a depth (float)raw * 0.001f, a confidence 1 where the filter removed the pixel's instance.  masks uint8 [V, h, w, 1]: 1
+ *   with C0 = 3; with C0 = 4 alpha > 0.5 and the image composited as pag_prepare_views does.
+ * Refused before any launch: mip outside [0, 8], B outside [0, 65535], sizes < 1, not divisible by f or above 2^30 pixels, views outside [0, V), C0
+ * other than 3 / 4, an unknown background, a destination without its source, counts without inst or with 2^24 pixels or more. */
+typedef struct pag_bup20_prepare_args {
+    const unsigned char *img;          /* [B, H0, W0, C0] */
+    const uint16_t *depth;             /* [B, H0, W0] */
+    const int32_t *sem, *inst;         /* [B, H0, W0] */
+    const float *sem_conf, *inst_conf; /* [B, H0, W0] */
+    const int32_t *counts;             /* [B, n_ids, 2] or NULL */
+    int32_t B, H0, W0, C0, mip, bg, n_ids;
+    int64_t view_offset, V;
+    float *imgs;
+    unsigned char *masks;
+    float *depths;
+    int64_t *semantics_pred, *instance_pred;
+    float *sem_conf_out, *inst_conf_out;
+} pag_bup20_prepare_args;
+int pag_bup20_pred_stats(const int32_t *inst, const void *depth_u16, int B, int H0, int W0, float max_depth, int n_ids, int32_t *counts, void *stream);
+int pag_bup20_prepare(const pag_bup20_prepare_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

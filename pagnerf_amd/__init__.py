@@ -30,9 +30,11 @@
     optim : Adam (torch.optim.Adam's interface on pag_adam_step) (optim.py) <- config_parser.py:667-673, trainer.py:583
     trainer: PanopticTrainer, LODAnneling (trainer.py) <- pc_nerf/trainer.py on wisp's BaseTrainer, utils/lod_anneling.py
     config : load_config, register_class, build_from_config (config.py) <- config_parser.py:557-603, :679-781
-    train  : `python -m pagnerf_amd.train` (train.py) <- main_interactive.py, on a NeRF-standard folder or arrays stored as .npz
+    train  : `python -m pagnerf_amd.train` (train.py) <- main_interactive.py, on a NeRF-standard folder, a BUP20 folder or arrays stored as .npz
     formats: load_nerf_standard, standard_cameras, decode_image, prepare_views_reference, prepare_labels_reference (formats.py)
              <- datasets/formats/nerf_standard.py, the label resample of datasets/formats/bup20.py:203-229 (`python -m pagnerf_amd.formats`: folder -> .npz)
+    bup20  : load_bup20, polygon_mask_reference, coco_labels_reference, pred_stats_reference, prepare_frames_reference, bup20_cameras (bup20.py)
+             <- datasets/formats/bup20.py:89-315 on datasets/formats/agrobot_base.py:22-556 (`python -m pagnerf_amd.bup20`: folder -> .npz)
 
 All compute goes through libpagnerf_hip.so (include/pagnerf_hip.h); there is no CPU fallback.
 """

@@ -134,6 +134,24 @@ class LabelPlane(ctypes.Structure):
 
 PREPARE_MAX_PLANES = 8
 
+
+class CocoTables(ctypes.Structure):
+    """pag_coco_tables (include/pagnerf_hip.h)."""
+    _fields_ = [("verts", c_vp), ("part_vert_begin", c_vp), ("point_begin", c_vp), ("part_key_begin", c_vp), ("part_key_count", c_vp), ("keys", c_vp),
+                ("ann_part_begin", c_vp), ("ann_label", c_vp), ("ann_cover", c_vp), ("cand", c_vp), ("frame_ann_begin", c_vp), ("frame_labelled", c_vp),
+                ("n_verts", c_i32), ("n_parts", c_i32), ("n_anns", c_i32), ("n_cand", c_i32), ("B", c_i32), ("max_part_keys", c_i32)]
+
+
+class Bup20PrepareArgs(ctypes.Structure):
+    """pag_bup20_prepare_args (include/pagnerf_hip.h)."""
+    _fields_ = [("img", c_vp), ("depth", c_vp), ("sem", c_vp), ("inst", c_vp), ("sem_conf", c_vp), ("inst_conf", c_vp), ("counts", c_vp),
+                ("B", c_i32), ("H0", c_i32), ("W0", c_i32), ("C0", c_i32), ("mip", c_i32), ("bg", c_i32), ("n_ids", c_i32),
+                ("view_offset", c_i64), ("V", c_i64), ("imgs", c_vp), ("masks", c_vp), ("depths", c_vp), ("semantics_pred", c_vp),
+                ("instance_pred", c_vp), ("sem_conf_out", c_vp), ("inst_conf_out", c_vp)]
+
+
+COCO_MAX_PART_KEYS = 4096           # PAG_COCO_MAX_PART_KEYS
+
 VIS_PICTURES, VIS_LABELS, VIS_MAX_ID = 15, 6, 1023
 
 
@@ -257,6 +275,10 @@ _SIGS = {
     "pag_vis_paint": (c_i32, [ctypes.POINTER(VisArgs), c_vp]),
     "pag_prepare_views": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_f32, c_f32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pag_prepare_labels": (c_i32, [ctypes.POINTER(LabelPlane), c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp]),
+    "pag_coco_keys": (c_i32, [ctypes.POINTER(CocoTables), c_i32, c_i32, c_vp]),
+    "pag_coco_labels": (c_i32, [ctypes.POINTER(CocoTables), c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "pag_bup20_pred_stats": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp]),
+    "pag_bup20_prepare": (c_i32, [ctypes.POINTER(Bup20PrepareArgs), c_vp]),
 }
 
 # The twelve grid-encoder entry points, pag_{hash,permuto}_encode_{fwd,fwd_add,bwd,bwd_set,bwd_xyz,bwd_rays}: the operation's leading arguments, the

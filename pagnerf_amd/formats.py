@@ -23,7 +23,7 @@ Both are arguments or one function, so a pinned value replaces them in one place
 THE LABEL EXTENSION is this package's own, not part of the NeRF-standard / instant-ngp layout: a frame may carry `semantic_path`, `instance_path`,
 `semantic_pred_path`, `instance_pred_path`, each an 8-bit grey PNG of the image's size; they become the modes `semantics`, `instance`, `semantics_pred`,
 `instance_pred` (int64 [V,h,w,1]).  Top-level `num_classes`, `num_instances`, `things_ids`, `stuff_ids` become `semantic_info`.  A label key on some
-frames only is an error.  BUP20's own loader (agrobot_base.py: pycocotools, cv2, detector predictions) stays out of scope.
+frames only is an error.  BUP20's own layout (agrobot_base.py: COCO annotations, detector predictions) is read by bup20.py.
 """
 import argparse
 import concurrent.futures

@@ -2099,3 +2099,137 @@ def prepare_labels(planes, mip, view_offset=0):
         a.src, a.dst = src.data_ptr(), dst.data_ptr()
     B, H0, W0 = size
     _call("pag_prepare_labels", arr, len(planes), B, H0, W0, mip, view_offset, V, L.stream())
+
+
+# ------------------------------------------------------------------------------------------- BUP20 loader
+_COCO_ARRAYS = ("verts", "part_vert_begin", "point_begin", "part_key_begin", "part_key_count", "keys", "ann_part_begin", "ann_label", "ann_cover", "cand",
+                "frame_ann_begin", "frame_labelled")
+
+
+class CocoDeviceTables:
+    """The tables of bup20.coco_tables on the GPU: the tensors (kept alive here) and the pag_coco_tables struct that points at them."""
+
+    def __init__(self, tensors, max_part_keys):
+        self.tensors = tensors
+        n = {k: t.numel() for k, t in tensors.items()}
+        self.B, n_parts, n_anns = n["frame_labelled"], n["part_key_count"], n["ann_label"]
+        if (n["part_vert_begin"], n["part_key_begin"], n["ann_part_begin"], n["ann_cover"], n["frame_ann_begin"], n["point_begin"]) != \
+                (n_parts + 1, n_parts + 1, n_anns + 1, n_anns, self.B + 1, n["verts"] // 2 + 1):
+            raise RuntimeError("coco_upload: table lengths disagree: %r" % (n,))
+        s = L.CocoTables()
+        for k, t in tensors.items():
+            setattr(s, k, t.data_ptr() if t.numel() else None)
+        s.n_verts, s.n_parts, s.n_anns, s.n_cand, s.B, s.max_part_keys = n["verts"] // 2, n_parts, n_anns, n["cand"], self.B, int(max_part_keys)
+        self.struct = s
+
+
+def coco_upload(tables, device):
+    """bup20.coco_tables' dict of int32 numpy arrays -> CocoDeviceTables on `device`.  The offsets are checked here, on the host, so that no kernel reads
+    or writes outside a table."""
+    t = {k: tables[k] for k in _COCO_ARRAYS}
+    for k, a in t.items():
+        if a.dtype.name != "int32":
+            raise RuntimeError("coco_upload: %s is %s, int32 expected" % (k, a.dtype))
+    nv, nk, n_parts, n_anns = len(t["verts"].reshape(-1)) // 2, len(t["keys"]), len(t["part_key_count"]), len(t["ann_label"])
+
+    def rising(name, top):
+        a = t[name]
+        if len(a) < 1 or a[0] != 0 or (a[1:] < a[:-1]).any() or a[-1] != top:
+            raise RuntimeError("coco_upload: %s does not rise from 0 to %d" % (name, top))
+
+    rising("part_vert_begin", nv)
+    rising("part_key_begin", nk)
+    rising("ann_part_begin", n_parts)
+    rising("frame_ann_begin", n_anns)
+    if len(t["point_begin"]) != nv + 1 or t["point_begin"][0] != 0 or (t["point_begin"][1:] <= t["point_begin"][:-1]).any():
+        raise RuntimeError("coco_upload: point_begin does not rise strictly from 0 over %d edges" % nv)
+    if n_parts and (t["part_key_count"] > t["part_key_begin"][1:] - t["part_key_begin"][:-1]).any():
+        raise RuntimeError("coco_upload: a part_key_count beyond its slice of keys")
+    if len(t["cand"]) and (int(t["cand"].min()) < 0 or int(t["cand"].max()) >= n_anns):
+        raise RuntimeError("coco_upload: a candidate outside the annotations")
+    return CocoDeviceTables({k: torch.from_numpy(a.reshape(-1)).to(device) for k, a in t.items()}, tables["max_part_keys"])
+
+
+def coco_keys(dev, H0, W0):
+    """pag_coco_keys: the sorted keys of every polygon part of the uploaded tables (bup20.polygon_keys_reference is the definition).  A part whose key bound
+    exceeds COCO_MAX_PART_KEYS is refused before any launch."""
+    _call("pag_coco_keys", ctypes.byref(dev.struct), int(H0), int(W0), L.stream())
+
+
+def coco_labels(dev, H0, W0, mip, max_label, view_offset=0, semantics=None, instance=None):
+    """pag_coco_labels after coco_keys: views [view_offset, view_offset + B) of semantics / instance int64 [V, h, w, 1] at h = H0 / 2^mip
+    (bup20.coco_labels_reference is the definition); frames without labels become -1.  Once per uploaded tables (the counting pass adds into them)."""
+    name = "coco_labels"
+    mip, view_offset, f = int(mip), int(view_offset), 1 << int(mip)
+    if not 0 <= mip <= 8 or H0 % f or W0 % f:
+        raise RuntimeError("%s: mip %d with source size %d x %d" % (name, mip, H0, W0))
+    V = _prepare_dst(name, "semantics", semantics, torch.int64, None, H0 // f, W0 // f, 1, view_offset, dev.B)
+    V = _prepare_dst(name, "instance", instance, torch.int64, V, H0 // f, W0 // f, 1, view_offset, dev.B)
+    if V is None:
+        return
+    p = lambda t: t.data_ptr() if t is not None else None
+    _call("pag_coco_labels", ctypes.byref(dev.struct), int(H0), int(W0), mip, int(max_label), view_offset, V, p(semantics), p(instance), L.stream())
+
+
+def _bup20_plane(name, what, t, dtype, shape):
+    if t is None:
+        return
+    _check_gpu(t)
+    if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+        raise RuntimeError("%s: %s is a contiguous %s %s, got %s %s" % (name, what, dtype, shape, t.dtype, tuple(t.shape)))
+
+
+def bup20_pred_stats(inst, depth_raw, max_depth, n_ids):
+    """pag_bup20_pred_stats: inst int32 [B, H0, W0] with ids in [0, n_ids), depth_raw int16 bit patterns of the 16-bit depth [B, H0, W0] -> a new int32
+    [B, n_ids, 2] of (pixels, pixels with 0 < depth <= max_depth) per view and id (bup20.pred_stats_reference is the definition)."""
+    name = "bup20_pred_stats"
+    _check_gpu(inst, depth_raw)
+    if inst.dim() != 3:
+        raise RuntimeError("%s: inst is [B, H0, W0], got %s" % (name, tuple(inst.shape)))
+    B, H0, W0 = inst.shape
+    _bup20_plane(name, "inst", inst, torch.int32, (B, H0, W0))
+    _bup20_plane(name, "depth_raw", depth_raw, torch.int16, (B, H0, W0))
+    counts = torch.zeros(B, int(n_ids), 2, dtype=torch.int32, device=inst.device)
+    _call("pag_bup20_pred_stats", inst.data_ptr(), depth_raw.data_ptr(), B, H0, W0, float(max_depth), int(n_ids), counts.data_ptr(), L.stream())
+    return counts
+
+
+def bup20_prepare(img_u8, mip, bg_color="white", view_offset=0, depth_raw=None, sem=None, inst=None, sem_conf=None, inst_conf=None, counts=None, imgs=None,
+                  masks=None, depths=None, semantics_pred=None, instance_pred=None, sem_conf_out=None, inst_conf_out=None):
+    """pag_bup20_prepare for the frames of a chunk (bup20.prepare_frames_reference is the definition): img_u8 uint8 [B, H0, W0, 3 or 4], depth_raw int16 bit
+    patterns, sem / inst int32, sem_conf / inst_conf f32 [B, H0, W0], counts from bup20_pred_stats or None -> views [view_offset, view_offset + B) of the
+    requested destinations, each the whole dataset's tensor: imgs f32 [V, h, w, 3], masks bool (or uint8), depths / sem_conf_out / inst_conf_out f32,
+    semantics_pred / instance_pred int64 [V, h, w, 1]."""
+    name = "bup20_prepare"
+    _check_gpu(img_u8, counts)
+    view_offset = int(view_offset)
+    mip, B, H0, W0, h, w = _prepare_sizes(name, img_u8, mip, 4)
+    C0 = img_u8.shape[3]
+    if C0 not in (3, 4):
+        raise RuntimeError("%s: %d source channels, 3 or 4 expected" % (name, C0))
+    if bg_color not in ("white", "black"):
+        raise RuntimeError("%s: bg_color %r is neither 'white' nor 'black'" % (name, bg_color))
+    if masks is not None and masks.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError("%s: masks is bool or uint8, got %s" % (name, masks.dtype))
+    for what, t, dtype in (("depth_raw", depth_raw, torch.int16), ("sem", sem, torch.int32), ("inst", inst, torch.int32), ("sem_conf", sem_conf, torch.float32),
+                           ("inst_conf", inst_conf, torch.float32)):
+        _bup20_plane(name, what, t, dtype, (B, H0, W0))
+    n_ids = 0
+    if counts is not None:
+        if counts.dtype != torch.int32 or counts.dim() != 3 or counts.shape[0] != B or counts.shape[2] != 2 or not counts.is_contiguous():
+            raise RuntimeError("%s: counts is a contiguous int32 [%d, n_ids, 2], got %s %s" % (name, B, counts.dtype, tuple(counts.shape)))
+        n_ids = counts.shape[1]
+    V = None
+    for what, t, dtype, C in (("imgs", imgs, torch.float32, 3), ("masks", masks, masks.dtype if masks is not None else None, 1),
+                              ("depths", depths, torch.float32, 1), ("semantics_pred", semantics_pred, torch.int64, 1),
+                              ("instance_pred", instance_pred, torch.int64, 1), ("sem_conf_out", sem_conf_out, torch.float32, 1),
+                              ("inst_conf_out", inst_conf_out, torch.float32, 1)):
+        V = _prepare_dst(name, what, t, dtype, V, h, w, C, view_offset, B)
+    if V is None:
+        return
+    p = lambda t: t.data_ptr() if t is not None else None
+    a = L.Bup20PrepareArgs(img=img_u8.data_ptr(), depth=p(depth_raw), sem=p(sem), inst=p(inst), sem_conf=p(sem_conf), inst_conf=p(inst_conf), counts=p(counts),
+                           B=B, H0=H0, W0=W0, C0=C0, mip=mip, bg=L.BG_WHITE if bg_color == "white" else L.BG_BLACK, n_ids=n_ids, view_offset=view_offset, V=V,
+                           imgs=p(imgs), masks=p(masks), depths=p(depths), semantics_pred=p(semantics_pred), instance_pred=p(instance_pred),
+                           sem_conf_out=p(sem_conf_out), inst_conf_out=p(inst_conf_out))
+    _call("pag_bup20_prepare", ctypes.byref(a), L.stream())

@@ -4,8 +4,11 @@
 The native counterpart of the reference's main_interactive.py: a shipped YAML, a dataset, and the trainer of trainer.py.
 
 A dataset is a NeRF-standard folder (transforms*.json and image files; formats.load_nerf_standard with the YAML's `mip`, `bg_color` and
-`dataset_num_workers`, split 'train' for --dataset and 'val' for --val-dataset; without --val-dataset the folder's own 'val' split when it has one), or
-an .npz of arrays (python -m pagnerf_amd.formats writes one from a folder).  The .npz holds the arrays of the dict MultiviewDataset.init() leaves:
+`dataset_num_workers`, split 'train' for --dataset and 'val' for --val-dataset; without --val-dataset the folder's own 'val' split when it has one), a
+BUP20 folder (it holds BUP_20.json or CKA_sweet_pepper_2020_summer.json, or the YAML says `multiview_dataset_format: bup20` and the folder has no
+transforms*.json; bup20.load_bup20 with the YAML's `load_modes`, `class_labels`, `dataset_center_idx`, `pose_src`, `max_depth`, `scale`, `offset` and
+`model_rescaling`; the one folder serves both splits), or an .npz of arrays (python -m pagnerf_amd.formats or python -m pagnerf_amd.bup20 writes one
+from a folder).  The .npz holds the arrays of the dict MultiviewDataset.init() leaves:
 
     imgs [V,H,W,3] float32 and every further per-view mode (semantics, instance, semantics_pred, instance_pred, sem_conf, inst_conf ...) [V,H,W,C]
     base_rays_origins, base_rays_dirs [H,W,3]   the camera-frame rays the views share (pose optimisation), base_rays_range [2] = (near, far)
@@ -14,7 +17,7 @@ an .npz of arrays (python -m pagnerf_amd.formats writes one from a folder).  The
     num_classes, num_instances (scalars), things_ids, stuff_ids (int arrays)    the `semantic_info` lists
     optional: scale (scalar), filenames [V]
 
-The NeRF-standard loader, with this package's label extension, is formats.py; BUP20's own loader (agrobot_base.py) is not part of this package.
+The NeRF-standard loader, with this package's label extension, is formats.py; BUP20's own loader (bup20.py, agrobot_base.py) is bup20.py.
 """
 import argparse
 import logging
@@ -55,15 +58,35 @@ def load_npz_dataset(path, device):
     return ds
 
 
+def is_bup20(path, cfg):
+    """Whether the folder `path` goes to bup20.load_bup20: it holds BUP_20.json / CKA_sweet_pepper_2020_summer.json, or the YAML's
+    multiview_dataset_format is one of the reference's four spellings of bup20 and the folder is not a NeRF-standard one (no transforms*.json)."""
+    import glob
+    from . import bup20
+    if bup20.is_bup20_folder(path):
+        return True
+    return cfg.get("multiview_dataset_format") in bup20.FORMAT_NAMES and not glob.glob(os.path.join(path, "transforms*.json"))
+
+
 def load_dataset(path, split, cfg, device):
-    """--dataset / --val-dataset: a folder goes to formats.load_nerf_standard (split `split`; mip, bg_color and dataset_num_workers from the YAML
-    namespace), anything else to load_npz_dataset."""
+    """--dataset / --val-dataset: a BUP20 folder (is_bup20) goes to bup20.load_bup20 with load_modes, class_labels, dataset_center_idx, pose_src,
+    max_depth, scale, offset and model_rescaling from the YAML namespace (and `seq_num_frames`, this package's own key: the reference fixes the window at
+    40), any other folder to formats.load_nerf_standard (split `split`; mip, bg_color
+    and dataset_num_workers from the namespace for both), anything else to load_npz_dataset."""
     path = os.path.expanduser(path)
     if not os.path.isdir(path):
         return load_npz_dataset(path, device)
-    from .formats import load_nerf_standard
-    return load_nerf_standard(path, split=split, mip=int(cfg.get("mip") or 0), bg_color=cfg.get("bg_color") or "white", device=device,
-                              num_workers=int(cfg.get("dataset_num_workers") or 0))
+    from . import bup20, formats
+    common = dict(mip=int(cfg.get("mip") or 0), bg_color=cfg.get("bg_color") or "white", device=device, num_workers=int(cfg.get("dataset_num_workers") or 0))
+    if is_bup20(path, cfg):
+        max_depth = cfg.get("max_depth")
+        return bup20.load_bup20(path, split, load_modes=cfg.get("load_modes") or (), class_labels=cfg.get("class_labels") or (),
+                                dataset_center_idx=int(cfg.get("dataset_center_idx") or 0), pose_src=cfg.get("pose_src") or "odom",
+                                max_depth=-1 if max_depth is None else max_depth, scale=cfg.get("scale"), offset=cfg.get("offset"),
+                                model_rescaling=cfg.get("model_rescaling") or "snap_to_bottom", seq_num_frames=int(cfg.get("seq_num_frames") or 40),
+                                add_noise_to_train_poses=bool(cfg.get("add_noise_to_train_poses")), dataset_mode=cfg.get("dataset_mode") or "label_window",
+                                **common)
+    return formats.load_nerf_standard(path, split=split, **common)
 
 
 def save_map(trainer, dataset, path):
@@ -112,8 +135,11 @@ def main(argv=None):
     dataset = load_dataset(args.dataset, "train", cfg, device)
     val_root = args.val_dataset
     if not val_root and os.path.isdir(os.path.expanduser(args.dataset)):
-        from .formats import transforms_files
-        val_root = args.dataset if "val" in transforms_files(args.dataset) else None
+        if is_bup20(os.path.expanduser(args.dataset), cfg):
+            val_root = args.dataset                                         # a BUP20 folder serves both splits
+        else:
+            from .formats import transforms_files
+            val_root = args.dataset if "val" in transforms_files(args.dataset) else None
     val_dataset = load_dataset(val_root, "val", cfg, device) if val_root else None
     _, trainer = config.build_from_config(cfg, dataset, val_dataset, device=device)
     if args.resume:
