@@ -764,6 +764,41 @@ int pag_map_select(const float *points_in, int64_t n, const float *value, float 
                    int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Fused panoptic voxel map: the exported points of all views reduced to one row per occupied voxel, and the per-instance table of that map
+ * (csrc/voxelmap.hip).  Additive to ABI 14.  The two reductions are ordered appends behind a device counter with the contract of the map export
+ * above: kept runs land in row order behind *count (i64 [1], device), a slot at or past `cap` is counted and not written, three launches, no host
+ * synchronisation, no float atomics.  Every sum is taken in an order fixed by the sorted row sequence and a compile-time group width (16 lanes per
+ * voxel run, 256 threads per label run), so the results are bit-identical from run to run and however the points were chunked before the sort.
+ * n = 0 is a no-op; n <= 2^31.
+ * ------------------------------------------------------------------------------------------ */
+
+/* Workspace of one fuse / table call over n rows (0 for n outside (0, 2^31]); about n / 21 bytes. */
+int64_t pag_voxel_workspace_bytes(int64_t n);
+
+/* points f32 [n,3] -> keys i64 [n]: per axis i = floorf((p - origin) / voxel_size), both roundings in fp32 and in that order, a true division;
+ * key = iz | iy << 21 | ix << 42 (x slowest).  INT64_MAX when a coordinate is not finite, an index is < 0 or >= 2^21, or - limits_host f32 [2,3]
+ * = [[min], [max]] given - the point is not strictly inside the box.  origin_host f32 [3] and limits_host are host arrays.  One launch. */
+int pag_voxel_keys(const float *points, int64_t n, const float *origin_host, float voxel_size, const float *limits_host, int64_t *keys,
+                   void *stream);
+
+/* Rows ordered by (key, id): keys i64 [n] ascending (the INT64_MAX rows last), ids i64 [n] ascending inside a run of equal keys, points f32 [n,3]
+ * and color f32 [n,3] (or NULL) permuted alike.  Every run of equal keys with at least min_votes (>= 1) rows gives one output row, in key order:
+ * points / color f32 [cap,3] the mean of the members (fp32 sum / (float) rows), ids_out i64 [cap] the most frequent id of the run (on equal counts
+ * the smaller id, signed), count_out i32 [cap] the rows, agreement f32 [cap] = (float) winner's rows / (float) rows, voxels i32 [cap,3] = (ix, iy, iz). */
+int pag_voxel_fuse(const int64_t *keys, const int64_t *ids, const float *points, const float *color, int64_t n, int64_t min_votes,
+                   float *points_out, float *color_out, int64_t *ids_out, int32_t *count_out, float *agreement, int32_t *voxels,
+                   int64_t cap, int64_t *count, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Voxel rows ordered by label (labels i64 [n] ascending; points f32 [n,3], color f32 [n,3] or NULL, voxel_count i32 [n] permuted alike).  Every run
+ * of a label that is not one of the n_ignore (<= 8) labels of ignore_host (host array) gives one row, in label order: ids_out i64 [cap], voxels_out
+ * i64 [cap] the rows, observations i64 [cap] the sum of voxel_count, centroid f32 [cap,3] the mean of the points, bbox_min / bbox_max f32 [cap,3],
+ * color_out f32 [cap,3] the mean colour (untouched without color). */
+int pag_label_table(const int64_t *labels, const float *points, const float *color, const int32_t *voxel_count, int64_t n,
+                    const int64_t *ignore_host, int n_ignore, int64_t *ids_out, int64_t *voxels_out, int64_t *observations,
+                    float *centroid, float *bbox_min, float *bbox_max, float *color_out, int64_t cap, int64_t *count, void *workspace,
+                    int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-ray training loss of the rendered buffers (pc_nerf/trainer.py:443-446 rgb, :459-465 semantics,
  * loss/lin_assignment_things.py:80 instance term after the assignment) - one launch forward, one backward
  * ------------------------------------------------------------------------------------------ */

@@ -1,0 +1,417 @@
+// Fused panoptic voxel map: the exported map points of all views (map.hip) reduced to one row per occupied voxel, and the per-instance table of it.
+//
+// As tensor ops the fusion is `unique` over voxel keys, `unique` over (key, id) pairs, several index_add_ calls, a scatter-arg-max with tie handling
+// and a boolean gather: about twenty launches and, the output sizes being dynamic, several host synchronisations.  Here:
+//   1. voxel_keys_kernel    one thread per point: key = iz | iy << 21 | ix << 42 with i = floorf((p - o) / v) per axis (x slowest: the lattice order of
+//                           get_dense_occupied_points), INT64_MAX for a dropped row
+//   -  the host layer orders the rows by (key, id) with two stable torch.sort calls (rocPRIM's radix sort; plumbing)
+//   2. an ORDERED APPEND over the sorted rows, map.hip's count / scan / write with "row starts a kept run" as the predicate:
+//        vox_count_kernel   the kept run heads of each 256-row block
+//        vox_scan_kernel    one workgroup: exclusive scan of the block counts on top of the device counter
+//        voxel_fuse_kernel  a 16-lane group per kept run / label_table_kernel: the 256-thread workgroup per kept run
+// A run's end is found by a galloping upper_bound over the sorted keys (ids inside a voxel run are sorted too: the same search gives the id runs).
+// Lane j of a group takes rows j, j + W, ... of the run in that order, the lane partials are combined by an xor-shuffle tree (W = 16) or by the
+// shuffle tree of each wave and then the four waves in wave order (W = 256): the order of every sum depends on the sorted sequence and W alone, not
+// on the grid, the occupancy or how the points were chunked.  No float atomics; rows at or past the capacity are counted and not written.
+// The vote: the id with the most rows in the run, on equal counts the smaller id (signed): a max-reduction over the id-run heads under the total
+// order (length descending, id ascending).  Compiled with -ffp-contract=off: the key is two roundings (subtract, divide), the mean one division.
+#include "common.h"
+
+namespace {
+
+constexpr int VOX_BLOCK = 256;
+constexpr int VOX_WAVES = VOX_BLOCK / PAG_WAVE;
+constexpr int VOX_GROUP = 16;                       // lanes per voxel run
+constexpr int VOX_GROUPS = PAG_WAVE / VOX_GROUP;    // runs a wave serves per pass
+constexpr int VOX_MAX_IGNORE = 8;
+constexpr int64_t VOX_DROPPED = INT64_MAX;
+constexpr int64_t VOX_MAX_ROWS = (int64_t)1 << 31;
+constexpr float VOX_AXIS = 2097152.0f;              // 2^21 cells per axis
+
+struct KeyArgs {
+    const float *points;
+    int64_t n;
+    float origin[3], voxel_size;
+    int has_limits;
+    float lo[3], hi[3];
+    int64_t *keys;
+};
+
+__global__ __launch_bounds__(VOX_BLOCK) void voxel_keys_kernel(KeyArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    bool ok = true;
+    int64_t key = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float p = a.points[i * 3 + k];
+        const float f = floorf((p - a.origin[k]) / a.voxel_size);
+        ok = ok && f >= 0.0f && f < VOX_AXIS;       // false for NaN / inf, which a non-finite coordinate gives
+        if (a.has_limits) ok = ok && p > a.lo[k] && p < a.hi[k];
+        key = key << 21 | (ok ? (int64_t)f : 0);
+    }
+    a.keys[i] = ok ? key : VOX_DROPPED;
+}
+
+// First index in (lo, n] whose element differs from v = a[lo]; a is ascending from lo on.  Doubling steps, then bisection: about 2 log2(run) reads.
+__device__ __forceinline__ int64_t run_end(const int64_t *__restrict__ a, int64_t lo, int64_t n, int64_t v) {
+    int64_t known = lo, step = 1;
+    while (known + step < n && a[known + step] == v) {
+        known += step;
+        step <<= 1;
+    }
+    int64_t hi = known + step < n ? known + step : n;      // a[hi] != v, or hi == n
+    int64_t l = known + 1;
+    while (l < hi) {
+        const int64_t mid = l + ((hi - l) >> 1);
+        if (a[mid] == v) l = mid + 1;
+        else hi = mid;
+    }
+    return l;
+}
+
+// rows ordered by (key, id); a row is kept when it starts a run of at least min_votes equal keys (the keys are sorted: the run is that long iff the
+// row min_votes - 1 further on has the same key)
+struct FusePred {
+    const int64_t *keys;
+    int64_t n;
+    int64_t min_votes;
+    __device__ __forceinline__ bool operator()(int64_t i) const {
+        if (i >= n) return false;
+        const int64_t k = keys[i];
+        if (k == VOX_DROPPED || (i > 0 && keys[i - 1] == k)) return false;
+        const int64_t last = i + min_votes - 1;
+        return last < n && keys[last] == k;
+    }
+};
+
+// voxel rows ordered by label; a row is kept when it starts a run of a label that is not ignored
+struct LabelPred {
+    const int64_t *labels;
+    int64_t n;
+    int n_ignore;
+    int64_t ignore[VOX_MAX_IGNORE];
+    __device__ __forceinline__ bool operator()(int64_t i) const {
+        if (i >= n) return false;
+        const int64_t v = labels[i];
+        if (i > 0 && labels[i - 1] == v) return false;
+        bool keep = true;
+#pragma unroll
+        for (int k = 0; k < VOX_MAX_IGNORE; ++k) keep = keep && !(k < n_ignore && ignore[k] == v);
+        return keep;
+    }
+};
+
+template <class Pred>
+__global__ __launch_bounds__(VOX_BLOCK) void vox_count_kernel(Pred p, int32_t *__restrict__ block_count) {
+    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    const unsigned long long m = __ballot(p(i));
+    __shared__ int wc[VOX_WAVES];
+    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < VOX_WAVES; ++w) s += wc[w];
+        block_count[blockIdx.x] = s;
+    }
+}
+
+// One workgroup: block_offset[b] = *count + (kept rows of the blocks below b), then *count += all kept rows (map.hip's scan pass).
+__global__ __launch_bounds__(VOX_BLOCK) void vox_scan_kernel(const int32_t *__restrict__ block_count, int64_t nb, int64_t *__restrict__ block_offset,
+                                                             int64_t *__restrict__ count) {
+    __shared__ int64_t sh[VOX_BLOCK];
+    __shared__ int64_t carry;
+    if (threadIdx.x == 0) carry = *count;
+    __syncthreads();
+    for (int64_t b0 = 0; b0 < nb; b0 += VOX_BLOCK) {
+        const int64_t b = b0 + threadIdx.x;
+        const int64_t mine = b < nb ? (int64_t)block_count[b] : 0;
+        sh[threadIdx.x] = mine;
+        __syncthreads();
+        for (int s = 1; s < VOX_BLOCK; s <<= 1) {
+            const int64_t add = (int)threadIdx.x >= s ? sh[threadIdx.x - s] : 0;
+            __syncthreads();
+            sh[threadIdx.x] += add;
+            __syncthreads();
+        }
+        const int64_t base = carry;
+        if (b < nb) block_offset[b] = base + sh[threadIdx.x] - mine;
+        __syncthreads();
+        if (threadIdx.x == VOX_BLOCK - 1) carry = base + sh[threadIdx.x];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *count = carry;
+}
+
+struct FuseArgs {
+    const int64_t *ids;
+    const float *points, *color;
+    float *points_out, *color_out, *agreement;
+    int64_t *ids_out;
+    int32_t *count_out, *voxels;
+    int64_t cap;
+};
+
+// the vote's total order: more rows win, on equal rows the smaller id
+__device__ __forceinline__ bool vote_better(int64_t la, int64_t ia, int64_t lb, int64_t ib) { return la > lb || (la == lb && ia < ib); }
+
+__global__ __launch_bounds__(VOX_BLOCK) void voxel_fuse_kernel(FusePred p, FuseArgs a, const int64_t *__restrict__ block_offset) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    const bool keep = p(i);
+    const unsigned long long m = __ballot(keep);
+    const int rank = __popcll(m & ((1ull << lane) - 1ull));
+    const int wcount = __popcll(m);
+    __shared__ int wc[VOX_WAVES];
+    __shared__ uint8_t kept_lane[VOX_WAVES][PAG_WAVE];
+    if (lane == 0) wc[wave] = wcount;
+    if (keep) kept_lane[wave][rank] = (uint8_t)lane;
+    __syncthreads();
+    int64_t wbase = block_offset[blockIdx.x];
+    for (int q = 0; q < wave; ++q) wbase += wc[q];
+    // the wave's kept runs, four per pass: group g of 16 lanes takes the run that starts at kept row k0 + g, whose destination is wbase + k0 + g
+    const int g = lane / VOX_GROUP, l = lane % VOX_GROUP;
+    const int64_t row0 = (int64_t)blockIdx.x * VOX_BLOCK + wave * PAG_WAVE;
+    for (int k0 = 0; k0 < wcount; k0 += VOX_GROUPS) {       // wcount is uniform over the wave
+        const int k = k0 + g;
+        const bool active = k < wcount && wbase + k < a.cap;
+        float s[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        int64_t best_len = 0, best_id = 0, start = 0, end = 0;
+        if (active) {
+            start = row0 + kept_lane[wave][k];
+            end = run_end(p.keys, start, p.n, p.keys[start]);
+            for (int64_t r = start + l; r < end; r += VOX_GROUP) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) s[c] += a.points[r * 3 + c];
+                if (a.color)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) s[3 + c] += a.color[r * 3 + c];
+                const int64_t id = a.ids[r];
+                if (r == start || a.ids[r - 1] != id) {     // an id run starts here
+                    const int64_t len = run_end(a.ids, r, end, id) - r;
+                    if (vote_better(len, id, best_len, best_id)) {
+                        best_len = len;
+                        best_id = id;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int x = VOX_GROUP / 2; x >= 1; x >>= 1) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) s[c] += __shfl_xor(s[c], x);
+            const long long ol = __shfl_xor((long long)best_len, x), oi = __shfl_xor((long long)best_id, x);
+            if (vote_better(ol, oi, best_len, best_id)) {
+                best_len = ol;
+                best_id = oi;
+            }
+        }
+        if (active && l == 0) {
+            const int64_t dst = wbase + k, rows = end - start, key = p.keys[start];
+            const float fn = (float)rows;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.points_out[dst * 3 + c] = s[c] / fn;
+            if (a.color)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) a.color_out[dst * 3 + c] = s[3 + c] / fn;
+            a.ids_out[dst] = best_id;
+            a.count_out[dst] = rows > INT32_MAX ? INT32_MAX : (int32_t)rows;
+            a.agreement[dst] = (float)best_len / fn;
+            a.voxels[dst * 3 + 0] = (int32_t)(key >> 42);
+            a.voxels[dst * 3 + 1] = (int32_t)(key >> 21 & 0x1fffff);
+            a.voxels[dst * 3 + 2] = (int32_t)(key & 0x1fffff);
+        }
+    }
+}
+
+struct TableArgs {
+    const float *points, *color;
+    const int32_t *count;
+    int64_t *ids_out, *voxels_out, *obs_out;
+    float *centroid, *bbox_min, *bbox_max, *color_out;
+    int64_t cap;
+};
+
+__global__ __launch_bounds__(VOX_BLOCK) void label_table_kernel(LabelPred p, TableArgs a, const int64_t *__restrict__ block_offset) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t block0 = (int64_t)blockIdx.x * VOX_BLOCK;
+    const bool keep = p(block0 + threadIdx.x);
+    const unsigned long long m = __ballot(keep);
+    const int rank = __popcll(m & ((1ull << lane) - 1ull));
+    __shared__ int wc[VOX_WAVES];
+    __shared__ uint8_t kept_row[VOX_BLOCK];
+    __shared__ float part_f[VOX_WAVES][12];
+    __shared__ int64_t part_obs[VOX_WAVES];
+    if (lane == 0) wc[wave] = __popcll(m);
+    __syncthreads();
+    int below = 0, total = 0;
+#pragma unroll
+    for (int q = 0; q < VOX_WAVES; ++q) {
+        below += q < wave ? wc[q] : 0;
+        total += wc[q];
+    }
+    if (keep) kept_row[below + rank] = (uint8_t)threadIdx.x;
+    __syncthreads();
+    const int64_t base = block_offset[blockIdx.x];
+    // the block's kept runs one after the other, each reduced by the whole workgroup: thread t takes rows t, t + 256, ... of the run
+    for (int h = 0; h < total; ++h) {                       // total and base are uniform over the workgroup
+        const int64_t dst = base + h;
+        if (dst >= a.cap) break;
+        const int64_t start = block0 + kept_row[h];
+        const int64_t label = p.labels[start];
+        const int64_t end = run_end(p.labels, start, p.n, label);
+        float s[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        int64_t obs = 0;
+        for (int64_t r = start + threadIdx.x; r < end; r += VOX_BLOCK) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float v = a.points[r * 3 + c];
+                s[c] += v;
+                lo[c] = fminf(lo[c], v);
+                hi[c] = fmaxf(hi[c], v);
+            }
+            if (a.color)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) s[3 + c] += a.color[r * 3 + c];
+            obs += a.count[r];
+        }
+#pragma unroll
+        for (int x = PAG_WAVE / 2; x >= 1; x >>= 1) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) s[c] += __shfl_xor(s[c], x);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                lo[c] = fminf(lo[c], __shfl_xor(lo[c], x));
+                hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], x));
+            }
+            obs += __shfl_xor((long long)obs, x);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) part_f[wave][c] = s[c];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                part_f[wave][6 + c] = lo[c];
+                part_f[wave][9 + c] = hi[c];
+            }
+            part_obs[wave] = obs;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float t[12];
+#pragma unroll
+            for (int c = 0; c < 12; ++c) t[c] = part_f[0][c];
+            int64_t o = part_obs[0];
+            for (int w = 1; w < VOX_WAVES; ++w) {           // the waves in wave order
+#pragma unroll
+                for (int c = 0; c < 6; ++c) t[c] += part_f[w][c];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    t[6 + c] = fminf(t[6 + c], part_f[w][6 + c]);
+                    t[9 + c] = fmaxf(t[9 + c], part_f[w][9 + c]);
+                }
+                o += part_obs[w];
+            }
+            const float fn = (float)(end - start);
+            a.ids_out[dst] = label;
+            a.voxels_out[dst] = end - start;
+            a.obs_out[dst] = o;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                a.centroid[dst * 3 + c] = t[c] / fn;
+                a.bbox_min[dst * 3 + c] = t[6 + c];
+                a.bbox_max[dst * 3 + c] = t[9 + c];
+                if (a.color_out) a.color_out[dst * 3 + c] = t[3 + c] / fn;
+            }
+        }
+        __syncthreads();                                    // the partials are reused by the next run
+    }
+}
+
+int64_t vox_blocks(int64_t n) { return (n + VOX_BLOCK - 1) / VOX_BLOCK; }
+int64_t vox_align(int64_t b) { return (b + 255) / 256 * 256; }
+
+}  // namespace
+
+extern "C" int64_t pag_voxel_workspace_bytes(int64_t n) {
+    if (n <= 0 || n > VOX_MAX_ROWS) return 0;
+    const int64_t nb = vox_blocks(n);
+    return vox_align(nb * 8) + vox_align(nb * 4);
+}
+
+extern "C" int pag_voxel_keys(const float *points, int64_t n, const float *origin_host, float voxel_size, const float *limits_host, int64_t *keys,
+                              void *stream) {
+    PAG_CHECK_ARG(n >= 0 && n <= VOX_MAX_ROWS, "pag_voxel_keys: n %lld not in [0, 2^31]", (long long)n);
+    PAG_CHECK_ARG(voxel_size > 0.0f && voxel_size <= 3.0e38f, "pag_voxel_keys: voxel_size %g is not a positive finite number", (double)voxel_size);
+    PAG_CHECK_ARG(origin_host, "pag_voxel_keys: NULL origin");
+    if (n == 0) return PAG_OK;
+    PAG_CHECK_ARG(points && keys, "pag_voxel_keys: NULL points / keys");
+    KeyArgs a = {};
+    a.points = points, a.n = n, a.voxel_size = voxel_size, a.keys = keys, a.has_limits = limits_host != nullptr;
+    for (int k = 0; k < 3; ++k) {
+        a.origin[k] = origin_host[k];
+        if (limits_host) a.lo[k] = limits_host[k], a.hi[k] = limits_host[3 + k];
+    }
+    hipLaunchKernelGGL(voxel_keys_kernel, dim3((unsigned)vox_blocks(n)), dim3(VOX_BLOCK), 0, (hipStream_t)stream, a);
+    PAG_CHECK_LAUNCH("pag_voxel_keys");
+    return PAG_OK;
+}
+
+extern "C" int pag_voxel_fuse(const int64_t *keys, const int64_t *ids, const float *points, const float *color, int64_t n, int64_t min_votes,
+                              float *points_out, float *color_out, int64_t *ids_out, int32_t *count_out, float *agreement, int32_t *voxels,
+                              int64_t cap, int64_t *count, void *workspace, int64_t workspace_bytes, void *stream) {
+    PAG_CHECK_ARG(n >= 0 && n <= VOX_MAX_ROWS && cap >= 0 && min_votes >= 1 && min_votes <= VOX_MAX_ROWS,
+                  "pag_voxel_fuse: n %lld not in [0, 2^31], cap %lld < 0 or min_votes %lld not in [1, 2^31]", (long long)n, (long long)cap,
+                  (long long)min_votes);
+    if (n == 0) return PAG_OK;
+    PAG_CHECK_ARG(keys && ids && points, "pag_voxel_fuse: NULL keys / ids / points");
+    PAG_CHECK_ARG(count && (cap == 0 || (points_out && ids_out && count_out && agreement && voxels && (color_out || !color))),
+                  "pag_voxel_fuse: NULL counter / output");
+    PAG_CHECK_ARG(workspace && workspace_bytes >= pag_voxel_workspace_bytes(n), "pag_voxel_fuse: workspace smaller than pag_voxel_workspace_bytes(n)");
+    const int64_t nb = vox_blocks(n);
+    int64_t *block_offset = (int64_t *)workspace;
+    int32_t *block_count = (int32_t *)((char *)workspace + vox_align(nb * 8));
+    FusePred p = {keys, n, min_votes};
+    FuseArgs a = {};
+    a.ids = ids, a.points = points, a.color = color;
+    a.points_out = points_out, a.color_out = color_out, a.agreement = agreement, a.ids_out = ids_out, a.count_out = count_out, a.voxels = voxels;
+    a.cap = cap;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(vox_count_kernel<FusePred>, dim3((unsigned)nb), dim3(VOX_BLOCK), 0, st, p, block_count);
+    hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(VOX_BLOCK), 0, st, (const int32_t *)block_count, nb, block_offset, count);
+    hipLaunchKernelGGL(voxel_fuse_kernel, dim3((unsigned)nb), dim3(VOX_BLOCK), 0, st, p, a, (const int64_t *)block_offset);
+    PAG_CHECK_LAUNCH("pag_voxel_fuse");
+    return PAG_OK;
+}
+
+extern "C" int pag_label_table(const int64_t *labels, const float *points, const float *color, const int32_t *voxel_count, int64_t n,
+                               const int64_t *ignore_host, int n_ignore, int64_t *ids_out, int64_t *voxels_out, int64_t *observations,
+                               float *centroid, float *bbox_min, float *bbox_max, float *color_out, int64_t cap, int64_t *count, void *workspace,
+                               int64_t workspace_bytes, void *stream) {
+    PAG_CHECK_ARG(n >= 0 && n <= VOX_MAX_ROWS && cap >= 0, "pag_label_table: n %lld not in [0, 2^31] or cap %lld < 0", (long long)n, (long long)cap);
+    PAG_CHECK_ARG(n_ignore >= 0 && n_ignore <= VOX_MAX_IGNORE && (n_ignore == 0 || ignore_host), "pag_label_table: %d ignored labels (0..%d), or a NULL list",
+                  n_ignore, VOX_MAX_IGNORE);
+    if (n == 0) return PAG_OK;
+    PAG_CHECK_ARG(labels && points && voxel_count, "pag_label_table: NULL labels / points / voxel_count");
+    PAG_CHECK_ARG(count && (cap == 0 || (ids_out && voxels_out && observations && centroid && bbox_min && bbox_max && (color_out || !color))),
+                  "pag_label_table: NULL counter / output");
+    PAG_CHECK_ARG(workspace && workspace_bytes >= pag_voxel_workspace_bytes(n), "pag_label_table: workspace smaller than pag_voxel_workspace_bytes(n)");
+    const int64_t nb = vox_blocks(n);
+    int64_t *block_offset = (int64_t *)workspace;
+    int32_t *block_count = (int32_t *)((char *)workspace + vox_align(nb * 8));
+    LabelPred p = {};
+    p.labels = labels, p.n = n, p.n_ignore = n_ignore;
+    for (int k = 0; k < n_ignore; ++k) p.ignore[k] = ignore_host[k];
+    TableArgs a = {};
+    a.points = points, a.color = color, a.count = voxel_count;
+    a.ids_out = ids_out, a.voxels_out = voxels_out, a.obs_out = observations;
+    a.centroid = centroid, a.bbox_min = bbox_min, a.bbox_max = bbox_max, a.color_out = color ? color_out : nullptr, a.cap = cap;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(vox_count_kernel<LabelPred>, dim3((unsigned)nb), dim3(VOX_BLOCK), 0, st, p, block_count);
+    hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(VOX_BLOCK), 0, st, (const int32_t *)block_count, nb, block_offset, count);
+    hipLaunchKernelGGL(label_table_kernel, dim3((unsigned)nb), dim3(VOX_BLOCK), 0, st, p, a, (const int64_t *)block_offset);
+    PAG_CHECK_LAUNCH("pag_label_table");
+    return PAG_OK;
+}

@@ -15,6 +15,11 @@ the capacity; nothing is written out of bounds).  One synchronisation at the end
 
 Quirks of the reference kept on purpose: `samples = points + (rand / res * 2 - 1)` shifts the query by about -1 instead of
 jittering it inside a cell; the density is queried at the shifted samples and the UN-shifted lattice points are kept; `limits` is a strict box.
+
+Beyond the reference: the FUSED VOXEL MAP (csrc/voxelmap.hip; second half of this file).  The views export holds a surface spot once per camera that
+saw it, each with that view's own id; VoxelMap / fuse_map reduce such clouds to one row per occupied voxel (mean point and colour, the id most points
+voted for, count, agreement), instance_table gives the per-instance table of the result, and `python -m pagnerf_amd.map_export fuse` does both on map
+files.  fuse_points_reference / label_table_reference are the tensor-op definitions.
 """
 import pickle
 
@@ -179,9 +184,260 @@ def generate_pc_map(nef, blas_level, name="nerf_pc", min_density=None, limits=No
     return [{"name": name, "points": pts.detach().cpu(), "instances": ids.detach().cpu()}]
 
 
+# ------------------------------------------------------------------------------------------- the fused voxel map (csrc/voxelmap.hip)
+# Every view contributes one point per kept pixel, labelled by that view's own argmax: a surface spot is in the cloud once per camera that saw it,
+# with ids that need not agree.  The fused map has one row per occupied voxel of edge `voxel_size` on the lattice anchored at `origin`: the mean
+# position and colour of the voxel's points, the id most of them carry (THE VOTE: every point one vote, the id with the most votes wins, on equal
+# votes the smaller id), the number of points and the winner's share of them.  fuse_points_reference is the definition; VoxelMap is the device path.
+VOXEL_AXIS_BITS = 21
+DROPPED_KEY = 2 ** 63 - 1
+
+
+def _reference_keys(points, voxel_size, origin, limits):
+    """The voxel key of every row in tensor ops (fp32: subtract, divide, floor), DROPPED_KEY for a dropped row."""
+    p = points.detach().reshape(-1, 3).float()
+    o = torch.as_tensor(origin, dtype=torch.float32, device=p.device).reshape(3)
+    v = torch.tensor(float(voxel_size), dtype=torch.float32, device=p.device)
+    idx = torch.floor((p - o) / v)
+    ok = (torch.isfinite(p) & (idx >= 0) & (idx < 2.0 ** VOXEL_AXIS_BITS)).all(-1)
+    if limits is not None and torch.as_tensor(limits).numel() > 0:
+        lim = torch.as_tensor(limits, dtype=torch.float32, device=p.device).reshape(2, 3)
+        ok = ok & ((p > lim[0]) & (p < lim[1])).all(-1)                                   # the strict box of _lattice_box
+    i = torch.where(ok[:, None], idx, torch.zeros_like(idx)).long()
+    key = i[:, 2] | (i[:, 1] << VOXEL_AXIS_BITS) | (i[:, 0] << (2 * VOXEL_AXIS_BITS))
+    return torch.where(ok, key, torch.full_like(key, DROPPED_KEY))
+
+
+def _group_mean(values, inv, groups, counts):
+    """fp64 sums per group cast to fp32, then one fp32 division by the count."""
+    s = torch.zeros(groups, values.shape[1], dtype=torch.float64, device=values.device).index_add_(0, inv, values.double())
+    return s.float() / counts.float()[:, None]
+
+
+def _check_voxel_size(voxel_size):
+    v = float(voxel_size)
+    if not (v > 0.0 and np.isfinite(np.float32(v)) and np.float32(v) > 0):
+        raise ValueError("voxel_size must be a positive finite number, got %r" % (voxel_size,))
+    return v
+
+
+@torch.no_grad()
+def fuse_points_reference(points, ids, color=None, voxel_size=2.0 / 256, origin=None, limits=None, min_votes=1):
+    """The fused voxel map as tensor ops - the definition (runs wherever its inputs live; sums in fp64).  points f32 [K,3], ids i64 [K], color f32
+    [K,3] or None -> {'points' f32 [V,3], 'color' f32 [V,3] (with color), 'instances' i64 [V], 'count' i32 [V], 'agreement' f32 [V], 'voxels' i32
+    [V,3], 'voxel_size', 'origin' f32 [3]} with one row per voxel that holds at least min_votes points, in ascending key order (x slowest)."""
+    voxel_size = _check_voxel_size(voxel_size)
+    origin = (-1.0, -1.0, -1.0) if origin is None else origin
+    p = points.detach().reshape(-1, 3).float()
+    dev = p.device
+    ids = ids.detach().reshape(-1).to(torch.int64)
+    keys = _reference_keys(p, voxel_size, origin, limits)
+    valid = keys != DROPPED_KEY
+    p, ids, keys = p[valid], ids[valid], keys[valid]
+    ukeys, inv, cnt = torch.unique(keys, return_inverse=True, return_counts=True)
+    V = ukeys.numel()
+    out = {"points": _group_mean(p, inv, V, cnt)}
+    if color is not None:
+        out["color"] = _group_mean(color.detach().reshape(-1, 3).float()[valid], inv, V, cnt)
+    # the vote: rows per (voxel, id) pair; unique sorts the pairs by voxel, then by id (signed), so the first pair that reaches a voxel's maximum
+    # carries the smallest of the tied ids
+    pairs, pc = torch.unique(torch.stack((inv, ids), 1), dim=0, return_counts=True)
+    pv, pid = (pairs[:, 0], pairs[:, 1]) if pairs.numel() else (inv[:0], ids[:0])
+    best = torch.zeros(V, dtype=torch.int64, device=dev).scatter_reduce_(0, pv, pc, "amax", include_self=False)
+    pos = torch.arange(pv.numel(), device=dev)
+    first = torch.full((V,), pv.numel(), dtype=torch.int64, device=dev).scatter_reduce_(
+        0, pv[pc == best[pv]], pos[pc == best[pv]], "amin", include_self=True)
+    out["instances"] = pid[first] if V else ids[:0]
+    out["count"] = cnt.to(torch.int32)
+    out["agreement"] = best.float() / cnt.float()
+    out["voxels"] = torch.stack((ukeys >> (2 * VOXEL_AXIS_BITS), (ukeys >> VOXEL_AXIS_BITS) & (2 ** VOXEL_AXIS_BITS - 1),
+                                 ukeys & (2 ** VOXEL_AXIS_BITS - 1)), 1).to(torch.int32)
+    keep = cnt >= int(min_votes)
+    out = {k: v[keep] for k, v in out.items()}
+    out["voxel_size"] = voxel_size
+    out["origin"] = torch.as_tensor(origin, dtype=torch.float32, device=dev).reshape(3)
+    return out
+
+
+def _with_volume(table, voxel_size):
+    table["volume"] = table["voxels"].double() * float(voxel_size) ** 3
+    return table
+
+
+@torch.no_grad()
+def label_table_reference(map, ignore=(0,)):
+    """The per-instance table of a fused map as tensor ops - the definition.  -> {'ids' i64 [T], 'voxels' i64 [T], 'observations' i64 [T] (the sum of
+    'count'), 'centroid' / 'bbox_min' / 'bbox_max' f32 [T,3] (of the voxel points), 'color' f32 [T,3] (when the map has colour), 'volume' f64 [T] =
+    voxels * voxel_size^3}, one row per instance id outside `ignore`, ascending."""
+    lab, p = map["instances"].reshape(-1), map["points"].reshape(-1, 3)
+    ulab, inv, cnt = torch.unique(lab, return_inverse=True, return_counts=True)
+    T = ulab.numel()
+    out = {"ids": ulab, "voxels": cnt,
+           "observations": torch.zeros(T, dtype=torch.int64, device=lab.device).index_add_(0, inv, map["count"].reshape(-1).long()),
+           "centroid": _group_mean(p, inv, T, cnt)}
+    idx = inv[:, None].expand(-1, 3)
+    out["bbox_min"] = torch.zeros(T, 3, device=p.device).scatter_reduce_(0, idx, p, "amin", include_self=False)
+    out["bbox_max"] = torch.zeros(T, 3, device=p.device).scatter_reduce_(0, idx, p, "amax", include_self=False)
+    if "color" in map:
+        out["color"] = _group_mean(map["color"].reshape(-1, 3), inv, T, cnt)
+    keep = torch.ones(T, dtype=torch.bool, device=lab.device)
+    for v in ignore:
+        keep &= ulab != int(v)
+    return _with_volume({k: v[keep] for k, v in out.items()}, map["voxel_size"])
+
+
+def rows_by_key_and_id(keys, ids, points, color=None):
+    """The rows in (key, id) order, rows of equal (key, id) in their given order: a stable sort by id, then a stable sort by key (rocPRIM's radix
+    sort through torch.sort; no synchronisation).  -> (keys, ids, points, color) as pag_voxel_fuse takes them."""
+    ids, first = torch.sort(ids, stable=True)
+    keys, second = torch.sort(keys.index_select(0, first), stable=True)
+    order = first.index_select(0, second)
+    return keys, ids.index_select(0, second), points.index_select(0, order), (color.index_select(0, order) if color is not None else None)
+
+
+class VoxelMap:
+    """The device path of fuse_points_reference: add() collects chunks of map points (one key launch each, no synchronisation), finish() orders the
+    rows by (key, id) with two stable sorts and reduces them in one ordered-append call; its one synchronisation reads the voxel counter.  The result
+    does not depend on how the points were split over add() calls, bit for bit.  Outputs are sized for all K rows (52 bytes each) unless
+    `capacity` says otherwise; a map of more voxels than that raises with the count it needed."""
+
+    def __init__(self, voxel_size, origin=(-1.0, -1.0, -1.0), limits=None, min_votes=1, device="cuda", capacity=None):
+        self.voxel_size = _check_voxel_size(voxel_size)
+        self.origin = tuple(float(v) for v in origin)
+        self.limits = None if limits is None or torch.as_tensor(limits).numel() == 0 else torch.as_tensor(limits, dtype=torch.float32).reshape(2, 3).cpu()
+        self.min_votes = int(min_votes)
+        if self.min_votes < 1:
+            raise ValueError("min_votes must be at least 1")
+        self.device = torch.device(device)
+        self.capacity = capacity
+        self._origin = torch.tensor(self.origin, dtype=torch.float32, device=self.device)      # made here: finish() copies nothing from the host
+        self._chunks = []
+        self._color = True
+
+    def add(self, points, ids, color=None):
+        points = points.detach().reshape(-1, 3).to(self.device, torch.float32)
+        ids = ids.detach().reshape(-1).to(self.device, torch.int64)
+        if ids.numel() != points.shape[0] or (color is not None and color.numel() != points.numel()):
+            raise ValueError("add: points [k,3], ids [k] and color [k,3] must describe the same rows")
+        if color is None:
+            self._color = False
+        if points.shape[0] == 0:
+            return self
+        color = color.detach().reshape(-1, 3).to(self.device, torch.float32) if color is not None else None
+        self._chunks.append((points, ids, color, ops.voxel_keys(points, self.origin, self.voxel_size, self.limits)))
+        return self
+
+    def _empty(self, cap, color):
+        dev = self.device
+        out = {"points": torch.empty(cap, 3, device=dev)}
+        if color:
+            out["color"] = torch.empty(cap, 3, device=dev)
+        out.update(instances=torch.empty(cap, dtype=torch.int64, device=dev), count=torch.empty(cap, dtype=torch.int32, device=dev),
+                   agreement=torch.empty(cap, device=dev), voxels=torch.empty(cap, 3, dtype=torch.int32, device=dev))
+        return out
+
+    @torch.no_grad()
+    def finish(self):
+        K = sum(c[0].shape[0] for c in self._chunks)
+        color = self._color and K > 0
+        cap = K if self.capacity is None else min(int(self.capacity), K)
+        out = self._empty(cap, self._color)
+        n = 0
+        if K > 0:
+            cat = lambda j: self._chunks[0][j] if len(self._chunks) == 1 else torch.cat([c[j] for c in self._chunks])          # noqa: E731
+            keys, ids, points, col = rows_by_key_and_id(cat(3), cat(1), cat(0), cat(2) if color else None)
+            counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+            ops.voxel_fuse(keys, ids, points, col, self.min_votes, out["points"], out.get("color"), out["instances"], out["count"], out["agreement"],
+                           out["voxels"], counter)
+            n = int(counter.item())                                                         # the one synchronisation
+            if n > cap:
+                raise RuntimeError("the fused map has %d voxels, the outputs hold %d: pass capacity >= %d" % (n, cap, n))
+        out = {k: v[:n] for k, v in out.items()}
+        out["voxel_size"] = self.voxel_size
+        out["origin"] = self._origin.clone()
+        return out
+
+
+def _entry_ids(d):
+    return d["inst_embedding"] if "inst_embedding" in d else d["instances"]
+
+
+def fuse_map(data, voxel_size, origin=(-1.0, -1.0, -1.0), limits=None, min_votes=1, device="cuda", capacity=None, name="nerf_pc_fused"):
+    """The entries of a map list (what generate_pc_map_from_views / generate_pc_map return and nerf_pc.pkl holds: 'points', 'inst_embedding' or
+    'instances', optionally 'color') fused into ONE entry with CPU tensors: fuse_points_reference's keys with 'name'.  Ids are taken as they are
+    (matching the ids of different training windows is not done here).  device: where it runs; "cpu" is the tensor-op definition."""
+    colored = all("color" in d for d in data)
+    if torch.device(device).type == "cpu":
+        pts = torch.cat([torch.as_tensor(d["points"]).reshape(-1, 3).float() for d in data]) if data else torch.zeros(0, 3)
+        ids = torch.cat([torch.as_tensor(_entry_ids(d)).reshape(-1).long() for d in data]) if data else torch.zeros(0, dtype=torch.int64)
+        col = torch.cat([torch.as_tensor(d["color"]).reshape(-1, 3).float() for d in data]) if data and colored else None
+        fused = fuse_points_reference(pts, ids, col, voxel_size, origin, limits, min_votes)
+    else:
+        vm = VoxelMap(voxel_size, origin, limits, min_votes, device, capacity)
+        for d in data:
+            vm.add(torch.as_tensor(d["points"]), torch.as_tensor(_entry_ids(d)), torch.as_tensor(d["color"]) if colored else None)
+        fused = vm.finish()
+    fused = {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in fused.items()}
+    fused["name"] = name
+    return fused
+
+
+TABLE_FIELDS = ("ids", "voxels", "observations", "centroid", "bbox_min", "bbox_max", "color", "volume")
+
+
+@torch.no_grad()
+def instance_table(fused, ignore=(0,), device=None, capacity=None):
+    """The per-instance table of a fused map (label_table_reference's keys): voxel count, observation total, centroid, bounding box, mean colour
+    and volume of every instance id outside `ignore`.  Runs on `device` (default: where the map lives, "cuda" for a CPU map; "cpu" is the tensor-op
+    definition): one stable sort by id and one ordered-append call, one synchronisation; the result lives where the map does."""
+    home = fused["instances"].device
+    dev = torch.device(device) if device is not None else (home if home.type != "cpu" else torch.device("cuda"))
+    if dev.type == "cpu":
+        cpu = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in fused.items()}
+        return {k: (v.to(home) if torch.is_tensor(v) else v) for k, v in label_table_reference(cpu, ignore).items()}
+    n = fused["instances"].numel()
+    cap = n if capacity is None else min(int(capacity), n)
+    has_color = "color" in fused
+    out = {"ids": torch.empty(cap, dtype=torch.int64, device=dev), "voxels": torch.empty(cap, dtype=torch.int64, device=dev),
+           "observations": torch.empty(cap, dtype=torch.int64, device=dev), "centroid": torch.empty(cap, 3, device=dev),
+           "bbox_min": torch.empty(cap, 3, device=dev), "bbox_max": torch.empty(cap, 3, device=dev)}
+    if has_color:
+        out["color"] = torch.empty(cap, 3, device=dev)
+    t = 0
+    if n > 0:
+        lab, order = torch.sort(fused["instances"].reshape(-1).to(dev), stable=True)
+        take = lambda k: fused[k].to(dev).index_select(0, order)                           # noqa: E731
+        counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        ops.label_table(lab, take("points"), take("color") if has_color else None, take("count"), ignore, out["ids"], out["voxels"],
+                        out["observations"], out["centroid"], out["bbox_min"], out["bbox_max"], out.get("color"), counter)
+        t = int(counter.item())
+        if t > cap:
+            raise RuntimeError("the table has %d instances, the outputs hold %d: pass capacity >= %d" % (t, cap, t))
+    return _with_volume({k: v[:t].to(home) for k, v in out.items()}, fused["voxel_size"])
+
+
+def save_instance_table(table, path):
+    """One header line, one line per instance: id, voxels, observations, volume, centroid, bounding box and (when present) colour; floats are
+    written with repr, so reading them back gives the same values."""
+    import csv
+    cols = [("id", "ids", None), ("voxels", "voxels", None), ("observations", "observations", None), ("volume", "volume", None)]
+    for key, stem in (("centroid", "centroid"), ("bbox_min", "min"), ("bbox_max", "max")):
+        cols += [("%s_%s" % (stem, a), key, j) for j, a in enumerate("xyz")]
+    if "color" in table:
+        cols += [(c, "color", j) for j, c in enumerate(("red", "green", "blue"))]
+    arrays = {k: np.asarray(torch.as_tensor(table[k]).cpu()) for _, k, _ in cols}
+    with open(str(path), "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow([c for c, _, _ in cols])
+        for r in range(arrays["ids"].shape[0]):
+            row = [arrays[k][r] if j is None else arrays[k][r, j] for _, k, j in cols]
+            w.writerow([repr(v.item()) for v in row])
+    return str(path)
+
+
 def save_map(data, path):
     """The reference's nerf_pc.pkl: a pickle of the list; a path ending in .ply instead gets a little-endian binary PLY of all entries' points
-    (x y z float, red green blue uchar when colours exist, instance int)."""
+    (x y z float, red green blue uchar when colours exist, instance int; count int and agreement float when every entry is a fused map)."""
     path = str(path)
     if not path.lower().endswith(".ply"):
         with open(path, "wb") as fh:
@@ -191,7 +447,13 @@ def save_map(data, path):
     ids = np.concatenate([np.asarray(d["inst_embedding"] if "inst_embedding" in d else d["instances"]).reshape(-1) for d in data], 0)
     has_color = all("color" in d for d in data)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if has_color else []) + [("instance", "<i4")]
+    fused = len(data) > 0 and all("count" in d for d in data)
+    if fused:
+        fields += [("count", "<i4"), ("agreement", "<f4")]
     v = np.empty(pts.shape[0], dtype=fields)
+    if fused:
+        v["count"] = np.concatenate([np.asarray(d["count"]).reshape(-1) for d in data], 0).astype("<i4")
+        v["agreement"] = np.concatenate([np.asarray(d["agreement"], dtype="<f4").reshape(-1) for d in data], 0)
     v["x"], v["y"], v["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
     if has_color:
         col = np.concatenate([np.asarray(d["color"], dtype=np.float32).reshape(-1, 3) for d in data], 0)
@@ -205,3 +467,43 @@ def save_map(data, path):
         fh.write(header.encode("ascii"))
         fh.write(v.tobytes())
     return path
+
+
+def main(argv=None):
+    """python -m pagnerf_amd.map_export fuse IN.pkl [IN.pkl ...] --voxel-size V [--min-votes N] [--limits x0 y0 z0 x1 y1 z1] --out OUT.ply|OUT.pkl
+    [--table OUT.csv]"""
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m pagnerf_amd.map_export")
+    sub = ap.add_subparsers(dest="command", required=True)
+    fu = sub.add_parser("fuse", help="fuse exported map files into one voxel map",
+                        description="Fuses the point clouds of map files (what --save-map and the reference's --save-map-only write: a pickled list of "
+                        "dicts with 'points', 'inst_embedding' or 'instances' and optionally 'color') into one voxel map: per occupied voxel the mean "
+                        "point and colour, the instance id most points voted for (ties: the smaller id), the point count and the agreement.  Ids are "
+                        "taken as they are.  The inputs are pickles: unpickling runs code, so give it files you trust and nothing else.")
+    fu.add_argument("inputs", nargs="+", metavar="IN.pkl", help="map files (pickles: trusted files only)")
+    fu.add_argument("--voxel-size", type=float, required=True, metavar="V", help="voxel edge in the map's units (the scene cube is [-1, 1]^3)")
+    fu.add_argument("--min-votes", type=int, default=1, metavar="N", help="drop voxels that hold fewer than N points")
+    fu.add_argument("--limits", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="keep points strictly inside this box")
+    fu.add_argument("--origin", type=float, nargs=3, default=(-1.0, -1.0, -1.0), metavar=("X", "Y", "Z"), help="corner the voxel lattice is anchored at")
+    fu.add_argument("--ignore", type=int, nargs="*", default=[0], metavar="ID", help="instance ids left out of the table (default: 0)")
+    fu.add_argument("--out", required=True, metavar="OUT.ply|OUT.pkl", help="the fused map (a .ply, or a pickle of a one-entry list)")
+    fu.add_argument("--table", metavar="OUT.csv", help="also write the per-instance table")
+    fu.add_argument("--device", default="cuda", help="where it runs; cpu selects the tensor-op definition")
+    args = ap.parse_args(argv)
+    data = []
+    for path in args.inputs:
+        with open(path, "rb") as fh:
+            loaded = pickle.load(fh)
+        data += loaded if isinstance(loaded, (list, tuple)) else [loaded]
+    limits = None if args.limits is None else [args.limits[:3], args.limits[3:]]
+    fused = fuse_map(data, args.voxel_size, origin=args.origin, limits=limits, min_votes=args.min_votes, device=args.device)
+    save_map([fused], args.out)
+    if args.table:
+        save_instance_table(instance_table(fused, ignore=args.ignore, device=args.device), args.table)
+    print("%d points -> %d voxels: %s" % (sum(int(torch.as_tensor(d["points"]).reshape(-1, 3).shape[0]) for d in data), fused["points"].shape[0], args.out))
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

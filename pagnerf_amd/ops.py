@@ -1974,6 +1974,81 @@ def map_select(points_in, points, count, value=None, threshold=0.0, inst=None, i
           ids_out.data_ptr() if ids_out is not None else None, points.shape[0], count.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
 
 
+# ------------------------------------------------------------------------------------------- voxel map fusion (csrc/voxelmap.hip)
+def _voxel_workspace(n, dev):
+    return torch.empty(max(int(L.load().pag_voxel_workspace_bytes(n)), 8), dtype=torch.uint8, device=dev)
+
+
+def voxel_keys(points, origin, voxel_size, limits=None):
+    """points f32 [n,3] -> keys i64 [n]: iz | iy << 21 | ix << 42 with i = floor((p - origin) / voxel_size) in fp32, INT64_MAX for a row that is not
+    finite, outside [0, 2^21) on an axis or not strictly inside limits [[min], [max]] (pag_voxel_keys; origin / limits are host values)."""
+    _check_gpu(points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError("voxel_keys: points [n,3], got %s" % (tuple(points.shape),))
+    n = points.shape[0]
+    keys = torch.empty(n, dtype=torch.int64, device=points.device)
+    pts = points.detach().contiguous().float()
+    org = (ctypes.c_float * 3)(*[float(v) for v in origin])
+    lim = None
+    if limits is not None:
+        flat = [float(v) for v in torch.as_tensor(limits, dtype=torch.float32).reshape(-1).tolist()]
+        if len(flat) != 6:
+            raise RuntimeError("voxel_keys: limits must be [2,3] = [[min], [max]]")
+        lim = (ctypes.c_float * 6)(*flat)
+    _call("pag_voxel_keys", pts.data_ptr(), n, org, float(voxel_size), lim, keys.data_ptr(), L.stream())
+    return keys
+
+
+def voxel_fuse(keys, ids, points, color, min_votes, points_out, color_out, ids_out, count_out, agreement, voxels, count):
+    """Rows ordered by (key, id) -> one row per run of equal keys with at least min_votes rows, appended in key order behind the device counter
+    `count` i64 [1]: mean point / colour, the most frequent id (ties: the smaller), the rows, the winner's share, the voxel index (pag_voxel_fuse)."""
+    _check_gpu(keys, ids, points, color, points_out, color_out, ids_out, count_out, agreement, voxels, count)
+    n = keys.numel()
+    if n == 0:
+        return
+    if keys.dtype != torch.int64 or ids.dtype != torch.int64 or ids.numel() != n or tuple(points.shape) != (n, 3) or points.dtype != torch.float32 or (
+            color is not None and (tuple(color.shape) != (n, 3) or color.dtype != torch.float32)):
+        raise RuntimeError("voxel_fuse: keys / ids int64 [n], points / color f32 [n,3]")
+    cap = points_out.shape[0]
+    outs = [(points_out, torch.float32, (cap, 3)), (ids_out, torch.int64, (cap,)), (count_out, torch.int32, (cap,)), (agreement, torch.float32, (cap,)),
+            (voxels, torch.int32, (cap, 3))] + ([(color_out, torch.float32, (cap, 3))] if color is not None else [])
+    if count.dtype != torch.int64 or any(t is None or t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in outs):
+        raise RuntimeError("voxel_fuse: points_out / color_out f32 [cap,3], ids_out int64 [cap], count_out int32 [cap], agreement f32 [cap], "
+                           "voxels int32 [cap,3], contiguous; count int64 [1]")
+    keys, ids, points = keys.contiguous(), ids.contiguous(), points.contiguous()
+    color = color.contiguous() if color is not None else None
+    ws = _voxel_workspace(n, keys.device)
+    _call("pag_voxel_fuse", keys.data_ptr(), ids.data_ptr(), points.data_ptr(), color.data_ptr() if color is not None else None, n, int(min_votes),
+          points_out.data_ptr(), color_out.data_ptr() if color is not None else None, ids_out.data_ptr(), count_out.data_ptr(), agreement.data_ptr(),
+          voxels.data_ptr(), cap, count.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
+
+
+def label_table(labels, points, color, voxel_count, ignore, ids_out, voxels_out, observations, centroid, bbox_min, bbox_max, color_out, count):
+    """Voxel rows ordered by label -> one row per run of a label outside `ignore`, appended in label order behind the device counter: the label, its
+    voxels, the sum of voxel_count, the centroid, the bounding box and the mean colour (pag_label_table)."""
+    _check_gpu(labels, points, color, voxel_count, ids_out, voxels_out, observations, centroid, bbox_min, bbox_max, color_out, count)
+    n = labels.numel()
+    if n == 0:
+        return
+    if labels.dtype != torch.int64 or tuple(points.shape) != (n, 3) or points.dtype != torch.float32 or voxel_count.dtype != torch.int32 or (
+            voxel_count.numel() != n) or (color is not None and (tuple(color.shape) != (n, 3) or color.dtype != torch.float32)):
+        raise RuntimeError("label_table: labels int64 [n], points / color f32 [n,3], voxel_count int32 [n]")
+    cap = ids_out.shape[0]
+    outs = [(t, torch.int64, (cap,)) for t in (ids_out, voxels_out, observations)] + [(t, torch.float32, (cap, 3)) for t in (centroid, bbox_min, bbox_max)]
+    outs += [(color_out, torch.float32, (cap, 3))] if color is not None else []
+    if count.dtype != torch.int64 or any(t is None or t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in outs):
+        raise RuntimeError("label_table: ids_out / voxels_out / observations int64 [cap], centroid / bbox_min / bbox_max / color_out f32 [cap,3], "
+                           "contiguous; count int64 [1]")
+    ignore = [int(v) for v in ignore]
+    ign = (ctypes.c_int64 * max(1, len(ignore)))(*ignore)
+    labels, points, voxel_count = labels.contiguous(), points.contiguous(), voxel_count.contiguous()
+    color = color.contiguous() if color is not None else None
+    ws = _voxel_workspace(n, labels.device)
+    _call("pag_label_table", labels.data_ptr(), points.data_ptr(), color.data_ptr() if color is not None else None, voxel_count.data_ptr(), n, ign,
+          len(ignore), ids_out.data_ptr(), voxels_out.data_ptr(), observations.data_ptr(), centroid.data_ptr(), bbox_min.data_ptr(),
+          bbox_max.data_ptr(), color_out.data_ptr() if color is not None else None, cap, count.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
+
+
 def sample_copy_width(src_ptr, dst_ptr, row_bytes, convert=L.SAMPLE_COPY):
     """Bytes per copy element pag_sample_batch uses for a mode with these base addresses and destination row size (16 / 8 / 4 / 2 / 1; for the uint8 -> f32
     conversion 4 or 1 source bytes per step); 0 = the mode would be refused.  Host arithmetic only."""

@@ -1,5 +1,5 @@
 """python -m pagnerf_amd.train --config YAML --dataset TRAIN.npz|DIR [--val-dataset VAL.npz|DIR] [--log-dir DIR] [--resume CKPT] [--valid-only]
-                              [--val-pictures] [--save-map PATH] [--set key=value ...]
+                              [--val-pictures] [--save-map PATH [--map-voxel-size V [--map-min-votes N]]] [--set key=value ...]
 
 The native counterpart of the reference's main_interactive.py: a shipped YAML, a dataset, and the trainer of trainer.py.
 
@@ -89,8 +89,10 @@ def load_dataset(path, split, cfg, device):
     return formats.load_nerf_standard(path, split=split, **common)
 
 
-def save_map(trainer, dataset, path):
-    """--save-map: the panoptic point cloud of the trained field from the training views (map_export.generate_pc_map_from_views)."""
+def save_map(trainer, dataset, path, voxel_size=None, min_votes=1):
+    """--save-map: the panoptic point cloud of the trained field from the training views (map_export.generate_pc_map_from_views).  With voxel_size
+    (--map-voxel-size) the cloud is fused into the voxel map (map_export.fuse_map) before it is written, and the per-instance table goes beside it
+    as PATH with its suffix replaced by .instances.csv."""
     from . import map_export
     from .core import Rays
     leaf = {l.field: l.src for l in dataset._leaves if l.key == "base_rays"}
@@ -99,6 +101,11 @@ def save_map(trainer, dataset, path):
     near, far = dataset._rays_range["base_rays"]
     cloud = map_export.generate_pc_map_from_views(trainer.pipeline, Rays(leaf["origins"], leaf["dirs"], near, far),
                                                   cam_ids=list(range(dataset.num_imgs)), render_batch=trainer.render_batch or 20000)
+    if voxel_size is not None:
+        device = trainer.pipeline.camera_extrinsics.device
+        fused = map_export.fuse_map(cloud, voxel_size, min_votes=min_votes, device=device, name=cloud[0]["name"])
+        map_export.save_instance_table(map_export.instance_table(fused, device=device), os.path.splitext(str(path))[0] + ".instances.csv")
+        cloud = [fused]
     map_export.save_map(cloud, path)
     return path
 
@@ -115,6 +122,9 @@ def main(argv=None):
     ap.add_argument("--val-pictures", action="store_true", help="validation writes its frames as PNG files under <log_dir>/val/epoch_<e>/ (with "
                     "--valid-only --resume CKPT: render what was trained)")
     ap.add_argument("--save-map", metavar="PATH", help="after training export the panoptic point cloud of the training views")
+    ap.add_argument("--map-voxel-size", type=float, metavar="V", help="--save-map writes the fused voxel map of edge V (one row per occupied voxel: mean "
+                    "point and colour, voted instance id, count, agreement) and the instance table as PATH with the suffix .instances.csv")
+    ap.add_argument("--map-min-votes", type=int, default=1, metavar="N", help="with --map-voxel-size: drop voxels that hold fewer than N points")
     ap.add_argument("--set", action="append", default=[], metavar="key=value", help="override an option of the flattened namespace (repeatable)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
@@ -152,7 +162,7 @@ def main(argv=None):
     if val_dataset is not None and not (trainer.plan and trainer.plan["validate_after"]):      # the last epoch's own validation is not repeated
         trainer.validate(trainer.epoch - 1)
     if args.save_map:
-        save_map(trainer, dataset, args.save_map)
+        save_map(trainer, dataset, args.save_map, args.map_voxel_size, args.map_min_votes)
     return 0
 
 
