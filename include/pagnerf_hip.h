@@ -798,6 +798,22 @@ int pag_label_table(const int64_t *labels, const float *points, const float *col
                     float *centroid, float *bbox_min, float *bbox_max, float *color_out, int64_t cap, int64_t *count, void *workspace,
                     int64_t workspace_bytes, void *stream);
 
+/* Connected components of a fused map (additive to ABI 14; pagnerf_amd.map_export.connected_components_reference is the definition).
+ *   voxels i32 [n,3] = (ix, iy, iz), rows STRICTLY ascending by key iz | iy << 21 | ix << 42 (what pag_voxel_fuse writes); ids i64 [n]
+ *   connectivity 6 / 18 / 26: rows are linked when their indices differ by an offset with at most 1 / 2 / 3 non-zero components, each -1 or +1; an
+ *   index outside [0, 2^21) does not exist (nothing is borrowed across an axis of the key).  same_id != 0: linked rows must also carry equal ids.
+ *   Rows whose id is one of the n_ignore (<= 8) ids of ignore_host (host array) link nothing and get component 0.
+ *   component i64 [n]: 1 .. C, the components numbered by their first row; count i64 [1] = C; status i32 [1]: 0, or bit 0 a row's key is not greater
+ *   than the row's before, bit 1 an index outside [0, 2^21), bit 2 a loop cap of n + 1 rounds exceeded (the result is then undefined, nothing is
+ *   accessed out of range).  count and status are device words, OVERWRITTEN.
+ * A lock-free union-find over int32 parent[n] (the larger root is hooked under the smaller with a compare-and-swap: a component's root is its first
+ * row in any interleaving, so the same input gives the same output), then the ordered append above over the root rows.  Seven launches and two
+ * memsets, no host synchronisation, no thread waits on another.  workspace: pag_voxel_components_workspace_bytes(n) bytes (16 n and the append's
+ * tables; 0 for n outside (0, 2^31)).  n = 0 is a no-op; n < 2^31. */
+int64_t pag_voxel_components_workspace_bytes(int64_t n);
+int pag_voxel_components(const int32_t *voxels, const int64_t *ids, int64_t n, int connectivity, int same_id, const int64_t *ignore_host,
+                         int n_ignore, void *workspace, int64_t workspace_bytes, int64_t *component, int64_t *count, int32_t *status, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Per-ray training loss of the rendered buffers (pc_nerf/trainer.py:443-446 rgb, :459-465 semantics,
  * loss/lin_assignment_things.py:80 instance term after the assignment) - one launch forward, one backward

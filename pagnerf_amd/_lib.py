@@ -251,6 +251,8 @@ _SIGS = {
     "pag_voxel_fuse": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "pag_label_table": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(ctypes.c_int64), c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
                                 c_vp, c_i64, c_vp]),
+    "pag_voxel_components_workspace_bytes": (c_i64, [c_i64]),
+    "pag_voxel_components": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(ctypes.c_int64), c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "pag_mlp_dz0_slots_bytes": (c_i64, [c_i64, c_i64]),
     "pag_mlp_dz0_slots_sum": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pag_encode_bwd_rays_workspace_bytes": (c_i64, [c_i64, c_i64]),

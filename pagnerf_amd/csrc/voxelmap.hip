@@ -1,4 +1,5 @@
 // Fused panoptic voxel map: the exported map points of all views (map.hip) reduced to one row per occupied voxel, and the per-instance table of it.
+// Further down: the connected components of the fused map (a lock-free union-find over the sorted rows).
 //
 // As tensor ops the fusion is `unique` over voxel keys, `unique` over (key, id) pairs, several index_add_ calls, a scatter-arg-max with tie handling
 // and a boolean gather: about twenty launches and, the output sizes being dynamic, several host synchronisations.  Here:
@@ -330,6 +331,187 @@ __global__ __launch_bounds__(VOX_BLOCK) void label_table_kernel(LabelPred p, Tab
     }
 }
 
+// ------------------------------------------------------------------------------------------- connected components of the fused map
+// The map's rows ascend by key with z fastest, so the neighbours of a voxel in column (ix + dx, iy + dy) are adjacent rows found by ONE lower-bound
+// search, and (0, 0, -1) is the row before.  A row visits the lexicographically negative half of its neighbourhood (all of them earlier rows) and
+// unites itself with each neighbour it finds in a lock-free union-find over int32 parent[V]:
+//   cc_prepare_kernel   key of every row (-1: an index outside [0, 2^21)), parent[i] = i, the contract bits of `status`
+//   cc_link_kernel      the unions: find both roots, hook the LARGER root under the smaller with a compare-and-swap
+//   cc_flatten_kernel   root[i], a walk over the finished forest
+//   vox_count_kernel<CcRootPred> / vox_scan_kernel / cc_number_kernel   the ordered append over "row is its own root and not ignored": root rows
+//                       get 1, 2, ... in row order
+//   cc_label_kernel     every other row takes its root's number, ignored rows 0
+// parent[x] <= x always and only a root (parent[x] == x) is ever hooked, under a smaller index: a component's final root is its smallest row, however
+// the lanes interleave, so the numbering is that of the definition.  NO THREAD WAITS ON ANOTHER: a failed compare-and-swap means another thread
+// hooked that root under a strictly smaller one, and the retry goes on from there; every walk and retry loop is also capped at V + 1 rounds
+// (CC_CAP in `status`, never reached on valid input).  In the link kernel parent is read and written by relaxed agent-scope atomics only.
+constexpr int CC_ORDER = 1, CC_RANGE = 2, CC_CAP = 4;      // bits of the status word
+constexpr int64_t CC_AXIS_MAX = 0x1fffff;
+
+struct IgnoreSet {
+    int n;
+    int64_t v[VOX_MAX_IGNORE];
+    __device__ __forceinline__ bool has(int64_t id) const {
+        bool hit = false;
+#pragma unroll
+        for (int k = 0; k < VOX_MAX_IGNORE; ++k) hit = hit || (k < n && v[k] == id);
+        return hit;
+    }
+};
+
+struct CcArgs {
+    const int32_t *voxels;
+    const int64_t *ids;
+    int64_t n;
+    int max_nonzero, same_id;       // offsets with at most 1 / 2 / 3 non-zero components: 6 / 18 / 26 neighbours
+    IgnoreSet ignore;
+    int64_t *keys;
+    int32_t *parent, *root, *status;
+};
+
+__device__ __forceinline__ int64_t cc_key(const int32_t *__restrict__ voxels, int64_t i) {
+    const int64_t x = voxels[i * 3], y = voxels[i * 3 + 1], z = voxels[i * 3 + 2];
+    const bool ok = x >= 0 && x <= CC_AXIS_MAX && y >= 0 && y <= CC_AXIS_MAX && z >= 0 && z <= CC_AXIS_MAX;
+    return ok ? (x << 42 | y << 21 | z) : -1;
+}
+
+__global__ __launch_bounds__(VOX_BLOCK) void cc_prepare_kernel(CcArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const int64_t key = cc_key(a.voxels, i);
+    a.keys[i] = key;
+    a.parent[i] = (int32_t)i;
+    int bad = key < 0 ? CC_RANGE : 0;
+    if (key >= 0 && i > 0 && cc_key(a.voxels, i - 1) >= key) bad |= CC_ORDER;
+    if (bad) atomicOr(a.status, bad);
+}
+
+__device__ __forceinline__ int32_t cc_load(int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// true: *p was `expected` and is now `desired`; false: `expected` holds what was there
+__device__ __forceinline__ bool cc_cas(int32_t *p, int32_t &expected, int32_t desired) {
+    return __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The root above x; every step goes to a strictly smaller index.  On the way x's parent is replaced by its grandparent (only where x is not a
+// root, and only by an ancestor: whether that swap succeeds does not matter).
+__device__ __forceinline__ int32_t cc_find(int32_t *parent, int32_t x, int64_t cap, int32_t *status) {
+    for (int64_t it = 0; it < cap; ++it) {
+        const int32_t p = cc_load(parent + x);
+        if (p == x) return x;
+        const int32_t g = cc_load(parent + p);
+        if (g != p) {
+            int32_t was = p;
+            cc_cas(parent + x, was, g);
+        }
+        x = g;
+    }
+    atomicOr(status, CC_CAP);
+    return x;
+}
+
+__device__ __forceinline__ void cc_union(int32_t *parent, int32_t a, int32_t b, int64_t cap, int32_t *status) {
+    int32_t ra = cc_find(parent, a, cap, status), rb = cc_find(parent, b, cap, status);
+    for (int64_t it = 0; it < cap; ++it) {
+        if (ra == rb) return;
+        const int32_t hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
+        int32_t seen = hi;
+        if (cc_cas(parent + hi, seen, lo)) return;
+        ra = cc_find(parent, seen, cap, status);        // hi was hooked under seen < hi meanwhile: go on from there
+        rb = lo;
+    }
+    atomicOr(status, CC_CAP);
+}
+
+__device__ __forceinline__ void cc_link(const CcArgs &a, int64_t i, int64_t j, int64_t id, int64_t cap) {
+    const int64_t other = a.ids[j];
+    if (a.same_id ? other != id : a.ignore.has(other)) return;
+    cc_union(a.parent, (int32_t)i, (int32_t)j, cap, a.status);
+}
+
+__global__ __launch_bounds__(VOX_BLOCK) void cc_link_kernel(CcArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const int64_t key = a.keys[i];
+    if (key < 0 || (i > 0 && a.keys[i - 1] >= key)) return;       // the contract is broken here (status says so): the row links nothing
+    const int64_t id = a.ids[i];
+    if (a.ignore.has(id)) return;
+    const int64_t cap = a.n + 1;
+    const int64_t ix = key >> 42, iy = key >> 21 & CC_AXIS_MAX, iz = key & CC_AXIS_MAX;
+    if (i > 0 && iz > 0 && a.keys[i - 1] == key - 1) cc_link(a, i, i - 1, id, cap);       // (0, 0, -1)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {                           // (dx, dy) = (-1, -1), (-1, 0), (-1, 1), (0, -1)
+        const int dx = q < 3 ? -1 : 0, dy = q < 3 ? q - 1 : -1;
+        const int planar = (dx != 0) + (dy != 0);
+        if (planar > a.max_nonzero) continue;
+        const int64_t nx = ix + dx, ny = iy + dy;
+        if (nx < 0 || ny < 0 || ny > CC_AXIS_MAX) continue; // no such column: nothing is borrowed from the next axis
+        const bool dz = planar < a.max_nonzero;             // dz = -1, +1 are in the neighbourhood as well
+        const int64_t column = nx << 42 | ny << 21;
+        const int64_t first = column | (dz && iz > 0 ? iz - 1 : iz), last = column | (dz && iz < CC_AXIS_MAX ? iz + 1 : iz);
+        int64_t lo = 0, hi = i;                             // the neighbours are earlier rows: lower bound of `first` in keys[0, i)
+        while (lo < hi) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (a.keys[mid] < first) lo = mid + 1;
+            else hi = mid;
+        }
+        for (int t = 0; t < 3; ++t) {
+            const int64_t j = lo + t;
+            if (j >= i) break;
+            const int64_t k = a.keys[j];
+            if (k < first || k > last) break;
+            cc_link(a, i, j, id, cap);
+        }
+    }
+}
+
+__global__ __launch_bounds__(VOX_BLOCK) void cc_flatten_kernel(CcArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const int64_t cap = a.n + 1;
+    int32_t x = (int32_t)i;
+    int64_t it = 0;
+    for (; it < cap; ++it) {
+        const int32_t p = a.parent[x];
+        if (p == x) break;
+        x = p;
+    }
+    if (it == cap) atomicOr(a.status, CC_CAP);
+    a.root[i] = x;
+}
+
+// rows in map order; a row is kept when it is the root of its component and its id is not ignored
+struct CcRootPred {
+    const int32_t *root;
+    const int64_t *ids, *keys;
+    int64_t n;
+    IgnoreSet ignore;
+    __device__ __forceinline__ bool operator()(int64_t i) const { return i < n && root[i] == (int32_t)i && keys[i] >= 0 && !ignore.has(ids[i]); }
+};
+
+// the write pass of the ordered append: root row i, the k-th kept row of the map, gets component k + 1
+__global__ __launch_bounds__(VOX_BLOCK) void cc_number_kernel(CcRootPred p, const int64_t *__restrict__ block_offset, int64_t *__restrict__ component) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    const bool keep = p(i);
+    const unsigned long long m = __ballot(keep);
+    __shared__ int wc[VOX_WAVES];
+    if (lane == 0) wc[wave] = __popcll(m);
+    __syncthreads();
+    int64_t base = block_offset[blockIdx.x];
+    for (int q = 0; q < wave; ++q) base += wc[q];
+    if (keep) component[i] = base + __popcll(m & ((1ull << lane) - 1ull)) + 1;
+}
+
+// Every other row: its root's number (a root row that was kept, written by the launch before and not here), 0 for a root that was not kept.
+__global__ __launch_bounds__(VOX_BLOCK) void cc_label_kernel(CcRootPred p, int64_t *component) {
+    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    if (i >= p.n) return;
+    const int32_t r = p.root[i];
+    if (r != (int32_t)i) component[i] = component[r];
+    else if (!p(i)) component[i] = 0;
+}
+
 int64_t vox_blocks(int64_t n) { return (n + VOX_BLOCK - 1) / VOX_BLOCK; }
 int64_t vox_align(int64_t b) { return (b + 255) / 256 * 256; }
 
@@ -413,5 +595,51 @@ extern "C" int pag_label_table(const int64_t *labels, const float *points, const
     hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(VOX_BLOCK), 0, st, (const int32_t *)block_count, nb, block_offset, count);
     hipLaunchKernelGGL(label_table_kernel, dim3((unsigned)nb), dim3(VOX_BLOCK), 0, st, p, a, (const int64_t *)block_offset);
     PAG_CHECK_LAUNCH("pag_label_table");
+    return PAG_OK;
+}
+
+extern "C" int64_t pag_voxel_components_workspace_bytes(int64_t n) {
+    if (n <= 0 || n >= VOX_MAX_ROWS) return 0;
+    return vox_align(n * 8) + 2 * vox_align(n * 4) + pag_voxel_workspace_bytes(n);      // keys, parent, root, the ordered append's block tables
+}
+
+extern "C" int pag_voxel_components(const int32_t *voxels, const int64_t *ids, int64_t n, int connectivity, int same_id, const int64_t *ignore_host,
+                                    int n_ignore, void *workspace, int64_t workspace_bytes, int64_t *component, int64_t *count, int32_t *status,
+                                    void *stream) {
+    PAG_CHECK_ARG(n >= 0 && n < VOX_MAX_ROWS, "pag_voxel_components: n %lld not in [0, 2^31)", (long long)n);
+    PAG_CHECK_ARG(connectivity == 6 || connectivity == 18 || connectivity == 26, "pag_voxel_components: connectivity %d is not 6, 18 or 26", connectivity);
+    PAG_CHECK_ARG(n_ignore >= 0 && n_ignore <= VOX_MAX_IGNORE && (n_ignore == 0 || ignore_host),
+                  "pag_voxel_components: n_ignore %d ignored ids (0..%d), or a NULL list", n_ignore, VOX_MAX_IGNORE);
+    if (n == 0) return PAG_OK;
+    PAG_CHECK_ARG(voxels && ids, "pag_voxel_components: NULL voxels / ids");
+    PAG_CHECK_ARG(component && count && status, "pag_voxel_components: NULL component / count / status");
+    PAG_CHECK_ARG(workspace && workspace_bytes >= pag_voxel_components_workspace_bytes(n),
+                  "pag_voxel_components: workspace smaller than pag_voxel_components_workspace_bytes(n)");
+    const int64_t nb = vox_blocks(n);
+    char *ws = (char *)workspace;
+    CcArgs a = {};
+    a.voxels = voxels, a.ids = ids, a.n = n, a.same_id = same_id != 0, a.status = status;
+    a.max_nonzero = connectivity == 6 ? 1 : connectivity == 18 ? 2 : 3;
+    a.ignore.n = n_ignore;
+    for (int k = 0; k < n_ignore; ++k) a.ignore.v[k] = ignore_host[k];
+    a.keys = (int64_t *)ws, ws += vox_align(n * 8);
+    a.parent = (int32_t *)ws, ws += vox_align(n * 4);
+    a.root = (int32_t *)ws, ws += vox_align(n * 4);
+    int64_t *block_offset = (int64_t *)ws;
+    int32_t *block_count = (int32_t *)(ws + vox_align(nb * 8));
+    CcRootPred p = {a.root, ids, a.keys, n, a.ignore};
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(count, 0, sizeof(int64_t), st);
+    if (e == hipSuccess) e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
+    PAG_CHECK_ARG(e == hipSuccess, "pag_voxel_components: hipMemsetAsync failed: %s", hipGetErrorString(e));
+    const dim3 grid((unsigned)nb), block(VOX_BLOCK);
+    hipLaunchKernelGGL(cc_prepare_kernel, grid, block, 0, st, a);
+    hipLaunchKernelGGL(cc_link_kernel, grid, block, 0, st, a);
+    hipLaunchKernelGGL(cc_flatten_kernel, grid, block, 0, st, a);
+    hipLaunchKernelGGL(vox_count_kernel<CcRootPred>, grid, block, 0, st, p, block_count);
+    hipLaunchKernelGGL(vox_scan_kernel, dim3(1), block, 0, st, (const int32_t *)block_count, nb, block_offset, count);
+    hipLaunchKernelGGL(cc_number_kernel, grid, block, 0, st, p, (const int64_t *)block_offset, component);
+    hipLaunchKernelGGL(cc_label_kernel, grid, block, 0, st, p, component);
+    PAG_CHECK_LAUNCH("pag_voxel_components");
     return PAG_OK;
 }

@@ -19,7 +19,8 @@ jittering it inside a cell; the density is queried at the shifted samples and th
 Beyond the reference: the FUSED VOXEL MAP (csrc/voxelmap.hip; second half of this file).  The views export holds a surface spot once per camera that
 saw it, each with that view's own id; VoxelMap / fuse_map reduce such clouds to one row per occupied voxel (mean point and colour, the id most points
 voted for, count, agreement), instance_table gives the per-instance table of the result, and `python -m pagnerf_amd.map_export fuse` does both on map
-files.  fuse_points_reference / label_table_reference are the tensor-op definitions.
+files.  fuse_points_reference / label_table_reference are the tensor-op definitions.  connected_components / clean_map / component_table split the
+fused map into connected components of equal-id voxels on the device (floaters dropped, reused ids told apart); their *_reference forms define them.
 """
 import pickle
 
@@ -416,11 +417,229 @@ def instance_table(fused, ignore=(0,), device=None, capacity=None):
     return _with_volume({k: v[:t].to(home) for k, v in out.items()}, fused["voxel_size"])
 
 
+# ------------------------------------------------------------------------------------------- connected components of the fused map
+# An instance id of the fused map is one object only if its voxels are one blob: a few mislabelled voxels far away stretch its box, and the instance
+# head may give one id to two distant objects.  The components of equal-id voxels on the lattice separate these: connected_components_reference is
+# the definition, connected_components the device path (pag_voxel_components), clean_map drops small components and keeps or splits the rest.
+CONNECTIVITIES = {6: 1, 18: 2, 26: 3}                      # neighbours -> the most non-zero components of a neighbour offset
+CLEAN_MODES = ("keep", "largest", "split")
+MAX_IGNORE = 8
+ROW_FIELDS = ("points", "color", "instances", "count", "agreement", "voxels", "component")
+_STATUS_TEXT = ((1, "the rows do not ascend strictly by voxel key"), (2, "a voxel index lies outside [0, 2^21)"),
+                (4, "a union-find walk exceeded its cap of V + 1 rounds"))
+
+
+def _check_components_args(connectivity, ignore):
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError("connectivity must be 6, 18 or 26, got %r" % (connectivity,))
+    ignore = tuple(int(v) for v in ignore)
+    if len(ignore) > MAX_IGNORE:
+        raise ValueError("at most %d ignored ids, got %d" % (MAX_IGNORE, len(ignore)))
+    return ignore
+
+
+def _raise_status(status):
+    raise ValueError("connected_components: " + "; ".join(text for bit, text in _STATUS_TEXT if status & bit))
+
+
+@torch.no_grad()
+def connected_components_reference(fused, connectivity=26, same_id=True, ignore=(0,)):
+    """The connected components of a fused map - the definition (NumPy on the CPU).  Reads 'voxels' i32 [V,3] (rows strictly ascending by key iz | iy
+    << 21 | ix << 42, else ValueError) and 'instances' i64 [V].  Rows whose id is in `ignore` get component 0 and link nothing; two other rows are
+    linked when their voxel indices differ by an offset of the neighbourhood (6: faces, 18: and edges, 26: and corners) and - same_id - their ids
+    are equal; an index outside [0, 2^21) does not exist.  Components are the transitive closure, numbered 1 .. C by their first row.
+    -> {'component' i64 [V], 'components' C}."""
+    import itertools
+    ignore = _check_components_args(connectivity, ignore)
+    vox = np.asarray(torch.as_tensor(fused["voxels"]).cpu()).reshape(-1, 3).astype(np.int64)
+    ids = np.asarray(torch.as_tensor(fused["instances"]).cpu()).reshape(-1).astype(np.int64)
+    V, lim = ids.shape[0], 2 ** VOXEL_AXIS_BITS
+    if vox.shape[0] != V:
+        raise ValueError("connected_components: voxels [V,3] and instances [V] must describe the same rows")
+    pack = lambda v: v[:, 2] | (v[:, 1] << VOXEL_AXIS_BITS) | (v[:, 0] << (2 * VOXEL_AXIS_BITS))       # noqa: E731
+    status = 2 * int(((vox < 0) | (vox >= lim)).any())
+    keys = pack(vox)
+    status |= int(status == 0 and bool((keys[1:] <= keys[:-1]).any()))
+    if status:
+        _raise_status(status)
+    if V == 0:
+        return {"component": torch.zeros(0, dtype=torch.int64), "components": 0}
+    live = ~np.isin(ids, np.asarray(ignore, np.int64))
+    rows = np.nonzero(live)[0]
+    most = CONNECTIVITIES[connectivity]
+    ea, eb = [], []
+    for off in itertools.product((-1, 0, 1), repeat=3):
+        if not off < (0, 0, 0) or sum(o != 0 for o in off) > most:                         # the forward half: every pair of neighbours once
+            continue
+        nb = vox[rows] + np.asarray(off, np.int64)
+        ok = ((nb >= 0) & (nb < lim)).all(1)                                               # per axis: the key arithmetic never borrows
+        src, want = rows[ok], pack(nb[ok])
+        at = np.minimum(np.searchsorted(keys, want), V - 1)
+        hit = (keys[at] == want) & live[at]
+        if same_id:
+            hit &= ids[at] == ids[src]
+        ea.append(src[hit])
+        eb.append(at[hit])
+    ea, eb = np.concatenate(ea), np.concatenate(eb)
+    parent = np.arange(V)
+    while True:                                                                            # smallest-row propagation: hook the roots, flatten, repeat
+        ra, rb = parent[ea], parent[eb]
+        if np.array_equal(ra, rb):
+            break
+        low = np.minimum(ra, rb)
+        np.minimum.at(parent, ra, low)
+        np.minimum.at(parent, rb, low)
+        while True:
+            up = parent[parent]
+            if np.array_equal(up, parent):
+                break
+            parent = up
+    is_root = live & (parent == np.arange(V))                                              # a component's root is its first row
+    number = np.cumsum(is_root)
+    component = np.where(live, number[parent], 0).astype(np.int64)
+    return {"component": torch.from_numpy(component), "components": int(is_root.sum())}
+
+
+@torch.no_grad()
+def connected_components(fused, connectivity=26, same_id=True, ignore=(0,), device=None):
+    """connected_components_reference on the device (pag_voxel_components: a lock-free union-find over the sorted rows and an ordered append over the
+    roots) -> {'component' i64 [V] where the map lives, 'components' C}.  Runs on `device` (default: where the map lives, "cuda" for a CPU map;
+    "cpu" selects the definition).  One synchronisation: the read of the count and the status word; a map that breaks the contract raises ValueError."""
+    ignore = _check_components_args(connectivity, ignore)
+    home = torch.as_tensor(fused["instances"]).device
+    dev = torch.device(device) if device is not None else (home if home.type != "cpu" else torch.device("cuda"))
+    if dev.type == "cpu":
+        out = connected_components_reference(fused, connectivity, same_id, ignore)
+        return {"component": out["component"].to(home), "components": out["components"]}
+    ids = torch.as_tensor(fused["instances"]).reshape(-1).to(dev, torch.int64)
+    vox = torch.as_tensor(fused["voxels"]).reshape(-1, 3).to(dev, torch.int32)
+    if vox.shape[0] != ids.numel():
+        raise ValueError("connected_components: voxels [V,3] and instances [V] must describe the same rows")
+    component = torch.empty(ids.numel(), dtype=torch.int64, device=dev)
+    count_status = torch.empty(2, dtype=torch.int64, device=dev)
+    ops.voxel_components(vox, ids, connectivity, same_id, ignore, component, count_status)
+    count, status = count_status.tolist()                                                  # the one synchronisation
+    if status:
+        _raise_status(status)
+    return {"component": component.to(home), "components": int(count)}
+
+
+def _clean_args(min_voxels, mode):
+    if mode not in CLEAN_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (", ".join(CLEAN_MODES), mode))
+    if int(min_voxels) < 1:
+        raise ValueError("min_voxels must be at least 1")
+    return int(min_voxels)
+
+
+@torch.no_grad()
+def clean_map_reference(fused, min_voxels=1, connectivity=26, mode="keep", ignore=(0,)):
+    """clean_map on the CPU, row by row - the definition."""
+    min_voxels = _clean_args(min_voxels, mode)
+    cc = connected_components_reference(fused, connectivity, True, ignore)
+    comp, C = cc["component"].numpy(), cc["components"]
+    ids = np.asarray(torch.as_tensor(fused["instances"]).cpu()).reshape(-1).astype(np.int64)
+    size = np.bincount(comp, minlength=C + 1)
+    cid = {}
+    for r in range(ids.shape[0]):
+        cid.setdefault(int(comp[r]), int(ids[r]))
+    alive = [c for c in range(1, C + 1) if size[c] >= min_voxels]
+    winner = {}
+    for c in alive:                                                                        # per id the most voxels; ascending c: a tie stays with the smaller number
+        if cid[c] not in winner or size[c] > size[winner[cid[c]]]:
+            winner[cid[c]] = c
+    if mode == "largest":
+        alive = [c for c in alive if winner[cid[c]] == c]
+    new_id = dict(cid)
+    if mode == "split":
+        nxt = max(int(ids.max()) if ids.size else 0, 0)
+        for c in alive:
+            if winner[cid[c]] != c:
+                nxt += 1
+                new_id[c] = nxt
+    number = {c: k + 1 for k, c in enumerate(alive)}
+    rows = [r for r in range(ids.shape[0]) if comp[r] == 0 or int(comp[r]) in number]
+    idx = torch.tensor(rows, dtype=torch.int64)
+    out = {k: (torch.as_tensor(v).cpu().index_select(0, idx) if k in ROW_FIELDS else v) for k, v in fused.items()}
+    out["instances"] = torch.tensor([int(ids[r]) if comp[r] == 0 else new_id[int(comp[r])] for r in rows], dtype=torch.int64)
+    out["component"] = torch.tensor([number.get(int(comp[r]), 0) for r in rows], dtype=torch.int64)
+    return out
+
+
+@torch.no_grad()
+def clean_map(fused, min_voxels=1, connectivity=26, mode="keep", ignore=(0,), device=None):
+    """A fused map without its floaters, its reused ids told apart: the map's keys plus 'component' i64 [V'], rows still ascending by key.
+      1  the components of equal-id voxels (connected_components, same_id)
+      2  every row whose component has fewer than min_voxels voxels is dropped; rows with an ignored id never are
+      3  mode "keep": ids stay; "largest": per id only the surviving component with the most voxels stays (equal sizes: the smaller component
+         number); "split": that component keeps the id, every other surviving component becomes a new instance max(ids of the input, 0) + 1, + 2,
+         ... in ascending component number
+      4  'component' of the surviving rows is renumbered densely in the same order
+    Steps 2 - 4 are tensor ops on C-length tables and one row mask.  Two synchronisations: the component count and the kept rows.  Rows are
+    selected, never recomputed.  device as in connected_components ("cpu": clean_map_reference); the result lives where the map does."""
+    min_voxels = _clean_args(min_voxels, mode)
+    ignore = _check_components_args(connectivity, ignore)
+    home = torch.as_tensor(fused["instances"]).device
+    dev = torch.device(device) if device is not None else (home if home.type != "cpu" else torch.device("cuda"))
+    if dev.type == "cpu":
+        cpu = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in fused.items()}
+        return {k: (v.to(home) if torch.is_tensor(v) else v) for k, v in clean_map_reference(cpu, min_voxels, connectivity, mode, ignore).items()}
+    on_dev = {k: (torch.as_tensor(v).to(dev) if k in ROW_FIELDS else v) for k, v in fused.items()}
+    cc = connected_components(on_dev, connectivity, True, ignore, dev)                      # synchronisation 1
+    comp, C = cc["component"], cc["components"]
+    ids = on_dev["instances"].reshape(-1).to(torch.int64)
+    if ids.numel() == 0:
+        return dict(fused, component=comp.to(home))
+    size = torch.zeros(C + 1, dtype=torch.int64, device=dev).index_add_(0, comp, torch.ones_like(comp))
+    cid = torch.zeros(C + 1, dtype=torch.int64, device=dev).scatter_(0, comp, ids)          # one id per component: every row writes the same value
+    real = torch.arange(C + 1, device=dev) > 0                                             # entry 0 stands for the ignored rows
+    keep = (size >= min_voxels) | ~real
+    new_ids = ids
+    if mode != "keep" and C > 0:
+        # the components ordered by (id, voxels descending, number): two stable sorts; dropped components count as -1 voxels
+        _, by_size = torch.sort(torch.where(keep, size, torch.full_like(size, -1))[1:], descending=True, stable=True)
+        sorted_id, by_id = torch.sort(cid[1:].index_select(0, by_size), stable=True)
+        order = by_size.index_select(0, by_id) + 1
+        first = torch.ones(C, dtype=torch.bool, device=dev)
+        first[1:] = sorted_id[1:] != sorted_id[:-1]
+        winner = torch.zeros(C + 1, dtype=torch.bool, device=dev).index_put_((order,), first) & keep
+        if mode == "largest":
+            keep = keep & (winner | ~real)
+        else:
+            extra = keep & ~winner & real
+            fresh = ids.max().clamp_min(0) + torch.cumsum(extra.long(), 0)
+            new_ids = torch.where(comp > 0, torch.where(extra, fresh, cid).index_select(0, comp), ids)
+    kept = keep & real
+    number = torch.cumsum(kept.long(), 0) * kept.long()
+    rows = torch.nonzero(keep.index_select(0, comp)).reshape(-1)                            # synchronisation 2
+    on_dev["instances"], on_dev["component"] = new_ids, number.index_select(0, comp)
+    out = {k: (on_dev[k].index_select(0, rows).to(home) if k in ROW_FIELDS else v) for k, v in on_dev.items()}
+    return out
+
+
+@torch.no_grad()
+def component_table(fused, device=None, capacity=None):
+    """instance_table over the labels 'component' of a map that has them (clean_map's result, or a map with connected_components' 'component' added):
+    one row per component other than 0, 'ids' the component number, and a column 'instance' i64 [T] with the id of the component's first row."""
+    if "component" not in fused:
+        raise ValueError("component_table needs a map with 'component' (clean_map, or connected_components' result added to the map)")
+    comp = torch.as_tensor(fused["component"]).reshape(-1).to(torch.int64)
+    table = instance_table(dict(fused, instances=comp), ignore=(0,), device=device, capacity=capacity)
+    V = comp.numel()
+    ids = torch.as_tensor(fused["instances"]).reshape(-1).to(comp.device, torch.int64)
+    first_row = torch.full((V + 1,), max(V - 1, 0), dtype=torch.int64, device=comp.device).scatter_reduce_(
+        0, comp, torch.arange(V, device=comp.device), "amin", include_self=True)
+    where = table["ids"].to(comp.device)
+    table["instance"] = (ids.index_select(0, first_row.index_select(0, where)) if V else ids[:0]).to(table["ids"].device)
+    return table
+
+
 def save_instance_table(table, path):
     """One header line, one line per instance: id, voxels, observations, volume, centroid, bounding box and (when present) colour; floats are
-    written with repr, so reading them back gives the same values."""
+    written with repr, so reading them back gives the same values.  A component table (component_table) has the column `instance` after `id`."""
     import csv
-    cols = [("id", "ids", None), ("voxels", "voxels", None), ("observations", "observations", None), ("volume", "volume", None)]
+    cols = [("id", "ids", None)] + ([("instance", "instance", None)] if "instance" in table else [])
+    cols += [("voxels", "voxels", None), ("observations", "observations", None), ("volume", "volume", None)]
     for key, stem in (("centroid", "centroid"), ("bbox_min", "min"), ("bbox_max", "max")):
         cols += [("%s_%s" % (stem, a), key, j) for j, a in enumerate("xyz")]
     if "color" in table:
@@ -437,7 +656,8 @@ def save_instance_table(table, path):
 
 def save_map(data, path):
     """The reference's nerf_pc.pkl: a pickle of the list; a path ending in .ply instead gets a little-endian binary PLY of all entries' points
-    (x y z float, red green blue uchar when colours exist, instance int; count int and agreement float when every entry is a fused map)."""
+    (x y z float, red green blue uchar when colours exist, instance int; count int and agreement float when every entry is a fused map; component
+    int when every entry has component labels)."""
     path = str(path)
     if not path.lower().endswith(".ply"):
         with open(path, "wb") as fh:
@@ -450,7 +670,12 @@ def save_map(data, path):
     fused = len(data) > 0 and all("count" in d for d in data)
     if fused:
         fields += [("count", "<i4"), ("agreement", "<f4")]
+    labelled = len(data) > 0 and all("component" in d for d in data)
+    if labelled:
+        fields += [("component", "<i4")]
     v = np.empty(pts.shape[0], dtype=fields)
+    if labelled:
+        v["component"] = np.concatenate([np.asarray(d["component"]).reshape(-1) for d in data], 0).astype("<i4")
     if fused:
         v["count"] = np.concatenate([np.asarray(d["count"]).reshape(-1) for d in data], 0).astype("<i4")
         v["agreement"] = np.concatenate([np.asarray(d["agreement"], dtype="<f4").reshape(-1) for d in data], 0)
@@ -471,7 +696,7 @@ def save_map(data, path):
 
 def main(argv=None):
     """python -m pagnerf_amd.map_export fuse IN.pkl [IN.pkl ...] --voxel-size V [--min-votes N] [--limits x0 y0 z0 x1 y1 z1] --out OUT.ply|OUT.pkl
-    [--table OUT.csv]"""
+    [--table OUT.csv] [--min-component N] [--connectivity 6|18|26] [--split keep|largest|split]"""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m pagnerf_amd.map_export")
     sub = ap.add_subparsers(dest="command", required=True)
@@ -489,6 +714,11 @@ def main(argv=None):
     fu.add_argument("--out", required=True, metavar="OUT.ply|OUT.pkl", help="the fused map (a .ply, or a pickle of a one-entry list)")
     fu.add_argument("--table", metavar="OUT.csv", help="also write the per-instance table")
     fu.add_argument("--device", default="cuda", help="where it runs; cpu selects the tensor-op definition")
+    fu.add_argument("--min-component", type=int, metavar="N", help="clean the fused map: drop connected components of equal-id voxels that have fewer than "
+                    "N voxels (ids of --ignore are left alone); the map gets a component label per voxel and --table becomes the per-component table")
+    fu.add_argument("--connectivity", type=int, choices=sorted(CONNECTIVITIES), metavar="6|18|26", help="neighbourhood of the components (default 26)")
+    fu.add_argument("--split", choices=CLEAN_MODES, metavar="keep|largest|split", help="an id with several components: keep them (default), keep only the "
+                    "largest, or make every further component a new instance")
     args = ap.parse_args(argv)
     data = []
     for path in args.inputs:
@@ -497,9 +727,14 @@ def main(argv=None):
         data += loaded if isinstance(loaded, (list, tuple)) else [loaded]
     limits = None if args.limits is None else [args.limits[:3], args.limits[3:]]
     fused = fuse_map(data, args.voxel_size, origin=args.origin, limits=limits, min_votes=args.min_votes, device=args.device)
+    clean = args.min_component is not None or args.connectivity is not None or args.split is not None
+    if clean:
+        fused = clean_map(fused, min_voxels=args.min_component or 1, connectivity=args.connectivity or 26, mode=args.split or "keep",
+                          ignore=args.ignore, device=args.device)
     save_map([fused], args.out)
     if args.table:
-        save_instance_table(instance_table(fused, ignore=args.ignore, device=args.device), args.table)
+        table = component_table(fused, device=args.device) if clean else instance_table(fused, ignore=args.ignore, device=args.device)
+        save_instance_table(table, args.table)
     print("%d points -> %d voxels: %s" % (sum(int(torch.as_tensor(d["points"]).reshape(-1, 3).shape[0]) for d in data), fused["points"].shape[0], args.out))
     return 0
 

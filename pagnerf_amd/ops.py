@@ -2049,6 +2049,27 @@ def label_table(labels, points, color, voxel_count, ignore, ids_out, voxels_out,
           bbox_max.data_ptr(), color_out.data_ptr() if color is not None else None, cap, count.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
 
 
+def voxel_components(voxels, ids, connectivity, same_id, ignore, component, count_status):
+    """The connected components of a fused map's rows (voxels i32 [n,3] ascending by key, ids i64 [n]) -> component i64 [n] (1 .. C by first row, 0
+    for an ignored id); count_status i64 [2] receives (C, status word), both overwritten (pag_voxel_components).  No synchronisation."""
+    _check_gpu(voxels, ids, component, count_status)
+    n = ids.numel()
+    if voxels.dtype != torch.int32 or tuple(voxels.shape) != (n, 3) or ids.dtype != torch.int64 or ids.dim() != 1:
+        raise RuntimeError("voxel_components: voxels int32 [n,3], ids int64 [n]")
+    if component.dtype != torch.int64 or tuple(component.shape) != (n,) or not component.is_contiguous() or count_status.dtype != torch.int64 or (
+            tuple(count_status.shape) != (2,)) or not count_status.is_contiguous():
+        raise RuntimeError("voxel_components: component int64 [n], count_status int64 [2], contiguous")
+    count_status.zero_()                                                                   # the status is an int32 word: its slot's upper half stays zero
+    if n == 0:
+        return
+    ignore = [int(v) for v in ignore]
+    ign = (ctypes.c_int64 * max(1, len(ignore)))(*ignore)
+    voxels, ids = voxels.contiguous(), ids.contiguous()
+    ws = torch.empty(max(int(L.load().pag_voxel_components_workspace_bytes(n)), 8), dtype=torch.uint8, device=ids.device)
+    _call("pag_voxel_components", voxels.data_ptr(), ids.data_ptr(), n, int(connectivity), int(bool(same_id)), ign, len(ignore), ws.data_ptr(), ws.numel(),
+          component.data_ptr(), count_status.data_ptr(), count_status.data_ptr() + 8, L.stream())
+
+
 def sample_copy_width(src_ptr, dst_ptr, row_bytes, convert=L.SAMPLE_COPY):
     """Bytes per copy element pag_sample_batch uses for a mode with these base addresses and destination row size (16 / 8 / 4 / 2 / 1; for the uint8 -> f32
     conversion 4 or 1 source bytes per step); 0 = the mode would be refused.  Host arithmetic only."""

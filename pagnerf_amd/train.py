@@ -1,5 +1,5 @@
 """python -m pagnerf_amd.train --config YAML --dataset TRAIN.npz|DIR [--val-dataset VAL.npz|DIR] [--log-dir DIR] [--resume CKPT] [--valid-only]
-                              [--val-pictures] [--save-map PATH [--map-voxel-size V [--map-min-votes N]]] [--set key=value ...]
+                              [--val-pictures] [--save-map PATH [--map-voxel-size V [--map-min-votes N] [--map-min-component N] [--map-split MODE]]] [--set key=value ...]
 
 The native counterpart of the reference's main_interactive.py: a shipped YAML, a dataset, and the trainer of trainer.py.
 
@@ -89,10 +89,12 @@ def load_dataset(path, split, cfg, device):
     return formats.load_nerf_standard(path, split=split, **common)
 
 
-def save_map(trainer, dataset, path, voxel_size=None, min_votes=1):
+def save_map(trainer, dataset, path, voxel_size=None, min_votes=1, min_component=None, split=None):
     """--save-map: the panoptic point cloud of the trained field from the training views (map_export.generate_pc_map_from_views).  With voxel_size
     (--map-voxel-size) the cloud is fused into the voxel map (map_export.fuse_map) before it is written, and the per-instance table goes beside it
-    as PATH with its suffix replaced by .instances.csv."""
+    as PATH with its suffix replaced by .instances.csv.  With min_component / split (--map-min-component / --map-split) the fused map is cleaned
+    first (map_export.clean_map: components of fewer than min_component voxels dropped, an id's further components kept, dropped or made new
+    instances), carries a component label per voxel, and the table is the per-component one."""
     from . import map_export
     from .core import Rays
     leaf = {l.field: l.src for l in dataset._leaves if l.key == "base_rays"}
@@ -104,7 +106,12 @@ def save_map(trainer, dataset, path, voxel_size=None, min_votes=1):
     if voxel_size is not None:
         device = trainer.pipeline.camera_extrinsics.device
         fused = map_export.fuse_map(cloud, voxel_size, min_votes=min_votes, device=device, name=cloud[0]["name"])
-        map_export.save_instance_table(map_export.instance_table(fused, device=device), os.path.splitext(str(path))[0] + ".instances.csv")
+        if min_component is not None or split is not None:
+            fused = map_export.clean_map(fused, min_voxels=min_component or 1, mode=split or "keep", device=device)
+            table = map_export.component_table(fused, device=device)
+        else:
+            table = map_export.instance_table(fused, device=device)
+        map_export.save_instance_table(table, os.path.splitext(str(path))[0] + ".instances.csv")
         cloud = [fused]
     map_export.save_map(cloud, path)
     return path
@@ -125,6 +132,10 @@ def main(argv=None):
     ap.add_argument("--map-voxel-size", type=float, metavar="V", help="--save-map writes the fused voxel map of edge V (one row per occupied voxel: mean "
                     "point and colour, voted instance id, count, agreement) and the instance table as PATH with the suffix .instances.csv")
     ap.add_argument("--map-min-votes", type=int, default=1, metavar="N", help="with --map-voxel-size: drop voxels that hold fewer than N points")
+    ap.add_argument("--map-min-component", type=int, metavar="N", help="with --map-voxel-size: drop connected components of equal-id voxels that have fewer "
+                    "than N voxels; the map gets a component label per voxel and the table one row per component")
+    ap.add_argument("--map-split", choices=("keep", "largest", "split"), metavar="MODE", help="with --map-voxel-size: an id with several components keeps "
+                    "them (keep), keeps only the largest (largest) or gives every further component a new id (split)")
     ap.add_argument("--set", action="append", default=[], metavar="key=value", help="override an option of the flattened namespace (repeatable)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
@@ -162,7 +173,7 @@ def main(argv=None):
     if val_dataset is not None and not (trainer.plan and trainer.plan["validate_after"]):      # the last epoch's own validation is not repeated
         trainer.validate(trainer.epoch - 1)
     if args.save_map:
-        save_map(trainer, dataset, args.save_map, args.map_voxel_size, args.map_min_votes)
+        save_map(trainer, dataset, args.save_map, args.map_voxel_size, args.map_min_votes, args.map_min_component, args.map_split)
     return 0
 
 
