@@ -814,6 +814,36 @@ int64_t pag_voxel_components_workspace_bytes(int64_t n);
 int pag_voxel_components(const int32_t *voxels, const int64_t *ids, int64_t n, int connectivity, int same_id, const int64_t *ignore_host,
                          int n_ignore, void *workspace, int64_t workspace_bytes, int64_t *component, int64_t *count, int32_t *status, void *stream);
 
+/* Two fused maps on one lattice: the shared voxels per pair of ids, the IoU / cost of the id association, and the merged map (additive to ABI 14;
+ * pagnerf_amd.map_export.overlap_table_reference / associate_maps_reference / merge_maps_reference are the definitions).  Each map: voxels i32
+ * [n,3] with rows STRICTLY ascending by key as above, ids i64 [n], uniq i64 [T] the map's distinct ids ascending (signed).
+ *
+ * pag_voxel_overlap: keys i64 [n] (-1: an index outside [0, 2^21)) and slot i32 [n] (the position of the row's id in uniq; -1: not in it) of both
+ *   maps, and table i32 [Ta,Tb] (ZEROED BY THE CALLER): table[slot_a, slot_b] += 1 for every key both maps hold (a lower-bound search per row of a
+ *   in b's keys).  Integer atomics, combined per wave before they leave it when combine != 0 (equal results either way).  status i32 [1], OVERWRITTEN: bits 0 / 1 as in pag_voxel_components (either map), bit 3 an id
+ *   that is missing from its list.  A map that breaks the contract is read as data: nothing is accessed out of range.  One memset, three launches,
+ *   no host synchronisation, no thread waits on another.  na + nb < 2^31, Ta * Tb < 2^31; an empty map is allowed (T = 0, NULL columns).
+ * pag_overlap_cost: iou f32 [Ta,Tb] = (float) t / (float) (row_sum[i] + col_sum[j] - t), 0 where that denominator is 0 (row_sum i64 [Ta], col_sum
+ *   i64 [Tb]: the table's sums); cost f32 [R,C] = 1.0f - iou over the active ids act_a i32 [n_a] / act_b i32 [n_b] (positions in uniq), oriented
+ *   for pag_assign_solve: R = min(n_a, n_b) rows, the rows being b's ids when n_a > n_b.  No contraction; one launch.
+ * pag_voxel_merge: keys i64 [na + nb] = both maps' keys sorted stably (a's rows first) and order i64 [na + nb] = that sort's permutation.  Every
+ *   run of equal keys gives one row in key order behind *count (i64 [1], device, zeroed by the caller; a slot at or past cap is counted and not
+ *   written).  b's id is mapping[slot_b] (mapping i64 [Tb]).  A run of one row is copied bit for bit.  A run of a's row and b's row: count = cA + cB
+ *   (saturating), points / color = (pA * (float) cA + pB * (float) cB) / (float) count in that order without contraction, votes v = rintf(agreement *
+ *   (float) c); equal ids: that id with vA + vB votes, else the id with more votes (ties: the smaller id) and its own votes; agreement = (float) votes
+ *   / (float) count.  color_out NULL: no colour.  status i32 [1] is ORed into: bit 4 a run of three or more rows, or of two rows of one map (its first
+ *   row is copied).  workspace: pag_voxel_workspace_bytes(na + nb).  Three launches, no host synchronisation. */
+int pag_voxel_overlap(const int32_t *voxels_a, const int64_t *ids_a, int64_t na, const int64_t *uniq_a, int Ta, const int32_t *voxels_b,
+                      const int64_t *ids_b, int64_t nb, const int64_t *uniq_b, int Tb, int combine, int64_t *keys_a, int32_t *slot_a, int64_t *keys_b,
+                      int32_t *slot_b, int32_t *table, int32_t *status, void *stream);
+int pag_overlap_cost(const int32_t *table, const int64_t *row_sum, const int64_t *col_sum, int Ta, int Tb, const int32_t *act_a, int n_a,
+                     const int32_t *act_b, int n_b, float *iou, float *cost, void *stream);
+int pag_voxel_merge(const int64_t *keys, const int64_t *order, int64_t na, int64_t nb, const float *points_a, const float *color_a,
+                    const int64_t *ids_a, const int32_t *count_a, const float *agreement_a, const int32_t *voxels_a, const float *points_b,
+                    const float *color_b, const int32_t *slot_b, const int64_t *mapping, int Tb, const int32_t *count_b, const float *agreement_b,
+                    const int32_t *voxels_b, float *points_out, float *color_out, int64_t *ids_out, int32_t *count_out, float *agreement_out,
+                    int32_t *voxels_out, int64_t cap, int64_t *count, int32_t *status, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Per-ray training loss of the rendered buffers (pc_nerf/trainer.py:443-446 rgb, :459-465 semantics,
  * loss/lin_assignment_things.py:80 instance term after the assignment) - one launch forward, one backward

@@ -24,6 +24,8 @@
             voxel map of the exported points and its per-instance table (`python -m pagnerf_amd.map_export fuse`); no counterpart in the reference
             connected_components, clean_map, component_table, connected_components_reference, clean_map_reference (map_export.py): the fused
             map split into connected components of equal-id voxels (floaters dropped, reused ids told apart)
+            overlap_table, associate_maps, relabel_map, merge_maps, merge_map_sequence and their *_reference definitions (map_export.py): the ids of
+            two windows' fused maps matched by voxel overlap and the maps merged (`python -m pagnerf_amd.map_export merge`)
     regularizers: tv_loss, tv_l1_loss, tv_l2_loss, grid_tv_loss, grid_tv_l1_loss, grid_tv_l2_loss, step_tv_terms (regularizers.py)
              <- loss/regularizers.py:41-70, pc_nerf/trainer.py:556-574 (the grid total-variation terms)
     dataset: DeviceMultiviewDataset, BatchSampler, SampleRays, sample_indices, epoch_views (dataset.py)
@@ -58,7 +60,9 @@ from .metrics import (MaskMeanAveragePrecision, MulticlassIoU, PanopticQuality, 
 from .map_export import (MapAccumulator, generate_pc_map, generate_pc_map_from_views, get_dense_occupied_points,    # noqa: F401
                          map_points_from_buffers, pinhole_base_rays, render_points_at_depth, save_map,
                          VoxelMap, fuse_map, fuse_points_reference, instance_table, label_table_reference, save_instance_table,
-                         clean_map, clean_map_reference, component_table, connected_components, connected_components_reference)
+                         clean_map, clean_map_reference, component_table, connected_components, connected_components_reference,
+                         associate_maps, associate_maps_reference, merge_map_sequence, merge_map_sequence_reference, merge_maps,
+                         merge_maps_reference, overlap_table, overlap_table_reference, relabel_map)
 from .regularizers import (grid_tv_l1_loss, grid_tv_l2_loss, grid_tv_loss, step_tv_terms, tv_l1_loss, tv_l2_loss,    # noqa: F401
                            tv_loss)
 from .dataset import BatchSampler, DeviceMultiviewDataset, SampleRays, epoch_views, sample_indices    # noqa: F401

@@ -253,6 +253,10 @@ _SIGS = {
                                 c_vp, c_i64, c_vp]),
     "pag_voxel_components_workspace_bytes": (c_i64, [c_i64]),
     "pag_voxel_components": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(ctypes.c_int64), c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "pag_voxel_overlap": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pag_overlap_cost": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "pag_voxel_merge": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "pag_mlp_dz0_slots_bytes": (c_i64, [c_i64, c_i64]),
     "pag_mlp_dz0_slots_sum": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pag_encode_bwd_rays_workspace_bytes": (c_i64, [c_i64, c_i64]),

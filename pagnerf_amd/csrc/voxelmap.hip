@@ -1,5 +1,6 @@
 // Fused panoptic voxel map: the exported map points of all views (map.hip) reduced to one row per occupied voxel, and the per-instance table of it.
-// Further down: the connected components of the fused map (a lock-free union-find over the sorted rows).
+// Further down: the connected components of the fused map (a lock-free union-find over the sorted rows), and two fused maps joined by voxel key:
+// the overlap table of their ids, the cost of the id association, and the merged map.
 //
 // As tensor ops the fusion is `unique` over voxel keys, `unique` over (key, id) pairs, several index_add_ calls, a scatter-arg-max with tie handling
 // and a boolean gather: about twenty launches and, the output sizes being dynamic, several host synchronisations.  Here:
@@ -512,6 +513,202 @@ __global__ __launch_bounds__(VOX_BLOCK) void cc_label_kernel(CcRootPred p, int64
     else if (!p(i)) component[i] = 0;
 }
 
+// ------------------------------------------------------------------------------------------- two fused maps: the join, the overlap table, the merge
+// Both maps ascend strictly by key, so "which voxels do they share, and under which pair of ids" is a join of two sorted columns:
+//   ov_prepare_kernel   per map: key of every row (cc_key; the contract bits of `status` as above) and the row's SLOT, the position of its id in the
+//                       map's sorted distinct ids (a lower-bound search; the list is staged in LDS when it has at most OV_LDS_IDS entries)
+//   ov_join_kernel      one thread per row of a: a lower-bound search for its key in b's keys; a hit adds 1 to table[slot_a * Tb + slot_b]
+//   ov_cost_kernel      the fp32 IoU of every table entry and the cost 1 - IoU of the active sub-matrix, in the orientation the solver takes
+//   vox_count_kernel<MergePred> / vox_scan_kernel / voxel_merge_kernel   the ordered append over the rows of both maps sorted stably by key (a's
+//                       rows first): a run of one row is copied, a run of two (one of each map) is merged, in key order behind the device counter
+// The search is the plain per-thread one over all of b.  The range of b that a workgroup's 256 rows need could be found once and staged in LDS, but
+// its length is not bounded (a sparse block of a spans any number of rows of b), so the staged form needs this search as its fallback anyway; it also
+// puts two dependent searches and a barrier in front of every lane's own.  Neighbouring lanes hold neighbouring keys: the upper levels of their
+// searches read the same addresses (one request per wave) and the lower ones neighbouring lines, which stay in L2 (b's keys: 8 bytes a voxel).
+// The adds are combined before they leave the wave (HIP guide, Guideline 12): contiguous rows mostly share their pair, and background x background
+// may own most of the map, all on one address.  Per round the first remaining lane's pair is broadcast, the lanes holding it are balloted, the
+// leader adds the popcount: at most 64 rounds, one when the wave is of one pair.  Integer atomics only: the table does not depend on arrival order.
+// NO THREAD WAITS ON ANOTHER.  Every index taken from data (slot, search bound, table offset, sort order) is checked before it is an address.
+constexpr int OV_ID = 8, OV_RUN = 16;                      // further bits of the status word: an id missing from its list, a run the merge cannot reduce
+constexpr int OV_LDS_IDS = 2048;
+
+template <class P>
+__device__ __forceinline__ int ov_lower_bound(P a, int n, int64_t v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(VOX_BLOCK) void ov_prepare_kernel(const int32_t *__restrict__ voxels, const int64_t *__restrict__ ids, int64_t n,
+                                                               const int64_t *__restrict__ uniq, int T, int64_t *__restrict__ keys,
+                                                               int32_t *__restrict__ slot, int32_t *__restrict__ status) {
+    __shared__ int64_t staged[OV_LDS_IDS];
+    const bool in_lds = T <= OV_LDS_IDS;                    // uniform over the grid
+    if (in_lds) {
+        for (int t = threadIdx.x; t < T; t += VOX_BLOCK) staged[t] = uniq[t];
+        __syncthreads();
+    }
+    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int64_t key = cc_key(voxels, i);
+    keys[i] = key;
+    int bad = key < 0 ? CC_RANGE : 0;
+    if (key >= 0 && i > 0 && cc_key(voxels, i - 1) >= key) bad |= CC_ORDER;
+    const int64_t id = ids[i];
+    int s = in_lds ? ov_lower_bound((const int64_t *)staged, T, id) : ov_lower_bound(uniq, T, id);
+    if (s >= T || (in_lds ? staged[s] : uniq[s]) != id) {
+        s = -1;
+        bad |= OV_ID;
+    }
+    slot[i] = s;
+    if (bad) atomicOr(status, bad);
+}
+
+template <bool COMBINE>
+__global__ __launch_bounds__(VOX_BLOCK) void ov_join_kernel(const int64_t *__restrict__ keys_a, const int32_t *__restrict__ slot_a, int64_t na,
+                                                            const int64_t *__restrict__ keys_b, const int32_t *__restrict__ slot_b, int64_t nb, int Ta,
+                                                            int Tb, int32_t *__restrict__ table) {
+    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    bool has = false;
+    int32_t pair = 0;
+    if (i < na) {
+        const int64_t key = keys_a[i];
+        int64_t lo = 0, hi = nb;
+        while (lo < hi) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (keys_b[mid] < key) lo = mid + 1;
+            else hi = mid;
+        }
+        const bool hit = key >= 0 && lo < nb && keys_b[lo] == key;
+        if (hit) {
+            const int sa = slot_a[i], sb = slot_b[lo];
+            has = sa >= 0 && sa < Ta && sb >= 0 && sb < Tb;
+            pair = has ? sa * Tb + sb : 0;
+        }
+    }
+    if (!COMBINE) {
+        if (has) atomicAdd(table + pair, 1);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(has);                // uniform over the wave: every lane takes every round
+    while (todo) {
+        const int leader = __builtin_ctzll(todo);
+        const int32_t p = __shfl(pair, leader);
+        const unsigned long long same = __ballot(has && pair == p);
+        if (lane == leader) atomicAdd(table + p, __popcll(same));
+        todo &= ~same;
+    }
+}
+
+// threads [0, Ta * Tb): iou of a table entry; threads [0, R * C): the cost of the active sub-matrix.  rows <= columns for the solver: `transposed`
+// says that the solver's rows are b's active ids.  iou = (float) t / (float) (r_i + c_j - t), 0 where that denominator is 0; cost = 1.0f - iou.
+__global__ __launch_bounds__(VOX_BLOCK) void ov_cost_kernel(const int32_t *__restrict__ table, const int64_t *__restrict__ row_sum,
+                                                            const int64_t *__restrict__ col_sum, int Ta, int Tb, const int32_t *__restrict__ act_a,
+                                                            const int32_t *__restrict__ act_b, int R, int C, int transposed, float *__restrict__ iou,
+                                                            float *__restrict__ cost) {
+    const int64_t x = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    auto iou_of = [&](int i, int j) -> float {
+        const int64_t t = table[(int64_t)i * Tb + j], den = row_sum[i] + col_sum[j] - t;
+        const float num = (float)t, d = (float)den;
+        return den != 0 ? num / d : 0.0f;
+    };
+    if (x < (int64_t)Ta * Tb) iou[x] = iou_of((int)(x / Tb), (int)(x % Tb));
+    if (x < (int64_t)R * C) {
+        const int r = (int)(x / C), c = (int)(x % C);
+        const int i = transposed ? act_a[c] : act_a[r], j = transposed ? act_b[r] : act_b[c];
+        const bool ok = i >= 0 && i < Ta && j >= 0 && j < Tb;
+        cost[x] = ok ? 1.0f - iou_of(i, j) : 1.0f;
+    }
+}
+
+// the rows of both maps sorted stably by key; a row is kept when it starts a run
+struct MergePred {
+    const int64_t *keys;
+    int64_t n;
+    __device__ __forceinline__ bool operator()(int64_t i) const { return i < n && (i == 0 || keys[i - 1] != keys[i]); }
+};
+
+struct MergeArgs {
+    const int64_t *order;           // sorted position -> row of the concatenation (a's rows, then b's)
+    int64_t na, nb;
+    const float *points[2], *color[2], *agreement[2];
+    const int64_t *ids_a;
+    const int32_t *count[2], *voxels[2], *slot_b;
+    const int64_t *mapping;         // b's id by slot
+    int Tb;
+    float *points_out, *color_out, *agreement_out;
+    int64_t *ids_out;
+    int32_t *count_out, *voxels_out, *status;
+    int64_t cap;
+};
+
+__device__ __forceinline__ int64_t merge_id(const MergeArgs &a, int m, int64_t r) {
+    if (m == 0) return a.ids_a[r];
+    const int s = a.slot_b[r];
+    return s >= 0 && s < a.Tb ? a.mapping[s] : 0;
+}
+
+__global__ __launch_bounds__(VOX_BLOCK) void voxel_merge_kernel(MergePred p, MergeArgs a, const int64_t *__restrict__ block_offset) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    const bool keep = p(i);
+    const unsigned long long m = __ballot(keep);
+    __shared__ int wc[VOX_WAVES];
+    if (lane == 0) wc[wave] = __popcll(m);
+    __syncthreads();
+    int64_t dst = block_offset[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+    for (int q = 0; q < wave; ++q) dst += wc[q];
+    if (!keep || dst >= a.cap) return;
+    const int64_t key = p.keys[i], total = a.na + a.nb;
+    const bool two = i + 1 < p.n && p.keys[i + 1] == key;
+    int64_t s0 = a.order[i], s1 = two ? a.order[i + 1] : 0;
+    s0 = s0 < 0 ? 0 : (s0 >= total ? total - 1 : s0);
+    s1 = s1 < 0 ? 0 : (s1 >= total ? total - 1 : s1);
+    bool merge = two && s0 < a.na && s1 >= a.na;            // the sort is stable: a's row comes first
+    if ((two && !merge) || (i + 2 < p.n && p.keys[i + 2] == key)) {
+        atomicOr(a.status, OV_RUN);
+        merge = false;
+    }
+    const int m0 = s0 >= a.na;
+    const int64_t r0 = m0 ? s0 - a.na : s0;
+    const bool colored = a.color_out != nullptr;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a.voxels_out[dst * 3 + c] = a.voxels[m0][r0 * 3 + c];
+    if (!merge) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            a.points_out[dst * 3 + c] = a.points[m0][r0 * 3 + c];
+            if (colored) a.color_out[dst * 3 + c] = a.color[m0][r0 * 3 + c];
+        }
+        a.ids_out[dst] = merge_id(a, m0, r0);
+        a.count_out[dst] = a.count[m0][r0];
+        a.agreement_out[dst] = a.agreement[m0][r0];
+        return;
+    }
+    const int64_t r1 = s1 - a.na;
+    const int32_t ca = a.count[0][r0], cb = a.count[1][r1];
+    const int64_t sum = (int64_t)ca + cb;
+    const int32_t cn = sum > INT32_MAX ? INT32_MAX : (int32_t)sum;
+    const float fa = (float)ca, fb = (float)cb, fn = (float)cn;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        a.points_out[dst * 3 + c] = (a.points[0][r0 * 3 + c] * fa + a.points[1][r1 * 3 + c] * fb) / fn;
+        if (colored) a.color_out[dst * 3 + c] = (a.color[0][r0 * 3 + c] * fa + a.color[1][r1 * 3 + c] * fb) / fn;
+    }
+    const int64_t va = (int64_t)rintf(a.agreement[0][r0] * fa), vb = (int64_t)rintf(a.agreement[1][r1] * fb);
+    const int64_t ia = merge_id(a, 0, r0), ib = merge_id(a, 1, r1);
+    const bool a_wins = vote_better(va, ia, vb, ib);
+    const int64_t votes = ia == ib ? va + vb : (a_wins ? va : vb);
+    a.ids_out[dst] = a_wins ? ia : ib;
+    a.count_out[dst] = cn;
+    a.agreement_out[dst] = (float)votes / fn;
+}
+
 int64_t vox_blocks(int64_t n) { return (n + VOX_BLOCK - 1) / VOX_BLOCK; }
 int64_t vox_align(int64_t b) { return (b + 255) / 256 * 256; }
 
@@ -641,5 +838,85 @@ extern "C" int pag_voxel_components(const int32_t *voxels, const int64_t *ids, i
     hipLaunchKernelGGL(cc_number_kernel, grid, block, 0, st, p, (const int64_t *)block_offset, component);
     hipLaunchKernelGGL(cc_label_kernel, grid, block, 0, st, p, component);
     PAG_CHECK_LAUNCH("pag_voxel_components");
+    return PAG_OK;
+}
+
+extern "C" int pag_voxel_overlap(const int32_t *voxels_a, const int64_t *ids_a, int64_t na, const int64_t *uniq_a, int Ta, const int32_t *voxels_b,
+                                 const int64_t *ids_b, int64_t nb, const int64_t *uniq_b, int Tb, int combine, int64_t *keys_a, int32_t *slot_a,
+                                 int64_t *keys_b, int32_t *slot_b, int32_t *table, int32_t *status, void *stream) {
+    PAG_CHECK_ARG(na >= 0 && nb >= 0 && na + nb < VOX_MAX_ROWS, "pag_voxel_overlap: rows %lld / %lld: negative, or together not below 2^31", (long long)na,
+                  (long long)nb);
+    PAG_CHECK_ARG(Ta >= 0 && Tb >= 0 && (int64_t)Ta * Tb <= INT32_MAX && Ta <= na && Tb <= nb,
+                  "pag_voxel_overlap: Ta %d / Tb %d ids: negative, more than rows, or a table of more than 2^31 - 1 entries", Ta, Tb);
+    PAG_CHECK_ARG(status, "pag_voxel_overlap: NULL status");
+    PAG_CHECK_ARG(na == 0 || (voxels_a && ids_a && uniq_a && keys_a && slot_a && Ta >= 1), "pag_voxel_overlap: NULL voxels / ids / id list / keys / slot of a, or no id");
+    PAG_CHECK_ARG(nb == 0 || (voxels_b && ids_b && uniq_b && keys_b && slot_b && Tb >= 1), "pag_voxel_overlap: NULL voxels / ids / id list / keys / slot of b, or no id");
+    PAG_CHECK_ARG(table || na == 0 || nb == 0, "pag_voxel_overlap: NULL table");
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
+    PAG_CHECK_ARG(e == hipSuccess, "pag_voxel_overlap: hipMemsetAsync failed: %s", hipGetErrorString(e));
+    const dim3 block(VOX_BLOCK);
+    if (na > 0) hipLaunchKernelGGL(ov_prepare_kernel, dim3((unsigned)vox_blocks(na)), block, 0, st, voxels_a, ids_a, na, uniq_a, Ta, keys_a, slot_a, status);
+    if (nb > 0) hipLaunchKernelGGL(ov_prepare_kernel, dim3((unsigned)vox_blocks(nb)), block, 0, st, voxels_b, ids_b, nb, uniq_b, Tb, keys_b, slot_b, status);
+    if (na > 0 && nb > 0) {
+        if (combine)
+            hipLaunchKernelGGL(ov_join_kernel<true>, dim3((unsigned)vox_blocks(na)), block, 0, st, (const int64_t *)keys_a, (const int32_t *)slot_a, na,
+                               (const int64_t *)keys_b, (const int32_t *)slot_b, nb, Ta, Tb, table);
+        else
+            hipLaunchKernelGGL(ov_join_kernel<false>, dim3((unsigned)vox_blocks(na)), block, 0, st, (const int64_t *)keys_a, (const int32_t *)slot_a, na,
+                               (const int64_t *)keys_b, (const int32_t *)slot_b, nb, Ta, Tb, table);
+    }
+    PAG_CHECK_LAUNCH("pag_voxel_overlap");
+    return PAG_OK;
+}
+
+extern "C" int pag_overlap_cost(const int32_t *table, const int64_t *row_sum, const int64_t *col_sum, int Ta, int Tb, const int32_t *act_a, int n_a,
+                                const int32_t *act_b, int n_b, float *iou, float *cost, void *stream) {
+    PAG_CHECK_ARG(Ta >= 0 && Tb >= 0 && (int64_t)Ta * Tb <= INT32_MAX, "pag_overlap_cost: Ta %d / Tb %d: negative, or more than 2^31 - 1 entries", Ta, Tb);
+    PAG_CHECK_ARG(n_a >= 0 && n_a <= Ta && n_b >= 0 && n_b <= Tb, "pag_overlap_cost: active ids %d / %d not in [0, Ta] / [0, Tb]", n_a, n_b);
+    const int64_t entries = (int64_t)Ta * Tb, active = (int64_t)n_a * n_b;
+    if (entries == 0) return PAG_OK;
+    PAG_CHECK_ARG(table && row_sum && col_sum && iou, "pag_overlap_cost: NULL table / sums / iou");
+    PAG_CHECK_ARG(active == 0 || (act_a && act_b && cost), "pag_overlap_cost: NULL active lists / cost");
+    const int transposed = n_a > n_b;
+    const int R = active == 0 ? 0 : (transposed ? n_b : n_a), C = active == 0 ? 0 : (transposed ? n_a : n_b);
+    hipLaunchKernelGGL(ov_cost_kernel, dim3((unsigned)vox_blocks(entries)), dim3(VOX_BLOCK), 0, (hipStream_t)stream, table, row_sum, col_sum, Ta, Tb, act_a,
+                       act_b, R, C, transposed, iou, cost);
+    PAG_CHECK_LAUNCH("pag_overlap_cost");
+    return PAG_OK;
+}
+
+extern "C" int pag_voxel_merge(const int64_t *keys, const int64_t *order, int64_t na, int64_t nb, const float *points_a, const float *color_a,
+                               const int64_t *ids_a, const int32_t *count_a, const float *agreement_a, const int32_t *voxels_a, const float *points_b,
+                               const float *color_b, const int32_t *slot_b, const int64_t *mapping, int Tb, const int32_t *count_b,
+                               const float *agreement_b, const int32_t *voxels_b, float *points_out, float *color_out, int64_t *ids_out,
+                               int32_t *count_out, float *agreement_out, int32_t *voxels_out, int64_t cap, int64_t *count, int32_t *status,
+                               void *workspace, int64_t workspace_bytes, void *stream) {
+    PAG_CHECK_ARG(na >= 0 && nb >= 0 && na + nb < VOX_MAX_ROWS && cap >= 0 && Tb >= 0 && Tb <= nb,
+                  "pag_voxel_merge: rows %lld / %lld: negative, or together not below 2^31; cap %lld < 0; Tb %d not in [0, rows of b]", (long long)na,
+                  (long long)nb, (long long)cap, Tb);
+    const int64_t n = na + nb;
+    if (n == 0) return PAG_OK;
+    PAG_CHECK_ARG(keys && order && count && status, "pag_voxel_merge: NULL keys / order / counter / status");
+    PAG_CHECK_ARG(na == 0 || (points_a && ids_a && count_a && agreement_a && voxels_a), "pag_voxel_merge: NULL column of a");
+    PAG_CHECK_ARG(nb == 0 || (points_b && slot_b && mapping && Tb >= 1 && count_b && agreement_b && voxels_b), "pag_voxel_merge: NULL column of b, or no id");
+    PAG_CHECK_ARG(cap == 0 || (points_out && ids_out && count_out && agreement_out && voxels_out), "pag_voxel_merge: NULL output");
+    PAG_CHECK_ARG(!color_out || ((na == 0 || color_a) && (nb == 0 || color_b)), "pag_voxel_merge: color_out without the colour of both maps");
+    PAG_CHECK_ARG(workspace && workspace_bytes >= pag_voxel_workspace_bytes(n), "pag_voxel_merge: workspace smaller than pag_voxel_workspace_bytes(na + nb)");
+    const int64_t blocks = vox_blocks(n);
+    int64_t *block_offset = (int64_t *)workspace;
+    int32_t *block_count = (int32_t *)((char *)workspace + vox_align(blocks * 8));
+    MergePred p = {keys, n};
+    MergeArgs a = {};
+    a.order = order, a.na = na, a.nb = nb, a.ids_a = ids_a, a.slot_b = slot_b, a.mapping = mapping, a.Tb = Tb;
+    a.points[0] = points_a, a.points[1] = points_b, a.color[0] = color_a, a.color[1] = color_b, a.agreement[0] = agreement_a, a.agreement[1] = agreement_b;
+    a.count[0] = count_a, a.count[1] = count_b, a.voxels[0] = voxels_a, a.voxels[1] = voxels_b;
+    a.points_out = points_out, a.color_out = color_out, a.agreement_out = agreement_out, a.ids_out = ids_out, a.count_out = count_out;
+    a.voxels_out = voxels_out, a.status = status, a.cap = cap;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(vox_count_kernel<MergePred>, dim3((unsigned)blocks), dim3(VOX_BLOCK), 0, st, p, block_count);
+    hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(VOX_BLOCK), 0, st, (const int32_t *)block_count, blocks, block_offset, count);
+    hipLaunchKernelGGL(voxel_merge_kernel, dim3((unsigned)blocks), dim3(VOX_BLOCK), 0, st, p, a, (const int64_t *)block_offset);
+    PAG_CHECK_LAUNCH("pag_voxel_merge");
     return PAG_OK;
 }

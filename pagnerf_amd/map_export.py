@@ -21,6 +21,8 @@ saw it, each with that view's own id; VoxelMap / fuse_map reduce such clouds to 
 voted for, count, agreement), instance_table gives the per-instance table of the result, and `python -m pagnerf_amd.map_export fuse` does both on map
 files.  fuse_points_reference / label_table_reference are the tensor-op definitions.  connected_components / clean_map / component_table split the
 fused map into connected components of equal-id voxels on the device (floaters dropped, reused ids told apart); their *_reference forms define them.
+overlap_table / associate_maps / merge_maps / merge_map_sequence match the ids of different training windows' maps by voxel overlap and merge the
+maps (`python -m pagnerf_amd.map_export merge`); again the *_reference forms are the definitions.
 """
 import pickle
 
@@ -315,8 +317,9 @@ class VoxelMap:
         self._chunks = []
         self._color = True
 
-    def add(self, points, ids, color=None):
-        points = points.detach().reshape(-1, 3).to(self.device, torch.float32)
+    def add(self, points, ids, color=None, scale=None, offset=None):
+        """scale / offset[3]: the chunk's frame; p * scale + offset (fp32: one multiplication, one addition) is what gets keyed and averaged."""
+        points = _to_frame(points.detach().reshape(-1, 3).to(self.device, torch.float32), scale, offset)
         ids = ids.detach().reshape(-1).to(self.device, torch.int64)
         if ids.numel() != points.shape[0] or (color is not None and color.numel() != points.numel()):
             raise ValueError("add: points [k,3], ids [k] and color [k,3] must describe the same rows")
@@ -359,24 +362,39 @@ class VoxelMap:
         return out
 
 
+def _to_frame(points, scale, offset):
+    """p * scale + offset in fp32 tensor ops, a multiplication and an addition (no contraction: two launches); the points as they are with both None."""
+    if scale is None and offset is None:
+        return points
+    s = torch.tensor(1.0 if scale is None else float(scale), dtype=torch.float32, device=points.device)
+    o = torch.as_tensor((0.0, 0.0, 0.0) if offset is None else offset, dtype=torch.float32).reshape(3).to(points.device)
+    return points * s + o
+
+
 def _entry_ids(d):
     return d["inst_embedding"] if "inst_embedding" in d else d["instances"]
 
 
-def fuse_map(data, voxel_size, origin=(-1.0, -1.0, -1.0), limits=None, min_votes=1, device="cuda", capacity=None, name="nerf_pc_fused"):
+def fuse_map(data, voxel_size, origin=(-1.0, -1.0, -1.0), limits=None, min_votes=1, device="cuda", capacity=None, name="nerf_pc_fused", frames=None):
     """The entries of a map list (what generate_pc_map_from_views / generate_pc_map return and nerf_pc.pkl holds: 'points', 'inst_embedding' or
-    'instances', optionally 'color') fused into ONE entry with CPU tensors: fuse_points_reference's keys with 'name'.  Ids are taken as they are
-    (matching the ids of different training windows is not done here).  device: where it runs; "cpu" is the tensor-op definition."""
+    'instances', optionally 'color') fused into ONE entry with CPU tensors: fuse_points_reference's keys with 'name'.  Ids are taken as they are:
+    the entries must share one numbering (the views of ONE training window do).  Maps of different windows are fused one by one and then joined by
+    merge_maps / merge_map_sequence, which match their ids by voxel overlap.  frames: one (scale, offset[3]) per entry, p * scale + offset in fp32
+    before the points are keyed (separately normalised windows brought into one frame); None: the points as they are.  device: where it runs;
+    "cpu" is the tensor-op definition."""
     colored = all("color" in d for d in data)
+    if frames is not None and len(frames) != len(data):
+        raise ValueError("frames: one (scale, offset) per entry, got %d for %d entries" % (len(frames), len(data)))
+    frames = [(None, None)] * len(data) if frames is None else frames
     if torch.device(device).type == "cpu":
-        pts = torch.cat([torch.as_tensor(d["points"]).reshape(-1, 3).float() for d in data]) if data else torch.zeros(0, 3)
+        pts = torch.cat([_to_frame(torch.as_tensor(d["points"]).reshape(-1, 3).float(), *f) for d, f in zip(data, frames)]) if data else torch.zeros(0, 3)
         ids = torch.cat([torch.as_tensor(_entry_ids(d)).reshape(-1).long() for d in data]) if data else torch.zeros(0, dtype=torch.int64)
         col = torch.cat([torch.as_tensor(d["color"]).reshape(-1, 3).float() for d in data]) if data and colored else None
         fused = fuse_points_reference(pts, ids, col, voxel_size, origin, limits, min_votes)
     else:
         vm = VoxelMap(voxel_size, origin, limits, min_votes, device, capacity)
-        for d in data:
-            vm.add(torch.as_tensor(d["points"]), torch.as_tensor(_entry_ids(d)), torch.as_tensor(d["color"]) if colored else None)
+        for d, f in zip(data, frames):
+            vm.add(torch.as_tensor(d["points"]), torch.as_tensor(_entry_ids(d)), torch.as_tensor(d["color"]) if colored else None, *f)
         fused = vm.finish()
     fused = {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in fused.items()}
     fused["name"] = name
@@ -426,7 +444,8 @@ CLEAN_MODES = ("keep", "largest", "split")
 MAX_IGNORE = 8
 ROW_FIELDS = ("points", "color", "instances", "count", "agreement", "voxels", "component")
 _STATUS_TEXT = ((1, "the rows do not ascend strictly by voxel key"), (2, "a voxel index lies outside [0, 2^21)"),
-                (4, "a union-find walk exceeded its cap of V + 1 rounds"))
+                (4, "a union-find walk exceeded its cap of V + 1 rounds"), (8, "an id is missing from the map's id list"),
+                (16, "a voxel key occurs more than once in a map"))
 
 
 def _check_components_args(connectivity, ignore):
@@ -438,8 +457,8 @@ def _check_components_args(connectivity, ignore):
     return ignore
 
 
-def _raise_status(status):
-    raise ValueError("connected_components: " + "; ".join(text for bit, text in _STATUS_TEXT if status & bit))
+def _raise_status(status, what="connected_components"):
+    raise ValueError(what + ": " + "; ".join(text for bit, text in _STATUS_TEXT if status & bit))
 
 
 @torch.no_grad()
@@ -634,6 +653,377 @@ def component_table(fused, device=None, capacity=None):
     return table
 
 
+# ------------------------------------------------------------------------------------------- ids across maps: overlap, association, merge
+# Every training window has its own instance head, so the ids of two windows' maps are unrelated while the windows overlap in space.  Two fused
+# maps on ONE lattice (equal float32(voxel_size), equal origin) are joined by voxel key: overlap_table counts the shared voxels per pair of ids,
+# associate_maps matches the ids one to one by the IoU over the CO-OCCUPIED voxels (an instance cut by the window border is not punished for the
+# part the other window never saw) with the Hungarian step, merge_maps relabels the second map and unites the rows.  The *_reference forms (NumPy
+# on the CPU) are the definitions; the device path is pag_voxel_overlap / pag_overlap_cost / pag_assign_solve / pag_voxel_merge.
+MAX_DEVICE_MATCH = 256                                     # active ids per side pag_assign_solve takes
+
+
+def _np(t, dtype):
+    return np.asarray(torch.as_tensor(t).detach().cpu()).astype(dtype)
+
+
+def _check_same_lattice(a, b, what):
+    if np.float32(a["voxel_size"]) != np.float32(b["voxel_size"]):
+        raise ValueError("%s: the maps have different voxel_size (%r, %r): they must lie on one lattice" % (what, a["voxel_size"], b["voxel_size"]))
+    oa, ob = _np(a["origin"], np.float32).reshape(-1), _np(b["origin"], np.float32).reshape(-1)
+    if oa.shape != (3,) or ob.shape != (3,) or not np.array_equal(oa, ob):
+        raise ValueError("%s: the maps have different origin (%s, %s): they must lie on one lattice" % (what, oa.tolist(), ob.tolist()))
+
+
+def _checked_keys(m, what):
+    """-> (keys i64 [V], ids i64 [V]) of a fused map, the contract checked with connected_components' status bits and wording."""
+    vox, ids = _np(m["voxels"], np.int64).reshape(-1, 3), _np(m["instances"], np.int64).reshape(-1)
+    if vox.shape[0] != ids.shape[0]:
+        raise ValueError("%s: voxels [V,3] and instances [V] must describe the same rows" % what)
+    status = 2 * int(((vox < 0) | (vox >= 2 ** VOXEL_AXIS_BITS)).any())
+    keys = vox[:, 2] | (vox[:, 1] << VOXEL_AXIS_BITS) | (vox[:, 0] << (2 * VOXEL_AXIS_BITS))
+    status |= int(status == 0 and bool((keys[1:] <= keys[:-1]).any()))
+    if status:
+        _raise_status(status, what)
+    return keys, ids
+
+
+def _check_match_args(min_iou, ignore):
+    ignore = tuple(int(v) for v in ignore)
+    if len(ignore) > MAX_IGNORE:
+        raise ValueError("at most %d ignored ids, got %d" % (MAX_IGNORE, len(ignore)))
+    if not 0.0 <= float(min_iou) <= 1.0:
+        raise ValueError("min_iou must lie in [0, 1], got %r" % (min_iou,))
+    return float(min_iou), ignore
+
+
+@torch.no_grad()
+def overlap_table_reference(a, b, _what="overlap_table"):
+    """The shared voxels of two fused maps per pair of ids - the definition (NumPy on the CPU).  Both maps lie on one lattice (else ValueError) and
+    ascend strictly by voxel key (else ValueError, as connected_components).  -> {'ids_a' i64 [Ta], 'ids_b' i64 [Tb]: each map's distinct ids
+    ascending (signed), 'table' i64 [Ta,Tb]: the voxel keys present in both maps with id ids_a[i] in a and ids_b[j] in b (ignored ids counted like
+    any other), 'shared': the table's sum}."""
+    _check_same_lattice(a, b, _what)
+    (ka, ia), (kb, ib) = _checked_keys(a, _what), _checked_keys(b, _what)
+    ua, sa = np.unique(ia, return_inverse=True)
+    ub, sb = np.unique(ib, return_inverse=True)
+    _, ra, rb = np.intersect1d(ka, kb, assume_unique=True, return_indices=True)
+    table = np.zeros((ua.shape[0], ub.shape[0]), np.int64)
+    np.add.at(table, (sa.reshape(-1)[ra], sb.reshape(-1)[rb]), 1)
+    return {"ids_a": torch.from_numpy(ua), "ids_b": torch.from_numpy(ub), "table": torch.from_numpy(table), "shared": int(table.sum())}
+
+
+def _iou_of_table(table):
+    """fp32: (float) t / (float) (r_i + c_j - t) with the sums over ALL columns / rows, 0 where the denominator is 0 (no shared voxel on either side)."""
+    den = table.sum(1, keepdims=True) + table.sum(0, keepdims=True) - table
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iou = table.astype(np.float32) / den.astype(np.float32)
+    return np.where(den != 0, iou, np.float32(0.0)).astype(np.float32)
+
+
+def _active(table, ids_a, ids_b, ignore):
+    """The positions of the active ids of either side, ascending: not ignored, a positive entry against a partner that is not ignored."""
+    live_a, live_b = ~np.isin(ids_a, np.asarray(ignore, np.int64)), ~np.isin(ids_b, np.asarray(ignore, np.int64))
+    pos = (table > 0) & live_a[:, None] & live_b[None, :]
+    return np.nonzero(pos.any(1))[0], np.nonzero(pos.any(0))[0]
+
+
+def _mapping_of_pairs(ids_a, ids_b, pair_pos, ignore):
+    """mapping i64 [Tb] from the matched positions [(i, j)]: the partner's id, itself for an ignored id, else a fresh id above every id of both maps,
+    in ascending order of the old id."""
+    top = max([0] + ([int(ids_a.max())] if ids_a.size else []) + ([int(ids_b.max())] if ids_b.size else []))
+    partner = {int(j): int(ids_a[i]) for i, j in pair_pos}
+    mapping = np.empty(ids_b.shape[0], np.int64)
+    for j, old in enumerate(ids_b.tolist()):
+        if j in partner:
+            mapping[j] = partner[j]
+        elif old in ignore:
+            mapping[j] = old
+        else:
+            top += 1
+            mapping[j] = top
+    return mapping
+
+
+@torch.no_grad()
+def associate_maps_reference(a, b, min_iou=0.25, ignore=(0,), _what="associate_maps"):
+    """The ids of b matched to the ids of a - the definition (NumPy and SciPy on the CPU).  From overlap_table_reference's table, iou[i,j] = table[i,j]
+    / (r_i + c_j - table[i,j]) with r_i / c_j the row / column sums over ALL columns / rows (ignored ids included): the IoU over the co-occupied
+    voxels, so an instance cut by the window border is not punished for the part the other window never saw.  fp32: two conversions, one division;
+    cost = 1.0f - iou.  The ACTIVE ids (not in `ignore`, a positive entry against a partner not in `ignore`), ascending, give the cost sub-matrix
+    that scipy.optimize.linear_sum_assignment solves in float64; an assigned pair is MATCHED when table[i,j] > 0 and iou[i,j] >= float32(min_iou).
+    ONE TO ONE ONLY: an instance of a that b sees as two keeps the better half, the other half becomes a fresh id (and the other way round).
+    -> {'ids_a', 'ids_b', 'table', 'iou' f32 [Ta,Tb], 'pairs' i64 [P,2] = (id_a, id_b) ascending by id_a, 'mapping' i64 [Tb]: the id ids_b[j] takes in
+    a's numbering - the matched partner's id, itself for an ignored id, else a fresh id from max(ids_a.max(), ids_b.max(), 0) + 1 upwards in ascending
+    order of the old id}."""
+    from scipy.optimize import linear_sum_assignment
+    min_iou, ignore = _check_match_args(min_iou, ignore)
+    out = overlap_table_reference(a, b, _what)
+    ids_a, ids_b, table = out["ids_a"].numpy(), out["ids_b"].numpy(), out["table"].numpy()
+    iou = _iou_of_table(table)
+    act_a, act_b = _active(table, ids_a, ids_b, ignore)
+    pairs = []
+    if act_a.size and act_b.size:
+        cost = np.float32(1.0) - iou[np.ix_(act_a, act_b)]
+        rows, cols = linear_sum_assignment(cost.astype(np.float64))
+        pairs = [(int(act_a[r]), int(act_b[c])) for r, c in zip(rows, cols)]
+        pairs = sorted((i, j) for i, j in pairs if table[i, j] > 0 and iou[i, j] >= np.float32(min_iou))
+    out.pop("shared")
+    out["iou"] = torch.from_numpy(iou)
+    out["pairs"] = torch.tensor([(int(ids_a[i]), int(ids_b[j])) for i, j in pairs], dtype=torch.int64).reshape(-1, 2)
+    out["mapping"] = torch.from_numpy(_mapping_of_pairs(ids_a, ids_b, pairs, ignore))
+    return out
+
+
+def relabel_map(m, ids, mapping):
+    """The map with every id ids[j] replaced by mapping[j] (ids i64 [T] ascending and holding every id of the map, e.g. associate_maps' 'ids_b' and
+    'mapping'); everything else is shared with m.  ValueError for an id of the map that `ids` lacks.  Tensor ops where the map lives."""
+    inst = torch.as_tensor(m["instances"]).reshape(-1).to(torch.int64)
+    ids = torch.as_tensor(ids).reshape(-1).to(inst.device, torch.int64)
+    mapping = torch.as_tensor(mapping).reshape(-1).to(inst.device, torch.int64)
+    if ids.numel() != mapping.numel():
+        raise ValueError("relabel_map: ids [T] and mapping [T] must have one length")
+    if inst.numel() == 0:
+        return dict(m, instances=inst)
+    if ids.numel() == 0:
+        raise ValueError("relabel_map: the map has ids and the list is empty")
+    slot = torch.searchsorted(ids, inst).clamp_max(ids.numel() - 1)
+    if not bool((ids.index_select(0, slot) == inst).all()):
+        raise ValueError("relabel_map: an id of the map is missing from ids")
+    return dict(m, instances=mapping.index_select(0, slot))
+
+
+def _checked_mapping(mapping, ids_b, what):
+    mapping = _np(mapping, np.int64).reshape(-1)
+    if mapping.shape[0] != ids_b.shape[0]:
+        raise ValueError("%s: mapping must hold one id per distinct id of b, ascending (%d), got %d" % (what, ids_b.shape[0], mapping.shape[0]))
+    return mapping
+
+
+@torch.no_grad()
+def merge_maps_reference(a, b, mapping=None, min_iou=0.25, ignore=(0,), _what="merge_maps"):
+    """Two fused maps on one lattice as one - the definition (NumPy on the CPU).  b is relabelled through `mapping` (i64 [Tb], one id per distinct id
+    of b in ascending order; None: associate_maps_reference(a, b, min_iou, ignore)['mapping']).  The result holds the union of the voxel rows in
+    ascending key order.  A voxel of one map only is copied bit for bit (b's with its new id).  A voxel of both, cA / cB the counts: count = cA + cB;
+    points (and color, kept only when BOTH maps carry it) = (pA * float(cA) + pB * float(cB)) / float(cA + cB) in fp32 in exactly this order, no
+    contraction; votes vA = rint(agreementA * cA), vB likewise; equal ids: that id with vA + vB votes; different ids: the id with more votes (ties: the
+    smaller id) with its own votes; agreement = float(votes) / float(count).  'component' is dropped (stale after a merge); voxel_size, origin and
+    'name' are a's.  A fused row has forgotten its minority votes, so this is NOT the fusion of the two windows' raw points: where the maps disagree
+    the losing side's votes for the winner, if any, are lost, and a third id can never win."""
+    min_iou, ignore = _check_match_args(min_iou, ignore)
+    _check_same_lattice(a, b, _what)
+    (ka, ia), (kb, ib) = _checked_keys(a, _what), _checked_keys(b, _what)
+    ub, sb = np.unique(ib, return_inverse=True)
+    if mapping is None:
+        mapping = associate_maps_reference(a, b, min_iou, ignore, _what=_what)["mapping"]
+    ib = _checked_mapping(mapping, ub, _what)[sb.reshape(-1)] if ib.size else ib
+    keys = np.union1d(ka, kb)
+    pa, pb = np.searchsorted(keys, ka), np.searchsorted(keys, kb)
+    V = keys.shape[0]
+    in_a, in_b = np.zeros(V, bool), np.zeros(V, bool)
+    in_a[pa], in_b[pb] = True, True
+    both = in_a & in_b
+    colored = "color" in a and "color" in b
+
+    def spread(field, dtype, width):
+        ca, cb = (np.zeros((V,) + width, dtype) for _ in range(2))
+        ca[pa], cb[pb] = _np(a[field], dtype).reshape((-1,) + width), _np(b[field], dtype).reshape((-1,) + width)
+        return ca, cb
+    cnt_a, cnt_b = spread("count", np.int32, ())
+    agr_a, agr_b = spread("agreement", np.float32, ())
+    vox_a, vox_b = spread("voxels", np.int32, (3,))
+    id_a, id_b = np.zeros(V, np.int64), np.zeros(V, np.int64)
+    id_a[pa], id_b[pb] = ia, ib
+    total = np.minimum(cnt_a.astype(np.int64) + cnt_b, 2 ** 31 - 1).astype(np.int32)
+    fa, fb, fn = cnt_a.astype(np.float32), cnt_b.astype(np.float32), total.astype(np.float32)
+    out = {}
+    for field in ("points", "color") if colored else ("points",):
+        xa, xb = spread(field, np.float32, (3,))
+        with np.errstate(all="ignore"):
+            mixed = (xa * fa[:, None] + xb * fb[:, None]) / fn[:, None]
+        out[field] = torch.from_numpy(np.where(both[:, None], mixed, np.where(in_a[:, None], xa, xb)))
+    with np.errstate(all="ignore"):
+        va, vb = np.rint(agr_a * fa).astype(np.int64), np.rint(agr_b * fb).astype(np.int64)
+        a_wins = (va > vb) | ((va == vb) & (id_a < id_b))
+        votes = np.where(id_a == id_b, va + vb, np.where(a_wins, va, vb))
+        agreement = votes.astype(np.float32) / fn
+    out["instances"] = torch.from_numpy(np.where(both, np.where(a_wins, id_a, id_b), np.where(in_a, id_a, id_b)))
+    out["count"] = torch.from_numpy(np.where(both, total, np.where(in_a, cnt_a, cnt_b)))
+    out["agreement"] = torch.from_numpy(np.where(both, agreement, np.where(in_a, agr_a, agr_b)).astype(np.float32))
+    out["voxels"] = torch.from_numpy(np.where(in_a[:, None], vox_a, vox_b))
+    out["voxel_size"] = a["voxel_size"]
+    out["origin"] = torch.as_tensor(a["origin"]).detach().cpu().clone()
+    if "name" in a:
+        out["name"] = a["name"]
+    return out
+
+
+def merge_map_sequence_reference(maps, min_iou=0.25, ignore=(0,)):
+    """merge_maps_reference as a left fold over `maps` in the given order; the running map plays a."""
+    return _fold(maps, lambda a, b: merge_maps_reference(a, b, None, min_iou, ignore))
+
+
+def _fold(maps, step):
+    maps = list(maps)
+    if not maps:
+        raise ValueError("merge_map_sequence: no map")
+    out = {k: v for k, v in maps[0].items() if k != "component"}
+    for m in maps[1:]:
+        out = step(out, m)
+    return out
+
+
+def _home_and_device(a, device):
+    home = torch.as_tensor(a["instances"]).device
+    return home, (torch.device(device) if device is not None else (home if home.type != "cpu" else torch.device("cuda")))
+
+
+def _cpu_map(m):
+    return {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in m.items()}
+
+
+def _to_home(out, home):
+    return {k: (v.to(home) if torch.is_tensor(v) else v) for k, v in out.items()}
+
+
+def _device_join(a, b, dev, what, combine=True):
+    """The device half shared by overlap_table / associate_maps / merge_maps: both maps' rows on `dev`, their distinct ids (synchronisations: the
+    lattice check and the sizes of the two lists) and pag_voxel_overlap's keys, slots and table.  The status word is not read here."""
+    _check_same_lattice(a, b, what)
+    rows = []
+    for m in (a, b):
+        ids = torch.as_tensor(m["instances"]).reshape(-1).to(dev, torch.int64)
+        vox = torch.as_tensor(m["voxels"]).reshape(-1, 3).to(dev, torch.int32)
+        if vox.shape[0] != ids.numel():
+            raise ValueError("%s: voxels [V,3] and instances [V] must describe the same rows" % what)
+        rows.append((vox, ids, torch.unique(ids)))
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    j = ops.voxel_overlap(*rows[0], *rows[1], status, combine=combine)
+    j.update(ids_a=rows[0][2], ids_b=rows[1][2], status=status)
+    return j
+
+
+@torch.no_grad()
+def overlap_table(a, b, device=None):
+    """overlap_table_reference on the device (pag_voxel_overlap: the join of the two sorted key columns, the adds combined per wave).  Runs on
+    `device` (default: where a lives, "cuda" for a CPU map; "cpu" selects the definition); the result lives where a does.  The synchronisations do not grow with
+    the maps (the lattice check, the two id lists, one read of the status word); a map that breaks the contract raises ValueError."""
+    home, dev = _home_and_device(a, device)
+    if dev.type == "cpu":
+        return _to_home(overlap_table_reference(_cpu_map(a), _cpu_map(b)), home)
+    j = _device_join(a, b, dev, "overlap_table")
+    table = j["table"].long()
+    status, shared = torch.stack((j["status"][0].long(), table.sum())).tolist()
+    if status:
+        _raise_status(status, "overlap_table")
+    return {"ids_a": j["ids_a"].to(home), "ids_b": j["ids_b"].to(home), "table": table.to(home), "shared": int(shared)}
+
+
+def _device_associate(j, min_iou, ignore, dev, what):
+    """From the join to the association, all on T-length tables: activity flags and their compaction (tensor ops), pag_overlap_cost, pag_assign_solve,
+    the fresh-id numbering and the mapping (tensor ops).  Two reads of device results: (status, active counts) and the solver's status with the pair count."""
+    ids_a, ids_b, table = j["ids_a"], j["ids_b"], j["table"]
+    Ta, Tb = table.shape
+    ign = torch.tensor(ignore if ignore else [0], dtype=torch.int64, device=dev)[:len(ignore)]
+    live_a, live_b = ~torch.isin(ids_a, ign), ~torch.isin(ids_b, ign)
+    pos = (table > 0) & live_a[:, None] & live_b[None, :]
+    on_a, on_b = pos.any(1), pos.any(0)
+    status, n_a, n_b = torch.stack((j["status"][0].long(), on_a.sum(), on_b.sum())).tolist()           # synchronisation
+    if status:
+        _raise_status(status, what)
+    if max(n_a, n_b) > MAX_DEVICE_MATCH:
+        raise ValueError('%s: %d and %d active ids, the device solver takes %d per side: pass device="cpu"' % (what, n_a, n_b, MAX_DEVICE_MATCH))
+    # the active positions ascending, without a data-dependent shape: a stable sort of the flags
+    act_a = torch.sort((~on_a).to(torch.uint8), stable=True)[1][:n_a].to(torch.int32)
+    act_b = torch.sort((~on_b).to(torch.uint8), stable=True)[1][:n_b].to(torch.int32)
+    wide = table.long()
+    iou, cost, transposed = ops.overlap_cost(table, wide.sum(1), wide.sum(0), act_a, act_b)
+    matched = torch.zeros(Ta, Tb, dtype=torch.bool, device=dev)
+    solved = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n_a and n_b:
+        R, C = cost.shape
+        info = torch.tensor([R, 0], dtype=torch.int32, device=dev)
+        targets = torch.empty(R, dtype=torch.int64, device=dev)
+        ops._call("pag_assign_solve", cost.data_ptr(), 1, R, C, info.data_ptr(), None, targets.data_ptr(), solved.data_ptr(), ops.L.stream())
+        rows_of, cols_of = (act_b, act_a) if transposed else (act_a, act_b)
+        r, c = rows_of.long(), cols_of.long().index_select(0, (targets - 1).clamp(0, C - 1))
+        i, k = (c, r) if transposed else (r, c)
+        ok = (table[i, k] > 0) & (iou[i, k] >= torch.tensor(min_iou, dtype=torch.float32, device=dev))
+        matched[i, k] = ok
+    has_partner = matched.any(0)
+    partner = ids_a.index_select(0, matched.to(torch.uint8).argmax(0)) if Ta else ids_b
+    fresh = ~has_partner & live_b
+    top = torch.stack([t.max() for t in (ids_a, ids_b) if t.numel()] + [torch.zeros((), dtype=torch.int64, device=dev)]).max()
+    mapping = torch.where(has_partner, partner, torch.where(fresh, top + torch.cumsum(fresh.long(), 0), ids_b))
+    failed, P = torch.stack((solved[0].long(), has_partner.sum())).tolist()                            # synchronisation
+    if failed:
+        raise RuntimeError("%s: pag_assign_solve did not solve the assignment (status %d)" % (what, failed))
+    by_a = matched.any(1)
+    rows = torch.sort((~by_a).to(torch.uint8), stable=True)[1][:P]
+    pairs = torch.stack((ids_a.index_select(0, rows), ids_b.index_select(0, matched.to(torch.uint8).argmax(1).index_select(0, rows))), 1) if Tb else \
+        torch.zeros(0, 2, dtype=torch.int64, device=dev)
+    return {"ids_a": ids_a, "ids_b": ids_b, "table": wide, "iou": iou, "pairs": pairs.reshape(-1, 2), "mapping": mapping}
+
+
+@torch.no_grad()
+def associate_maps(a, b, min_iou=0.25, ignore=(0,), device=None):
+    """associate_maps_reference on the device: pag_voxel_overlap's table, pag_overlap_cost's fp32 IoU and cost in the definition's op order, the
+    Hungarian step by pag_assign_solve (SciPy's algorithm, the same pairs); the T-length bookkeeping is tensor ops.  One to one only, as the
+    definition.  Runs on `device` (default: where a lives, "cuda" for a CPU map; "cpu" selects the definition); the result lives where a does.
+    Nine synchronisations as torch's debug mode counts them, whatever the maps' size.  More than 256 active ids on either side: ValueError (pass device="cpu"); nothing falls back."""
+    min_iou, ignore = _check_match_args(min_iou, ignore)
+    home, dev = _home_and_device(a, device)
+    if dev.type == "cpu":
+        return _to_home(associate_maps_reference(_cpu_map(a), _cpu_map(b), min_iou, ignore), home)
+    return _to_home(_device_associate(_device_join(a, b, dev, "associate_maps"), min_iou, ignore, dev, "associate_maps"), home)
+
+
+@torch.no_grad()
+def merge_maps(a, b, mapping=None, min_iou=0.25, ignore=(0,), device=None, capacity=None):
+    """merge_maps_reference on the device: the join (pag_voxel_overlap), the association unless `mapping` is given, one stable sort of both maps' keys
+    (torch.sort; a's rows first) and pag_voxel_merge, an ordered append over the runs of one or two rows in the definition's op order.  Runs on
+    `device` (default: where a lives, "cuda" for a CPU map; "cpu" selects the definition); the result lives where a does.  Outputs are sized for
+    all rows of both maps (52 bytes each, 40 without colour) unless `capacity` says otherwise; a merged map of more voxels raises with the count it
+    needed.  Ten synchronisations as torch's debug mode counts them, whatever the maps' size (six with `mapping`)."""
+    min_iou, ignore = _check_match_args(min_iou, ignore)
+    home, dev = _home_and_device(a, device)
+    if dev.type == "cpu":
+        return _to_home(merge_maps_reference(_cpu_map(a), _cpu_map(b), None if mapping is None else torch.as_tensor(mapping).cpu(), min_iou, ignore), home)
+    j = _device_join(a, b, dev, "merge_maps")
+    if mapping is None:
+        mapping = _device_associate(j, min_iou, ignore, dev, "merge_maps")["mapping"]
+    else:
+        mapping = torch.as_tensor(mapping).reshape(-1).to(dev, torch.int64)
+        if mapping.numel() != j["ids_b"].numel():
+            raise ValueError("merge_maps: mapping must hold one id per distinct id of b, ascending (%d), got %d" % (j["ids_b"].numel(), mapping.numel()))
+    colored = "color" in a and "color" in b
+    kinds = dict(points=torch.float32, color=torch.float32, count=torch.int32, agreement=torch.float32, voxels=torch.int32, instances=torch.int64)
+    fields = [k for k in kinds if k != "color" or colored]
+    on_dev = [{k: torch.as_tensor(m[k]).to(dev, kinds[k]).reshape((-1, 3) if k in ("points", "color", "voxels") else (-1,)).contiguous() for k in fields}
+              for m in (a, b)]
+    n = j["keys_a"].numel() + j["keys_b"].numel()
+    cap = n if capacity is None else min(int(capacity), n)
+    out = {k: torch.empty((cap, 3) if k in ("points", "color", "voxels") else (cap,), dtype=kinds[k], device=dev) for k in fields}
+    counter = torch.zeros(1, dtype=torch.int64, device=dev)
+    keys, order = torch.sort(torch.cat((j["keys_a"], j["keys_b"])), stable=True)
+    ops.voxel_merge(keys, order, on_dev[0], on_dev[1], j["slot_b"], mapping.contiguous(), out, counter, j["status"])
+    status, rows = torch.stack((j["status"][0].long(), counter[0])).tolist()                           # synchronisation
+    if status:
+        _raise_status(status, "merge_maps")
+    if rows > cap:
+        raise RuntimeError("the merged map has %d voxels, the outputs hold %d: pass capacity >= %d" % (rows, cap, rows))
+    out = {k: v[:rows].to(home) for k, v in out.items()}
+    out["voxel_size"] = a["voxel_size"]
+    out["origin"] = torch.as_tensor(a["origin"]).detach().clone()
+    if "name" in a:
+        out["name"] = a["name"]
+    return out
+
+
+def merge_map_sequence(maps, min_iou=0.25, ignore=(0,), device=None, capacity=None):
+    """merge_maps as a left fold over `maps` in the given order; the running map plays a (merge_map_sequence_reference on the device)."""
+    return _fold(maps, lambda a, b: merge_maps(a, b, None, min_iou, ignore, device, capacity))
+
+
 def save_instance_table(table, path):
     """One header line, one line per instance: id, voxels, observations, volume, centroid, bounding box and (when present) colour; floats are
     written with repr, so reading them back gives the same values.  A component table (component_table) has the column `instance` after `id`."""
@@ -696,7 +1086,9 @@ def save_map(data, path):
 
 def main(argv=None):
     """python -m pagnerf_amd.map_export fuse IN.pkl [IN.pkl ...] --voxel-size V [--min-votes N] [--limits x0 y0 z0 x1 y1 z1] --out OUT.ply|OUT.pkl
-    [--table OUT.csv] [--min-component N] [--connectivity 6|18|26] [--split keep|largest|split]"""
+    [--table OUT.csv] [--min-component N] [--connectivity 6|18|26] [--split keep|largest|split]
+    python -m pagnerf_amd.map_export merge A.pkl B.pkl [C.pkl ...] --out OUT.ply|OUT.pkl [--voxel-size V] [--frame S X Y Z ...] [--min-iou F]
+    [--ignore ID ...] [--table OUT.csv] [--pairs OUT.csv] [--min-component N] [--connectivity 6|18|26] [--split keep|largest|split]"""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m pagnerf_amd.map_export")
     sub = ap.add_subparsers(dest="command", required=True)
@@ -719,7 +1111,34 @@ def main(argv=None):
     fu.add_argument("--connectivity", type=int, choices=sorted(CONNECTIVITIES), metavar="6|18|26", help="neighbourhood of the components (default 26)")
     fu.add_argument("--split", choices=CLEAN_MODES, metavar="keep|largest|split", help="an id with several components: keep them (default), keep only the "
                     "largest, or make every further component a new instance")
+    me = sub.add_parser("merge", help="match the instance ids of several windows' maps and merge them into one",
+                        description="Merges the maps of several training windows into one voxel map with ONE id numbering.  Every input is a fused "
+                        "one-entry map (what `fuse` writes as .pkl) or a raw export, which is fused first (--voxel-size is then required).  The maps are "
+                        "merged from left to right: the ids of the next map are matched one to one to the ids of the map so far by the IoU over the "
+                        "voxels both hold (Hungarian assignment), matched ids take their partner's id, every other id becomes a new one, and the rows "
+                        "are united.  Ids that are reused for distant objects match badly: cleaning every input with --min-component / --split split "
+                        "before it is matched is the recommended route.  The inputs are pickles: trusted files only.")
+    me.add_argument("inputs", nargs="+", metavar="IN.pkl", help="fused maps or raw exports, one per window (pickles: trusted files only)")
+    me.add_argument("--voxel-size", type=float, metavar="V", help="voxel edge; required when an input is a raw export")
+    me.add_argument("--min-votes", type=int, default=1, metavar="N", help="raw exports: drop voxels that hold fewer than N points")
+    me.add_argument("--limits", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="raw exports: keep points strictly inside this box")
+    me.add_argument("--origin", type=float, nargs=3, default=(-1.0, -1.0, -1.0), metavar=("X", "Y", "Z"), help="raw exports: corner the voxel lattice is anchored at")
+    me.add_argument("--frame", type=float, nargs=4, action="append", metavar=("S", "X", "Y", "Z"), help="once per input, in order: the raw export's "
+                    "points become p * S + (X, Y, Z) before they are keyed (separately normalised windows brought into one frame)")
+    me.add_argument("--min-iou", type=float, default=0.25, metavar="F", help="least IoU over the co-occupied voxels of a matched pair (default 0.25)")
+    me.add_argument("--ignore", type=int, nargs="*", default=[0], metavar="ID", help="instance ids never matched and left out of the table (default: 0)")
+    me.add_argument("--out", required=True, metavar="OUT.ply|OUT.pkl", help="the merged map (a .ply, or a pickle of a one-entry list)")
+    me.add_argument("--table", metavar="OUT.csv", help="also write the per-instance table of the merged map")
+    me.add_argument("--pairs", metavar="OUT.csv", help="also write step, id_a, id_b, shared voxels and iou of every matched pair of every merge step")
+    me.add_argument("--device", default="cuda", help="where it runs; cpu selects the definitions")
+    me.add_argument("--min-component", type=int, metavar="N", help="clean every input before it is matched: drop connected components of equal-id voxels "
+                    "that have fewer than N voxels (recommended, with --split split)")
+    me.add_argument("--connectivity", type=int, choices=sorted(CONNECTIVITIES), metavar="6|18|26", help="neighbourhood of the components (default 26)")
+    me.add_argument("--split", choices=CLEAN_MODES, metavar="keep|largest|split", help="an id with several components in one input: keep them (default), "
+                    "keep only the largest, or make every further component a new instance (recommended: every id is then one blob)")
     args = ap.parse_args(argv)
+    if args.command == "merge":
+        return _merge_command(args)
     data = []
     for path in args.inputs:
         with open(path, "rb") as fh:
@@ -736,6 +1155,51 @@ def main(argv=None):
         table = component_table(fused, device=args.device) if clean else instance_table(fused, ignore=args.ignore, device=args.device)
         save_instance_table(table, args.table)
     print("%d points -> %d voxels: %s" % (sum(int(torch.as_tensor(d["points"]).reshape(-1, 3).shape[0]) for d in data), fused["points"].shape[0], args.out))
+    return 0
+
+
+def _merge_command(args):
+    import csv
+    if args.frame is not None and len(args.frame) != len(args.inputs):
+        raise SystemExit("merge: --frame must be given once per input (%d), got %d" % (len(args.inputs), len(args.frame)))
+    limits = None if args.limits is None else [args.limits[:3], args.limits[3:]]
+    clean = args.min_component is not None or args.connectivity is not None or args.split is not None
+    maps = []
+    for n, path in enumerate(args.inputs):
+        with open(path, "rb") as fh:
+            loaded = pickle.load(fh)
+        loaded = list(loaded) if isinstance(loaded, (list, tuple)) else [loaded]
+        if len(loaded) == 1 and "voxels" in loaded[0] and "count" in loaded[0]:
+            if args.frame is not None and tuple(args.frame[n]) != (1.0, 0.0, 0.0, 0.0):
+                raise SystemExit("merge: %s is a fused map already; --frame applies to raw exports (fuse it with the frame instead)" % path)
+            m = loaded[0]
+        else:
+            if args.voxel_size is None:
+                raise SystemExit("merge: %s is a raw export: --voxel-size is required to fuse it" % path)
+            frame = None if args.frame is None else [(args.frame[n][0], args.frame[n][1:])] * len(loaded)
+            m = fuse_map(loaded, args.voxel_size, origin=args.origin, limits=limits, min_votes=args.min_votes, device=args.device, frames=frame)
+        if clean:
+            m = clean_map(m, min_voxels=args.min_component or 1, connectivity=args.connectivity or 26, mode=args.split or "keep", ignore=args.ignore,
+                          device=args.device)
+        maps.append(m)
+    merged, steps = {k: v for k, v in maps[0].items() if k != "component"}, []
+    for n, m in enumerate(maps[1:]):
+        found = associate_maps(merged, m, min_iou=args.min_iou, ignore=args.ignore, device=args.device)
+        ia, ib = found["ids_a"].tolist(), found["ids_b"].tolist()
+        for id_a, id_b in found["pairs"].tolist():
+            i, j = ia.index(id_a), ib.index(id_b)
+            steps.append([n + 1, id_a, id_b, int(found["table"][i, j]), repr(float(found["iou"][i, j]))])
+        merged = merge_maps(merged, m, mapping=found["mapping"], device=args.device)
+    merged["name"] = "nerf_pc_merged"
+    save_map([merged], args.out)
+    if args.table:
+        save_instance_table(instance_table(merged, ignore=args.ignore, device=args.device), args.table)
+    if args.pairs:
+        with open(args.pairs, "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(["step", "id_a", "id_b", "shared_voxels", "iou"])
+            w.writerows(steps)
+    print("%d maps, %d matched pairs -> %d voxels: %s" % (len(maps), len(steps), merged["points"].shape[0], args.out))
     return 0
 
 

@@ -2070,6 +2070,75 @@ def voxel_components(voxels, ids, connectivity, same_id, ignore, component, coun
           component.data_ptr(), count_status.data_ptr(), count_status.data_ptr() + 8, L.stream())
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None and t.numel() > 0 else None
+
+
+def voxel_overlap(voxels_a, ids_a, uniq_a, voxels_b, ids_b, uniq_b, status, combine=True):
+    """The join of two fused maps' rows (voxels i32 [n,3] ascending by key, ids i64 [n], uniq i64 [T] the distinct ids ascending) ->
+    {'keys_a', 'keys_b' i64 [n], 'slot_a', 'slot_b' i32 [n], 'table' i32 [Ta,Tb]}; status i32 [1] is overwritten
+    with the contract bits (pag_voxel_overlap).  No synchronisation."""
+    _check_gpu(voxels_a, ids_a, uniq_a, voxels_b, ids_b, uniq_b, status)
+    na, nb, Ta, Tb = ids_a.numel(), ids_b.numel(), uniq_a.numel(), uniq_b.numel()
+    for v, i, u in ((voxels_a, ids_a, uniq_a), (voxels_b, ids_b, uniq_b)):
+        if v.dtype != torch.int32 or tuple(v.shape) != (i.numel(), 3) or i.dtype != torch.int64 or i.dim() != 1 or u.dtype != torch.int64 or u.dim() != 1:
+            raise RuntimeError("voxel_overlap: voxels int32 [n,3], ids int64 [n], uniq int64 [T]")
+    if status.dtype != torch.int32 or status.numel() != 1:
+        raise RuntimeError("voxel_overlap: status int32 [1]")
+    dev = status.device
+    out = {"keys_a": torch.empty(na, dtype=torch.int64, device=dev), "keys_b": torch.empty(nb, dtype=torch.int64, device=dev),
+           "slot_a": torch.empty(na, dtype=torch.int32, device=dev), "slot_b": torch.empty(nb, dtype=torch.int32, device=dev),
+           "table": torch.zeros(Ta, Tb, dtype=torch.int32, device=dev)}
+    voxels_a, ids_a, uniq_a, voxels_b, ids_b, uniq_b = (t.contiguous() for t in (voxels_a, ids_a, uniq_a, voxels_b, ids_b, uniq_b))
+    _call("pag_voxel_overlap", _ptr(voxels_a), _ptr(ids_a), na, _ptr(uniq_a), Ta, _ptr(voxels_b), _ptr(ids_b), nb, _ptr(uniq_b), Tb, int(bool(combine)),
+          _ptr(out["keys_a"]), _ptr(out["slot_a"]), _ptr(out["keys_b"]), _ptr(out["slot_b"]), _ptr(out["table"]), status.data_ptr(), L.stream())
+    return out
+
+
+def overlap_cost(table, row_sum, col_sum, act_a, act_b):
+    """table i32 [Ta,Tb] with its sums i64 [Ta] / [Tb] and the active positions act_a / act_b i32 -> (iou f32 [Ta,Tb], cost f32 [R,C], transposed):
+    the fp32 IoU of every entry and 1 - IoU of the active sub-matrix with R = min(n_a, n_b) rows, b's ids as rows when transposed (pag_overlap_cost)."""
+    _check_gpu(table, row_sum, col_sum, act_a, act_b)
+    Ta, Tb = table.shape
+    n_a, n_b = act_a.numel(), act_b.numel()
+    if table.dtype != torch.int32 or row_sum.dtype != torch.int64 or col_sum.dtype != torch.int64 or row_sum.numel() != Ta or col_sum.numel() != Tb or (
+            act_a.dtype != torch.int32 or act_b.dtype != torch.int32):
+        raise RuntimeError("overlap_cost: table int32 [Ta,Tb], row_sum int64 [Ta], col_sum int64 [Tb], act_a / act_b int32")
+    transposed = n_a > n_b
+    iou = torch.empty(Ta, Tb, dtype=torch.float32, device=table.device)
+    cost = torch.empty(min(n_a, n_b), max(n_a, n_b), dtype=torch.float32, device=table.device)
+    table, row_sum, col_sum, act_a, act_b = (t.contiguous() for t in (table, row_sum, col_sum, act_a, act_b))
+    _call("pag_overlap_cost", _ptr(table), _ptr(row_sum), _ptr(col_sum), Ta, Tb, _ptr(act_a), n_a, _ptr(act_b), n_b, _ptr(iou), _ptr(cost), L.stream())
+    return iou, cost, transposed
+
+
+def voxel_merge(keys, order, a, b, slot_b, mapping, out, count, status):
+    """The rows of two fused maps (a, b: dicts of 'points', 'instances' (a only), 'count', 'agreement', 'voxels', optionally 'color'), given both maps'
+    keys sorted stably and that sort's permutation, merged into the columns of `out` in key order behind the device counter `count` i64 [1]; b's ids
+    are mapping[slot_b]; colour is merged when out has 'color'; status i32 [1] is ORed into (pag_voxel_merge).  No synchronisation."""
+    cols = [a[k] for k in ("points", "instances", "count", "agreement", "voxels")] + [b[k] for k in ("points", "count", "agreement", "voxels")]
+    _check_gpu(keys, order, slot_b, mapping, count, status, *cols, *out.values())
+    na, nb = a["count"].numel(), b["count"].numel()
+    n, cap = na + nb, out["points"].shape[0]
+    if n == 0:
+        return
+    color = "color" in out
+    want = [(keys, torch.int64, (n,)), (order, torch.int64, (n,)), (slot_b, torch.int32, (nb,)), (a["instances"], torch.int64, (na,))]
+    for m, k in ((a, na), (b, nb), (out, cap)):
+        want += [(m["points"], torch.float32, (k, 3)), (m["count"], torch.int32, (k,)), (m["agreement"], torch.float32, (k,)), (m["voxels"], torch.int32, (k, 3))]
+        want += [(m.get("color"), torch.float32, (k, 3))] if color else []
+    want += [(out["instances"], torch.int64, (cap,))]
+    if any(t is None or t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in want) or mapping.dtype != torch.int64 or (
+            not mapping.is_contiguous()) or count.dtype != torch.int64 or status.dtype != torch.int32:
+        raise RuntimeError("voxel_merge: keys / order int64 [na + nb], slot_b int32 [nb], mapping int64 [Tb]; per map points / color f32 [n,3], instances "
+                           "int64 [n], count int32 [n], agreement f32 [n], voxels int32 [n,3], contiguous; count int64 [1], status int32 [1]")
+    ws = _voxel_workspace(n, keys.device)
+    _call("pag_voxel_merge", keys.data_ptr(), order.data_ptr(), na, nb, _ptr(a["points"]), _ptr(a.get("color")) if color else None, _ptr(a["instances"]),
+          _ptr(a["count"]), _ptr(a["agreement"]), _ptr(a["voxels"]), _ptr(b["points"]), _ptr(b.get("color")) if color else None, _ptr(slot_b), _ptr(mapping),
+          mapping.numel(), _ptr(b["count"]), _ptr(b["agreement"]), _ptr(b["voxels"]), _ptr(out["points"]), _ptr(out.get("color")), _ptr(out["instances"]),
+          _ptr(out["count"]), _ptr(out["agreement"]), _ptr(out["voxels"]), cap, count.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
+
+
 def sample_copy_width(src_ptr, dst_ptr, row_bytes, convert=L.SAMPLE_COPY):
     """Bytes per copy element pag_sample_batch uses for a mode with these base addresses and destination row size (16 / 8 / 4 / 2 / 1; for the uint8 -> f32
     conversion 4 or 1 source bytes per step); 0 = the mode would be refused.  Host arithmetic only."""
