@@ -2,23 +2,19 @@
 //
 // render_points_at_depth (:107-120) as tensor ops is an argmax over [n, 200] probabilities, five masks, the unprojection of every ray and three
 // boolean-index gathers (one host synchronisation each) per rendered chunk; get_dense_occupied_points / generate_pc_map (:46-79, :143-169) are the
-// same select without the camera.  Here a call is an ORDERED APPEND behind a running device counter, three launches, no host synchronisation:
-//   1. map_count_kernel  one thread per row: the predicate, a 64-bit ballot per wave, the kept rows of each 256-row block -> block_count
-//   2. map_scan_kernel   one workgroup: exclusive scan of the block counts on top of the counter -> block_offset; counter += kept rows
-//   3. map_write_kernel  the predicate again (the same device function on the same inputs), destination = block offset + kept rows of the lower
-//                        waves + kept lanes below (popcount of the ballot): ray order is kept whatever the chunking; rows at or past the
-//                        capacity are counted and not written.  Only KEPT rays are unprojected, copy their colour and have their instance row
-//                        read: the [n, I] rows are 800 of the ~850 bytes a ray owns at I = 200, and 50 - 95 % of the rays are dropped.
+// same select without the camera.  Here a call is an ORDERED APPEND behind a running device counter (ordered_append.h: count, scan and write pass,
+// three launches, no host synchronisation) with MapPred as the predicate and map_write_kernel as the write pass: ray order is kept whatever the
+// chunking; rows at or past the capacity are counted and not written.  Only KEPT rays are unprojected, copy their colour and have their instance
+// row read: the [n, I] rows are 800 of the ~850 bytes a ray owns at I = 200, and 50 - 95 % of the rays are dropped.
 // The instance id is torch.argmax's: the first index of the maximum, a NaN counting as the maximum (the first NaN wins).  A row is read by a
 // 16-lane group (four kept rows per wave pass, float4 loads where the row length and stride allow, scalar loads otherwise) and reduced with xor
 // shuffles under a total order on (value, index), so the result does not depend on how the elements were spread over the lanes.
 // The point is pose_points_kernel's: sum_k (o_c - t + d_c depth)[k] R[k], same op order; compiled with -ffp-contract=off.
+#include "ordered_append.h"
 #include "pose_common.h"
 
 namespace {
 
-constexpr int MAP_BLOCK = 256;
-constexpr int MAP_WAVES = MAP_BLOCK / PAG_WAVE;
 constexpr int MAP_EMPTY = 0x7fffffff;      // index of "no element yet": loses every tie
 
 enum { MAP_PRED_VIEWS = 0, MAP_PRED_VALUE = 1, MAP_PRED_IDS64 = 2, MAP_PRED_IDS32 = 3 };
@@ -35,20 +31,19 @@ struct MapPred {
     float threshold;
     const int64_t *ids64;
     const int32_t *ids32;
+    __device__ __forceinline__ bool operator()(int64_t i) const {
+        if (i >= n) return false;
+        switch (mode) {
+        case MAP_PRED_VIEWS: {
+            const float d = depth[i];
+            return density[i] > min_density && alpha[i] > min_alpha && hit[i] != 0 && d < depth_max && d > depth_min;
+        }
+        case MAP_PRED_VALUE: return value[i] > threshold;
+        case MAP_PRED_IDS64: return ids64[i] != 0;
+        default: return ids32[i] != 0;
+        }
+    }
 };
-
-__device__ __forceinline__ bool map_keep(const MapPred &p, int64_t i) {
-    if (i >= p.n) return false;
-    switch (p.mode) {
-    case MAP_PRED_VIEWS: {
-        const float d = p.depth[i];
-        return p.density[i] > p.min_density && p.alpha[i] > p.min_alpha && p.hit[i] != 0 && d < p.depth_max && d > p.depth_min;
-    }
-    case MAP_PRED_VALUE: return p.value[i] > p.threshold;
-    case MAP_PRED_IDS64: return p.ids64[i] != 0;
-    default: return p.ids32[i] != 0;
-    }
-}
 
 // torch.argmax's order: a beats b when a is NaN and b is not, when a > b, or on equal rank (both NaN, or a == b) when its index is lower
 __device__ __forceinline__ bool map_better(float a, int ia, float b, int ib) {
@@ -99,55 +94,13 @@ __device__ __forceinline__ int map_group_argmax(const float *__restrict__ inst, 
 }
 
 // ids32[row] = argmax of every row (the dense export's `argmax != 0` predicate needs all of them): 16 rows per workgroup
-__global__ __launch_bounds__(MAP_BLOCK) void map_argmax_kernel(const float *__restrict__ inst, int64_t n, int I, int64_t stride, int vec4,
+__global__ __launch_bounds__(OA_BLOCK) void map_argmax_kernel(const float *__restrict__ inst, int64_t n, int I, int64_t stride, int vec4,
                                                                int32_t *__restrict__ ids32) {
     const int l = threadIdx.x & 15;
-    const int64_t row = (int64_t)blockIdx.x * (MAP_BLOCK / 16) + (threadIdx.x >> 4);
+    const int64_t row = (int64_t)blockIdx.x * (OA_BLOCK / 16) + (threadIdx.x >> 4);
     const bool active = row < n;
     const int bi = map_group_argmax(inst, row, I, stride, vec4 != 0, active, l);
     if (active && l == 0) ids32[row] = bi;
-}
-
-__global__ __launch_bounds__(MAP_BLOCK) void map_count_kernel(MapPred p, int32_t *__restrict__ block_count) {
-    const int64_t i = (int64_t)blockIdx.x * MAP_BLOCK + threadIdx.x;
-    const unsigned long long m = __ballot(map_keep(p, i));
-    __shared__ int wc[MAP_WAVES];
-    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < MAP_WAVES; ++w) s += wc[w];
-        block_count[blockIdx.x] = s;
-    }
-}
-
-// One workgroup: block_offset[b] = *count + (kept rows of the blocks below b), then *count += all kept rows.  The counter is read and written by
-// this workgroup alone, and the stream orders the calls, so appends of successive calls line up without the host.
-__global__ __launch_bounds__(MAP_BLOCK) void map_scan_kernel(const int32_t *__restrict__ block_count, int64_t nb, int64_t *__restrict__ block_offset,
-                                                             int64_t *__restrict__ count) {
-    __shared__ int64_t sh[MAP_BLOCK];
-    __shared__ int64_t carry;
-    if (threadIdx.x == 0) carry = *count;
-    __syncthreads();
-    for (int64_t b0 = 0; b0 < nb; b0 += MAP_BLOCK) {
-        const int64_t b = b0 + threadIdx.x;
-        const int64_t mine = b < nb ? (int64_t)block_count[b] : 0;
-        sh[threadIdx.x] = mine;
-        __syncthreads();
-        for (int s = 1; s < MAP_BLOCK; s <<= 1) {
-            const int64_t add = (int)threadIdx.x >= s ? sh[threadIdx.x - s] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += add;
-            __syncthreads();
-        }
-        const int64_t base = carry;
-        if (b < nb) block_offset[b] = base + sh[threadIdx.x] - mine;
-        __syncthreads();
-        if (threadIdx.x == MAP_BLOCK - 1) carry = base + sh[threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = carry;
 }
 
 struct MapWrite {
@@ -172,20 +125,18 @@ struct MapWrite {
     int64_t cap;
 };
 
-__global__ __launch_bounds__(MAP_BLOCK) void map_write_kernel(MapPred p, MapWrite w, const int64_t *__restrict__ block_offset) {
+__global__ __launch_bounds__(OA_BLOCK) void map_write_kernel(MapPred p, MapWrite w, const int64_t *__restrict__ block_offset) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t i = (int64_t)blockIdx.x * MAP_BLOCK + threadIdx.x;
-    const bool keep = map_keep(p, i);
-    const unsigned long long m = __ballot(keep);
-    const int rank = __popcll(m & ((1ull << lane) - 1ull));
-    const int wcount = __popcll(m);
-    __shared__ int wc[MAP_WAVES];
-    __shared__ uint8_t kept_lane[MAP_WAVES][PAG_WAVE];
+    const int64_t i = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
+    const bool keep = p(i);
+    __shared__ int wc[OA_WAVES];
+    __shared__ uint8_t kept_lane[OA_WAVES][PAG_WAVE];
+    const OaVote vote = oa_vote(keep);
+    const int rank = vote.rank, wcount = vote.wcount;
     if (lane == 0) wc[wave] = wcount;
     if (keep) kept_lane[wave][rank] = (uint8_t)lane;
     __syncthreads();
-    int64_t wbase = block_offset[blockIdx.x];
-    for (int q = 0; q < wave; ++q) wbase += wc[q];
+    const int64_t wbase = oa_wave_base(block_offset, wc);
     const int64_t dst = wbase + rank;
     if (keep && dst < w.cap) {
         if (w.params) {
@@ -216,7 +167,7 @@ __global__ __launch_bounds__(MAP_BLOCK) void map_write_kernel(MapPred p, MapWrit
     if (w.inst && w.ids_out) {
         // the wave's kept rows, four per pass: group g of 16 lanes takes kept row k0 + g, whose destination is wbase + k0 + g
         const int g = lane >> 4, l = lane & 15;
-        const int64_t row0 = (int64_t)blockIdx.x * MAP_BLOCK + wave * PAG_WAVE;
+        const int64_t row0 = (int64_t)blockIdx.x * OA_BLOCK + wave * PAG_WAVE;
         for (int k0 = 0; k0 < wcount; k0 += 4) {          // wcount is uniform over the wave
             const int k = k0 + g;
             const bool active = k < wcount && wbase + k < w.cap;
@@ -226,9 +177,6 @@ __global__ __launch_bounds__(MAP_BLOCK) void map_write_kernel(MapPred p, MapWrit
         }
     }
 }
-
-int64_t map_blocks(int64_t n) { return (n + MAP_BLOCK - 1) / MAP_BLOCK; }
-int64_t map_align(int64_t b) { return (b + 255) / 256 * 256; }
 
 constexpr int64_t MAP_MAX_ROWS = (int64_t)1 << 31;
 
@@ -240,31 +188,28 @@ int map_check_inst(const char *name, const float *inst, int I, int64_t stride) {
 
 bool map_vec4(const float *inst, int I, int64_t stride) { return inst && I % 4 == 0 && stride % 4 == 0 && ((uintptr_t)inst & 15) == 0; }
 
-// the three launches of an append (plus the all-rows argmax of the `argmax != 0` predicate)
+// an append, after the all-rows argmax of the `argmax != 0` predicate into the workspace's ids32 plane (behind the append's block tables; it writes
+// the workspace before oa_append has checked it, hence the check of its own)
 int map_append(const char *name, MapPred p, MapWrite w, bool argmax_all, int64_t *count, void *workspace, int64_t workspace_bytes, hipStream_t st) {
-    const int64_t n = p.n, nb = map_blocks(n);
-    PAG_CHECK_ARG(workspace && workspace_bytes >= pag_map_workspace_bytes(n), "%s: workspace smaller than pag_map_workspace_bytes(n)", name);
-    int64_t *block_offset = (int64_t *)workspace;
-    int32_t *block_count = (int32_t *)((char *)workspace + map_align(nb * 8));
-    int32_t *ids32 = (int32_t *)((char *)workspace + map_align(nb * 8) + map_align(nb * 4));
+    const int64_t n = p.n, nb = oa_blocks(n), need = pag_map_workspace_bytes(n);
     if (argmax_all) {
-        hipLaunchKernelGGL(map_argmax_kernel, dim3((unsigned)((n + 15) / 16)), dim3(MAP_BLOCK), 0, st, w.inst, n, w.I, w.inst_stride, w.vec4, ids32);
+        PAG_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace smaller than pag_map_workspace_bytes(n)", name);
+        int32_t *ids32 = (int32_t *)((char *)workspace + oa_align(nb * 8) + oa_align(nb * 4));
+        hipLaunchKernelGGL(map_argmax_kernel, dim3((unsigned)((n + 15) / 16)), dim3(OA_BLOCK), 0, st, w.inst, n, w.I, w.inst_stride, w.vec4, ids32);
         p.ids32 = ids32;
         w.ids32 = ids32;
         w.inst = nullptr;
     }
-    hipLaunchKernelGGL(map_count_kernel, dim3((unsigned)nb), dim3(MAP_BLOCK), 0, st, p, block_count);
-    hipLaunchKernelGGL(map_scan_kernel, dim3(1), dim3(MAP_BLOCK), 0, st, (const int32_t *)block_count, nb, block_offset, count);
-    hipLaunchKernelGGL(map_write_kernel, dim3((unsigned)nb), dim3(MAP_BLOCK), 0, st, p, w, (const int64_t *)block_offset);
-    PAG_CHECK_LAUNCH(name);
-    return PAG_OK;
+    return oa_append(name, "pag_map_workspace_bytes(n)", need, p, count, workspace, workspace_bytes, st, [&](dim3 grid, dim3 block, const int64_t *block_offset) {
+        hipLaunchKernelGGL(map_write_kernel, grid, block, 0, st, p, w, block_offset);
+    });
 }
 }  // namespace
 
 extern "C" int64_t pag_map_workspace_bytes(int64_t n) {
     if (n <= 0 || n > MAP_MAX_ROWS) return 0;
-    const int64_t nb = map_blocks(n);
-    return map_align(nb * 8) + map_align(nb * 4) + map_align(n * 4);
+    const int64_t nb = oa_blocks(n);
+    return oa_align(nb * 8) + oa_align(nb * 4) + oa_align(n * 4);
 }
 
 extern "C" int pag_map_points(const float *params, int64_t C, const int32_t *cam, int64_t n_cam, int64_t rays_per_camera, const float *origins_c,

@@ -7,28 +7,31 @@
 //   1. voxel_keys_kernel    one thread per point: key = iz | iy << 21 | ix << 42 with i = floorf((p - o) / v) per axis (x slowest: the lattice order of
 //                           get_dense_occupied_points), INT64_MAX for a dropped row
 //   -  the host layer orders the rows by (key, id) with two stable torch.sort calls (rocPRIM's radix sort; plumbing)
-//   2. an ORDERED APPEND over the sorted rows, map.hip's count / scan / write with "row starts a kept run" as the predicate:
-//        vox_count_kernel   the kept run heads of each 256-row block
-//        vox_scan_kernel    one workgroup: exclusive scan of the block counts on top of the device counter
-//        voxel_fuse_kernel  a 16-lane group per kept run / label_table_kernel: the 256-thread workgroup per kept run
+//   2. an ORDERED APPEND over the sorted rows (ordered_append.h: count, scan and write pass) with "row starts a kept run" as the predicate and as
+//      the write pass voxel_fuse_kernel, a 16-lane group per kept run / label_table_kernel, the 256-thread workgroup per kept run
 // A run's end is found by a galloping upper_bound over the sorted keys (ids inside a voxel run are sorted too: the same search gives the id runs).
 // Lane j of a group takes rows j, j + W, ... of the run in that order, the lane partials are combined by an xor-shuffle tree (W = 16) or by the
 // shuffle tree of each wave and then the four waves in wave order (W = 256): the order of every sum depends on the sorted sequence and W alone, not
 // on the grid, the occupancy or how the points were chunked.  No float atomics; rows at or past the capacity are counted and not written.
 // The vote: the id with the most rows in the run, on equal counts the smaller id (signed): a max-reduction over the id-run heads under the total
 // order (length descending, id ascending).  Compiled with -ffp-contract=off: the key is two roundings (subtract, divide), the mean one division.
-#include "common.h"
+#include "ordered_append.h"
 
 namespace {
 
-constexpr int VOX_BLOCK = 256;
-constexpr int VOX_WAVES = VOX_BLOCK / PAG_WAVE;
 constexpr int VOX_GROUP = 16;                       // lanes per voxel run
 constexpr int VOX_GROUPS = PAG_WAVE / VOX_GROUP;    // runs a wave serves per pass
 constexpr int VOX_MAX_IGNORE = 8;
 constexpr int64_t VOX_DROPPED = INT64_MAX;
 constexpr int64_t VOX_MAX_ROWS = (int64_t)1 << 31;
 constexpr float VOX_AXIS = 2097152.0f;              // 2^21 cells per axis
+constexpr int64_t CC_AXIS_MAX = 0x1fffff;
+
+// a voxel's key, x slowest: ix << 42 | iy << 21 | iz, every index in [0, CC_AXIS_MAX]
+__device__ __forceinline__ int64_t vox_pack(int64_t x, int64_t y, int64_t z) { return x << 42 | y << 21 | z; }
+__device__ __forceinline__ void vox_unpack(int64_t key, int64_t &x, int64_t &y, int64_t &z) {
+    x = key >> 42, y = key >> 21 & CC_AXIS_MAX, z = key & CC_AXIS_MAX;
+}
 
 struct KeyArgs {
     const float *points;
@@ -39,8 +42,8 @@ struct KeyArgs {
     int64_t *keys;
 };
 
-__global__ __launch_bounds__(VOX_BLOCK) void voxel_keys_kernel(KeyArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(OA_BLOCK) void voxel_keys_kernel(KeyArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     bool ok = true;
     int64_t key = 0;
@@ -104,48 +107,6 @@ struct LabelPred {
     }
 };
 
-template <class Pred>
-__global__ __launch_bounds__(VOX_BLOCK) void vox_count_kernel(Pred p, int32_t *__restrict__ block_count) {
-    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
-    const unsigned long long m = __ballot(p(i));
-    __shared__ int wc[VOX_WAVES];
-    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < VOX_WAVES; ++w) s += wc[w];
-        block_count[blockIdx.x] = s;
-    }
-}
-
-// One workgroup: block_offset[b] = *count + (kept rows of the blocks below b), then *count += all kept rows (map.hip's scan pass).
-__global__ __launch_bounds__(VOX_BLOCK) void vox_scan_kernel(const int32_t *__restrict__ block_count, int64_t nb, int64_t *__restrict__ block_offset,
-                                                             int64_t *__restrict__ count) {
-    __shared__ int64_t sh[VOX_BLOCK];
-    __shared__ int64_t carry;
-    if (threadIdx.x == 0) carry = *count;
-    __syncthreads();
-    for (int64_t b0 = 0; b0 < nb; b0 += VOX_BLOCK) {
-        const int64_t b = b0 + threadIdx.x;
-        const int64_t mine = b < nb ? (int64_t)block_count[b] : 0;
-        sh[threadIdx.x] = mine;
-        __syncthreads();
-        for (int s = 1; s < VOX_BLOCK; s <<= 1) {
-            const int64_t add = (int)threadIdx.x >= s ? sh[threadIdx.x - s] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += add;
-            __syncthreads();
-        }
-        const int64_t base = carry;
-        if (b < nb) block_offset[b] = base + sh[threadIdx.x] - mine;
-        __syncthreads();
-        if (threadIdx.x == VOX_BLOCK - 1) carry = base + sh[threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = carry;
-}
-
 struct FuseArgs {
     const int64_t *ids;
     const float *points, *color;
@@ -158,23 +119,21 @@ struct FuseArgs {
 // the vote's total order: more rows win, on equal rows the smaller id
 __device__ __forceinline__ bool vote_better(int64_t la, int64_t ia, int64_t lb, int64_t ib) { return la > lb || (la == lb && ia < ib); }
 
-__global__ __launch_bounds__(VOX_BLOCK) void voxel_fuse_kernel(FusePred p, FuseArgs a, const int64_t *__restrict__ block_offset) {
+__global__ __launch_bounds__(OA_BLOCK) void voxel_fuse_kernel(FusePred p, FuseArgs a, const int64_t *__restrict__ block_offset) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
     const bool keep = p(i);
-    const unsigned long long m = __ballot(keep);
-    const int rank = __popcll(m & ((1ull << lane) - 1ull));
-    const int wcount = __popcll(m);
-    __shared__ int wc[VOX_WAVES];
-    __shared__ uint8_t kept_lane[VOX_WAVES][PAG_WAVE];
+    __shared__ int wc[OA_WAVES];
+    __shared__ uint8_t kept_lane[OA_WAVES][PAG_WAVE];
+    const OaVote vote = oa_vote(keep);
+    const int wcount = vote.wcount;
     if (lane == 0) wc[wave] = wcount;
-    if (keep) kept_lane[wave][rank] = (uint8_t)lane;
+    if (keep) kept_lane[wave][vote.rank] = (uint8_t)lane;
     __syncthreads();
-    int64_t wbase = block_offset[blockIdx.x];
-    for (int q = 0; q < wave; ++q) wbase += wc[q];
+    const int64_t wbase = oa_wave_base(block_offset, wc);
     // the wave's kept runs, four per pass: group g of 16 lanes takes the run that starts at kept row k0 + g, whose destination is wbase + k0 + g
     const int g = lane / VOX_GROUP, l = lane % VOX_GROUP;
-    const int64_t row0 = (int64_t)blockIdx.x * VOX_BLOCK + wave * PAG_WAVE;
+    const int64_t row0 = (int64_t)blockIdx.x * OA_BLOCK + wave * PAG_WAVE;
     for (int k0 = 0; k0 < wcount; k0 += VOX_GROUPS) {       // wcount is uniform over the wave
         const int k = k0 + g;
         const bool active = k < wcount && wbase + k < a.cap;
@@ -220,9 +179,11 @@ __global__ __launch_bounds__(VOX_BLOCK) void voxel_fuse_kernel(FusePred p, FuseA
             a.ids_out[dst] = best_id;
             a.count_out[dst] = rows > INT32_MAX ? INT32_MAX : (int32_t)rows;
             a.agreement[dst] = (float)best_len / fn;
-            a.voxels[dst * 3 + 0] = (int32_t)(key >> 42);
-            a.voxels[dst * 3 + 1] = (int32_t)(key >> 21 & 0x1fffff);
-            a.voxels[dst * 3 + 2] = (int32_t)(key & 0x1fffff);
+            int64_t ix, iy, iz;
+            vox_unpack(key, ix, iy, iz);
+            a.voxels[dst * 3 + 0] = (int32_t)ix;
+            a.voxels[dst * 3 + 1] = (int32_t)iy;
+            a.voxels[dst * 3 + 2] = (int32_t)iz;
         }
     }
 }
@@ -235,25 +196,25 @@ struct TableArgs {
     int64_t cap;
 };
 
-__global__ __launch_bounds__(VOX_BLOCK) void label_table_kernel(LabelPred p, TableArgs a, const int64_t *__restrict__ block_offset) {
+__global__ __launch_bounds__(OA_BLOCK) void label_table_kernel(LabelPred p, TableArgs a, const int64_t *__restrict__ block_offset) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t block0 = (int64_t)blockIdx.x * VOX_BLOCK;
+    const int64_t block0 = (int64_t)blockIdx.x * OA_BLOCK;
     const bool keep = p(block0 + threadIdx.x);
-    const unsigned long long m = __ballot(keep);
-    const int rank = __popcll(m & ((1ull << lane) - 1ull));
-    __shared__ int wc[VOX_WAVES];
-    __shared__ uint8_t kept_row[VOX_BLOCK];
-    __shared__ float part_f[VOX_WAVES][12];
-    __shared__ int64_t part_obs[VOX_WAVES];
-    if (lane == 0) wc[wave] = __popcll(m);
+    __shared__ int wc[OA_WAVES];
+    __shared__ uint8_t kept_row[OA_BLOCK];
+    __shared__ float part_f[OA_WAVES][12];
+    __shared__ int64_t part_obs[OA_WAVES];
+    const OaVote vote = oa_vote(keep);
+    if (lane == 0) wc[wave] = vote.wcount;
     __syncthreads();
+    // the kept rows of the whole block are listed (a run is served by all four waves), so the wave counts are used as they are, not as a wave base
     int below = 0, total = 0;
 #pragma unroll
-    for (int q = 0; q < VOX_WAVES; ++q) {
+    for (int q = 0; q < OA_WAVES; ++q) {
         below += q < wave ? wc[q] : 0;
         total += wc[q];
     }
-    if (keep) kept_row[below + rank] = (uint8_t)threadIdx.x;
+    if (keep) kept_row[below + vote.rank] = (uint8_t)threadIdx.x;
     __syncthreads();
     const int64_t base = block_offset[blockIdx.x];
     // the block's kept runs one after the other, each reduced by the whole workgroup: thread t takes rows t, t + 256, ... of the run
@@ -266,7 +227,7 @@ __global__ __launch_bounds__(VOX_BLOCK) void label_table_kernel(LabelPred p, Tab
         float s[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
         int64_t obs = 0;
-        for (int64_t r = start + threadIdx.x; r < end; r += VOX_BLOCK) {
+        for (int64_t r = start + threadIdx.x; r < end; r += OA_BLOCK) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float v = a.points[r * 3 + c];
@@ -306,7 +267,7 @@ __global__ __launch_bounds__(VOX_BLOCK) void label_table_kernel(LabelPred p, Tab
 #pragma unroll
             for (int c = 0; c < 12; ++c) t[c] = part_f[0][c];
             int64_t o = part_obs[0];
-            for (int w = 1; w < VOX_WAVES; ++w) {           // the waves in wave order
+            for (int w = 1; w < OA_WAVES; ++w) {           // the waves in wave order
 #pragma unroll
                 for (int c = 0; c < 6; ++c) t[c] += part_f[w][c];
 #pragma unroll
@@ -339,15 +300,14 @@ __global__ __launch_bounds__(VOX_BLOCK) void label_table_kernel(LabelPred p, Tab
 //   cc_prepare_kernel   key of every row (-1: an index outside [0, 2^21)), parent[i] = i, the contract bits of `status`
 //   cc_link_kernel      the unions: find both roots, hook the LARGER root under the smaller with a compare-and-swap
 //   cc_flatten_kernel   root[i], a walk over the finished forest
-//   vox_count_kernel<CcRootPred> / vox_scan_kernel / cc_number_kernel   the ordered append over "row is its own root and not ignored": root rows
-//                       get 1, 2, ... in row order
+//   cc_number_kernel    the write pass of the ordered append over "row is its own root and not ignored" (CcRootPred): root rows get 1, 2, ... in
+//                       row order
 //   cc_label_kernel     every other row takes its root's number, ignored rows 0
 // parent[x] <= x always and only a root (parent[x] == x) is ever hooked, under a smaller index: a component's final root is its smallest row, however
 // the lanes interleave, so the numbering is that of the definition.  NO THREAD WAITS ON ANOTHER: a failed compare-and-swap means another thread
 // hooked that root under a strictly smaller one, and the retry goes on from there; every walk and retry loop is also capped at V + 1 rounds
 // (CC_CAP in `status`, never reached on valid input).  In the link kernel parent is read and written by relaxed agent-scope atomics only.
 constexpr int CC_ORDER = 1, CC_RANGE = 2, CC_CAP = 4;      // bits of the status word
-constexpr int64_t CC_AXIS_MAX = 0x1fffff;
 
 struct IgnoreSet {
     int n;
@@ -373,11 +333,11 @@ struct CcArgs {
 __device__ __forceinline__ int64_t cc_key(const int32_t *__restrict__ voxels, int64_t i) {
     const int64_t x = voxels[i * 3], y = voxels[i * 3 + 1], z = voxels[i * 3 + 2];
     const bool ok = x >= 0 && x <= CC_AXIS_MAX && y >= 0 && y <= CC_AXIS_MAX && z >= 0 && z <= CC_AXIS_MAX;
-    return ok ? (x << 42 | y << 21 | z) : -1;
+    return ok ? vox_pack(x, y, z) : -1;
 }
 
-__global__ __launch_bounds__(VOX_BLOCK) void cc_prepare_kernel(CcArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(OA_BLOCK) void cc_prepare_kernel(CcArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     const int64_t key = cc_key(a.voxels, i);
     a.keys[i] = key;
@@ -430,15 +390,16 @@ __device__ __forceinline__ void cc_link(const CcArgs &a, int64_t i, int64_t j, i
     cc_union(a.parent, (int32_t)i, (int32_t)j, cap, a.status);
 }
 
-__global__ __launch_bounds__(VOX_BLOCK) void cc_link_kernel(CcArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(OA_BLOCK) void cc_link_kernel(CcArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     const int64_t key = a.keys[i];
     if (key < 0 || (i > 0 && a.keys[i - 1] >= key)) return;       // the contract is broken here (status says so): the row links nothing
     const int64_t id = a.ids[i];
     if (a.ignore.has(id)) return;
     const int64_t cap = a.n + 1;
-    const int64_t ix = key >> 42, iy = key >> 21 & CC_AXIS_MAX, iz = key & CC_AXIS_MAX;
+    int64_t ix, iy, iz;
+    vox_unpack(key, ix, iy, iz);
     if (i > 0 && iz > 0 && a.keys[i - 1] == key - 1) cc_link(a, i, i - 1, id, cap);       // (0, 0, -1)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                           // (dx, dy) = (-1, -1), (-1, 0), (-1, 1), (0, -1)
@@ -448,7 +409,7 @@ __global__ __launch_bounds__(VOX_BLOCK) void cc_link_kernel(CcArgs a) {
         const int64_t nx = ix + dx, ny = iy + dy;
         if (nx < 0 || ny < 0 || ny > CC_AXIS_MAX) continue; // no such column: nothing is borrowed from the next axis
         const bool dz = planar < a.max_nonzero;             // dz = -1, +1 are in the neighbourhood as well
-        const int64_t column = nx << 42 | ny << 21;
+        const int64_t column = vox_pack(nx, ny, 0);
         const int64_t first = column | (dz && iz > 0 ? iz - 1 : iz), last = column | (dz && iz < CC_AXIS_MAX ? iz + 1 : iz);
         int64_t lo = 0, hi = i;                             // the neighbours are earlier rows: lower bound of `first` in keys[0, i)
         while (lo < hi) {
@@ -466,8 +427,8 @@ __global__ __launch_bounds__(VOX_BLOCK) void cc_link_kernel(CcArgs a) {
     }
 }
 
-__global__ __launch_bounds__(VOX_BLOCK) void cc_flatten_kernel(CcArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(OA_BLOCK) void cc_flatten_kernel(CcArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     const int64_t cap = a.n + 1;
     int32_t x = (int32_t)i;
@@ -491,22 +452,21 @@ struct CcRootPred {
 };
 
 // the write pass of the ordered append: root row i, the k-th kept row of the map, gets component k + 1
-__global__ __launch_bounds__(VOX_BLOCK) void cc_number_kernel(CcRootPred p, const int64_t *__restrict__ block_offset, int64_t *__restrict__ component) {
+__global__ __launch_bounds__(OA_BLOCK) void cc_number_kernel(CcRootPred p, const int64_t *__restrict__ block_offset, int64_t *__restrict__ component) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
     const bool keep = p(i);
-    const unsigned long long m = __ballot(keep);
-    __shared__ int wc[VOX_WAVES];
-    if (lane == 0) wc[wave] = __popcll(m);
+    __shared__ int wc[OA_WAVES];
+    const OaVote vote = oa_vote(keep);
+    if (lane == 0) wc[wave] = vote.wcount;
     __syncthreads();
-    int64_t base = block_offset[blockIdx.x];
-    for (int q = 0; q < wave; ++q) base += wc[q];
-    if (keep) component[i] = base + __popcll(m & ((1ull << lane) - 1ull)) + 1;
+    const int64_t base = oa_wave_base(block_offset, wc);
+    if (keep) component[i] = base + vote.rank + 1;
 }
 
 // Every other row: its root's number (a root row that was kept, written by the launch before and not here), 0 for a root that was not kept.
-__global__ __launch_bounds__(VOX_BLOCK) void cc_label_kernel(CcRootPred p, int64_t *component) {
-    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(OA_BLOCK) void cc_label_kernel(CcRootPred p, int64_t *component) {
+    const int64_t i = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
     if (i >= p.n) return;
     const int32_t r = p.root[i];
     if (r != (int32_t)i) component[i] = component[r];
@@ -519,8 +479,8 @@ __global__ __launch_bounds__(VOX_BLOCK) void cc_label_kernel(CcRootPred p, int64
 //                       map's sorted distinct ids (a lower-bound search; the list is staged in LDS when it has at most OV_LDS_IDS entries)
 //   ov_join_kernel      one thread per row of a: a lower-bound search for its key in b's keys; a hit adds 1 to table[slot_a * Tb + slot_b]
 //   ov_cost_kernel      the fp32 IoU of every table entry and the cost 1 - IoU of the active sub-matrix, in the orientation the solver takes
-//   vox_count_kernel<MergePred> / vox_scan_kernel / voxel_merge_kernel   the ordered append over the rows of both maps sorted stably by key (a's
-//                       rows first): a run of one row is copied, a run of two (one of each map) is merged, in key order behind the device counter
+//   voxel_merge_kernel  the write pass of the ordered append (MergePred) over the rows of both maps sorted stably by key (a's rows first): a run
+//                       of one row is copied, a run of two (one of each map) is merged, in key order behind the device counter
 // The search is the plain per-thread one over all of b.  The range of b that a workgroup's 256 rows need could be found once and staged in LDS, but
 // its length is not bounded (a sparse block of a spans any number of rows of b), so the staged form needs this search as its fallback anyway; it also
 // puts two dependent searches and a barrier in front of every lane's own.  Neighbouring lanes hold neighbouring keys: the upper levels of their
@@ -532,27 +492,27 @@ __global__ __launch_bounds__(VOX_BLOCK) void cc_label_kernel(CcRootPred p, int64
 constexpr int OV_ID = 8, OV_RUN = 16;                      // further bits of the status word: an id missing from its list, a run the merge cannot reduce
 constexpr int OV_LDS_IDS = 2048;
 
-template <class P>
-__device__ __forceinline__ int ov_lower_bound(P a, int n, int64_t v) {
-    int lo = 0, hi = n;
+template <class P, class I>
+__device__ __forceinline__ I ov_lower_bound(P a, I n, int64_t v) {
+    I lo = 0, hi = n;
     while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
+        const I mid = lo + ((hi - lo) >> 1);
         if (a[mid] < v) lo = mid + 1;
         else hi = mid;
     }
     return lo;
 }
 
-__global__ __launch_bounds__(VOX_BLOCK) void ov_prepare_kernel(const int32_t *__restrict__ voxels, const int64_t *__restrict__ ids, int64_t n,
+__global__ __launch_bounds__(OA_BLOCK) void ov_prepare_kernel(const int32_t *__restrict__ voxels, const int64_t *__restrict__ ids, int64_t n,
                                                                const int64_t *__restrict__ uniq, int T, int64_t *__restrict__ keys,
                                                                int32_t *__restrict__ slot, int32_t *__restrict__ status) {
     __shared__ int64_t staged[OV_LDS_IDS];
     const bool in_lds = T <= OV_LDS_IDS;                    // uniform over the grid
     if (in_lds) {
-        for (int t = threadIdx.x; t < T; t += VOX_BLOCK) staged[t] = uniq[t];
+        for (int t = threadIdx.x; t < T; t += OA_BLOCK) staged[t] = uniq[t];
         __syncthreads();
     }
-    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
     if (i >= n) return;
     const int64_t key = cc_key(voxels, i);
     keys[i] = key;
@@ -569,20 +529,15 @@ __global__ __launch_bounds__(VOX_BLOCK) void ov_prepare_kernel(const int32_t *__
 }
 
 template <bool COMBINE>
-__global__ __launch_bounds__(VOX_BLOCK) void ov_join_kernel(const int64_t *__restrict__ keys_a, const int32_t *__restrict__ slot_a, int64_t na,
+__global__ __launch_bounds__(OA_BLOCK) void ov_join_kernel(const int64_t *__restrict__ keys_a, const int32_t *__restrict__ slot_a, int64_t na,
                                                             const int64_t *__restrict__ keys_b, const int32_t *__restrict__ slot_b, int64_t nb, int Ta,
                                                             int Tb, int32_t *__restrict__ table) {
-    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
     bool has = false;
     int32_t pair = 0;
     if (i < na) {
         const int64_t key = keys_a[i];
-        int64_t lo = 0, hi = nb;
-        while (lo < hi) {
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            if (keys_b[mid] < key) lo = mid + 1;
-            else hi = mid;
-        }
+        const int64_t lo = ov_lower_bound(keys_b, nb, key);
         const bool hit = key >= 0 && lo < nb && keys_b[lo] == key;
         if (hit) {
             const int sa = slot_a[i], sb = slot_b[lo];
@@ -607,11 +562,11 @@ __global__ __launch_bounds__(VOX_BLOCK) void ov_join_kernel(const int64_t *__res
 
 // threads [0, Ta * Tb): iou of a table entry; threads [0, R * C): the cost of the active sub-matrix.  rows <= columns for the solver: `transposed`
 // says that the solver's rows are b's active ids.  iou = (float) t / (float) (r_i + c_j - t), 0 where that denominator is 0; cost = 1.0f - iou.
-__global__ __launch_bounds__(VOX_BLOCK) void ov_cost_kernel(const int32_t *__restrict__ table, const int64_t *__restrict__ row_sum,
+__global__ __launch_bounds__(OA_BLOCK) void ov_cost_kernel(const int32_t *__restrict__ table, const int64_t *__restrict__ row_sum,
                                                             const int64_t *__restrict__ col_sum, int Ta, int Tb, const int32_t *__restrict__ act_a,
                                                             const int32_t *__restrict__ act_b, int R, int C, int transposed, float *__restrict__ iou,
                                                             float *__restrict__ cost) {
-    const int64_t x = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    const int64_t x = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
     auto iou_of = [&](int i, int j) -> float {
         const int64_t t = table[(int64_t)i * Tb + j], den = row_sum[i] + col_sum[j] - t;
         const float num = (float)t, d = (float)den;
@@ -653,16 +608,15 @@ __device__ __forceinline__ int64_t merge_id(const MergeArgs &a, int m, int64_t r
     return s >= 0 && s < a.Tb ? a.mapping[s] : 0;
 }
 
-__global__ __launch_bounds__(VOX_BLOCK) void voxel_merge_kernel(MergePred p, MergeArgs a, const int64_t *__restrict__ block_offset) {
+__global__ __launch_bounds__(OA_BLOCK) void voxel_merge_kernel(MergePred p, MergeArgs a, const int64_t *__restrict__ block_offset) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t i = (int64_t)blockIdx.x * VOX_BLOCK + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * OA_BLOCK + threadIdx.x;
     const bool keep = p(i);
-    const unsigned long long m = __ballot(keep);
-    __shared__ int wc[VOX_WAVES];
-    if (lane == 0) wc[wave] = __popcll(m);
+    __shared__ int wc[OA_WAVES];
+    const OaVote vote = oa_vote(keep);
+    if (lane == 0) wc[wave] = vote.wcount;
     __syncthreads();
-    int64_t dst = block_offset[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-    for (int q = 0; q < wave; ++q) dst += wc[q];
+    const int64_t dst = oa_wave_base(block_offset, wc) + vote.rank;
     if (!keep || dst >= a.cap) return;
     const int64_t key = p.keys[i], total = a.na + a.nb;
     const bool two = i + 1 < p.n && p.keys[i + 1] == key;
@@ -709,15 +663,12 @@ __global__ __launch_bounds__(VOX_BLOCK) void voxel_merge_kernel(MergePred p, Mer
     a.agreement_out[dst] = (float)votes / fn;
 }
 
-int64_t vox_blocks(int64_t n) { return (n + VOX_BLOCK - 1) / VOX_BLOCK; }
-int64_t vox_align(int64_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 extern "C" int64_t pag_voxel_workspace_bytes(int64_t n) {
     if (n <= 0 || n > VOX_MAX_ROWS) return 0;
-    const int64_t nb = vox_blocks(n);
-    return vox_align(nb * 8) + vox_align(nb * 4);
+    const int64_t nb = oa_blocks(n);
+    return oa_align(nb * 8) + oa_align(nb * 4);
 }
 
 extern "C" int pag_voxel_keys(const float *points, int64_t n, const float *origin_host, float voxel_size, const float *limits_host, int64_t *keys,
@@ -733,7 +684,7 @@ extern "C" int pag_voxel_keys(const float *points, int64_t n, const float *origi
         a.origin[k] = origin_host[k];
         if (limits_host) a.lo[k] = limits_host[k], a.hi[k] = limits_host[3 + k];
     }
-    hipLaunchKernelGGL(voxel_keys_kernel, dim3((unsigned)vox_blocks(n)), dim3(VOX_BLOCK), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(voxel_keys_kernel, dim3((unsigned)oa_blocks(n)), dim3(OA_BLOCK), 0, (hipStream_t)stream, a);
     PAG_CHECK_LAUNCH("pag_voxel_keys");
     return PAG_OK;
 }
@@ -748,21 +699,14 @@ extern "C" int pag_voxel_fuse(const int64_t *keys, const int64_t *ids, const flo
     PAG_CHECK_ARG(keys && ids && points, "pag_voxel_fuse: NULL keys / ids / points");
     PAG_CHECK_ARG(count && (cap == 0 || (points_out && ids_out && count_out && agreement && voxels && (color_out || !color))),
                   "pag_voxel_fuse: NULL counter / output");
-    PAG_CHECK_ARG(workspace && workspace_bytes >= pag_voxel_workspace_bytes(n), "pag_voxel_fuse: workspace smaller than pag_voxel_workspace_bytes(n)");
-    const int64_t nb = vox_blocks(n);
-    int64_t *block_offset = (int64_t *)workspace;
-    int32_t *block_count = (int32_t *)((char *)workspace + vox_align(nb * 8));
     FusePred p = {keys, n, min_votes};
     FuseArgs a = {};
     a.ids = ids, a.points = points, a.color = color;
     a.points_out = points_out, a.color_out = color_out, a.agreement = agreement, a.ids_out = ids_out, a.count_out = count_out, a.voxels = voxels;
     a.cap = cap;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(vox_count_kernel<FusePred>, dim3((unsigned)nb), dim3(VOX_BLOCK), 0, st, p, block_count);
-    hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(VOX_BLOCK), 0, st, (const int32_t *)block_count, nb, block_offset, count);
-    hipLaunchKernelGGL(voxel_fuse_kernel, dim3((unsigned)nb), dim3(VOX_BLOCK), 0, st, p, a, (const int64_t *)block_offset);
-    PAG_CHECK_LAUNCH("pag_voxel_fuse");
-    return PAG_OK;
+    return oa_append("pag_voxel_fuse", "pag_voxel_workspace_bytes(n)", pag_voxel_workspace_bytes(n), p, count, workspace, workspace_bytes, st,
+                     [&](dim3 grid, dim3 block, const int64_t *block_offset) { hipLaunchKernelGGL(voxel_fuse_kernel, grid, block, 0, st, p, a, block_offset); });
 }
 
 extern "C" int pag_label_table(const int64_t *labels, const float *points, const float *color, const int32_t *voxel_count, int64_t n,
@@ -776,10 +720,6 @@ extern "C" int pag_label_table(const int64_t *labels, const float *points, const
     PAG_CHECK_ARG(labels && points && voxel_count, "pag_label_table: NULL labels / points / voxel_count");
     PAG_CHECK_ARG(count && (cap == 0 || (ids_out && voxels_out && observations && centroid && bbox_min && bbox_max && (color_out || !color))),
                   "pag_label_table: NULL counter / output");
-    PAG_CHECK_ARG(workspace && workspace_bytes >= pag_voxel_workspace_bytes(n), "pag_label_table: workspace smaller than pag_voxel_workspace_bytes(n)");
-    const int64_t nb = vox_blocks(n);
-    int64_t *block_offset = (int64_t *)workspace;
-    int32_t *block_count = (int32_t *)((char *)workspace + vox_align(nb * 8));
     LabelPred p = {};
     p.labels = labels, p.n = n, p.n_ignore = n_ignore;
     for (int k = 0; k < n_ignore; ++k) p.ignore[k] = ignore_host[k];
@@ -788,16 +728,13 @@ extern "C" int pag_label_table(const int64_t *labels, const float *points, const
     a.ids_out = ids_out, a.voxels_out = voxels_out, a.obs_out = observations;
     a.centroid = centroid, a.bbox_min = bbox_min, a.bbox_max = bbox_max, a.color_out = color ? color_out : nullptr, a.cap = cap;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(vox_count_kernel<LabelPred>, dim3((unsigned)nb), dim3(VOX_BLOCK), 0, st, p, block_count);
-    hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(VOX_BLOCK), 0, st, (const int32_t *)block_count, nb, block_offset, count);
-    hipLaunchKernelGGL(label_table_kernel, dim3((unsigned)nb), dim3(VOX_BLOCK), 0, st, p, a, (const int64_t *)block_offset);
-    PAG_CHECK_LAUNCH("pag_label_table");
-    return PAG_OK;
+    return oa_append("pag_label_table", "pag_voxel_workspace_bytes(n)", pag_voxel_workspace_bytes(n), p, count, workspace, workspace_bytes, st,
+                     [&](dim3 grid, dim3 block, const int64_t *block_offset) { hipLaunchKernelGGL(label_table_kernel, grid, block, 0, st, p, a, block_offset); });
 }
 
 extern "C" int64_t pag_voxel_components_workspace_bytes(int64_t n) {
     if (n <= 0 || n >= VOX_MAX_ROWS) return 0;
-    return vox_align(n * 8) + 2 * vox_align(n * 4) + pag_voxel_workspace_bytes(n);      // keys, parent, root, the ordered append's block tables
+    return oa_align(n * 8) + 2 * oa_align(n * 4) + pag_voxel_workspace_bytes(n);      // keys, parent, root, the ordered append's block tables
 }
 
 extern "C" int pag_voxel_components(const int32_t *voxels, const int64_t *ids, int64_t n, int connectivity, int same_id, const int64_t *ignore_host,
@@ -812,33 +749,30 @@ extern "C" int pag_voxel_components(const int32_t *voxels, const int64_t *ids, i
     PAG_CHECK_ARG(component && count && status, "pag_voxel_components: NULL component / count / status");
     PAG_CHECK_ARG(workspace && workspace_bytes >= pag_voxel_components_workspace_bytes(n),
                   "pag_voxel_components: workspace smaller than pag_voxel_components_workspace_bytes(n)");
-    const int64_t nb = vox_blocks(n);
+    const int64_t nb = oa_blocks(n);
     char *ws = (char *)workspace;
     CcArgs a = {};
     a.voxels = voxels, a.ids = ids, a.n = n, a.same_id = same_id != 0, a.status = status;
     a.max_nonzero = connectivity == 6 ? 1 : connectivity == 18 ? 2 : 3;
     a.ignore.n = n_ignore;
     for (int k = 0; k < n_ignore; ++k) a.ignore.v[k] = ignore_host[k];
-    a.keys = (int64_t *)ws, ws += vox_align(n * 8);
-    a.parent = (int32_t *)ws, ws += vox_align(n * 4);
-    a.root = (int32_t *)ws, ws += vox_align(n * 4);
-    int64_t *block_offset = (int64_t *)ws;
-    int32_t *block_count = (int32_t *)(ws + vox_align(nb * 8));
+    a.keys = (int64_t *)ws, ws += oa_align(n * 8);
+    a.parent = (int32_t *)ws, ws += oa_align(n * 4);
+    a.root = (int32_t *)ws, ws += oa_align(n * 4);       // the ordered append's block tables follow
     CcRootPred p = {a.root, ids, a.keys, n, a.ignore};
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(count, 0, sizeof(int64_t), st);
     if (e == hipSuccess) e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
     PAG_CHECK_ARG(e == hipSuccess, "pag_voxel_components: hipMemsetAsync failed: %s", hipGetErrorString(e));
-    const dim3 grid((unsigned)nb), block(VOX_BLOCK);
+    const dim3 grid((unsigned)nb), block(OA_BLOCK);
     hipLaunchKernelGGL(cc_prepare_kernel, grid, block, 0, st, a);
     hipLaunchKernelGGL(cc_link_kernel, grid, block, 0, st, a);
     hipLaunchKernelGGL(cc_flatten_kernel, grid, block, 0, st, a);
-    hipLaunchKernelGGL(vox_count_kernel<CcRootPred>, grid, block, 0, st, p, block_count);
-    hipLaunchKernelGGL(vox_scan_kernel, dim3(1), block, 0, st, (const int32_t *)block_count, nb, block_offset, count);
-    hipLaunchKernelGGL(cc_number_kernel, grid, block, 0, st, p, (const int64_t *)block_offset, component);
-    hipLaunchKernelGGL(cc_label_kernel, grid, block, 0, st, p, component);
-    PAG_CHECK_LAUNCH("pag_voxel_components");
-    return PAG_OK;
+    return oa_append("pag_voxel_components", "pag_voxel_components_workspace_bytes(n)", pag_voxel_workspace_bytes(n), p, count, ws,
+                     workspace_bytes - (ws - (char *)workspace), st, [&](dim3, dim3, const int64_t *block_offset) {
+                         hipLaunchKernelGGL(cc_number_kernel, grid, block, 0, st, p, block_offset, component);
+                         hipLaunchKernelGGL(cc_label_kernel, grid, block, 0, st, p, component);
+                     });
 }
 
 extern "C" int pag_voxel_overlap(const int32_t *voxels_a, const int64_t *ids_a, int64_t na, const int64_t *uniq_a, int Ta, const int32_t *voxels_b,
@@ -855,15 +789,15 @@ extern "C" int pag_voxel_overlap(const int32_t *voxels_a, const int64_t *ids_a, 
     hipStream_t st = (hipStream_t)stream;
     const hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
     PAG_CHECK_ARG(e == hipSuccess, "pag_voxel_overlap: hipMemsetAsync failed: %s", hipGetErrorString(e));
-    const dim3 block(VOX_BLOCK);
-    if (na > 0) hipLaunchKernelGGL(ov_prepare_kernel, dim3((unsigned)vox_blocks(na)), block, 0, st, voxels_a, ids_a, na, uniq_a, Ta, keys_a, slot_a, status);
-    if (nb > 0) hipLaunchKernelGGL(ov_prepare_kernel, dim3((unsigned)vox_blocks(nb)), block, 0, st, voxels_b, ids_b, nb, uniq_b, Tb, keys_b, slot_b, status);
+    const dim3 block(OA_BLOCK);
+    if (na > 0) hipLaunchKernelGGL(ov_prepare_kernel, dim3((unsigned)oa_blocks(na)), block, 0, st, voxels_a, ids_a, na, uniq_a, Ta, keys_a, slot_a, status);
+    if (nb > 0) hipLaunchKernelGGL(ov_prepare_kernel, dim3((unsigned)oa_blocks(nb)), block, 0, st, voxels_b, ids_b, nb, uniq_b, Tb, keys_b, slot_b, status);
     if (na > 0 && nb > 0) {
         if (combine)
-            hipLaunchKernelGGL(ov_join_kernel<true>, dim3((unsigned)vox_blocks(na)), block, 0, st, (const int64_t *)keys_a, (const int32_t *)slot_a, na,
+            hipLaunchKernelGGL(ov_join_kernel<true>, dim3((unsigned)oa_blocks(na)), block, 0, st, (const int64_t *)keys_a, (const int32_t *)slot_a, na,
                                (const int64_t *)keys_b, (const int32_t *)slot_b, nb, Ta, Tb, table);
         else
-            hipLaunchKernelGGL(ov_join_kernel<false>, dim3((unsigned)vox_blocks(na)), block, 0, st, (const int64_t *)keys_a, (const int32_t *)slot_a, na,
+            hipLaunchKernelGGL(ov_join_kernel<false>, dim3((unsigned)oa_blocks(na)), block, 0, st, (const int64_t *)keys_a, (const int32_t *)slot_a, na,
                                (const int64_t *)keys_b, (const int32_t *)slot_b, nb, Ta, Tb, table);
     }
     PAG_CHECK_LAUNCH("pag_voxel_overlap");
@@ -880,7 +814,7 @@ extern "C" int pag_overlap_cost(const int32_t *table, const int64_t *row_sum, co
     PAG_CHECK_ARG(active == 0 || (act_a && act_b && cost), "pag_overlap_cost: NULL active lists / cost");
     const int transposed = n_a > n_b;
     const int R = active == 0 ? 0 : (transposed ? n_b : n_a), C = active == 0 ? 0 : (transposed ? n_a : n_b);
-    hipLaunchKernelGGL(ov_cost_kernel, dim3((unsigned)vox_blocks(entries)), dim3(VOX_BLOCK), 0, (hipStream_t)stream, table, row_sum, col_sum, Ta, Tb, act_a,
+    hipLaunchKernelGGL(ov_cost_kernel, dim3((unsigned)oa_blocks(entries)), dim3(OA_BLOCK), 0, (hipStream_t)stream, table, row_sum, col_sum, Ta, Tb, act_a,
                        act_b, R, C, transposed, iou, cost);
     PAG_CHECK_LAUNCH("pag_overlap_cost");
     return PAG_OK;
@@ -902,10 +836,6 @@ extern "C" int pag_voxel_merge(const int64_t *keys, const int64_t *order, int64_
     PAG_CHECK_ARG(nb == 0 || (points_b && slot_b && mapping && Tb >= 1 && count_b && agreement_b && voxels_b), "pag_voxel_merge: NULL column of b, or no id");
     PAG_CHECK_ARG(cap == 0 || (points_out && ids_out && count_out && agreement_out && voxels_out), "pag_voxel_merge: NULL output");
     PAG_CHECK_ARG(!color_out || ((na == 0 || color_a) && (nb == 0 || color_b)), "pag_voxel_merge: color_out without the colour of both maps");
-    PAG_CHECK_ARG(workspace && workspace_bytes >= pag_voxel_workspace_bytes(n), "pag_voxel_merge: workspace smaller than pag_voxel_workspace_bytes(na + nb)");
-    const int64_t blocks = vox_blocks(n);
-    int64_t *block_offset = (int64_t *)workspace;
-    int32_t *block_count = (int32_t *)((char *)workspace + vox_align(blocks * 8));
     MergePred p = {keys, n};
     MergeArgs a = {};
     a.order = order, a.na = na, a.nb = nb, a.ids_a = ids_a, a.slot_b = slot_b, a.mapping = mapping, a.Tb = Tb;
@@ -914,9 +844,6 @@ extern "C" int pag_voxel_merge(const int64_t *keys, const int64_t *order, int64_
     a.points_out = points_out, a.color_out = color_out, a.agreement_out = agreement_out, a.ids_out = ids_out, a.count_out = count_out;
     a.voxels_out = voxels_out, a.status = status, a.cap = cap;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(vox_count_kernel<MergePred>, dim3((unsigned)blocks), dim3(VOX_BLOCK), 0, st, p, block_count);
-    hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(VOX_BLOCK), 0, st, (const int32_t *)block_count, blocks, block_offset, count);
-    hipLaunchKernelGGL(voxel_merge_kernel, dim3((unsigned)blocks), dim3(VOX_BLOCK), 0, st, p, a, (const int64_t *)block_offset);
-    PAG_CHECK_LAUNCH("pag_voxel_merge");
-    return PAG_OK;
+    return oa_append("pag_voxel_merge", "pag_voxel_workspace_bytes(na + nb)", pag_voxel_workspace_bytes(n), p, count, workspace, workspace_bytes, st,
+                     [&](dim3 grid, dim3 block, const int64_t *block_offset) { hipLaunchKernelGGL(voxel_merge_kernel, grid, block, 0, st, p, a, block_offset); });
 }

@@ -48,6 +48,30 @@ def pinhole_base_rays(width, height, focal_x, focal_y, x0=0.0, y0=0.0, mip=0, de
     return Rays(torch.zeros_like(d), d)
 
 
+def _home_and_device(a, device):
+    """Where map `a` lives, and where a call runs: `device`, else where the map lives, "cuda" for a CPU map."""
+    home = torch.as_tensor(a["instances"]).device
+    return home, (torch.device(device) if device is not None else (home if home.type != "cpu" else torch.device("cuda")))
+
+
+def _cpu_map(m):
+    return {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in m.items()}
+
+
+def _to_home(out, home):
+    return {k: (v.to(home) if torch.is_tensor(v) else v) for k, v in out.items()}
+
+
+def _trim(counter, cap, what, cols):
+    """The end of an ordered append into columns of `cap` rows: the kept rows (the device counter i64 [1], read here - a synchronisation - or a number
+    the caller has read already) -> the columns cut to them.  More rows than fit raises with the capacity it needed; `what` is the caller's
+    '... %d ..., ... hold %d' half of the message."""
+    k = int(counter.item()) if torch.is_tensor(counter) else int(counter)
+    if k > cap:
+        raise RuntimeError((what + ": pass capacity >= %d") % (k, cap, k))
+    return {name: (v[:k] if v is not None else None) for name, v in cols.items()}
+
+
 class MapAccumulator:
     """The append target of the export kernels: points / color f32 [capacity,3], ids i64 [capacity] and the running device counter."""
 
@@ -60,10 +84,8 @@ class MapAccumulator:
 
     def finish(self):
         """The one synchronisation: read the counter, -> (points, color, ids) trimmed to the kept rows."""
-        k = int(self.count.item())
-        if k > self.capacity:
-            raise RuntimeError("map export kept %d points, the accumulator holds %d: pass capacity >= %d" % (k, self.capacity, k))
-        return self.points[:k], (self.color[:k] if self.color is not None else None), (self.ids[:k] if self.ids is not None else None)
+        cols = {"points": self.points, "color": self.color, "ids": self.ids}
+        return tuple(_trim(self.count, self.capacity, "map export kept %d points, the accumulator holds %d", cols).values())
 
 
 def _labels_of(labels, inst):
@@ -346,17 +368,14 @@ class VoxelMap:
         color = self._color and K > 0
         cap = K if self.capacity is None else min(int(self.capacity), K)
         out = self._empty(cap, self._color)
-        n = 0
+        counter = 0
         if K > 0:
             cat = lambda j: self._chunks[0][j] if len(self._chunks) == 1 else torch.cat([c[j] for c in self._chunks])          # noqa: E731
             keys, ids, points, col = rows_by_key_and_id(cat(3), cat(1), cat(0), cat(2) if color else None)
             counter = torch.zeros(1, dtype=torch.int64, device=self.device)
             ops.voxel_fuse(keys, ids, points, col, self.min_votes, out["points"], out.get("color"), out["instances"], out["count"], out["agreement"],
                            out["voxels"], counter)
-            n = int(counter.item())                                                         # the one synchronisation
-            if n > cap:
-                raise RuntimeError("the fused map has %d voxels, the outputs hold %d: pass capacity >= %d" % (n, cap, n))
-        out = {k: v[:n] for k, v in out.items()}
+        out = _trim(counter, cap, "the fused map has %d voxels, the outputs hold %d", out)     # the one synchronisation
         out["voxel_size"] = self.voxel_size
         out["origin"] = self._origin.clone()
         return out
@@ -409,11 +428,9 @@ def instance_table(fused, ignore=(0,), device=None, capacity=None):
     """The per-instance table of a fused map (label_table_reference's keys): voxel count, observation total, centroid, bounding box, mean colour
     and volume of every instance id outside `ignore`.  Runs on `device` (default: where the map lives, "cuda" for a CPU map; "cpu" is the tensor-op
     definition): one stable sort by id and one ordered-append call, one synchronisation; the result lives where the map does."""
-    home = fused["instances"].device
-    dev = torch.device(device) if device is not None else (home if home.type != "cpu" else torch.device("cuda"))
+    home, dev = _home_and_device(fused, device)
     if dev.type == "cpu":
-        cpu = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in fused.items()}
-        return {k: (v.to(home) if torch.is_tensor(v) else v) for k, v in label_table_reference(cpu, ignore).items()}
+        return _to_home(label_table_reference(_cpu_map(fused), ignore), home)
     n = fused["instances"].numel()
     cap = n if capacity is None else min(int(capacity), n)
     has_color = "color" in fused
@@ -422,17 +439,15 @@ def instance_table(fused, ignore=(0,), device=None, capacity=None):
            "bbox_min": torch.empty(cap, 3, device=dev), "bbox_max": torch.empty(cap, 3, device=dev)}
     if has_color:
         out["color"] = torch.empty(cap, 3, device=dev)
-    t = 0
+    counter = 0
     if n > 0:
         lab, order = torch.sort(fused["instances"].reshape(-1).to(dev), stable=True)
         take = lambda k: fused[k].to(dev).index_select(0, order)                           # noqa: E731
         counter = torch.zeros(1, dtype=torch.int64, device=dev)
         ops.label_table(lab, take("points"), take("color") if has_color else None, take("count"), ignore, out["ids"], out["voxels"],
                         out["observations"], out["centroid"], out["bbox_min"], out["bbox_max"], out.get("color"), counter)
-        t = int(counter.item())
-        if t > cap:
-            raise RuntimeError("the table has %d instances, the outputs hold %d: pass capacity >= %d" % (t, cap, t))
-    return _with_volume({k: v[:t].to(home) for k, v in out.items()}, fused["voxel_size"])
+    out = _trim(counter, cap, "the table has %d instances, the outputs hold %d", out)
+    return _with_volume(_to_home(out, home), fused["voxel_size"])
 
 
 # ------------------------------------------------------------------------------------------- connected components of the fused map
@@ -525,11 +540,9 @@ def connected_components(fused, connectivity=26, same_id=True, ignore=(0,), devi
     roots) -> {'component' i64 [V] where the map lives, 'components' C}.  Runs on `device` (default: where the map lives, "cuda" for a CPU map;
     "cpu" selects the definition).  One synchronisation: the read of the count and the status word; a map that breaks the contract raises ValueError."""
     ignore = _check_components_args(connectivity, ignore)
-    home = torch.as_tensor(fused["instances"]).device
-    dev = torch.device(device) if device is not None else (home if home.type != "cpu" else torch.device("cuda"))
+    home, dev = _home_and_device(fused, device)
     if dev.type == "cpu":
-        out = connected_components_reference(fused, connectivity, same_id, ignore)
-        return {"component": out["component"].to(home), "components": out["components"]}
+        return _to_home(connected_components_reference(fused, connectivity, same_id, ignore), home)
     ids = torch.as_tensor(fused["instances"]).reshape(-1).to(dev, torch.int64)
     vox = torch.as_tensor(fused["voxels"]).reshape(-1, 3).to(dev, torch.int32)
     if vox.shape[0] != ids.numel():
@@ -598,11 +611,9 @@ def clean_map(fused, min_voxels=1, connectivity=26, mode="keep", ignore=(0,), de
     selected, never recomputed.  device as in connected_components ("cpu": clean_map_reference); the result lives where the map does."""
     min_voxels = _clean_args(min_voxels, mode)
     ignore = _check_components_args(connectivity, ignore)
-    home = torch.as_tensor(fused["instances"]).device
-    dev = torch.device(device) if device is not None else (home if home.type != "cpu" else torch.device("cuda"))
+    home, dev = _home_and_device(fused, device)
     if dev.type == "cpu":
-        cpu = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in fused.items()}
-        return {k: (v.to(home) if torch.is_tensor(v) else v) for k, v in clean_map_reference(cpu, min_voxels, connectivity, mode, ignore).items()}
+        return _to_home(clean_map_reference(_cpu_map(fused), min_voxels, connectivity, mode, ignore), home)
     on_dev = {k: (torch.as_tensor(v).to(dev) if k in ROW_FIELDS else v) for k, v in fused.items()}
     cc = connected_components(on_dev, connectivity, True, ignore, dev)                      # synchronisation 1
     comp, C = cc["component"], cc["components"]
@@ -872,19 +883,6 @@ def _fold(maps, step):
     return out
 
 
-def _home_and_device(a, device):
-    home = torch.as_tensor(a["instances"]).device
-    return home, (torch.device(device) if device is not None else (home if home.type != "cpu" else torch.device("cuda")))
-
-
-def _cpu_map(m):
-    return {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in m.items()}
-
-
-def _to_home(out, home):
-    return {k: (v.to(home) if torch.is_tensor(v) else v) for k, v in out.items()}
-
-
 def _device_join(a, b, dev, what, combine=True):
     """The device half shared by overlap_table / associate_maps / merge_maps: both maps' rows on `dev`, their distinct ids (synchronisations: the
     lattice check and the sizes of the two lists) and pag_voxel_overlap's keys, slots and table.  The status word is not read here."""
@@ -1009,9 +1007,7 @@ def merge_maps(a, b, mapping=None, min_iou=0.25, ignore=(0,), device=None, capac
     status, rows = torch.stack((j["status"][0].long(), counter[0])).tolist()                           # synchronisation
     if status:
         _raise_status(status, "merge_maps")
-    if rows > cap:
-        raise RuntimeError("the merged map has %d voxels, the outputs hold %d: pass capacity >= %d" % (rows, cap, rows))
-    out = {k: v[:rows].to(home) for k, v in out.items()}
+    out = _to_home(_trim(rows, cap, "the merged map has %d voxels, the outputs hold %d", out), home)
     out["voxel_size"] = a["voxel_size"]
     out["origin"] = torch.as_tensor(a["origin"]).detach().clone()
     if "name" in a:

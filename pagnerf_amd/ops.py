@@ -1915,8 +1915,20 @@ def _map_inst(name, n, inst, ids):
     return None, 0, 0, None, ()
 
 
-def _map_workspace(n, dev):
-    return torch.empty(max(int(L.load().pag_map_workspace_bytes(n)), 8), dtype=torch.uint8, device=dev)
+def _workspace(size_fn, n, dev):
+    """The scratch buffer of an ordered append over n rows; size_fn names the library's pag_*_workspace_bytes function."""
+    return torch.empty(max(int(getattr(L.load(), size_fn)(n)), 8), dtype=torch.uint8, device=dev)
+
+
+def _bad_columns(cols):
+    """cols: [(tensor, dtype, shape)] -> True when one is missing, of another dtype or shape, or not contiguous."""
+    return any(t is None or t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in cols)
+
+
+def _ignore_array(ignore):
+    """An ignore list -> (c_int64 array of at least one element, its length)."""
+    ignore = [int(v) for v in ignore]
+    return (ctypes.c_int64 * max(1, len(ignore)))(*ignore), len(ignore)
 
 
 def map_points(params, cam, rays_per_camera, origins_c, dirs_c, ray0, depth, alpha, hit, density, rgb, points, color, ids_out, count, inst=None,
@@ -1945,7 +1957,7 @@ def map_points(params, cam, rays_per_camera, origins_c, dirs_c, ray0, depth, alp
     if ip is None and idp is None:
         raise RuntimeError("map_points: needs inst or ids")
     cam = cam.contiguous()
-    ws = _map_workspace(n, dep.device)
+    ws = _workspace("pag_map_workspace_bytes", n, dep.device)
     _call("pag_map_points", prm.data_ptr(), prm.shape[0], cam.data_ptr(), cam.numel(), int(rays_per_camera), oc.data_ptr(), dc.data_ptr(), int(ray0), n,
           dep.data_ptr(), alp.data_ptr(), h.data_ptr(), den.data_ptr(), col.data_ptr(), ip, I, stride, idp, float(min_density), float(min_alpha),
           float(depth_min), float(depth_max), points.data_ptr(), color.data_ptr(), ids_out.data_ptr(), cap, count.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -1969,16 +1981,12 @@ def map_select(points_in, points, count, value=None, threshold=0.0, inst=None, i
     ip, I, stride, idp, keep = _map_inst("map_select", n, inst, ids)
     if val is None and ip is None and idp is None:
         raise RuntimeError("map_select: needs value, inst or ids")
-    ws = _map_workspace(n, pin.device)
+    ws = _workspace("pag_map_workspace_bytes", n, pin.device)
     _call("pag_map_select", pin.data_ptr(), n, val.data_ptr() if val is not None else None, float(threshold), ip, I, stride, idp, points.data_ptr(),
           ids_out.data_ptr() if ids_out is not None else None, points.shape[0], count.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
 
 
 # ------------------------------------------------------------------------------------------- voxel map fusion (csrc/voxelmap.hip)
-def _voxel_workspace(n, dev):
-    return torch.empty(max(int(L.load().pag_voxel_workspace_bytes(n)), 8), dtype=torch.uint8, device=dev)
-
-
 def voxel_keys(points, origin, voxel_size, limits=None):
     """points f32 [n,3] -> keys i64 [n]: iz | iy << 21 | ix << 42 with i = floor((p - origin) / voxel_size) in fp32, INT64_MAX for a row that is not
     finite, outside [0, 2^21) on an axis or not strictly inside limits [[min], [max]] (pag_voxel_keys; origin / limits are host values)."""
@@ -2012,12 +2020,12 @@ def voxel_fuse(keys, ids, points, color, min_votes, points_out, color_out, ids_o
     cap = points_out.shape[0]
     outs = [(points_out, torch.float32, (cap, 3)), (ids_out, torch.int64, (cap,)), (count_out, torch.int32, (cap,)), (agreement, torch.float32, (cap,)),
             (voxels, torch.int32, (cap, 3))] + ([(color_out, torch.float32, (cap, 3))] if color is not None else [])
-    if count.dtype != torch.int64 or any(t is None or t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in outs):
+    if count.dtype != torch.int64 or _bad_columns(outs):
         raise RuntimeError("voxel_fuse: points_out / color_out f32 [cap,3], ids_out int64 [cap], count_out int32 [cap], agreement f32 [cap], "
                            "voxels int32 [cap,3], contiguous; count int64 [1]")
     keys, ids, points = keys.contiguous(), ids.contiguous(), points.contiguous()
     color = color.contiguous() if color is not None else None
-    ws = _voxel_workspace(n, keys.device)
+    ws = _workspace("pag_voxel_workspace_bytes", n, keys.device)
     _call("pag_voxel_fuse", keys.data_ptr(), ids.data_ptr(), points.data_ptr(), color.data_ptr() if color is not None else None, n, int(min_votes),
           points_out.data_ptr(), color_out.data_ptr() if color is not None else None, ids_out.data_ptr(), count_out.data_ptr(), agreement.data_ptr(),
           voxels.data_ptr(), cap, count.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
@@ -2036,16 +2044,15 @@ def label_table(labels, points, color, voxel_count, ignore, ids_out, voxels_out,
     cap = ids_out.shape[0]
     outs = [(t, torch.int64, (cap,)) for t in (ids_out, voxels_out, observations)] + [(t, torch.float32, (cap, 3)) for t in (centroid, bbox_min, bbox_max)]
     outs += [(color_out, torch.float32, (cap, 3))] if color is not None else []
-    if count.dtype != torch.int64 or any(t is None or t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in outs):
+    if count.dtype != torch.int64 or _bad_columns(outs):
         raise RuntimeError("label_table: ids_out / voxels_out / observations int64 [cap], centroid / bbox_min / bbox_max / color_out f32 [cap,3], "
                            "contiguous; count int64 [1]")
-    ignore = [int(v) for v in ignore]
-    ign = (ctypes.c_int64 * max(1, len(ignore)))(*ignore)
+    ign, n_ignore = _ignore_array(ignore)
     labels, points, voxel_count = labels.contiguous(), points.contiguous(), voxel_count.contiguous()
     color = color.contiguous() if color is not None else None
-    ws = _voxel_workspace(n, labels.device)
+    ws = _workspace("pag_voxel_workspace_bytes", n, labels.device)
     _call("pag_label_table", labels.data_ptr(), points.data_ptr(), color.data_ptr() if color is not None else None, voxel_count.data_ptr(), n, ign,
-          len(ignore), ids_out.data_ptr(), voxels_out.data_ptr(), observations.data_ptr(), centroid.data_ptr(), bbox_min.data_ptr(),
+          n_ignore, ids_out.data_ptr(), voxels_out.data_ptr(), observations.data_ptr(), centroid.data_ptr(), bbox_min.data_ptr(),
           bbox_max.data_ptr(), color_out.data_ptr() if color is not None else None, cap, count.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
 
 
@@ -2062,11 +2069,10 @@ def voxel_components(voxels, ids, connectivity, same_id, ignore, component, coun
     count_status.zero_()                                                                   # the status is an int32 word: its slot's upper half stays zero
     if n == 0:
         return
-    ignore = [int(v) for v in ignore]
-    ign = (ctypes.c_int64 * max(1, len(ignore)))(*ignore)
+    ign, n_ignore = _ignore_array(ignore)
     voxels, ids = voxels.contiguous(), ids.contiguous()
-    ws = torch.empty(max(int(L.load().pag_voxel_components_workspace_bytes(n)), 8), dtype=torch.uint8, device=ids.device)
-    _call("pag_voxel_components", voxels.data_ptr(), ids.data_ptr(), n, int(connectivity), int(bool(same_id)), ign, len(ignore), ws.data_ptr(), ws.numel(),
+    ws = _workspace("pag_voxel_components_workspace_bytes", n, ids.device)
+    _call("pag_voxel_components", voxels.data_ptr(), ids.data_ptr(), n, int(connectivity), int(bool(same_id)), ign, n_ignore, ws.data_ptr(), ws.numel(),
           component.data_ptr(), count_status.data_ptr(), count_status.data_ptr() + 8, L.stream())
 
 
@@ -2128,11 +2134,11 @@ def voxel_merge(keys, order, a, b, slot_b, mapping, out, count, status):
         want += [(m["points"], torch.float32, (k, 3)), (m["count"], torch.int32, (k,)), (m["agreement"], torch.float32, (k,)), (m["voxels"], torch.int32, (k, 3))]
         want += [(m.get("color"), torch.float32, (k, 3))] if color else []
     want += [(out["instances"], torch.int64, (cap,))]
-    if any(t is None or t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in want) or mapping.dtype != torch.int64 or (
+    if _bad_columns(want) or mapping.dtype != torch.int64 or (
             not mapping.is_contiguous()) or count.dtype != torch.int64 or status.dtype != torch.int32:
         raise RuntimeError("voxel_merge: keys / order int64 [na + nb], slot_b int32 [nb], mapping int64 [Tb]; per map points / color f32 [n,3], instances "
                            "int64 [n], count int32 [n], agreement f32 [n], voxels int32 [n,3], contiguous; count int64 [1], status int32 [1]")
-    ws = _voxel_workspace(n, keys.device)
+    ws = _workspace("pag_voxel_workspace_bytes", n, keys.device)
     _call("pag_voxel_merge", keys.data_ptr(), order.data_ptr(), na, nb, _ptr(a["points"]), _ptr(a.get("color")) if color else None, _ptr(a["instances"]),
           _ptr(a["count"]), _ptr(a["agreement"]), _ptr(a["voxels"]), _ptr(b["points"]), _ptr(b.get("color")) if color else None, _ptr(slot_b), _ptr(mapping),
           mapping.numel(), _ptr(b["count"]), _ptr(b["agreement"]), _ptr(b["voxels"]), _ptr(out["points"]), _ptr(out.get("color")), _ptr(out["instances"]),

@@ -30,6 +30,19 @@ def test_every_declared_symbol_is_exported(lib):
     assert lib.pag_abi_version() == _lib.ABI_VERSION == 14
 
 
+@pytest.mark.parametrize("n", [0, 1, 256, 257, 65536, 65537, 2 ** 31 - 1, 2 ** 31, 2 ** 31 + 1])
+def test_ordered_append_workspace_formulas(lib, n):
+    """The three workspace sizes of the ordered appends, from their documented layouts: block_offset i64 [nb] and block_count i32 [nb] for the
+    nb = ceil(n / 256) blocks, each plane rounded up to 256 bytes; the map export adds an i32 [n] plane of ids, the components put keys i64 [n],
+    parent and root i32 [n] in front.  0 outside the rows an entry point takes ([1, 2^31]; the components [1, 2^31))."""
+    nb = (n + 255) // 256
+    A = lambda b: (b + 255) // 256 * 256                                                  # noqa: E731
+    tables = A(8 * nb) + A(4 * nb)
+    assert lib.pag_map_workspace_bytes(n) == (tables + A(4 * n) if 1 <= n <= 2 ** 31 else 0)
+    assert lib.pag_voxel_workspace_bytes(n) == (tables if 1 <= n <= 2 ** 31 else 0)
+    assert lib.pag_voxel_components_workspace_bytes(n) == (A(8 * n) + 2 * A(4 * n) + tables if 1 <= n < 2 ** 31 else 0)
+
+
 def test_assignment_entry_points_validate_without_gpu(lib):
     """pag_assign_cost / pag_assign_nll_fwd / _bwd (ABI 10): empty batches are no-ops, bad sizes and NULL buffers are rejected before any launch."""
     assert lib.pag_assign_nll_fwd(None, 1, 0, 0, 200, 200, None, None, None, None, None, 199, 1, None, None, None, None, None) == 0

@@ -191,6 +191,32 @@ def test_capacity_guard(gpu_device):
     assert instance_table(m, ignore=(), capacity=5)["ids"].tolist() == [-6, -3, 0, 3, 6]
 
 
+def test_one_row_per_voxel_across_the_scan_chunks(gpu_device):
+    """65537 sorted rows of distinct keys are 257 blocks of kept rows, one block more than the scan takes per pass: voxel k lands at row 3 + k
+    behind a counter that starts at 3, every value as it went in (one row per voxel: the mean is the row)."""
+    from pagnerf_amd import ops
+    dev = gpu_device
+    n, start = 65537, 3
+    k = torch.arange(n, dtype=torch.int64, device=dev)
+    vox = torch.stack((k >> 12, k >> 6 & 63, k & 63), 1)
+    keys = vox[:, 0] << 42 | vox[:, 1] << 21 | vox[:, 2]
+    ids = k % 1000 - 3
+    pts = vox.float() + torch.tensor([0.5, 0.25, 0.75], device=dev)
+    col = (k % 256).float()[:, None] / 256 + torch.tensor([0.0, 0.25, 0.5], device=dev)
+    cap = start + n
+    out = dict(points=torch.full((cap, 3), -7.0, device=dev), color=torch.full((cap, 3), -7.0, device=dev),
+               instances=torch.full((cap,), -7, dtype=torch.int64, device=dev), count=torch.full((cap,), -7, dtype=torch.int32, device=dev),
+               agreement=torch.full((cap,), -7.0, device=dev), voxels=torch.full((cap, 3), -7, dtype=torch.int32, device=dev))
+    counter = torch.full((1,), start, dtype=torch.int64, device=dev)
+    ops.voxel_fuse(keys, ids, pts, col, 1, out["points"], out["color"], out["instances"], out["count"], out["agreement"], out["voxels"], counter)
+    assert int(counter.item()) == cap
+    want = dict(points=pts, color=col, instances=ids, count=torch.ones(n, dtype=torch.int32, device=dev), agreement=torch.ones(n, device=dev),
+                voxels=vox.int())
+    for name, b in out.items():
+        assert torch.equal(b[start:], want[name]), name
+        assert bool((b[:start] == -7).all()), name
+
+
 # ----------------------------------------------------------------------------------------------- end to end
 def test_views_export_fused_end_to_end(gpu_device):
     import pagnerf_amd
