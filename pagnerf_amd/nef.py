@@ -51,7 +51,8 @@ class BasicDecoder(nn.Module):
         return [l.weight for l in lins], [l.bias for l in lins]
 
     def forward(self, x1, x2=None, x2_index=None, out_act=L.ACT_NONE, mode=L.MLP_MFMA_BF16, out_dtype=torch.float32,
-                x1_grouped=None, x2_packs=None):
+                x1_grouped=None, x2_packs=None, hold=None):
+        """hold: an ops.decoder_hold() in which a 64-wide decoder parks its launch for the decoder that consumes its output."""
         W, b = self.weights()
         if self.hidden_dim == 128:
             if mode == L.MLP_MFMA_BF16 and x1.is_cuda:
@@ -66,7 +67,7 @@ class BasicDecoder(nn.Module):
                 x = torch.cat([x, x2[x2_index.long(), :self.input_dim - n1].float()], -1)
             return ops.wide_mlp_reference(x, W, b, out_act).to(out_dtype)
         return ops.fused_mlp(x1, W, b, x2=x2, x2_index=x2_index, in_dim=self.input_dim, out_act=out_act, mode=mode,
-                             out_dtype=out_dtype, x1_grouped=x1_grouped, x2_packs=x2_packs)
+                             out_dtype=out_dtype, x1_grouped=x1_grouped, x2_packs=x2_packs, hold=hold)
 
 
 _PARAM_NAMES = {}
@@ -293,11 +294,11 @@ class PanopticDeltaNeF(nn.Module):
         # with the colour decoder to follow, the density decoder's launch is parked and rides in the colour decoder's (ops.decoder_hold)
         # (128-wide density / colour decoders run as two plain nodes: the 64-wide family's cross-decoder fusions do not exist at that width)
         wide = self.decoder_density.hidden_dim == 128 or self.decoder_color.hidden_dim == 128
-        hold = ops.decoder_hold(feats) if (ops.CD_FUSED and "rgb" in compute_channels and feats.is_cuda and not wide) else None
+        hold = ops.decoder_hold() if (ops.CD_FUSED and "rgb" in compute_channels and feats.is_cuda and not wide) else None
         # everything between decoder_hold() and flush_hold() sits in ONE try / finally: whatever raises in between (the density decoder, the view
         # embedding, the colour decoder before it took the parked launch), the launch is issued or forgotten and no later trace can inherit it
         try:
-            density_feats = self.decoder_density(feats, mode=mode, out_dtype=self.feat_dtype, x1_grouped=grp)     # :184
+            density_feats = self.decoder_density(feats, mode=mode, out_dtype=self.feat_dtype, x1_grouped=grp, hold=hold)     # :184
             self._density_feats = density_feats.detach()             # the delta-density variant adds to its (detached) column 0 (pre-ReLU)
             if "rgb" in compute_channels:                                                 # :188, :196-204
                 if num_samples != 1 and ridx is None:                                  # one direction per pack entry -> per sample

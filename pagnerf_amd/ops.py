@@ -319,73 +319,6 @@ def _mm_f32(a, b):
         return (a @ b).float()
 
 
-def _recompute_ok(ctx, x1, x2, k1, in_dim, n_layers, out_dim, mode, grouped, stats_only, M, out_act, out_dtype, rank1_expected, col0):
-    """Forward-time mirror of csrc/mlp.hip::fused_kind() - the shapes whose backward (pag_mlp_bwd with wgrad_workspace) recomputes the hidden
-    activations, so that the forward need not write them.  Every condition fused_kind() checks that is knowable at forward time is
-    checked here (batch bound, layout, widths, output activation / dtype per kernel kind, whether the upstream gradient will be dense or
-    rank-1); a mismatch that still slips through (e.g. a _ColourDensity backward that receives no sigma gradient) takes
-    _recompute_hidden(), which is correct but costs a second forward - it warns once."""
-    if not WGRAD_FUSED or mode != L.MLP_MFMA_BF16 or x1.dtype != torch.bfloat16 or not ctx.needs_input_grad[0]:
-        return False
-    if ctx.needs_input_grad[1] and grouped is not None:       # only the colour-like kernel hands out dz_0 for the per-ray input's gradient
-        return False
-    if not (0 < M <= L.MLP_FUSED_WIDE_MAX_M) or n_layers not in (2, 3):
-        return False
-    if grouped is not None:
-        levels, feats = grouped
-        if levels < 1 or feats < 1 or ((levels + 7) // 8) * feats > 8:
-            return False
-        j = 7 // feats
-        if j < (levels + 7) // 8 and xcd8_level(7, j) < levels:      # staged position 63 is a real feature: no room for the bias column
-            return False
-        if x2 is not None:
-            return False
-        if out_dim > 32:                                      # wide softmax head: stage A + stage B (rank-1 gradient, statistics-only forward)
-            return stats_only and n_layers == 3 and 192 < out_dim <= 224 and out_act == L.ACT_SOFTMAX and out_dtype == torch.bfloat16
-        if rank1_expected:                                    # semantic-like: composited softmax head
-            return out_act == L.ACT_SOFTMAX and out_dim <= 8 and out_dtype == torch.bfloat16
-        return out_act == L.ACT_NONE and out_dim % 4 == 0 and out_dtype == torch.bfloat16      # density-like: dense bf16 gradient
-    return (x2 is not None and k1 == 16 and x2.shape[1] == 32 and in_dim <= 48 and out_dim <= 4 and out_act == L.ACT_SIGMOID
-            and out_dtype == torch.float32 and col0 and not rank1_expected)
-
-
-_WARNED_RECOMPUTE = False
-
-
-def _recompute_hidden(x1, x2, x2_index, Wc, bc, in_dim, k1, grouped, mode, hidden):
-    """Fill the missing entries of `hidden` by re-running the forward (pag_mlp_fwd with hidden_save) - the fallback for a backward
-    that the fused kernels cannot serve although the forward did not save the activations."""
-    global _WARNED_RECOMPUTE
-    if not _WARNED_RECOMPUTE:
-        _WARNED_RECOMPUTE = True
-        import warnings
-        warnings.warn("pagnerf_amd: a decoder backward could not use the fused kernels although its forward skipped the hidden activations; "
-                      "re-running the forward for them (correct, but one extra launch and an [M, out] scratch per backward)")
-    M = x1.shape[1] if grouped is not None else x1.shape[0]
-    n_layers = len(Wc)
-    dev = x1.device
-    full = [h if h is not None else torch.empty(M, 64, device=dev, dtype=torch.bfloat16 if mode == L.MLP_MFMA_BF16 else torch.float32) for h in hidden]
-    out_dim = Wc[-1].shape[0]
-    a = L.MlpFwdArgs()
-    a.x1, a.x1_dtype, a.k1 = L.ptr(x1), L.dtype_code(x1), k1
-    if grouped is not None:
-        a.x1_layout, a.x1_levels, a.x1_feats = L.LAYOUT_XCD8, grouped[0], grouped[1]
-    if x2 is not None:
-        a.x2, a.k2p, a.x2_index = L.ptr(x2), x2.shape[1], L.ptr(x2_index)
-    a.in_dim, a.n_layers, a.out_dim = in_dim, n_layers, out_dim
-    for i in range(n_layers):
-        a.W[i], a.b[i] = L.ptr(Wc[i]), L.ptr(bc[i])
-    scratch = torch.empty(M, out_dim, device=dev, dtype=torch.bfloat16)
-    a.out_act, a.out, a.out_dtype, a.mode = L.ACT_NONE, L.ptr(scratch), L.BF16, mode
-    for i, h in enumerate(full):
-        a.hidden_save[i] = L.ptr(h)
-    _call("pag_mlp_fwd", ctypes.byref(a), M, L.stream())
-    return full
-
-
-_OUTER_GRAD = True          # grad mode of the code that called the decoder op (see _apply_decoder)
-
-
 class _InferCtx:
     """Stand-in for the autograd ctx of a Function whose result nobody will differentiate (torch.no_grad(): validation renders, prune): nothing is saved,
     nothing needs a gradient; attributes a forward() parks on the ctx for its backward land on a plain object and die with it."""
@@ -403,11 +336,6 @@ class _InferCtx:
     def set_materialize_grads(self, value):
         pass
 
-    def __getattr__(self, name):          # only reached for attributes nobody set: the optional hand-offs (fwd_pair, fwd_hold, ...) read as absent
-        if name.startswith("__"):
-            raise AttributeError(name)
-        return None
-
 
 def _apply(fn, *args):
     """fn.apply(*args); under torch.no_grad() the forward is called directly with an _InferCtx - torch.autograd.Function.apply costs 10 - 15 us of host time
@@ -417,304 +345,406 @@ def _apply(fn, *args):
     return fn.forward(_InferCtx(len(args)), *args)
 
 
-def _apply_decoder(fn, *args):
-    """fn.apply(*args) with the caller's grad mode visible to the forward: under torch.no_grad() (validation renders, prune) the decoder
-    launches keep nothing for a backward - no hidden activations, no softmax statistics beyond what the statistics-only wide head hands to
-    its own compositing launch."""
-    global _OUTER_GRAD
-    prev, _OUTER_GRAD = _OUTER_GRAD, torch.is_grad_enabled()
-    try:
-        return _apply(fn, *args)
-    finally:
-        _OUTER_GRAD = prev
+def _need_grad(*tensors):
+    """Will anybody differentiate a decoder called on these inputs now?  Asked by the public wrappers BEFORE Function.apply: inside a Function's forward
+    grad mode is always off, and ctx.needs_input_grad / tensor.requires_grad still say True for a parameter inside a no_grad region.  Under
+    torch.no_grad() (validation renders, prune) the decoder launches keep nothing for a backward - no hidden activations, no softmax statistics beyond
+    what the statistics-only wide head hands to its own compositing launch."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
-class _FusedMLP(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x1, x2, x2_index, in_dim, out_act, mode, out_dtype, grouped, *wb):
-        _check_gpu(x1, x2, x2_index, *wb)
-        n_layers = len(wb) // 2
-        Ws, bs = wb[:n_layers], wb[n_layers:]
-        if grouped is not None:
-            M, k1 = x1.shape[1], 64
+class _Launch:
+    """One decoder launch that is PREPARED but not yet issued: it rides in another decoder's call where the library can, else its holder issues it.
+    args: the argument struct (None until a decoder parked its launch here); keep: the tensors the struct points into."""
+    __slots__ = ("entry", "bare", "args", "M", "keep", "taken", "fused", "out_ptr")
+
+    def __init__(self, entry, bare=False):
+        self.entry, self.bare = entry, bare        # bare: park only a launch that writes nothing but its output (all a consumer's launch can carry)
+        self.args, self.M, self.keep, self.taken, self.fused, self.out_ptr = None, 0, (), False, False, 0
+
+    def park(self, args, M, keep, fused=False, out_ptr=0):
+        self.args, self.M, self.keep, self.fused, self.out_ptr = args, M, keep, fused, out_ptr
+
+    @property
+    def pending(self):
+        return self.args is not None and not self.taken
+
+    def issue(self):
+        if self.pending:
+            _call(self.entry, ctypes.byref(self.args), self.M, L.stream())
+            self.taken = True
+
+
+class _DecoderCall:
+    """What a public wrapper asks of one decoder launch beyond its tensor operands - the single non-tensor argument handed to Function.apply.
+    x2_packs = (pack_start, ray_of_pack): x2_index is constant inside each pack (d/d x2 only).  need_grad: _need_grad() of the wrapper's inputs.
+    col0_relu: also write relu(x1[:, 0]) (_ColourDensity).  rank1: the backward will hand over its gradient in rank-1 form (head_composite).
+    stats_only: a wide softmax head writes its statistics and last hidden layer, no [M,out] tensor.  composite: HeadCompositeArgs for the per-ray sum in
+    the decoder's own launch.  park: the _Launch in which this launch waits instead of being issued.  pair: the parked companion narrow head.
+    producer: the parked decoder whose output is this one's x1.  n_rays: N of head_composite()."""
+    __slots__ = ("in_dim", "out_act", "mode", "out_dtype", "grouped", "x2_packs", "need_grad", "col0_relu", "rank1", "stats_only", "composite", "park",
+                 "pair", "producer", "n_rays")
+
+    def __init__(self, in_dim, out_act, mode, out_dtype, grouped, x2_packs=None, need_grad=False, col0_relu=False, rank1=False, stats_only=False,
+                 composite=None, park=None, pair=None, producer=None, n_rays=0):
+        self.in_dim, self.out_act, self.mode, self.out_dtype = int(in_dim), out_act, mode, out_dtype
+        self.grouped = grouped if grouped is None else tuple(grouped)
+        self.x2_packs, self.need_grad, self.col0_relu, self.rank1, self.stats_only = x2_packs, need_grad, col0_relu, rank1, stats_only
+        self.composite, self.park, self.pair, self.producer, self.n_rays = composite, park, pair, producer, n_rays
+
+
+class _DecoderState:
+    """What a decoder forward leaves for its backward and for its caller (both families)."""
+    __slots__ = ("in_dim", "out_act", "mode", "out_dtype", "grouped", "x2_packs", "needs", "M", "k1", "n_layers", "n_hidden", "has_stats", "bc", "saved",
+                 "col0_relu", "composited", "head", "hc", "x1_shape", "x1_dtype")
+
+    def __init__(self, call, needs, M, k1, n_layers, saved, x1):
+        self.in_dim, self.out_act, self.mode, self.out_dtype, self.grouped = call.in_dim, call.out_act, call.mode, call.out_dtype, call.grouped
+        self.x2_packs = call.x2_packs
+        self.needs = (bool(needs[0]), bool(needs[1]))      # does x1 / x2 need a gradient?
+        self.M, self.k1, self.n_layers, self.saved = M, k1, n_layers, saved      # saved: the tensors of the backward, until an autograd ctx takes them
+        self.x1_shape, self.x1_dtype = tuple(x1.shape), x1.dtype
+        self.n_hidden, self.has_stats, self.bc = 0, False, None
+        self.col0_relu = None          # f32 [M] relu(x1[:, 0]) where the launch wrote it
+        self.composited = False        # the launch formed the per-ray sums itself (call.composite)
+        self.head = None               # statistics-only head: (last hidden layer, W_last, b_last, statistics) for the compositing launch
+        self.hc = None                 # head_composite: (weights, alpha, ridx) of the rank-1 gradient
+
+
+def _save(ctx, st):
+    """Hand the state's tensors to the autograd ctx (saved tensors) and the rest to ctx.state."""
+    ctx.save_for_backward(*st.saved)
+    st.saved = None
+    ctx.state, ctx.x2_packs = st, st.x2_packs      # x2_packs also on the node itself: out.grad_fn.x2_packs says whether d x2 will take the segmented sum
+
+
+def _operands(x1, x2, x2_index, Ws, bs, grouped):
+    """The decoders' operands as the kernels read them -> (x1 f32 / bf16, x2 f32, x2_index i32, W f32, b f32, M, k1), detached and contiguous."""
+    _check_gpu(x1, x2, x2_index, *Ws, *bs)
+    if grouped is not None:
+        M, k1 = x1.shape[1], 64
+    else:
+        M, k1 = x1.shape
+    x1 = x1.detach()
+    if not x1.is_contiguous():
+        x1 = x1.contiguous()
+    if x1.dtype not in (torch.float32, torch.bfloat16):
+        x1 = x1.float()
+    if x2 is not None:
+        x2 = x2.detach().contiguous().float()
+        x2_index = x2_index.detach().contiguous()
+        if x2_index.dtype != torch.int32:
+            x2_index = x2_index.int()
+    return x1, x2, x2_index, [w.detach().contiguous().float() for w in Ws], [b.detach().contiguous().float() for b in bs], M, k1
+
+
+def _fill_shape(a, k1, in_dim, out_dim, out_act, out_dtype, grouped):
+    """The shape fields the four decoder argument structs share by name - plain ints and dtypes, no tensor needed."""
+    a.k1, a.in_dim, a.out_dim, a.out_act, a.out_dtype = k1, in_dim, out_dim, out_act, L._DT[out_dtype]
+    if grouped is not None:
+        a.x1_layout, a.x1_levels, a.x1_feats = L.LAYOUT_XCD8, grouped[0], grouped[1]
+
+
+def _fill_operands(a, x1=None, x2=None, x2_index=None, W=(), b=()):
+    """The operand pointers the decoder argument structs share by name (those given)."""
+    if x1 is not None:
+        a.x1, a.x1_dtype = L.ptr(x1), L.dtype_code(x1)
+    if x2 is not None:
+        a.x2, a.k2p, a.x2_index = L.ptr(x2), x2.shape[1], L.ptr(x2_index)
+    for i, w in enumerate(W):
+        a.W[i] = L.ptr(w)
+    for i, v in enumerate(b):
+        a.b[i] = L.ptr(v)
+
+
+def _dx2(x2, x2_index, x2_packs, dz0, w_tail, seg=None):
+    """d x2[r] = (sum of dz_0 over the samples that gathered row r) @ w_tail, w_tail = W_0[:, k1:in_dim] - the per-ray view embedding's gradient (pose
+    optimisation: the view direction depends on the camera rotation, ba_pipeline.py:89-90).  seg: the per-row sums where the caller already has them.
+    With x2_packs (the tracer's calls) the sum is the segmented-sum launch, in a fixed order; without them it is index_add_, whose float atomics make
+    d x2 - and only d x2: d x1, dW and db never pass through an atomic - differ in the last bits from run to run."""
+    R, dev = x2.shape[0], x2.device
+    if seg is not None:
+        pass
+    elif x2_packs is not None:                 # rows gathered pack by pack: one segmented-sum launch (deterministic)
+        pack_start, ray_of_pack = x2_packs
+        seg = composite_feats(dz0, torch.ones(dz0.shape[0], device=dev), torch.ones(R, device=dev), pack_start, ray_of_pack, R)
+    else:
+        seg = torch.zeros(R, dz0.shape[1], device=dev).index_add_(0, x2_index.long(), dz0.float())
+    dx2 = torch.zeros_like(x2)
+    dx2[:, :w_tail.shape[1]] = seg @ w_tail
+    return dx2
+
+
+_NON_NULL = 1      # stands for a tensor that does not exist yet: pag_mlp_bwd_fused_supported() tests pointers for NULL only
+_BWD_FUSABLE = {}      # decoder shape -> the library's answer (a pure function of the shape: the struct is built once per shape, not in every eager forward)
+
+
+def _bwd_fusable(M, x1_dtype, needs, k1, k2p, in_dim, n_layers, out_dim, out_act, out_dtype, mode, grouped, rank1=False, has_stats=False,
+                 stats_only=False, col0=False):
+    """Forward-time question: will the backward of this decoder be one of the fused kernels (pag_mlp_bwd with wgrad_workspace), which recompute the
+    hidden activations, so that the forward need not write them?  Answered by the library's own rule (pag_mlp_bwd_fused_supported, host only) on the
+    backward's argument struct as it WILL be filled: a dense gradient or (rank1) g_ray / g_scale / g_index / g_ray_scale; has_stats: the softmax
+    statistics tensor is allocated; stats_only: no `out`; col0: the launch writes relu(x1[:, 0]), so the backward gets dx1_col0_add and _gate.
+    What the library cannot know stays here: the switch, the batch bound, whether d x1 is wanted, and d x2 with a grouped input (only the colour-like
+    kernel hands out dz_0 for the per-ray input's gradient).  A mismatch that still slips through (a _ColourDensity backward that receives no sigma
+    gradient) takes _recompute_hidden(), which is correct but costs a second forward - it warns once."""
+    if not (WGRAD_FUSED and 0 < M <= L.MLP_FUSED_WIDE_MAX_M and needs[0]) or (needs[1] and grouped is not None):
+        return False
+    key = (x1_dtype, k1, k2p, in_dim, n_layers, out_dim, out_act, out_dtype, mode, grouped, rank1, has_stats, stats_only, col0)
+    if key in _BWD_FUSABLE:
+        return _BWD_FUSABLE[key]
+    a = L.MlpBwdArgs()
+    _fill_shape(a, k1, in_dim, out_dim, out_act, out_dtype, grouped)
+    a.n_layers, a.mode = n_layers, mode
+    a.x1, a.x1_dtype, a.dx1, a.dx1_dtype = _NON_NULL, L._DT[x1_dtype], _NON_NULL, L._DT[x1_dtype]
+    if k2p:
+        a.x2, a.k2p, a.x2_index = _NON_NULL, k2p, _NON_NULL
+    if rank1:
+        a.g_ray = a.g_scale = a.g_index = a.g_ray_scale = _NON_NULL
+    else:
+        a.grad_out = _NON_NULL
+    if has_stats:
+        a.softmax_stats = a.b_last = _NON_NULL
+    if col0:
+        a.dx1_col0_add = a.dx1_col0_gate = _NON_NULL
+    if not stats_only:
+        a.out = _NON_NULL
+    _BWD_FUSABLE[key] = L.load().pag_mlp_bwd_fused_supported(ctypes.byref(a)) == 1
+    return _BWD_FUSABLE[key]
+
+
+_WARNED_RECOMPUTE = False
+
+
+def _recompute_hidden(st, x1, x2, x2_index, Wc, hidden):
+    """Fill the missing entries of `hidden` by re-running the forward (pag_mlp_fwd with hidden_save) - the fallback for a backward
+    that the fused kernels cannot serve although the forward did not save the activations."""
+    global _WARNED_RECOMPUTE
+    if not _WARNED_RECOMPUTE:
+        _WARNED_RECOMPUTE = True
+        import warnings
+        warnings.warn("pagnerf_amd: a decoder backward could not use the fused kernels although its forward skipped the hidden activations; "
+                      "re-running the forward for them (correct, but one extra launch and an [M, out] scratch per backward)")
+    M, dev = st.M, x1.device
+    full = [h if h is not None else torch.empty(M, 64, device=dev, dtype=torch.bfloat16 if st.mode == L.MLP_MFMA_BF16 else torch.float32) for h in hidden]
+    out_dim = Wc[-1].shape[0]
+    scratch = torch.empty(M, out_dim, device=dev, dtype=torch.bfloat16)
+    a = L.MlpFwdArgs()
+    _fill_shape(a, st.k1, st.in_dim, out_dim, L.ACT_NONE, torch.bfloat16, st.grouped)
+    _fill_operands(a, x1, x2, x2_index, Wc, st.bc)
+    a.n_layers, a.mode, a.out = st.n_layers, st.mode, L.ptr(scratch)
+    for i, h in enumerate(full):
+        a.hidden_save[i] = L.ptr(h)
+    _call("pag_mlp_fwd", ctypes.byref(a), M, L.stream())
+    return full
+
+
+def _mlp_forward(call, needs, x1, x2, x2_index, *wb):
+    """The 64-wide decoders' forward (pag_mlp_fwd).  needs = (x1 needs a gradient, x2 needs one) -> (out | None, _DecoderState)."""
+    lib = L.load()
+    n_layers = len(wb) // 2
+    x1, x2, x2_index, Wc, bc, M, k1 = _operands(x1, x2, x2_index, wb[:n_layers], wb[n_layers:], call.grouped)
+    in_dim, out_act, mode, out_dtype, grouped, need_grad = call.in_dim, call.out_act, call.mode, call.out_dtype, call.grouped, call.need_grad
+    dev, out_dim = x1.device, Wc[-1].shape[0]
+    mfma = mode == L.MLP_MFMA_BF16
+    wide_softmax = mfma and out_act == L.ACT_SOFTMAX and out_dim > 64 and out_dtype == torch.bfloat16
+    stats_only = call.stats_only and wide_softmax       # head_composite: no [M,out] tensor at all
+    # wide softmax heads: per-sample (max*log2e, 1/sum) lets the backward rebuild the probabilities from the saved
+    # hidden layer instead of streaming `out` through twice (pag_mlp_bwd_args.softmax_stats)
+    has_stats = wide_softmax and (need_grad or stats_only)
+    col0 = bool(call.col0_relu and mfma and grouped is None and x1.dtype == torch.bfloat16 and out_dim <= 64 and M)
+    out = None if stats_only else torch.empty(M, out_dim, device=dev, dtype=out_dtype)
+    # The fused backward kernels RECOMPUTE the hidden activations from x1 (bit-identical MFMA sequence), so the forward of a
+    # decoder they will serve does not write them: 268 MB per hidden layer at M = 2.1 M, in launches that run at the HBM rate.
+    # Wide head: the LAST hidden layer is kept (the probabilities are rebuilt from it).  A backward that turns out not to be
+    # fusable (no column-0 gradient, d x2 requested, ...) re-runs the forward for them (_recompute_hidden: rare, slow, correct).
+    recompute = need_grad and _bwd_fusable(M, x1.dtype, needs, k1, x2.shape[1] if x2 is not None else 0, in_dim, n_layers, out_dim, out_act, out_dtype,
+                                           mode, grouped, call.rank1, has_stats, stats_only, col0)
+    hidden = []
+    if need_grad or stats_only:
+        for i in range(n_layers - 1):
+            keep = (need_grad and not recompute) or (stats_only and i == n_layers - 2)
+            hidden.append(torch.empty(M, 64, device=dev, dtype=torch.bfloat16 if mfma else torch.float32) if keep else None)
+    a = L.MlpFwdArgs()
+    _fill_shape(a, k1, in_dim, out_dim, out_act, out_dtype, grouped)
+    _fill_operands(a, x1, x2, x2_index, Wc, bc)
+    a.n_layers, a.mode, a.out = n_layers, mode, L.ptr(out)
+    for i, h in enumerate(hidden):
+        a.hidden_save[i] = L.ptr(h)
+    stats = torch.empty(M, 2, device=dev) if has_stats else None
+    a.softmax_stats = L.ptr(stats)
+    st = _DecoderState(call, needs, M, k1, n_layers, (x1, x2, x2_index, out, *hidden, *Wc, *((stats, bc[-1]) if has_stats else ())), x1)
+    st.n_hidden, st.has_stats, st.bc = len(hidden), has_stats, bc
+    if col0:
+        st.col0_relu = torch.empty(M, device=dev)           # _ColourDensity: sigma from the same launch
+        a.x1_col0_relu = L.ptr(st.col0_relu)
+    if stats_only:
+        st.head = (hidden[-1], Wc[-1], bc[-1], stats)
+    park = call.park
+    if park is not None and park.bare and not (mfma and all(t is None for t in hidden) and stats is None and not col0):
+        park = None                              # nothing a consumer's launch could carry: issue it now
+    producer = call.producer
+    if producer is not None:
+        # the decoder whose output is this one's x1 waits in `producer`: in this launch where the library can (pag_mlp_fwd_args.x1_producer),
+        # else its own launch FIRST
+        if producer.pending and M and x1.data_ptr() == producer.out_ptr \
+                and lib.pag_mlp_fwd_producer_supported(ctypes.byref(a), ctypes.byref(producer.args), M) == 1:
+            a.x1_producer = ctypes.pointer(producer.args)
+            producer.taken = True
         else:
-            M, k1 = x1.shape
-        x1 = x1.detach()
-        if not x1.is_contiguous():
-            x1 = x1.contiguous()
-        if x1.dtype not in (torch.float32, torch.bfloat16):
-            x1 = x1.float()
-        out_dim = Ws[-1].shape[0]
-        # under torch.no_grad() (validation renders, prune) nothing is kept for a backward: no hidden activations, no softmax statistics
-        # beyond what the statistics-only wide head hands to its compositing launch
-        # (_OUTER_GRAD: the grad mode of the CALLER, recorded by _apply_decoder - inside an autograd.Function's forward grad mode is always
-        # off, and ctx.needs_input_grad / tensor.requires_grad still say True for a parameter inside a no_grad region)
-        any_grad = getattr(ctx, "any_grad", None)
-        need_grad = _OUTER_GRAD and bool(any(ctx.needs_input_grad) if any_grad is None else any_grad)
-        wide_softmax = mode == L.MLP_MFMA_BF16 and out_act == L.ACT_SOFTMAX and out_dim > 64 and out_dtype == torch.bfloat16
-        stats_only = bool(getattr(ctx, "stats_only", False)) and wide_softmax       # _HeadComposite: no [M,out] tensor at all
-        out = None if stats_only else torch.empty(M, out_dim, device=x1.device, dtype=out_dtype)
-        hdt = torch.bfloat16 if mode == L.MLP_MFMA_BF16 else torch.float32
-        # The fused backward kernels RECOMPUTE the hidden activations from x1 (bit-identical MFMA sequence), so the forward of a
-        # decoder they will serve does not write them: 268 MB per hidden layer at M = 2.1 M, in launches that run at the HBM rate.
-        # Wide head: the LAST hidden layer is kept (the probabilities are rebuilt from it).  A backward that turns out not to be
-        # fusable (no column-0 gradient, d x2 requested, ...) re-runs the forward for them (_recompute_hidden: rare, slow, correct).
-        recompute = need_grad and M > 0 and _recompute_ok(ctx, x1, x2, k1, in_dim, n_layers, out_dim, mode, grouped, stats_only, M, out_act,
-                                                          out_dtype, bool(getattr(ctx, "rank1_expected", False)),
-                                                          bool(getattr(ctx, "want_col0_relu", False)))
-        hidden = []
-        if need_grad or stats_only:
-            for i in range(n_layers - 1):
-                keep = (need_grad and not recompute) or (stats_only and i == n_layers - 2)
-                hidden.append(torch.empty(M, 64, device=x1.device, dtype=hdt) if keep else None)
-        a = L.MlpFwdArgs()
-        a.x1, a.x1_dtype, a.k1 = L.ptr(x1), L.dtype_code(x1), k1
-        if grouped is not None:
-            a.x1_layout, a.x1_levels, a.x1_feats = L.LAYOUT_XCD8, grouped[0], grouped[1]
-        if x2 is not None:
-            x2 = x2.detach().contiguous().float()
-            x2_index = x2_index.detach().contiguous()
-            if x2_index.dtype != torch.int32:
-                x2_index = x2_index.int()
-            a.x2, a.k2p, a.x2_index = L.ptr(x2), x2.shape[1], L.ptr(x2_index)
-        a.in_dim, a.n_layers, a.out_dim = in_dim, n_layers, out_dim
-        Wc = [w.detach().contiguous().float() for w in Ws]
-        bc = [b.detach().contiguous().float() for b in bs]
+            producer.issue()
+    if M and park is not None:
+        park.park(a, M, [x1, x2, x2_index, out, stats, st.col0_relu, *hidden, *Wc, *bc], out_ptr=out.data_ptr() if out is not None else 0)
+    elif M:
+        # A pair of decoders on one input (head_composite_pair): the narrow one's launch is PREPARED and parked (its call.park) and rides
+        # in the wide one's call (call.pair -> pag_mlp_fwd_args.pair) where the library can; else the caller issues it.
+        pair = call.pair
+        if pair is not None and pair.pending and M <= L.MLP_FUSED_WIDE_MAX_M and lib.pag_mlp_fwd_pair_supported(ctypes.byref(a), ctypes.byref(pair.args)) == 1:
+            a.pair = ctypes.pointer(pair.args)
+            pair.taken = True
+        # head_composite: the per-ray weighted sum in the decoder's own launch, one pass over the logits (pag_mlp_fwd_args.composite)
+        if call.composite is not None and HEAD_FWD_ONCE and stats_only and lib.pag_mlp_fwd_composite_supported(ctypes.byref(a), M) == 1:
+            a.composite = ctypes.pointer(call.composite)
+            st.composited = True
+        _call("pag_mlp_fwd", ctypes.byref(a), M, L.stream())
+    return out, st
+
+
+def _mlp_backward(st, saved, g, rank1=None, dx1_into=None, dx1_out=None, col0_add=None, col0_gate=None, wgrad_queue=None, hold=None, pair=None):
+    """The 64-wide decoders' backward (pag_mlp_bwd) -> (d x1, d x2, [dW], [db]).
+    rank1 = (g_ray f32 [N,out], g_scale f32 [M], g_index i32 [M], g_ray_scale f32 [N]) replaces the dense upstream gradient g.
+    dx1_into: an XCD8 gradient tensor of another decoder on the same input - this one's d x1 is added to it in place.
+    dx1_out: write d x1 into this tensor instead of a new one.
+    hold (_Launch): a fused launch is PREPARED, not issued - args and everything they point to are parked there, to ride in the
+    call of the other decoder of a pair (pair = that _Launch; pag_mlp_bwd_args.pair) or to be issued by the caller."""
+    lib = L.load()
+    in_dim, out_act, mode, out_dtype, grouped, n_layers, k1, M = st.in_dim, st.out_act, st.mode, st.out_dtype, st.grouped, st.n_layers, st.k1, st.M
+    x1, x2, x2_index, out = saved[:4]
+    hidden = list(saved[4:4 + st.n_hidden])
+    Wc = list(saved[4 + st.n_hidden:4 + st.n_hidden + n_layers])
+    stats, b_last = (saved[-2], saved[-1]) if st.has_stats else (None, None)
+    out_dim = Wc[-1].shape[0]
+    dev = x1.device
+    zdt = torch.bfloat16 if mode == L.MLP_MFMA_BF16 else torch.float32
+    need_dx = st.needs[0]
+    need_dx2 = st.needs[1] and x2 is not None
+    dx1 = (dx1_into if dx1_into is not None else (dx1_out if dx1_out is not None else torch.empty(x1.shape, device=dev, dtype=x1.dtype))) \
+        if need_dx else None
+    a = L.MlpBwdArgs()
+    if rank1 is None:
+        g = g.contiguous().to(out_dtype)       # grad_out travels in the output's dtype
+        a.grad_out = L.ptr(g)
+    else:
+        a.g_ray, a.g_scale, a.g_index, a.g_ray_scale = (L.ptr(t) for t in rank1)
+    _fill_shape(a, k1, in_dim, out_dim, out_act, out_dtype, grouped)
+    _fill_operands(a, W=Wc, b=st.bc)
+    a.out, a.n_layers, a.mode = L.ptr(out), n_layers, mode
+    a.dx1, a.dx1_dtype = L.ptr(dx1), (L.dtype_code(dx1) if need_dx else 0)
+    a.softmax_stats, a.b_last = L.ptr(stats), L.ptr(b_last)
+    a.dx1_accumulate = 1 if (need_dx and dx1_into is not None) else 0
+    fuse_col0 = col0_add is not None and need_dx and grouped is None and mode == L.MLP_MFMA_BF16 and out_dim <= 64
+    if col0_gate is not None and not fuse_col0:          # the gate only exists on the fused path's preconditions
+        col0_add, col0_gate = col0_add * (col0_gate > 0), None
+    if fuse_col0:
+        a.dx1_col0_add = L.ptr(col0_add)
+        if col0_gate is not None:
+            a.dx1_col0_gate = L.ptr(col0_gate)
+    # Weight gradients inside the backward-data launch (pag_mlp_bwd_args.wgrad_workspace) where the library has a fused
+    # kernel for this decoder shape: no dz tensors, no second pass over the activations.  d x2 (pose optimisation) is formed
+    # from dz_0, so that case keeps the dz tensors and the separate weight-gradient launches.
+    fused = False
+    dz0_fused = dz0_slots = ws = None
+    if WGRAD_FUSED and 0 < M <= L.MLP_FUSED_WIDE_MAX_M and mode == L.MLP_MFMA_BF16 and x1.dtype == torch.bfloat16 \
+            and (not need_dx2 or grouped is None):
+        _fill_operands(a, x1, x2, x2_index)
+        fused = lib.pag_mlp_bwd_fused_supported(ctypes.byref(a)) == 1
+        if fused and need_dx2:        # colour-like kernel: d x2 is formed from dz_0 below
+            packs = st.x2_packs
+            if DZ0_SLOTS and packs is not None and _one_pack_per_ray(packs[1], x2.shape[0]) and packs[0].shape[0] == x2.shape[0] + 1:
+                # samples packed ray by ray (x2_index non-decreasing): the per-ray sum of dz_0 starts inside the kernel - one 64-float row per
+                # (tile, ray) instead of the [M,64] tensor (pag_mlp_bwd_args.dz0_slots)
+                dz0_slots = torch.empty(lib.pag_mlp_dz0_slots_bytes(M, x2.shape[0]) // 4, device=dev)
+                a.dz0_slots = L.ptr(dz0_slots)
+            else:                     # dz_0 comes out as a tensor (pag_mlp_bwd_args.dz[0])
+                dz0_fused = torch.empty(M, 64, device=dev, dtype=torch.bfloat16)
+                a.dz[0] = L.ptr(dz0_fused)
+    if not fused and any(h is None for h in hidden):      # the forward counted on the fused kernels: rebuild what it skipped
+        hidden = _recompute_hidden(st, x1, x2, x2_index, Wc, hidden)
+    for i, h in enumerate(hidden):
+        a.hidden_save[i] = L.ptr(h)
+    dz = None
+    gW, gb = [], []
+    if fused:
+        ws_bytes = lib.pag_mlp_bwd_fused_workspace_bytes(ctypes.byref(a), M)
+        ws = torch.empty(ws_bytes // 4, device=dev)
+        a.wgrad_workspace, a.wgrad_workspace_bytes = L.ptr(ws), ws_bytes
+        for l in range(n_layers):
+            gW.append(torch.empty(Wc[l].shape[0], in_dim if l == 0 else 64, device=dev))
+            gb.append(torch.empty(Wc[l].shape[0], device=dev))
+            a.dW[l], a.db[l] = L.ptr(gW[l]), L.ptr(gb[l])
+    else:
+        dz = [torch.empty(M, 64, device=dev, dtype=zdt) for _ in range(n_layers - 1)] + [torch.empty(M, out_dim, device=dev, dtype=zdt)]
         for i in range(n_layers):
-            a.W[i], a.b[i] = L.ptr(Wc[i]), L.ptr(bc[i])
-        a.out_act, a.out, a.out_dtype, a.mode = out_act, L.ptr(out), L._DT[out_dtype], mode
-        for i, h in enumerate(hidden):
-            a.hidden_save[i] = L.ptr(h)
-        # wide softmax heads: per-sample (max*log2e, 1/sum) lets the backward rebuild the probabilities from the saved
-        # hidden layer instead of streaming `out` through twice (pag_mlp_bwd_args.softmax_stats)
-        stats = None
-        if wide_softmax and (need_grad or stats_only):
-            stats = torch.empty(M, 2, device=x1.device)
-            a.softmax_stats = L.ptr(stats)
-        ctx.col0_relu = None
-        if getattr(ctx, "want_col0_relu", False) and mode == L.MLP_MFMA_BF16 and grouped is None and x1.dtype == torch.bfloat16 \
-                and out_dim <= 64 and M:
-            ctx.col0_relu = torch.empty(M, device=x1.device)           # _ColourDensity: sigma from the same launch
-            a.x1_col0_relu = L.ptr(ctx.col0_relu)
-        # A pair of decoders on one input (_HeadCompositePair): the narrow one's launch is PREPARED and parked (ctx.fwd_hold) and rides
-        # in the wide one's call (ctx.fwd_pair -> pag_mlp_fwd_args.pair) where the library can; else the caller issues it.
-        hold, pair_hold = getattr(ctx, "fwd_hold", None), getattr(ctx, "fwd_pair", None)
-        global _NEXT_HOLD, _NEXT_PRODUCER
-        if hold is None and _NEXT_HOLD is not None and _NEXT_HOLD.get("x1_ptr") == x1.data_ptr():
-            # decoder_hold(x1): this launch is prepared and parked for the decoder that consumes its output
-            hold, _NEXT_HOLD = _NEXT_HOLD, None
-            if not (M and mode == L.MLP_MFMA_BF16 and all(t is None for t in hidden) and stats is None and ctx.col0_relu is None):
-                hold = None                              # nothing a consumer's launch could carry: issue it now
-        producer, _NEXT_PRODUCER = _NEXT_PRODUCER, None
-        if producer is not None and producer.get("args") is not None and not producer.get("taken"):
-            # the decoder whose output is this one's x1 waits in `producer`: in this launch where the library can (pag_mlp_fwd_args.x1_producer),
-            # else its own launch FIRST
-            if M and x1.data_ptr() == producer["out_ptr"] and L.load().pag_mlp_fwd_producer_supported(ctypes.byref(a), ctypes.byref(producer["args"]), M) == 1:
-                a.x1_producer = ctypes.pointer(producer["args"])
+            a.dz[i] = L.ptr(dz[i])
+    if M and hold is not None:       # issued later: inside the pair's other call or by the caller
+        hold.park(a, M, [x1, x2, x2_index, out, stats, b_last, g, dx1, col0_add, col0_gate, dz0_slots, dz0_fused, ws, *(rank1 or ()), *hidden, *Wc, *gW,
+                         *gb, *(dz or ())], fused=fused)
+    elif M:
+        if pair is not None and fused and pair.pending and pair.fused and lib.pag_mlp_bwd_pair_supported(ctypes.byref(a), ctypes.byref(pair.args)) == 1:
+            a.pair = ctypes.pointer(pair.args)
+            pair.taken = True
+        _call("pag_mlp_bwd", ctypes.byref(a), M, L.stream())
+    if col0_add is not None and need_dx and not fuse_col0:
+        dx1[:, 0] += col0_add.to(dx1.dtype)          # parity path: same sum with torch ops
+    if fused:
+        pass
+    elif mode == L.MLP_MFMA_BF16 and M:
+        # weight gradients on the matrix cores: per-workgroup fp32 slabs, summed here (deterministic)
+        specs = []
+        for l in range(n_layers):
+            n_out = Wc[l].shape[0]
+            sp = dict(dz=dz[l], n_out=n_out, a2=None, k2p=0, a2_index=None, levels=0, feats=0)
+            if l == 0 and grouped is not None:
+                sp.update(a1=x1, a1_dtype=L.BF16, a1_layout=L.LAYOUT_XCD8, k1=64, n_in=64, levels=grouped[0], feats=grouped[1])
+            elif l == 0:
+                sp.update(a1=x1, a1_dtype=L.dtype_code(x1), a1_layout=L.LAYOUT_STRIDED, k1=k1, n_in=in_dim,
+                          a2=x2, k2p=(x2.shape[1] if x2 is not None else 0), a2_index=x2_index)
             else:
-                _call("pag_mlp_fwd", ctypes.byref(producer["args"]), producer["M"], L.stream())
-            producer["taken"] = True
-        if M and hold is not None:
-            hold["out_ptr"] = out.data_ptr() if out is not None else 0
-            hold["args"], hold["M"] = a, M
-            hold["keep"] = [v for v in locals().values() if isinstance(v, (torch.Tensor, list, tuple))]
-        elif M:
-            if pair_hold is not None and pair_hold.get("args") is not None and M <= L.MLP_FUSED_WIDE_MAX_M \
-                    and L.load().pag_mlp_fwd_pair_supported(ctypes.byref(a), ctypes.byref(pair_hold["args"])) == 1:
-                a.pair = ctypes.pointer(pair_hold["args"])
-                pair_hold["taken"] = True
-            # _HeadComposite: the per-ray weighted sum in the decoder's own launch, one pass over the logits (pag_mlp_fwd_args.composite)
-            comp = getattr(ctx, "fwd_composite", None)
-            ctx.composited = False
-            if comp is not None and HEAD_FWD_ONCE and stats_only and L.load().pag_mlp_fwd_composite_supported(ctypes.byref(a), M) == 1:
-                hc = L.HeadCompositeArgs()
-                hc.pack_start, hc.ray_of_pack, hc.P = L.ptr(comp["pack_start"]), L.ptr(comp["ray_of_pack"]), comp["ray_of_pack"].shape[0]
-                hc.weights, hc.alpha, hc.out = L.ptr(comp["weights"]), L.ptr(comp["alpha"]), L.ptr(comp["out"])
-                hc.n_samples = int(M if SAMPLES_HINT is None else SAMPLES_HINT)
-                a.composite = ctypes.pointer(hc)
-                ctx.composited = True
-            _call("pag_mlp_fwd", ctypes.byref(a), M, L.stream())
-        ctx.cfg = (in_dim, out_act, mode, n_layers, k1, grouped)
-        ctx.x2_packs = None
-        ctx.has_stats = stats is not None
-        ctx.out_dtype = out_dtype
-        extra = (stats, bc[-1]) if stats is not None else ()
-        ctx.save_for_backward(x1, x2, x2_index, out, *hidden, *Wc, *extra)
-        ctx.n_hidden = len(hidden)
-        ctx.bc = bc
-        if stats_only:
-            ctx.fwd_state = (hidden[-1], Wc[-1], bc[-1], stats)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        return _FusedMLP._backward_impl(ctx, g, None)
-
-    @staticmethod
-    def _backward_impl(ctx, g, rank1, dx1_into=None, col0_add=None, col0_gate=None, wgrad_queue=None, dx1_out=None, hold=None,
-                       pair_hold=None):
-        """rank1 = (g_ray f32 [N,out], g_scale f32 [M], g_index i32 [M]) replaces the dense upstream gradient g.
-        dx1_into: an XCD8 gradient tensor of another decoder on the same input - this one's d x1 is added to it in place.
-        dx1_out: write d x1 into this tensor instead of a new one.
-        hold (dict): a fused launch is PREPARED, not issued - args and everything they point to are parked in the dict, to ride in the
-        call of the other decoder of a pair (pair_hold = that dict; pag_mlp_bwd_args.pair) or to be issued by the caller."""
-        lib = L.load()
-        in_dim, out_act, mode, n_layers, k1, grouped = ctx.cfg
-        saved = ctx.saved_tensors
-        x1, x2, x2_index, out = saved[:4]
-        hidden = list(saved[4:4 + ctx.n_hidden])
-        Wc = list(saved[4 + ctx.n_hidden:4 + ctx.n_hidden + n_layers])
-        stats, b_last = (saved[-2], saved[-1]) if getattr(ctx, "has_stats", False) else (None, None)
-        M = x1.shape[1] if grouped is not None else x1.shape[0]
-        out_dim = Wc[-1].shape[0]
-        dev = x1.device
-        zdt = torch.bfloat16 if mode == L.MLP_MFMA_BF16 else torch.float32
-        out_dtype = ctx.out_dtype
-        need_dx = ctx.needs_input_grad[0]
-        need_dx2 = ctx.needs_input_grad[1] and x2 is not None
-        dx1 = (dx1_into if dx1_into is not None else (dx1_out if dx1_out is not None else torch.empty(x1.shape, device=dev, dtype=x1.dtype))) \
-            if need_dx else None
-        k2p = x2.shape[1] if x2 is not None else 0
-        a = L.MlpBwdArgs()
-        if rank1 is None:
-            g = g.contiguous().to(out_dtype)       # grad_out travels in the output's dtype
-            a.grad_out = L.ptr(g)
+                sp.update(a1=hidden[l - 1], a1_dtype=L.BF16, a1_layout=L.LAYOUT_STRIDED, k1=64, n_in=64)
+            sp["w"] = torch.empty(n_out, in_dim if l == 0 else 64, device=dev)
+            sp["b"] = torch.empty(n_out, device=dev)
+            gW.append(sp["w"])
+            gb.append(sp["b"])
+            specs.append(sp)
+        if wgrad_queue is not None:
+            wgrad_queue.extend(specs)          # the caller launches several decoders' weight gradients together
         else:
-            g_ray, g_scale, g_index = rank1[:3]
-            a.g_ray, a.g_scale, a.g_index = L.ptr(g_ray), L.ptr(g_scale), L.ptr(g_index)
-            if len(rank1) > 3:
-                g_ray_scale = rank1[3].float()            # named: stays alive past the launch
-                a.g_ray_scale = L.ptr(g_ray_scale)
-        a.out, a.out_dtype, a.out_act = L.ptr(out), L._DT[out_dtype], out_act
-        a.k1, a.in_dim, a.n_layers, a.out_dim = k1, in_dim, n_layers, out_dim
-        if grouped is not None:
-            a.x1_layout, a.x1_levels, a.x1_feats = L.LAYOUT_XCD8, grouped[0], grouped[1]
-        for i in range(n_layers):
-            a.W[i] = L.ptr(Wc[i])
-        bc = getattr(ctx, "bc", None)
-        if bc is not None:
-            for i in range(n_layers):
-                a.b[i] = L.ptr(bc[i])
-        a.dx1, a.dx1_dtype, a.mode = L.ptr(dx1), (L.dtype_code(dx1) if need_dx else 0), mode
-        a.softmax_stats, a.b_last = L.ptr(stats), L.ptr(b_last)
-        a.dx1_accumulate = 1 if (need_dx and dx1_into is not None) else 0
-        fuse_col0 = col0_add is not None and need_dx and grouped is None and mode == L.MLP_MFMA_BF16 and out_dim <= 64
-        if col0_gate is not None and not fuse_col0:          # the gate only exists on the fused path's preconditions
-            col0_add, col0_gate = col0_add * (col0_gate > 0), None
-        if fuse_col0:
-            a.dx1_col0_add = L.ptr(col0_add)
-            if col0_gate is not None:
-                a.dx1_col0_gate = L.ptr(col0_gate)
-        # Weight gradients inside the backward-data launch (pag_mlp_bwd_args.wgrad_workspace) where the library has a fused
-        # kernel for this decoder shape: no dz tensors, no second pass over the activations.  d x2 (pose optimisation) is formed
-        # from dz_0, so that case keeps the dz tensors and the separate weight-gradient launches.
-        fused = False
-        dz0_fused = dz0_slots = None
-        if WGRAD_FUSED and 0 < M <= L.MLP_FUSED_WIDE_MAX_M and mode == L.MLP_MFMA_BF16 and x1.dtype == torch.bfloat16 \
-                and (not need_dx2 or grouped is None):
-            a.x1, a.x1_dtype = L.ptr(x1), L.BF16
-            if x2 is not None:
-                a.x2, a.k2p, a.x2_index = L.ptr(x2), k2p, L.ptr(x2_index)
-            fused = lib.pag_mlp_bwd_fused_supported(ctypes.byref(a)) == 1
-            if fused and need_dx2:        # colour-like kernel: d x2 is formed from dz_0 below
-                packs = ctx.x2_packs
-                if DZ0_SLOTS and packs is not None and _one_pack_per_ray(packs[1], x2.shape[0]) and packs[0].shape[0] == x2.shape[0] + 1:
-                    # samples packed ray by ray (x2_index non-decreasing): the per-ray sum of dz_0 starts inside the kernel - one 64-float row per
-                    # (tile, ray) instead of the [M,64] tensor (pag_mlp_bwd_args.dz0_slots)
-                    dz0_slots = torch.empty(lib.pag_mlp_dz0_slots_bytes(M, x2.shape[0]) // 4, device=dev)
-                    a.dz0_slots = L.ptr(dz0_slots)
-                else:                     # dz_0 comes out as a tensor (pag_mlp_bwd_args.dz[0])
-                    dz0_fused = torch.empty(M, 64, device=dev, dtype=torch.bfloat16)
-                    a.dz[0] = L.ptr(dz0_fused)
-        if not fused and any(h is None for h in hidden):      # the forward counted on the fused kernels: rebuild what it skipped
-            hidden = _recompute_hidden(x1, x2, x2_index, Wc, bc, in_dim, k1, grouped, mode, hidden)
-        for i, h in enumerate(hidden):
-            a.hidden_save[i] = L.ptr(h)
-        dz = None
-        gW, gb = [], []
-        if fused:
-            ws_bytes = lib.pag_mlp_bwd_fused_workspace_bytes(ctypes.byref(a), M)
-            ws = torch.empty(ws_bytes // 4, device=dev)
-            a.wgrad_workspace, a.wgrad_workspace_bytes = L.ptr(ws), ws_bytes
-            for l in range(n_layers):
-                gW.append(torch.empty(Wc[l].shape[0], in_dim if l == 0 else 64, device=dev))
-                gb.append(torch.empty(Wc[l].shape[0], device=dev))
-                a.dW[l], a.db[l] = L.ptr(gW[l]), L.ptr(gb[l])
-        else:
-            dz = [torch.empty(M, 64, device=dev, dtype=zdt) for _ in range(n_layers - 1)] + [torch.empty(M, out_dim, device=dev, dtype=zdt)]
-            for i in range(n_layers):
-                a.dz[i] = L.ptr(dz[i])
-        if M and hold is not None:
-            hold["args"], hold["M"], hold["fused"] = a, M, fused       # issued later: inside the pair's other call or by the caller
-            hold["keep"] = [v for v in locals().values() if isinstance(v, (torch.Tensor, list, tuple))]
-        elif M:
-            if pair_hold is not None and fused and pair_hold.get("fused") \
-                    and lib.pag_mlp_bwd_pair_supported(ctypes.byref(a), ctypes.byref(pair_hold["args"])) == 1:
-                a.pair = ctypes.pointer(pair_hold["args"])
-                pair_hold["taken"] = True
-            _call("pag_mlp_bwd", ctypes.byref(a), M, L.stream())
-        if col0_add is not None and need_dx and not fuse_col0:
-            dx1[:, 0] += col0_add.to(dx1.dtype)          # parity path: same sum with torch ops
-        if fused:
-            pass
-        elif mode == L.MLP_MFMA_BF16 and M:
-            # weight gradients on the matrix cores: per-workgroup fp32 slabs, summed here (deterministic)
-            specs = []
-            for l in range(n_layers):
-                n_out = Wc[l].shape[0]
-                sp = dict(dz=dz[l], n_out=n_out, a2=None, k2p=0, a2_index=None, levels=0, feats=0)
-                if l == 0 and grouped is not None:
-                    sp.update(a1=x1, a1_dtype=L.BF16, a1_layout=L.LAYOUT_XCD8, k1=64, n_in=64, levels=grouped[0], feats=grouped[1])
-                elif l == 0:
-                    sp.update(a1=x1, a1_dtype=L.dtype_code(x1), a1_layout=L.LAYOUT_STRIDED, k1=k1, n_in=in_dim,
-                              a2=x2, k2p=(x2.shape[1] if x2 is not None else 0), a2_index=x2_index)
-                else:
-                    sp.update(a1=hidden[l - 1], a1_dtype=L.BF16, a1_layout=L.LAYOUT_STRIDED, k1=64, n_in=64)
-                sp["w"] = torch.empty(n_out, in_dim if l == 0 else 64, device=dev)
-                sp["b"] = torch.empty(n_out, device=dev)
-                gW.append(sp["w"])
-                gb.append(sp["b"])
-                specs.append(sp)
-            if wgrad_queue is not None:
-                wgrad_queue.extend(specs)          # the caller launches several decoders' weight gradients together
+            _launch_wgrad(specs, M)
+    else:
+        # fp32 parity path: dz_l^T @ input_l as plain fp32 GEMMs (BLAS)
+        for l in range(n_layers):
+            z = dz[l]
+            if l == 0:
+                n1 = min(k1, in_dim)
+                w = _mm_f32(z.t(), x1[:, :n1].to(z.dtype))
+                if in_dim > k1:
+                    seg = torch.zeros(x2.shape[0], 64, device=dev, dtype=torch.float32)
+                    seg.index_add_(0, x2_index.long(), z.float())
+                    w = torch.cat([w, seg.t() @ x2[:, :in_dim - k1]], dim=1)
             else:
-                _launch_wgrad(specs, M)
-        else:
-            # fp32 parity path: dz_l^T @ input_l as plain fp32 GEMMs (BLAS)
-            for l in range(n_layers):
-                z = dz[l]
-                if l == 0:
-                    n1 = min(k1, in_dim)
-                    w = _mm_f32(z.t(), x1[:, :n1].to(z.dtype))
-                    if in_dim > k1:
-                        seg = torch.zeros(x2.shape[0], 64, device=dev, dtype=torch.float32)
-                        seg.index_add_(0, x2_index.long(), z.float())
-                        w = torch.cat([w, seg.t() @ x2[:, :in_dim - k1]], dim=1)
-                else:
-                    w = _mm_f32(z.t(), hidden[l - 1])
-                gW.append(w)
-                gb.append(z.sum(0, dtype=torch.float32))
-        dx2 = None
-        if need_dx2 and dz0_fused is not None:
-            dz = [dz0_fused]
-        if need_dx2:
-            # d x2[r] = (sum of dz_0 over the samples that gathered row r) @ W_0[:, k1:]  - the per-ray view embedding's
-            # gradient (pose optimisation: the view direction depends on the camera rotation, ba_pipeline.py:89-90)
-            R = x2.shape[0]
-            if dz0_slots is not None and M:                # the kernel left per-(tile, ray) sums: add each ray's rows
-                seg = torch.empty(R, 64, device=dev)
-                _call("pag_mlp_dz0_slots_sum", L.ptr(ctx.x2_packs[0]), R, L.ptr(dz0_slots), L.ptr(seg), L.stream())
-            elif M == 0:
-                seg = torch.zeros(R, 64, device=dev)
-            elif ctx.x2_packs is not None:                 # rows gathered pack by pack: one segmented-sum launch
-                pack_start, ray_of_pack = ctx.x2_packs
-                seg = composite_feats(dz[0], torch.ones(M, device=dev), torch.ones(R, device=dev), pack_start, ray_of_pack, R)
-            else:
-                seg = torch.zeros(R, dz[0].shape[1], device=dev).index_add_(0, x2_index.long(), dz[0].float())
-            w_tail = Wc[0][:, k1:in_dim]
-            dx2 = torch.zeros_like(x2)
-            dx2[:, :in_dim - k1] = seg @ w_tail
-        return (dx1, dx2, None, None, None, None, None, None, *gW, *gb)
+                w = _mm_f32(z.t(), hidden[l - 1])
+            gW.append(w)
+            gb.append(z.sum(0, dtype=torch.float32))
+    dx2 = None
+    if need_dx2:
+        R, seg = x2.shape[0], None
+        if dz0_slots is not None and M:                # the kernel left per-(tile, ray) sums: add each ray's rows
+            seg = torch.empty(R, 64, device=dev)
+            _call("pag_mlp_dz0_slots_sum", L.ptr(st.x2_packs[0]), R, L.ptr(dz0_slots), L.ptr(seg), L.stream())
+        elif M == 0:
+            seg = torch.zeros(R, 64, device=dev)
+        dx2 = _dx2(x2, x2_index, st.x2_packs, dz0_fused if dz0_fused is not None else dz[0] if dz else None, Wc[0][:, k1:in_dim], seg)
+    return dx1, dx2, gW, gb
 
 
 DZ0_SLOTS = os.environ.get("PAG_DZ0_SLOTS", "1") != "0"      # A/B switch: per-(tile, ray) sums of dz_0 inside the colour backward (pag_mlp_bwd_args.dz0_slots)
@@ -785,61 +815,72 @@ def affine_xcd8(x8, W, b, grouped):
     return _AffineXCD8.apply(x8, W, b, grouped)
 
 
-class _ColourDensity(_FusedMLP):
+def _decoder_grads(grads):
+    """(d x1, d x2, [dW], [db]) -> the backward's return for the inputs (call, x1, x2, x2_index, *W, *b)."""
+    dx1, dx2, gW, gb = grads
+    return (None, dx1, dx2, None, *gW, *gb)
+
+
+class _FusedMLP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, call, x1, x2, x2_index, *wb):
+        out, st = _mlp_forward(call, ctx.needs_input_grad[1:3], x1, x2, x2_index, *wb)
+        _save(ctx, st)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return _decoder_grads(_mlp_backward(ctx.state, ctx.saved_tensors, g))
+
+
+class _ColourDensity(torch.autograd.Function):
     """The colour decoder on cat(density_feats, PE) AND the density sigma = relu(density_feats[:, 0]) that
     pc_nerf/panoptic_delta_nef.py:188 reads off its x1, as one autograd node: the gradient of sigma is added to column 0 of
     the decoder's d x1 inside the backward kernel - no zero-padded [M,16] gradient, slice / cast / relu backward or add pass."""
 
     @staticmethod
-    def forward(ctx, x1, x2, x2_index, in_dim, out_act, mode, out_dtype, grouped, *wb):
-        ctx.want_col0_relu = True
-        rgb = _FusedMLP.forward(ctx, x1, x2, x2_index, in_dim, out_act, mode, out_dtype, grouped, *wb)
-        if ctx.col0_relu is not None:            # written by the decoder launch; the backward gates on it inside the kernel
-            ctx.pre = None
-            return rgb, ctx.col0_relu
-        pre = x1.detach()[:, 0].float()
-        ctx.pre = pre
-        return rgb, torch.relu(pre)
+    def forward(ctx, call, x1, x2, x2_index, *wb):
+        rgb, st = _mlp_forward(call, ctx.needs_input_grad[1:3], x1, x2, x2_index, *wb)
+        _save(ctx, st)
+        ctx.pre = None
+        if st.col0_relu is not None:            # written by the decoder launch; the backward gates on it inside the kernel
+            return rgb, st.col0_relu
+        ctx.pre = x1.detach()[:, 0].float()
+        return rgb, torch.relu(ctx.pre)
 
     @staticmethod
     def backward(ctx, g_rgb, g_sigma):
-        saved_out = ctx.saved_tensors[3]
+        st, saved = ctx.state, ctx.saved_tensors
         if g_rgb is None:
-            g_rgb = torch.zeros_like(saved_out)
+            g_rgb = torch.zeros_like(saved[3])
         if g_sigma is None:
-            return _FusedMLP._backward_impl(ctx, g_rgb, None)
+            return _decoder_grads(_mlp_backward(st, saved, g_rgb))
         if ctx.pre is None:
-            return _FusedMLP._backward_impl(ctx, g_rgb, None, col0_add=g_sigma.float().contiguous(), col0_gate=ctx.col0_relu)
-        add = (g_sigma.float() * (ctx.pre > 0)).contiguous()
-        return _FusedMLP._backward_impl(ctx, g_rgb, None, col0_add=add)
+            return _decoder_grads(_mlp_backward(st, saved, g_rgb, col0_add=g_sigma.float().contiguous(), col0_gate=st.col0_relu))
+        return _decoder_grads(_mlp_backward(st, saved, g_rgb, col0_add=(g_sigma.float() * (ctx.pre > 0)).contiguous()))
 
 
 def colour_and_density(x1, weights, biases, x2, x2_index, in_dim, out_act=L.ACT_SIGMOID, mode=L.MLP_MFMA_BF16,
                        out_dtype=torch.float32, x2_packs=None, producer=None):
     """-> (rgb [M,3], sigma f32 [M] = relu(x1[:,0])); x1 = the density decoder's [M,16] output (see _ColourDensity).
     producer: the decoder_hold() in which the density decoder's launch waits - evaluated in this decoder's launch where the library can."""
-    global _NEXT_PRODUCER
-    _NEXT_PRODUCER = producer
-    try:
-        rgb, sigma = _apply_decoder(_ColourDensity, x1, x2, x2_index, int(in_dim), out_act, mode, out_dtype, None, *weights, *biases)
-    finally:
-        _NEXT_PRODUCER = None            # a call that raised before _FusedMLP.forward took the producer must not leave it for an unrelated decoder
-    if x2_packs is not None and x2 is not None and x2.requires_grad and rgb.grad_fn is not None:
-        rgb.grad_fn.x2_packs = x2_packs
-    return rgb, sigma
+    call = _DecoderCall(in_dim, out_act, mode, out_dtype, None, x2_packs=x2_packs, need_grad=_need_grad(x1, x2, x2_index, *weights, *biases),
+                        col0_relu=True, producer=producer)
+    return _apply(_ColourDensity, call, x1, x2, x2_index, *weights, *biases)
 
 
 def fused_mlp(x1, weights, biases, x2=None, x2_index=None, in_dim=None, out_act=L.ACT_NONE, mode=L.MLP_MFMA_BF16,
-              out_dtype=torch.float32, x1_grouped=None, x2_packs=None):
+              out_dtype=torch.float32, x1_grouped=None, x2_packs=None, hold=None):
     """wisp BasicDecoder (Linear+ReLU ... Linear) [+ sigmoid/softmax] in one launch.
     x1 [M,k1] (+ optional per-ray x2 [R,k2p] gathered by x2_index [M]); weights[i] is [out,in].
-    x1_grouped=(levels, feats): x1 is the encoders' bf16 [8, M, 8] XCD-grouped tensor."""
+    x1_grouped=(levels, feats): x1 is the encoders' bf16 [8, M, 8] XCD-grouped tensor.
+    x2_packs=(pack_start, ray_of_pack): x2_index is constant inside each pack (d/d x2 only).
+    hold: a decoder_hold() - the launch is prepared and parked there for the decoder that consumes its output."""
     if in_dim is None:
         in_dim = weights[0].shape[1]
-    out = _apply_decoder(_FusedMLP, x1, x2, x2_index, int(in_dim), out_act, mode, out_dtype, x1_grouped, *weights, *biases)
-    if x2_packs is not None and x2 is not None and x2.requires_grad and out.grad_fn is not None:
-        out.grad_fn.x2_packs = x2_packs      # (pack_start, ray_of_pack): x2_index is constant inside each pack (d/d x2 only)
-    return out
+    call = _DecoderCall(in_dim, out_act, mode, out_dtype, x1_grouped, x2_packs=x2_packs, need_grad=_need_grad(x1, x2, x2_index, *weights, *biases),
+                        park=hold)
+    return _apply(_FusedMLP, call, x1, x2, x2_index, *weights, *biases)
 
 
 # ----------------------------------------------------------------------------- 128-wide decoders
@@ -868,108 +909,80 @@ def _native_plane(ws, col0, width, M):
     return p.permute(0, 4, 1, 2, 3, 5).reshape(Mp, width)[:M]
 
 
+def _mlp128_forward(call, needs, x1, x2, x2_index, *wb):
+    """The 128-wide decoders' forward (pag_mlp128_fwd) -> (out, _DecoderState)."""
+    n_hidden = len(wb) // 2 - 1
+    if any(v is None for v in wb[n_hidden + 1:]):
+        raise NotImplementedError("fused_mlp128 needs biases")
+    x1, x2, x2_index, Wc, bc, M, k1 = _operands(x1, x2, x2_index, wb[:n_hidden + 1], wb[n_hidden + 1:], call.grouped)
+    out_dim = Wc[-1].shape[0]
+    out = torch.empty(M, out_dim, device=x1.device, dtype=call.out_dtype)
+    a = L.Mlp128FwdArgs()
+    _fill_shape(a, k1, call.in_dim, out_dim, call.out_act, call.out_dtype, call.grouped)
+    _fill_operands(a, x1, x2, x2_index, Wc, bc)
+    a.n_hidden, a.hidden, a.out = n_hidden, Wc[0].shape[0], L.ptr(out)
+    ws = None
+    if call.need_grad and M:          # under torch.no_grad() nothing is saved and no workspace is asked for
+        nbytes = L.load().pag_mlp128_workspace_bytes(M, n_hidden, out_dim, 1)
+        L.check(min(nbytes, 0), "pag_mlp128_workspace_bytes")
+        ws = torch.empty(nbytes, device=x1.device, dtype=torch.uint8)
+        a.workspace, a.workspace_bytes = L.ptr(ws), nbytes
+    if M:
+        _call("pag_mlp128_fwd", ctypes.byref(a), M, L.stream())
+    return out, _DecoderState(call, needs, M, k1, n_hidden + 1, (x2, x2_index, out, ws, *Wc), x1)
+
+
+def _mlp128_backward(st, saved, g, dx1_into=None):
+    """The 128-wide decoders' backward (pag_mlp128_bwd) -> (d x1, d x2, [dW], [db]).
+    dx1_into: an XCD8 gradient tensor of another decoder on the same input - this one's d x1 is added to it in place."""
+    in_dim, out_dtype, k1, M, n_hidden = st.in_dim, st.out_dtype, st.k1, st.M, st.n_layers - 1
+    x2, x2_index, out, ws = saved[:4]
+    Wc = list(saved[4:])
+    dev, out_dim = out.device, out.shape[1]
+    need_dx = st.needs[0]
+    need_dx2 = st.needs[1] and x2 is not None
+    dx1 = (dx1_into if dx1_into is not None else torch.empty(st.x1_shape, device=dev, dtype=st.x1_dtype)) if need_dx else None
+    gW = [torch.empty_like(w) for w in Wc]
+    gb = [torch.empty(w.shape[0], device=dev) for w in Wc]
+    if M == 0:
+        for t in gW + gb:
+            t.zero_()
+        return dx1, (torch.zeros_like(x2) if need_dx2 else None), gW, gb
+    g = g.contiguous().to(out_dtype)       # grad_out travels in the output's dtype
+    a = L.Mlp128BwdArgs()
+    _fill_shape(a, k1, in_dim, out_dim, st.out_act, out_dtype, st.grouped)
+    _fill_operands(a, W=Wc)
+    a.grad_out, a.out, a.k2p, a.n_hidden, a.hidden = L.ptr(g), L.ptr(out), (x2.shape[1] if x2 is not None else 0), n_hidden, Wc[0].shape[0]
+    nbytes = L.load().pag_mlp128_workspace_bytes(M, n_hidden, out_dim, 2)
+    L.check(min(nbytes, 0), "pag_mlp128_workspace_bytes")
+    bws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    a.workspace, a.workspace_bytes, a.bwd_workspace, a.bwd_workspace_bytes = L.ptr(ws), ws.numel(), L.ptr(bws), nbytes
+    a.dx1, a.dx1_dtype = L.ptr(dx1), (L.dtype_code(dx1) if need_dx else 0)
+    a.dx1_accumulate = 1 if (need_dx and dx1_into is not None) else 0
+    for i in range(n_hidden + 1):
+        a.dW[i], a.db[i] = L.ptr(gW[i]), L.ptr(gb[i])
+    _call("pag_mlp128_bwd", ctypes.byref(a), M, L.stream())
+    dx2 = None
+    if need_dx2:
+        # dz_0 is the first plane of the backward workspace.  Not a hot path at this width: a segmented sum and one small matmul, with the weights
+        # as the kernels round them
+        dx2 = _dx2(x2, x2_index, st.x2_packs, _native_plane(bws, 0, 128, M), Wc[0][:, k1:in_dim].bfloat16().float())
+    return dx1, dx2, gW, gb
+
+
 class _FusedMLP128(torch.autograd.Function):
     """One BasicDecoder at hidden width 128 (pag_mlp128_fwd / pag_mlp128_bwd): no host read of device data, no shape that depends on device
     data, every buffer from torch's allocator - a captured step replays it."""
 
     @staticmethod
-    def forward(ctx, x1, x2, x2_index, in_dim, out_act, out_dtype, grouped, *wb):
-        _check_gpu(x1, x2, x2_index, *wb)
-        n_hidden = len(wb) // 2 - 1
-        Ws, bs = wb[:n_hidden + 1], wb[n_hidden + 1:]
-        if any(v is None for v in bs):
-            raise NotImplementedError("fused_mlp128 needs biases")
-        if grouped is not None:
-            M, k1 = x1.shape[1], 64
-        else:
-            M, k1 = x1.shape
-        x1 = x1.detach()
-        if not x1.is_contiguous():
-            x1 = x1.contiguous()
-        if x1.dtype not in (torch.float32, torch.bfloat16):
-            x1 = x1.float()
-        out_dim = Ws[-1].shape[0]
-        need_grad = _OUTER_GRAD and bool(any(ctx.needs_input_grad))
-        out = torch.empty(M, out_dim, device=x1.device, dtype=out_dtype)
-        a = L.Mlp128FwdArgs()
-        a.x1, a.x1_dtype, a.k1 = L.ptr(x1), L.dtype_code(x1), k1
-        if grouped is not None:
-            a.x1_layout, a.x1_levels, a.x1_feats = L.LAYOUT_XCD8, grouped[0], grouped[1]
-        if x2 is not None:
-            x2 = x2.detach().contiguous().float()
-            x2_index = x2_index.detach().contiguous()
-            if x2_index.dtype != torch.int32:
-                x2_index = x2_index.int()
-            a.x2, a.k2p, a.x2_index = L.ptr(x2), x2.shape[1], L.ptr(x2_index)
-        a.in_dim, a.n_hidden, a.hidden, a.out_dim = in_dim, n_hidden, Ws[0].shape[0], out_dim
-        Wc = [w.detach().contiguous().float() for w in Ws]
-        bc = [b.detach().contiguous().float() for b in bs]
-        for i in range(n_hidden + 1):
-            a.W[i], a.b[i] = L.ptr(Wc[i]), L.ptr(bc[i])
-        a.out_act, a.out, a.out_dtype = out_act, L.ptr(out), L._DT[out_dtype]
-        ws = None
-        if need_grad and M:          # under torch.no_grad() nothing is saved and no workspace is asked for
-            nbytes = L.load().pag_mlp128_workspace_bytes(M, n_hidden, out_dim, 1)
-            L.check(min(nbytes, 0), "pag_mlp128_workspace_bytes")
-            ws = torch.empty(nbytes, device=x1.device, dtype=torch.uint8)
-            a.workspace, a.workspace_bytes = L.ptr(ws), nbytes
-        if M:
-            _call("pag_mlp128_fwd", ctypes.byref(a), M, L.stream())
-        ctx.cfg = (in_dim, out_act, n_hidden, k1, grouped, M, out_dtype, tuple(x1.shape), x1.dtype)
-        ctx.x2_packs = None
-        ctx.save_for_backward(x2, x2_index, out, ws, *Wc)
+    def forward(ctx, call, x1, x2, x2_index, *wb):
+        out, st = _mlp128_forward(call, ctx.needs_input_grad[1:3], x1, x2, x2_index, *wb)
+        _save(ctx, st)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        return _FusedMLP128._backward_impl(ctx, g)
-
-    @staticmethod
-    def _backward_impl(ctx, g, dx1_into=None):
-        """dx1_into: an XCD8 gradient tensor of another decoder on the same input - this one's d x1 is added to it in place."""
-        in_dim, out_act, n_hidden, k1, grouped, M, out_dtype, x1_shape, x1_dtype = ctx.cfg
-        x2, x2_index, out, ws = ctx.saved_tensors[:4]
-        Wc = list(ctx.saved_tensors[4:])
-        dev, out_dim = out.device, out.shape[1]
-        need_dx = ctx.needs_input_grad[0]
-        need_dx2 = ctx.needs_input_grad[1] and x2 is not None
-        dx1 = (dx1_into if dx1_into is not None else torch.empty(x1_shape, device=dev, dtype=x1_dtype)) if need_dx else None
-        gW = [torch.empty_like(w) for w in Wc]
-        gb = [torch.empty(w.shape[0], device=dev) for w in Wc]
-        dx2 = torch.zeros_like(x2) if need_dx2 else None
-        if M == 0:
-            for t in gW + gb:
-                t.zero_()
-            return (dx1, dx2, None, None, None, None, None, *gW, *gb)
-        g = g.contiguous().to(out_dtype)       # grad_out travels in the output's dtype
-        a = L.Mlp128BwdArgs()
-        a.grad_out, a.out, a.out_dtype, a.out_act = L.ptr(g), L.ptr(out), L._DT[out_dtype], out_act
-        a.k1, a.k2p, a.in_dim, a.n_hidden, a.hidden, a.out_dim = k1, (x2.shape[1] if x2 is not None else 0), in_dim, n_hidden, Wc[0].shape[0], out_dim
-        if grouped is not None:
-            a.x1_layout, a.x1_levels, a.x1_feats = L.LAYOUT_XCD8, grouped[0], grouped[1]
-        nbytes = L.load().pag_mlp128_workspace_bytes(M, n_hidden, out_dim, 2)
-        L.check(min(nbytes, 0), "pag_mlp128_workspace_bytes")
-        bws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        a.workspace, a.workspace_bytes, a.bwd_workspace, a.bwd_workspace_bytes = L.ptr(ws), ws.numel(), L.ptr(bws), nbytes
-        a.dx1, a.dx1_dtype = L.ptr(dx1), (L.dtype_code(dx1) if need_dx else 0)
-        a.dx1_accumulate = 1 if (need_dx and dx1_into is not None) else 0
-        for i in range(n_hidden + 1):
-            a.W[i], a.dW[i], a.db[i] = L.ptr(Wc[i]), L.ptr(gW[i]), L.ptr(gb[i])
-        _call("pag_mlp128_bwd", ctypes.byref(a), M, L.stream())
-        if need_dx2:
-            # d x2[r] = (sum of dz_0 over the samples that gathered row r) @ W_0[:, k1:] - the per-ray view embedding's gradient (pose
-            # optimisation); dz_0 is the first plane of the backward workspace.  Not a hot path at this width: a segmented sum and one small matmul.
-            # With x2_packs (the tracer's calls) the sum is the segmented-sum launch, in a fixed order; without them it is index_add_, whose float
-            # atomics make d x2 - and only d x2: d x1, dW and db never pass through an atomic - differ in the last bits from run to run
-            dz0 = _native_plane(bws, 0, 128, M)
-            R = x2.shape[0]
-            if ctx.x2_packs is not None:                 # rows gathered pack by pack: one segmented-sum launch (deterministic)
-                pack_start, ray_of_pack = ctx.x2_packs
-                seg = composite_feats(dz0.contiguous(), torch.ones(M, device=dev), torch.ones(R, device=dev), pack_start, ray_of_pack, R)
-            else:
-                seg = torch.zeros(R, 128, device=dev).index_add_(0, x2_index.long(), dz0.float())
-            dx2[:, :in_dim - k1] = seg.float() @ Wc[0][:, k1:in_dim].bfloat16().float()          # the weights as the kernels round them
-        return (dx1, dx2, None, None, None, None, None, *gW, *gb)
+        return _decoder_grads(_mlp128_backward(ctx.state, ctx.saved_tensors, g))
 
 
 def fused_mlp128(x1, weights, biases, x2=None, x2_index=None, in_dim=None, out_act=L.ACT_NONE, mode=L.MLP_MFMA_BF16,
@@ -980,10 +993,8 @@ def fused_mlp128(x1, weights, biases, x2=None, x2_index=None, in_dim=None, out_a
         raise NotImplementedError("fused_mlp128 runs in MLP_MFMA_BF16 mode; the fp32 form at width 128 is ops.wide_mlp_reference")
     if in_dim is None:
         in_dim = weights[0].shape[1]
-    out = _apply_decoder(_FusedMLP128, x1, x2, x2_index, int(in_dim), out_act, out_dtype, x1_grouped, *weights, *biases)
-    if x2_packs is not None and x2 is not None and x2.requires_grad and out.grad_fn is not None:
-        out.grad_fn.x2_packs = x2_packs      # (pack_start, ray_of_pack): x2_index is constant inside each pack (d/d x2 only)
-    return out
+    call = _DecoderCall(in_dim, out_act, mode, out_dtype, x1_grouped, x2_packs=x2_packs, need_grad=_need_grad(x1, x2, x2_index, *weights, *biases))
+    return _apply(_FusedMLP128, call, x1, x2, x2_index, *weights, *biases)
 
 
 # ------------------------------------------------------------------------------------------ ray march
@@ -1644,31 +1655,19 @@ def composite_features(sigma, deltas, feats, ridx, pack_start, ray_of_pack, N):
     return _apply(_CompositeFeatsWeights, sigma, deltas, feats, ridx, pack_start, ray_of_pack, N)
 
 
-HEAD_REBUILD = True      # wide softmax heads under head_composite(): statistics-only forward + rebuilt probabilities
 CD_FUSED = os.environ.get("PAG_CD_FUSED", "1") != "0"      # density decoder + colour decoder in one launch (pag_mlp_fwd_args.x1_producer)
-_NEXT_HOLD = None
-_NEXT_PRODUCER = None
 
 
-def decoder_hold(x1):
-    """-> hold (dict): the next fused_mlp() call ON THE INPUT `x1` prepares its launch and parks it in `hold` instead of issuing it; hand `hold` to the
-    decoder that consumes its output (colour_and_density(..., producer=hold)), which carries it in its own launch or issues it first, and call
-    flush_hold(hold) afterwards in any case (issues the parked launch if nobody took it; forgets a hold no call picked up).  Single-threaded callers
-    only, as everything behind the plugin API."""
-    global _NEXT_HOLD
-    _NEXT_HOLD = {"x1_ptr": x1.data_ptr()}
-    return _NEXT_HOLD
+def decoder_hold():
+    """-> hold (_Launch): fused_mlp(..., hold=hold) prepares its launch and parks it in `hold` instead of issuing it; hand `hold` to the decoder that
+    consumes its output (colour_and_density(..., producer=hold)), which carries it in its own launch or issues it first, and call flush_hold(hold)
+    afterwards in any case (issues the parked launch if nobody took it)."""
+    return _Launch("pag_mlp_fwd", bare=True)
 
 
 def flush_hold(hold):
-    global _NEXT_HOLD, _NEXT_PRODUCER
-    if _NEXT_HOLD is hold:
-        _NEXT_HOLD = None                # the call it was meant for never came
-    if hold is not None and _NEXT_PRODUCER is hold:
-        _NEXT_PRODUCER = None            # ... nor may a later, unrelated decoder pick this launch up as its producer
-    if hold is not None and hold.get("args") is not None and not hold.get("taken"):
-        _call("pag_mlp_fwd", ctypes.byref(hold["args"]), hold["M"], L.stream())
-        hold["taken"] = True
+    if hold is not None:
+        hold.issue()
 
 
 HEAD_FWD_ONCE = os.environ.get("PAG_HEAD_FWD_ONCE", "1") != "0"      # wide softmax head: decoder + per-ray sum in one launch (0: statistics launch + pag_head_composite_fwd)
@@ -1677,90 +1676,85 @@ TAIL_ZERO = False        # graphs.py: batches carry filler samples past pack_sta
 SAMPLES_HINT = None      # graphs.py: the REAL sample count expected in a padded batch (pag_head_composite_fwd picks its per-pack work split from it)
 
 
-class _HeadComposite(_FusedMLP):
+def _head_call(in_dim, out_act, out_dtype, grouped, need_grad, **kw):
+    """The decoder request of head_composite(): a statistics-only forward where the head is a wide softmax (the probabilities are rebuilt from the last
+    hidden layer), and a backward that hands the decoder its gradient in rank-1 form (_head_backward)."""
+    return _DecoderCall(in_dim, out_act, L.MLP_MFMA_BF16, out_dtype, grouped, need_grad=need_grad, rank1=True, stats_only=True, **kw)
+
+
+def _head_forward(call, needs_x1, x1, weights_w, alpha, ridx, pack_start, ray_of_pack, *wb):
+    """Decoder, then the per-ray weighted sum -> (out f32 [N,C], _DecoderState)."""
+    # wide softmax head: where the library can, the decoder's launch forms the per-ray sums itself (pag_mlp_fwd_args.composite) - the output
+    # tensor and the compositing arguments are prepared first and ride in the request
+    C = wb[len(wb) // 2 - 1].shape[0]
+    M = x1.shape[1] if call.grouped is not None else x1.shape[0]
+    P, N = ray_of_pack.shape[0], call.n_rays
+    n_samples = int(M if SAMPLES_HINT is None else SAMPLES_HINT)
+    pre = None
+    # (one wave per SIMD holds a ray's 112 partial sums next to the 112 logits: worth it where rays are long - the dense march, 16 tiles per ray:
+    # 288 -> 260 us per 2.1 M samples; with the ~3 tiles per ray of the voxel march the two-launch form is faster, 375 against 434 us per 2.2 M)
+    if HEAD_FWD_ONCE and n_samples >= HEAD_FWD_ONCE_MIN_PER_RAY * P and C > 192 and P and M and call.out_act == L.ACT_SOFTMAX \
+            and call.out_dtype == torch.bfloat16:
+        pre = (weights_w.detach().contiguous(), alpha.detach().contiguous(),
+               (torch.empty if _one_pack_per_ray(ray_of_pack, N) else torch.zeros)(N, C, device=x1.device))
+        hc = call.composite = L.HeadCompositeArgs()
+        hc.pack_start, hc.ray_of_pack, hc.P = L.ptr(pack_start), L.ptr(ray_of_pack), P
+        hc.weights, hc.alpha, hc.out, hc.n_samples = L.ptr(pre[0]), L.ptr(pre[1]), L.ptr(pre[2]), n_samples
+    probs, st = _mlp_forward(call, (needs_x1, False), x1, None, None, *wb)
+    call.composite = None
+    if st.composited:
+        st.head = None
+        st.hc = (pre[0], pre[1], ridx)
+        return pre[2], st
+    return _head_composite(st, probs, x1.device, C, weights_w, alpha, ridx, pack_start, ray_of_pack, N), st
+
+
+def _head_composite(st, probs, dev, C, weights_w, alpha, ridx, pack_start, ray_of_pack, N):
+    """The per-ray weighted sum of a head whose decoder launch has been issued: of probs [M,C], or (probs None) of the statistics-only form."""
+    P, M = ray_of_pack.shape[0], st.M
+    # both compositing kernels used below write a row for every pack (zeros for an empty one)
+    full = M and _one_pack_per_ray(ray_of_pack, N) and (probs is None or C <= 16)
+    out = (torch.empty if full else torch.zeros)(N, C, device=dev)
+    weights_w = weights_w.detach().contiguous()
+    alpha = alpha.detach().contiguous()
+    if probs is None:
+        # wide softmax head: the forward wrote only the softmax statistics; the per-ray sums are formed from
+        # probabilities rebuilt on the fly (pag_head_composite_fwd) - the [M, C] tensor never exists
+        hidden_last, W_last, b_last, stats = st.head
+        st.head = None
+        if P and M:
+            _call("pag_head_composite_fwd", L.ptr(pack_start), L.ptr(ray_of_pack), P, L.ptr(hidden_last), L.ptr(W_last),
+                  L.ptr(b_last), C, L.ptr(stats), L.ptr(weights_w), L.ptr(alpha), L.ptr(out),
+                  int(M if SAMPLES_HINT is None else SAMPLES_HINT), L.stream())
+    elif P and M:
+        _call("pag_composite_feats_fwd", L.ptr(pack_start), L.ptr(ray_of_pack), P, L.ptr(weights_w), L.ptr(alpha),
+              L.ptr(probs), L.dtype_code(probs), C, L.ptr(out), L.stream())
+    st.hc = (weights_w, alpha, ridx)
+    return out
+
+
+def _head_backward(st, saved, g, **kw):
+    """-> (d x1, _, [dW], [db]): the upstream gradient goes to the decoder in rank-1 form, alpha[ray] * w_m * g[ray] (detached weights, :148-155);
+    the kernel forms the product."""
+    weights_w, alpha, ridx = st.hc
+    return _mlp_backward(st, saved, None, rank1=(g.contiguous().float(), weights_w.contiguous(), ridx.contiguous(), alpha.contiguous().float()), **kw)
+
+
+class _HeadComposite(torch.autograd.Function):
     """decoder (+ softmax) followed by the per-ray weighted sum of tracer :197-205, as ONE autograd node: the
     backward hands the decoder the gradient in rank-1 form (alpha * w_m * d out[ray]) so neither the [M,C] gradient
     nor a separate composite-backward launch exists."""
 
     @staticmethod
-    def forward(ctx, x1, weights_w, alpha, ridx, pack_start, ray_of_pack, N, in_dim, out_act, out_dtype, grouped, *wb):
-        # wide softmax head: where the library can, the decoder's launch forms the per-ray sums itself (pag_mlp_fwd_args.composite) - the output
-        # tensor and the compositing arguments are prepared first and handed to _FusedMLP.forward through the ctx
-        C = wb[len(wb) // 2 - 1].shape[0]
-        M = x1.shape[1] if grouped is not None else x1.shape[0]
-        P = ray_of_pack.shape[0]
-        pre = None
-        # (one wave per SIMD holds a ray's 112 partial sums next to the 112 logits: worth it where rays are long - the dense march, 16 tiles per ray:
-        # 288 -> 260 us per 2.1 M samples; with the ~3 tiles per ray of the voxel march the two-launch form is faster, 375 against 434 us per 2.2 M)
-        long_rays = (M if SAMPLES_HINT is None else SAMPLES_HINT) >= HEAD_FWD_ONCE_MIN_PER_RAY * P
-        if HEAD_FWD_ONCE and long_rays and HEAD_REBUILD and C > 192 and P and M and out_act == L.ACT_SOFTMAX and out_dtype == torch.bfloat16:
-            full = _one_pack_per_ray(ray_of_pack, N)
-            pre = dict(pack_start=pack_start, ray_of_pack=ray_of_pack, weights=weights_w.detach().contiguous(), alpha=alpha.detach().contiguous(),
-                       out=(torch.empty if full else torch.zeros)(N, C, device=x1.device))
-            ctx.fwd_composite = pre
-        probs = _HeadComposite._decode(ctx, x1, in_dim, out_act, out_dtype, grouped, *wb)
-        ctx.fwd_composite = None
-        if pre is not None and getattr(ctx, "composited", False):
-            ctx.fwd_state = None
-            ctx.hc = (pre["weights"], pre["alpha"], ridx)
-            return pre["out"]
-        return _HeadComposite._composite(ctx, probs, x1, weights_w, alpha, ridx, pack_start, ray_of_pack, N, grouped, *wb)
-
-    @staticmethod
-    def _decode(ctx, x1, in_dim, out_act, out_dtype, grouped, *wb):
-        ctx.stats_only = HEAD_REBUILD
-        ctx.rank1_expected = True            # the backward hands the decoder its gradient in rank-1 form (_backward_pair)
-        return _FusedMLP.forward(ctx, x1, None, None, in_dim, out_act, L.MLP_MFMA_BF16, out_dtype, grouped, *wb)
-
-    @staticmethod
-    def _composite(ctx, probs, x1, weights_w, alpha, ridx, pack_start, ray_of_pack, N, grouped, *wb):
-        C = wb[len(wb) // 2 - 1].shape[0]
-        P = ray_of_pack.shape[0]
-        M = x1.shape[1] if grouped is not None else x1.shape[0]
-        # both compositing kernels used below write a row for every pack (zeros for an empty one)
-        full = M and _one_pack_per_ray(ray_of_pack, N) and (probs is None or C <= 16)
-        out = (torch.empty if full else torch.zeros)(N, C, device=x1.device)
-        weights_w = weights_w.detach().contiguous()
-        alpha = alpha.detach().contiguous()
-        if probs is None:
-            # wide softmax head: the forward wrote only the softmax statistics; the per-ray sums are formed from
-            # probabilities rebuilt on the fly (pag_head_composite_fwd) - the [M, C] tensor never exists
-            hidden_last, W_last, b_last, stats = ctx.fwd_state
-            ctx.fwd_state = None
-            if P and M:
-                _call("pag_head_composite_fwd", L.ptr(pack_start), L.ptr(ray_of_pack), P, L.ptr(hidden_last), L.ptr(W_last),
-                      L.ptr(b_last), C, L.ptr(stats), L.ptr(weights_w), L.ptr(alpha), L.ptr(out),
-                      int(M if SAMPLES_HINT is None else SAMPLES_HINT), L.stream())
-        elif P and M:
-            _call("pag_composite_feats_fwd", L.ptr(pack_start), L.ptr(ray_of_pack), P, L.ptr(weights_w), L.ptr(alpha),
-                  L.ptr(probs), L.dtype_code(probs), C, L.ptr(out), L.stream())
-        ctx.hc = (weights_w, alpha, ridx)
+    def forward(ctx, call, x1, weights_w, alpha, ridx, pack_start, ray_of_pack, *wb):
+        out, st = _head_forward(call, ctx.needs_input_grad[1], x1, weights_w, alpha, ridx, pack_start, ray_of_pack, *wb)
+        _save(ctx, st)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        dx1, gwb = _HeadComposite._backward_pair(ctx, g, None)
-        return (dx1, None, None, None, None, None, None, None, None, None, None, *gwb)
-
-    @staticmethod
-    def _backward_pair(ctx, g, dx1_into, wgrad_queue=None, **kw):
-        weights_w, alpha, ridx = ctx.hc
-        # upstream gradient in rank-1 form: alpha[ray] * w_m * g[ray] (detached weights, :148-155); the kernel forms the product
-        grads = _FusedMLP._backward_impl(ctx, None, (g.contiguous().float(), weights_w.contiguous(), ridx.contiguous(), alpha.contiguous()),
-                                         dx1_into, wgrad_queue=wgrad_queue, **kw)
-        return grads[0], grads[8:]
-
-
-class _SubCtx:
-    """Per-head stand-in for the autograd ctx inside _HeadCompositePair."""
-
-    def __init__(self, needs_x1, any_grad):
-        self.needs_input_grad = (needs_x1, False)
-        self.any_grad = any_grad          # does ANY input of the enclosing node (features, weights, biases) need a gradient?
-        self.saved_tensors = ()
-
-    def save_for_backward(self, *tensors):
-        self.saved_tensors = tensors
+        dx1, _, gW, gb = _head_backward(ctx.state, ctx.saved_tensors, g)
+        return (None, dx1, None, None, None, None, None, *gW, *gb)
 
 
 class _HeadCompositePair(torch.autograd.Function):
@@ -1769,48 +1763,45 @@ class _HeadCompositePair(torch.autograd.Function):
     (pag_mlp_bwd_args.dx1_accumulate) instead of autograd summing two [8,M,8] tensors in a separate pass."""
 
     @staticmethod
-    def forward(ctx, x1, weights_w, alpha, ridx, pack_start, ray_of_pack, N, in_dims, out_dtype, grouped, n_a, *wb):
-        any_grad = any(ctx.needs_input_grad)
-        sub_a, sub_b = _SubCtx(ctx.needs_input_grad[0], any_grad), _SubCtx(ctx.needs_input_grad[0], any_grad)
+    def forward(ctx, calls, x1, weights_w, alpha, ridx, pack_start, ray_of_pack, *wb):
+        call_a, call_b, n_a = calls
         part_a, part_b = wb[:n_a], wb[n_a:]
-        # the second (narrow) decoder is prepared first and parked: where the library can, it is evaluated inside the first one's launch
-        # (pag_mlp_fwd_args.pair: the features are read once); its compositing pass follows either way
-        hold = {}
-        sub_b.fwd_hold = hold
-        probs_b = _HeadComposite._decode(sub_b, x1, in_dims[1], L.ACT_SOFTMAX, out_dtype, grouped, *part_b)
-        sub_a.fwd_pair = hold
-        out_a = _HeadComposite.forward(sub_a, x1, weights_w, alpha, ridx, pack_start, ray_of_pack, N, in_dims[0], L.ACT_SOFTMAX, out_dtype,
-                                       grouped, *part_a)
-        if hold.get("args") is not None and not hold.get("taken"):
-            _call("pag_mlp_fwd", ctypes.byref(hold["args"]), hold["M"], L.stream())
-        sub_a.fwd_pair = sub_b.fwd_hold = None
-        out_b = _HeadComposite._composite(sub_b, probs_b, x1, weights_w, alpha, ridx, pack_start, ray_of_pack, N, grouped, *part_b)
-        ctx.subs, ctx.n_a = [sub_a, sub_b], n_a
+        needs_x1 = ctx.needs_input_grad[1]
+        # the second (narrow) decoder is prepared first and parked (call_b.park): where the library can, it is evaluated inside the first one's launch
+        # (call_a.pair -> pag_mlp_fwd_args.pair: the features are read once); its compositing pass follows either way
+        probs_b, st_b = _mlp_forward(call_b, (needs_x1, False), x1, None, None, *part_b)
+        out_a, st_a = _head_forward(call_a, needs_x1, x1, weights_w, alpha, ridx, pack_start, ray_of_pack, *part_a)
+        call_b.park.issue()
+        out_b = _head_composite(st_b, probs_b, x1.device, part_b[len(part_b) // 2 - 1].shape[0], weights_w, alpha, ridx, pack_start, ray_of_pack,
+                                call_b.n_rays)
+        ctx.states = (st_a, st_b)          # the tensors stay in the states: saved tensors would add version-counter checks
         return out_a, out_b
 
     @staticmethod
     def backward(ctx, g_a, g_b):
-        sub_a, sub_b = ctx.subs
+        st_a, st_b = ctx.states
         # wide head first (it writes dx1), the narrow one accumulates.  Where the library can, the narrow head's backward rides in the wide
         # head's call (pag_mlp_bwd_args.pair: one read of the features, one write of the summed gradient): it is prepared first and parked.
         queue = []
-        x1 = sub_a.saved_tensors[0]
-        dx = torch.empty(x1.shape, device=x1.device, dtype=x1.dtype) if sub_a.needs_input_grad[0] else None
-        hold = {}
-        gb = _HeadComposite._backward_pair(sub_b, g_b, dx, queue, hold=hold if dx is not None else None)
-        ga = _HeadComposite._backward_pair(sub_a, g_a, None, queue, dx1_out=dx, pair_hold=hold)
-        if hold.get("args") is not None and not hold.get("taken"):          # not paired after all: the narrow head's own launch, after the wide one
-            _call("pag_mlp_bwd", ctypes.byref(hold["args"]), hold["M"], L.stream())
+        x1 = st_a.saved[0]
+        dx = torch.empty(x1.shape, device=x1.device, dtype=x1.dtype) if st_a.needs[0] else None
+        hold = _Launch("pag_mlp_bwd")
+        _, _, gW_b, gb_b = _head_backward(st_b, st_b.saved, g_b, dx1_into=dx, wgrad_queue=queue, hold=hold if dx is not None else None)
+        dx1, _, gW_a, gb_a = _head_backward(st_a, st_a.saved, g_a, wgrad_queue=queue, dx1_out=dx, pair=hold)
+        hold.issue()                                # not paired after all: the narrow head's own launch, after the wide one
         if queue:                                   # both heads' weight gradients: one narrow + one wide + one finish launch
             _launch_wgrad(queue, queue[0]["dz"].shape[0])
-        return (ga[0], None, None, None, None, None, None, None, None, None, None, *ga[1], *gb[1])
+        return (None, dx1, None, None, None, None, None, *gW_a, *gb_a, *gW_b, *gb_b)
 
 
 def head_composite_pair(x1, heads, w, alpha, ridx, pack_start, ray_of_pack, N, out_dtype=torch.bfloat16, x1_grouped=None):
     """heads = ((weights, biases, in_dim), (weights, biases, in_dim)) -> (out_a, out_b), each as head_composite()."""
     (wa, ba, ia), (wb_, bb, ib) = heads
-    return _apply_decoder(_HeadCompositePair, x1, w, alpha, ridx, pack_start, ray_of_pack, N, (int(ia), int(ib)), out_dtype, x1_grouped,
-                                    len(wa) + len(ba), *wa, *ba, *wb_, *bb)
+    need_grad = _need_grad(x1, w, alpha, ridx, pack_start, ray_of_pack, *wa, *ba, *wb_, *bb)
+    parked = _Launch("pag_mlp_fwd")
+    calls = (_head_call(ia, L.ACT_SOFTMAX, out_dtype, x1_grouped, need_grad, n_rays=N, pair=parked),
+             _head_call(ib, L.ACT_SOFTMAX, out_dtype, x1_grouped, need_grad, n_rays=N, park=parked), len(wa) + len(ba))
+    return _apply(_HeadCompositePair, calls, x1, w, alpha, ridx, pack_start, ray_of_pack, *wa, *ba, *wb_, *bb)
 
 
 def head_composite(x1, weights, biases, w, alpha, ridx, pack_start, ray_of_pack, N, in_dim=None, out_act=L.ACT_NONE,
@@ -1818,8 +1809,8 @@ def head_composite(x1, weights, biases, w, alpha, ridx, pack_start, ray_of_pack,
     """alpha[ray] * sum_i w_i * act(decoder(x1))[i]  ->  f32 [N, out_dim]; ridx i32 [M] = ray of each sample."""
     if in_dim is None:
         in_dim = weights[0].shape[1]
-    return _apply_decoder(_HeadComposite, x1, w, alpha, ridx, pack_start, ray_of_pack, N, int(in_dim), out_act, out_dtype, x1_grouped,
-                                *weights, *biases)
+    call = _head_call(in_dim, out_act, out_dtype, x1_grouped, _need_grad(x1, w, alpha, ridx, pack_start, ray_of_pack, *weights, *biases), n_rays=N)
+    return _apply(_HeadComposite, call, x1, w, alpha, ridx, pack_start, ray_of_pack, *weights, *biases)
 
 
 # --------------------------------------------------------------------------------------- render loss

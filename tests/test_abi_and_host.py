@@ -592,6 +592,57 @@ def test_xcd8_layout_is_the_snake_permutation():
     assert sums == {15}
 
 
+def test_forward_time_fused_backward_decision(lib):
+    """ops._bwd_fusable: the forward's "the backward will be one of the fused kernels" (so the hidden activations need not be written), asked of
+    pag_mlp_bwd_fused_supported on a prospective argument struct - the shipped decoder shapes and the edges of each rule."""
+    from pagnerf_amd import _lib as L, ops
+    bf16, f32, top = torch.bfloat16, torch.float32, L.MLP_FUSED_WIDE_MAX_M
+
+    def density(M=1000, x1_dtype=bf16, needs=(True, False), in_dim=48, out_dim=16, out_dtype=bf16, mode=L.MLP_MFMA_BF16, grouped=(24, 2)):
+        return ops._bwd_fusable(M, x1_dtype, needs, 64, 0, in_dim, 2, out_dim, L.ACT_NONE, out_dtype, mode, grouped)
+
+    def colour(x1_dtype=bf16, needs=(True, False), col0=True):
+        return ops._bwd_fusable(1000, x1_dtype, needs, 16, 32, 43, 3, 3, L.ACT_SIGMOID, f32, L.MLP_MFMA_BF16, None, col0=col0)
+
+    def head(n_layers, out_dim, rank1=True, wide=False):      # wide: the statistics-only 200-way form (statistics allocated, no `out`)
+        return ops._bwd_fusable(1000, bf16, (True, False), 64, 0, 48, n_layers, out_dim, L.ACT_SOFTMAX, bf16, L.MLP_MFMA_BF16, (24, 2), rank1=rank1,
+                                has_stats=wide, stats_only=wide)
+
+    cases = [
+        ("density", density(), True),
+        ("density M = max", density(M=top), True),
+        ("density M = max + 1", density(M=top + 1), False),
+        ("density M = 0", density(M=0), False),
+        ("density f32 output", density(out_dtype=f32), False),
+        ("density out_dim 6", density(out_dim=6), False),
+        ("density x1 needs no gradient", density(needs=(False, False)), False),
+        ("density MLP_FP32", density(mode=L.MLP_FP32), False),
+        ("density grouped (32,2)", density(grouped=(32, 2), in_dim=64), False),
+        ("density grouped (8,8)", density(grouped=(8, 8), in_dim=64), False),
+        ("density grouped (7,8)", density(grouped=(7, 8), in_dim=56), True),
+        ("colour with col0", colour(), True),
+        ("colour with col0, d x2", colour(needs=(True, True)), True),
+        ("colour without col0", colour(col0=False), False),
+        ("colour f32 x1", colour(x1_dtype=f32), False),
+        ("semantic head", head(2, 6), True),
+        ("semantic head, three layers", head(3, 6), True),
+        ("semantic head, dense gradient", head(2, 6, rank1=False), False),
+        ("semantic head, out_dim 12", head(2, 12), False),
+        ("instance head", head(3, 200, wide=True), True),
+        ("instance head, out 224", head(3, 224, wide=True), True),
+        ("instance head, out 192", head(3, 192, wide=True), False),
+        ("instance head, two layers", head(2, 200, wide=True), False),
+    ]
+    for name, got, want in cases:
+        assert got is want, name
+    was = ops.WGRAD_FUSED
+    ops.WGRAD_FUSED = False
+    try:
+        assert density() is False
+    finally:
+        ops.WGRAD_FUSED = was
+
+
 def test_graph_capacity_buckets_are_geometric_with_hysteresis():
     """pagnerf_amd/graphs.py::_State.capacity: every new capacity is a capture (two warm-up steps, a private memory pool), so batch-to-batch
     noise must not move it: geometric buckets (<= 1/32 of a power of two of filler), immediate growth, shrink only after SHRINK_WINDOW

@@ -114,16 +114,16 @@ def test_mlp128_exact_dx1_accumulate(gpu_device):
     want = held + ref.dx1
     assert torch.equal(E.bf16_round(want), want)
     into = E.to_xcd8(held.float(), *p.grouped, 0.0).to(dev)
-    res = ops._FusedMLP128._backward_impl(out.grad_fn, p.go.to(dev).bfloat16(), dx1_into=into)
+    dx1, _, dW, db = ops._mlp128_backward(out.grad_fn.state, out.grad_fn.saved_tensors, p.go.to(dev).bfloat16(), dx1_into=into)
     torch.cuda.synchronize()
-    assert res[0] is into
+    assert dx1 is into
     dx, pad = E.from_xcd8(into, *p.grouped)
     E.assert_bit_equal("dx1_accumulate dx1", dx, want)
     E.assert_bit_equal("dx1_accumulate padding", pad, torch.zeros(pad.shape, dtype=torch.float64))
     n = len(Wg)
     for i in range(n):
-        E.assert_bit_equal("dx1_accumulate dW%d" % i, res[7 + i], ref.dW[i])
-        E.assert_bit_equal("dx1_accumulate db%d" % i, res[7 + n + i], ref.db[i])
+        E.assert_bit_equal("dx1_accumulate dW%d" % i, dW[i], ref.dW[i])
+        E.assert_bit_equal("dx1_accumulate db%d" % i, db[i], ref.db[i])
 
 
 # ------------------------------------------------------------------------------------------------------------------------- (a) 64-wide
@@ -262,13 +262,13 @@ def test_colour_and_density(gpu_device, M):
     tag = "colour_and_density M=%d:" % M
     Wd, bd, x8g, _, _, _ = _leaves(pd, dev)
     Wc, bc, _, x2g, idx, _ = _leaves(pc, dev)
-    hold = ops.decoder_hold(x8g)
+    hold = ops.decoder_hold()
     try:
-        dens = ops.fused_mlp(x8g, Wd, bd, in_dim=48, out_act=L.ACT_NONE, out_dtype=torch.bfloat16, x1_grouped=pd.grouped)
+        dens = ops.fused_mlp(x8g, Wd, bd, in_dim=48, out_act=L.ACT_NONE, out_dtype=torch.bfloat16, x1_grouped=pd.grouped, hold=hold)
         rgb, sigma = ops.colour_and_density(dens, Wc, bc, x2g, idx, 43, out_act=L.ACT_SIGMOID, out_dtype=torch.float32, producer=hold)
     finally:
         ops.flush_hold(hold)
-    assert hold.get("taken")
+    assert hold.taken
     dens.retain_grad()
     g_sig = torch.from_numpy(np.random.RandomState(5).randint(-1, 2, size=M).astype(np.float64))
     ((rgb * pc.go.float().to(dev)).sum() + (sigma * g_sig.float().to(dev)).sum()).backward()

@@ -163,7 +163,7 @@ def test_backward_is_deterministic_and_accumulates_dx1(gpu_device):
     out = ops.fused_mlp128(xg, Wg, b, out_act=act, out_dtype=torch.bfloat16, x1_grouped=grouped)
     held = torch.randn(x8.shape, device=gpu_device).bfloat16() * (runs[0][-1] != 0)          # padding positions stay zero
     into = held.clone()
-    res = ops._FusedMLP128._backward_impl(out.grad_fn, go.bfloat16(), dx1_into=into)
+    res = ops._mlp128_backward(out.grad_fn.state, out.grad_fn.saved_tensors, go.bfloat16(), dx1_into=into)
     assert res[0] is into
     want = held.float() + runs[0][-1].float()
     assert float((into.float() - want).abs().max()) <= float(want.abs().max()) * 2.0 ** -7          # one bf16 rounding of the sum
