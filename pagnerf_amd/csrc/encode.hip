@@ -684,12 +684,12 @@ __global__ __launch_bounds__(tile_samples(KIND == 0 ? 8 : 4), (KIND == 1 ? BIN_W
             }
             if (has_scale) gv[f] *= scale[lc * F + f];
         }
-        {   // per-(tile, level) max |g| (positive floats order like their bit patterns): feeds the fixed-point scale of pass 2
-            float mx = 0.0f;
+        {   // per-(tile, level) max |g| (positive floats order like their bit patterns): feeds the fixed-point scale of pass 2.
+            // The max is taken on the bit patterns from the start: a NaN's pattern lies above infinity's, so a NaN poisons the level
+            // (fmaxf returns its other operand for a NaN and would drop it here - the level would then come back finite).
+            uint32_t mb = 0u;
 #pragma unroll
-            for (int f = 0; f < F; ++f) mx = fmaxf(mx, (live && lv) ? fabsf(gv[f]) : 0.0f);
-            uint32_t mb = __float_as_uint(mx);
-            if (mx != mx) mb = 0x7FC00000u;   // NaN poisons the level
+            for (int f = 0; f < F; ++f) mb = max(mb, (live && lv) ? __float_as_uint(fabsf(gv[f])) : 0u);
             mb = wave_max_to_lane63(mb);
             if (lane == 63 && mb) atomicMax(&cnt[j][NS_MAX + 1], mb);    // LDS, one per wave
         }
