@@ -30,7 +30,6 @@
 
 namespace {
 
-__device__ __forceinline__ int swap23(int a) { return (a & ~12) | ((a & 4) << 1) | ((a & 8) >> 1); }
 struct FwdParams {
     const void *x1;
     const float *x2;
@@ -3529,13 +3528,6 @@ inline unsigned mlp_grid(int64_t M) {
     return (unsigned)(blocks < cap ? (blocks > 0 ? blocks : 1) : cap);
 }
 
-// Kernels that ask for more than 64 KiB of dynamic LDS opt in once per kernel and process (gfx950 has 160 KiB per workgroup)
-template <auto Kernel>
-void raise_lds_limit(int bytes = LDS_MAX_BYTES) {
-    static const hipError_t once = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    (void)once;
-}
-
 // the wide softmax head whose forward writes softmax statistics and the last hidden layer instead of its [M, out_dim] output (mlp_fwd_wide_stats, head_fwd_once_kernel)
 bool is_wide_stats_head(const pag_mlp_fwd_args *a) {
     return a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && a->x1_layout == PAG_LAYOUT_XCD8 && !a->out && a->n_layers == 3 && a->softmax_stats &&
@@ -3581,12 +3573,12 @@ void launch_fwd_fast(const FwdParams &p, int n_layers, bool save, hipStream_t st
 template <bool SAVE0, bool PAIR>
 void launch_fwd_wide_stats(const FwdParams &p, unsigned grid, hipStream_t st) {
     constexpr int NW = wide_fwd_waves(PAIR);
-    raise_lds_limit<mlp_fwd_wide_stats<SAVE0, PAIR>>();
+    raise_lds_limit<mlp_fwd_wide_stats<SAVE0, PAIR>>(LDS_MAX_BYTES);
     hipLaunchKernelGGL((mlp_fwd_wide_stats<SAVE0, PAIR>), dim3(grid), dim3(NW * 64), FwdLds(3, OB_MAX, NW, PAIR).bytes, st, p);
 }
 template <bool PAIR>
 void launch_head_fwd_once(const FwdParams &p, const HeadCompParams &c, unsigned grid, hipStream_t st) {
-    raise_lds_limit<head_fwd_once_kernel<PAIR>>();
+    raise_lds_limit<head_fwd_once_kernel<PAIR>>(LDS_MAX_BYTES);
     hipLaunchKernelGGL((head_fwd_once_kernel<PAIR>), dim3(grid), dim3(256), FwdLds(3, OB_MAX, 4, PAIR, true).bytes, st, p, c);
 }
 
@@ -3615,7 +3607,7 @@ void launch_bwd_f32(const BwdParams &p, int n_layers, hipStream_t st) {
 
 template <int NL, int KIND, bool DXACC, int OBL = 1, int DZ0 = 0>
 void launch_bwd_fused(const BwdParams &p, unsigned grid, hipStream_t st) {
-    raise_lds_limit<mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>>();
+    raise_lds_limit<mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>>(LDS_MAX_BYTES);
     hipLaunchKernelGGL((mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>), dim3(grid), dim3(256), FusedLds(NL, OBL, DZ0).bytes, st, p);
 }
 template <int NL>
@@ -3631,7 +3623,7 @@ void launch_bwd_fused_kind(const BwdParams &p, int kind, bool acc, int dz0, unsi
 // stage A of the fused wide-head backward
 void launch_bwd_wide_blocks(const BwdParams &p, unsigned grid, hipStream_t st) {
     constexpr int OBW = 7;
-    raise_lds_limit<mlp_bwd_wide_blocks<OBW>>();
+    raise_lds_limit<mlp_bwd_wide_blocks<OBW>>(LDS_MAX_BYTES);
     hipLaunchKernelGGL((mlp_bwd_wide_blocks<OBW>), dim3(grid), dim3((OBW + 1) * 64), WideBlocksLds(OBW).bytes, st, p);
 }
 
@@ -3642,7 +3634,7 @@ void launch_bwd_wide_mfma(const BwdParams &p, hipStream_t st) {
     const size_t lds = WideMfmaLds(NL, OB, NW).bytes;
     const int64_t tiles = (p.M + 31) / 32;
     const unsigned grid = (unsigned)std::min<int64_t>((tiles + NW - 1) / NW, 256);      // one workgroup per CU, tiles grid-strided
-    raise_lds_limit<mlp_bwd_wide_mfma<DxT, NL, NW>>();
+    raise_lds_limit<mlp_bwd_wide_mfma<DxT, NL, NW>>(LDS_MAX_BYTES);
     hipLaunchKernelGGL((mlp_bwd_wide_mfma<DxT, NL, NW>), dim3(grid), dim3(NW * 64), lds, st, p);
 }
 
@@ -4081,7 +4073,7 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
         int n_fin = 3;
         if (b) {
             // the companion head runs in the same launch as the layers below the wide head: one read of the input, one write of the summed gradient
-            raise_lds_limit<mlp_bwd_pair>();
+            raise_lds_limit<mlp_bwd_pair>(LDS_MAX_BYTES);
             PairParams pp{pb, ps};
             hipLaunchKernelGGL(mlp_bwd_pair, dim3(grid), dim3(256), PairLds{}.bytes, st, pp);
             PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, layers below the wide head + companion head)");

@@ -1,4 +1,5 @@
-// Shared by the decoder translation units (mlp.hip, mlp_wgrad.hip, mlp_affine.hip, mlp_deep.hip, mlp_h128.hip; nothing else includes it): what more than one of them uses.
+// Shared by the decoder translation units (mlp.hip, mlp_wgrad.hip, mlp_affine.hip directly; mlp_deep.hip and mlp_h128.hip through mlp_native.h, which adds
+// the tile code those two share; nothing else includes it): what more than one of them uses.
 // The transposed-MFMA scheme of the decoders is described at the top of mlp.hip.
 #pragma once
 #include "common.h"
@@ -11,6 +12,8 @@ namespace pagmlp {
 
 constexpr int WG_MAX_BATCH = 6;         // layers per weight-gradient launch (grid.y)
 constexpr int WG_SLAB_COLS = 96;        // floats per weight-gradient slab row: columns 0..63 dW, column 64 db
+constexpr int NUM_CU = 256;             // MI355X: the persistent kernels launch at most one workgroup per CU and grid-stride over their batches
+constexpr int WT = 72;                  // row stride (bf16) of the transposed [column][64 samples] weight-gradient images (mlp_native.h, mlp_h128_lds.h)
 
 struct FinishParams {
     const float *slabs;
@@ -38,6 +41,8 @@ template <typename T>
 __device__ __forceinline__ T *lds_at(unsigned char *smem, int byte_offset) { return reinterpret_cast<T *>(smem) + byte_offset / (int)sizeof(T); }
 
 __device__ __forceinline__ int rho(int q, int h) { return (q & 3) + 8 * (q >> 2) + 4 * h; }
+// bits 2 and 3 exchanged: the input index of every weight image that is multiplied with register fragments (rho's row order against the hardware's k order)
+__host__ __device__ __forceinline__ int swap23(int a) { return (a & ~12) | ((a & 4) << 1) | ((a & 8) >> 1); }
 // staged position (8*g + e) of the XCD8 layout -> column level*F + f of the [M, L*F] feature row, or -1 (padding)
 // (a / d for the wave-uniform divisors of the staging loops: a shift when d is a power of two - the feature width and the pad sizes always
 // are - instead of the ~40-instruction software division; the loops below were bound by those: 25 k of a launch's clocks per workgroup)
@@ -68,5 +73,13 @@ __device__ __forceinline__ bf16x8 zero8() {
     return r;
 }
 
+// Kernels that ask for more than 64 KiB of dynamic LDS opt in once per kernel and process (gfx950 has 160 KiB per workgroup)
+template <auto Kernel>
+void raise_lds_limit(int bytes) {
+    static const hipError_t once = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    (void)once;
+}
+
+inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 }  // namespace

@@ -12,14 +12,11 @@
 //     = 256 FLOP per byte pulled from L2; a workgroup walks its batches one after another (grid = one workgroup per CU).
 //   * the positional encodings are computed in the kernel with the accurate sincosf (arguments reach 512 rad), written to a per-wave LDS scratch and
 //     read back in the B-fragment layout.
-// Training: the forward keeps every Linear's bf16 input ("native" layout below), deep_bwd_kernel runs the data gradients through the chain on the
+// Training: the forward keeps every Linear's bf16 input ("native" layout, mlp_native.h), deep_bwd_kernel runs the data gradients through the chain on the
 // transposed weights and writes every layer's dz (bf16), deep_wgrad_kernel forms dz^T . input per (layer, 128 input columns, slice of the samples)
 // into slabs and deep_wgrad_finish_kernel adds the slices in a fixed order: no atomics, two runs give the same bits.
-//
-// Native layout of a saved [samples x width] bf16 plane: per 32-sample tile and 32-column block, the 8-byte chunk (g, lane) holds columns
-// 32 blk + 8 g + 4 (lane >> 5) + 0..3 of sample (lane & 31) - exactly registers 4g .. 4g+3 of the accumulator block, so stores and the backward's
-// loads are whole 512-B wave transactions.
-#include "mlp_common.h"
+// The tile helpers (mm, init_bias, pack_frags, mask_frags, store_native, stage_transposed) are mlp_native.h's, shared with mlp_h128.hip.
+#include "mlp_native.h"
 
 namespace {
 
@@ -27,7 +24,6 @@ constexpr int DH = 256, DHH = 128;
 constexpr int S256 = 264, S128 = 136, S64 = 72, S16 = 24;      // LDS row strides (bf16 elements): width + 16 B
 constexpr int DEEP_WG = 512;
 constexpr int MAX_SPLIT = 32;
-constexpr int NUM_CU = 256;             // MI355X: the persistent kernels launch at most one workgroup per CU and grid-stride over their batches
 
 // forward image (bytes)
 constexpr int SZ_L0 = DH * S64 * 2 + DH * 4;
@@ -57,8 +53,6 @@ __host__ __device__ constexpr int sv_h(int l) { return 128 + l * DH; }          
 // dz planes: dz0 .. dz8, semantic hidden, colour hidden, semantic out (32), colour out (32), density (32)
 constexpr int DZ_S1 = 9 * DH, DZ_C1 = DZ_S1 + DHH, DZ_S2 = DZ_C1 + DHH, DZ_C2 = DZ_S2 + 32, DZ_D = DZ_C2 + 32, DZ_TOTAL = DZ_D + 32;
 
-__device__ __host__ __forceinline__ int swap23d(int a) { return (a & ~12) | ((a & 4) << 1) | ((a & 8) >> 1); }
-
 // ------------------------------------------------------------------------------------------------------------------------- weight images
 struct PackJob {
     int64_t dst;
@@ -81,7 +75,7 @@ __global__ void deep_pack_kernel(PackJobs jobs, char *blob) {
     bf16_t *d = reinterpret_cast<bf16_t *>(blob + J.dst);
     const int total = J.rows_pad * J.stride;
     for (int e = (int)(blockIdx.x * blockDim.x + threadIdx.x); e < total; e += step) {
-        const int row = e / J.stride, k = swap23d(e - row * J.stride);
+        const int row = e / J.stride, k = swap23(e - row * J.stride);
         float v = 0.0f;
         if (J.mode == 0) {
             if (row < J.n_out && k < J.ncols) v = J.W[(int64_t)row * J.ld + J.col0 + k];
@@ -96,79 +90,6 @@ __global__ void deep_pack_kernel(PackJobs jobs, char *blob) {
 __device__ __forceinline__ void stage(char *lds, const char *src, int bytes) {
 #pragma unroll 4
     for (int o = (int)threadIdx.x * 16; o < bytes; o += DEEP_WG * 16) *reinterpret_cast<uint4 *>(lds + o) = *reinterpret_cast<const uint4 *>(src + o);
-}
-
-// acc[blk] += W[32 blk .. 32 blk + 31][16 s ..] . b[s]: A fragments from the staged image (row stride `stride`), B fragments from registers
-template <int NB, int KS>
-__device__ __forceinline__ void mm(f32x16 (&acc)[NB], const bf16x8 *b, const bf16_t *w, int stride, int lane) {
-    const bf16_t *base = w + (lane & 31) * stride + 8 * (lane >> 5);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-#pragma unroll
-        for (int blk = 0; blk < NB; ++blk) {
-            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(base + blk * 32 * stride + 16 * s);
-            acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[s], acc[blk], 0, 0, 0);
-        }
-    }
-}
-
-template <int NB>
-__device__ __forceinline__ void init_bias(f32x16 (&acc)[NB], const float *bias, int h) {
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[blk][q] = bias[32 * blk + rho(q, h)];
-}
-
-template <int NB>
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NB]) {
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[blk][q] = 0.0f;
-}
-
-// accumulator blocks -> the next product's B fragments (2 per block), optionally through ReLU
-template <int NB>
-__device__ __forceinline__ void pack_frags(const f32x16 (&acc)[NB], bf16x8 *out, bool relu) {
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float v = acc[blk][8 * s + j];
-                out[2 * blk + s][j] = (bf16_t)(relu ? fmaxf(v, 0.0f) : v);
-            }
-}
-
-// backward: dz = acc where the saved activation is positive (native plane), rounded to bf16
-template <int NB>
-__device__ __forceinline__ void mask_frags(const f32x16 (&acc)[NB], const bf16_t *plane, int64_t tile, int lane, bf16x8 *out) {
-    const bf16x4 *p = reinterpret_cast<const bf16x4 *>(plane) + tile * (NB * 256) + lane;
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const bf16x4 a = p[(blk * 4 + g) * 64];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) out[2 * blk + (g >> 1)][4 * (g & 1) + i] = (bf16_t)((float)a[i] > 0.0f ? acc[blk][4 * g + i] : 0.0f);
-        }
-}
-
-template <int NB>
-__device__ __forceinline__ void store_native(bf16_t *plane, int64_t tile, int lane, const bf16x8 *f) {
-    bf16x4 *p = reinterpret_cast<bf16x4 *>(plane) + tile * (NB * 256) + lane;
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const bf16x8 v = f[2 * blk + (g >> 1)];
-            bf16x4 c;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) c[i] = v[4 * (g & 1) + i];
-            p[(blk * 4 + g) * 64] = c;
-        }
 }
 
 // PE10 of one sample (x, sin(x 2^k) frequency-major, cos(x 2^k)) into the wave's scratch row; lane half h takes the
@@ -413,25 +334,6 @@ constexpr int MAX_UNITS = 32;
 struct WgUnits {
     WgUnit u[MAX_UNITS];
 };
-constexpr int WT = 72;      // row stride of the transposed [column][64 samples] images
-
-// dst[(column) * WT + sample] from `nblk_take` column blocks (first: blk0) of a native plane with nblk_plane blocks, for the two tiles 2 p, 2 p + 1
-__device__ __forceinline__ void stage_transposed(bf16_t *dst, const bf16_t *plane, int nblk_plane, int blk0, int nblk_take, int64_t pair, int64_t ntile) {
-    const int n = nblk_take * 256;
-    for (int idx = threadIdx.x; idx < 2 * n; idx += DEEP_WG) {
-        const int sub = idx >= n, c = idx - sub * n;
-        const int64_t t = 2 * pair + sub;
-        bf16x4 v;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = (bf16_t)0.0f;
-        if (t < ntile) v = reinterpret_cast<const bf16x4 *>(plane)[(t * nblk_plane + blk0) * 256 + c];
-        const int ln = c & 63, g = (c >> 6) & 3, blk = c >> 8;
-        bf16_t *d = dst + (32 * blk + 8 * g + 4 * (ln >> 5)) * WT + sub * 32 + (ln & 31);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) d[i * WT] = v[i];
-    }
-}
-
 __global__ __launch_bounds__(DEEP_WG) void deep_wgrad_kernel(WgUnits U, int64_t ntile, int n_split) {
     __shared__ __attribute__((aligned(16))) bf16_t zT[DH * WT];
     __shared__ __attribute__((aligned(16))) bf16_t aT[128 * WT];
@@ -445,8 +347,8 @@ __global__ __launch_bounds__(DEEP_WG) void deep_wgrad_kernel(WgUnits U, int64_t 
     float bsum = 0.0f;
     for (int64_t p = p0; p < p1; ++p) {
         __syncthreads();
-        stage_transposed(zT, u.dz, u.dz_nblk, 0, u.dz_nblk, p, ntile);
-        stage_transposed(aT, u.a, u.a_nblk, u.a_blk0, u.n_cb, p, ntile);
+        stage_transposed<DEEP_WG>(zT, u.dz, u.dz_nblk, 0, u.dz_nblk, p, ntile);
+        stage_transposed<DEEP_WG>(aT, u.a, u.a_nblk, u.a_blk0, u.n_cb, p, ntile);
         __syncthreads();
         if (wave < u.dz_nblk) {
 #pragma unroll
@@ -500,7 +402,6 @@ __global__ void deep_wgrad_finish_kernel(WgUnits U, int n_split) {
 }
 
 // -------------------------------------------------------------------------------------------------------------------------------- host
-int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 int64_t tiles_padded(int64_t M) { return (M + 255) / 256 * 8; }
 int split_of(int64_t M) {
     const int64_t npair = ((M + 31) / 32 + 1) / 2;

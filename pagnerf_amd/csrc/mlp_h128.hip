@@ -12,15 +12,12 @@
 //     staging (they come from L2): no packed copy, so an inference forward needs no workspace at all.
 //   * the layer-0 input (XCD8 bf16 [8][M][8], strided [M,k1] bf16 / f32, optionally followed by per-ray f32 rows x2[x2_index[m]]) is read straight into
 //     B fragments: a fragment half is 4 consecutive input positions = one 8-byte (bf16) or 16-byte (f32) load.
-// Training: the forward keeps the layer-0 input and every hidden layer's post-ReLU output (bf16, "native" layout below); h128_bwd_kernel runs the data
+// Training: the forward keeps the layer-0 input and every hidden layer's post-ReLU output (bf16, "native" layout, mlp_native.h); h128_bwd_kernel runs the data
 // gradients through the chain on the transposed weights, writes every layer's dz (bf16) and d x1 in the input's form; h128_wgrad_kernel forms
 // dz^T . input per (layer, slice of the samples) into slabs and h128_wgrad_finish_kernel adds the slices in a fixed order: no atomics, two runs give the
 // same bits.  Every sample offset is 64-bit.
-//
-// Native layout of a [samples x width] bf16 plane (as mlp_deep.hip): per 32-sample tile and 32-column block, the 8-byte chunk (g, lane) holds columns
-// 32 blk + 8 g + 4 (lane >> 5) + 0..3 of sample (lane & 31) - registers 4g .. 4g+3 of the accumulator block, so stores and the backward's loads are whole
-// 512-B wave transactions.
-#include "mlp_common.h"
+// The tile helpers (mm, init_bias, pack_frags, mask_frags, store_native, stage_transposed) are mlp_native.h's, shared with mlp_deep.hip.
+#include "mlp_native.h"
 #include "mlp_h128_lds.h"
 
 namespace {
@@ -28,15 +25,12 @@ using namespace pagmlp128;
 
 constexpr int H128_WG = 512;
 constexpr int H128_BATCH = 256;         // samples per workgroup batch
-constexpr int NUM_CU = 256;             // MI355X: the persistent kernels launch at most one workgroup per CU and grid-stride over their batches
 constexpr float LOG2E = 1.44269504088896340736f;
 // sample slices of a weight-gradient unit (2 - 4 units per launch: 256 - 512 workgroups).  A constant: which tile pairs a slice adds, and in which order
 // the slices are added, must not depend on M (h128_wgrad_kernel)
 constexpr int N_SPLIT = 128;
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int swap23(int a) { return (a & ~12) | ((a & 4) << 1) | ((a & 8) >> 1); }
 
 // how the layer-0 input is addressed (forward: x1 / x2; backward: dx1)
 struct InForm {
@@ -78,91 +72,10 @@ __device__ __forceinline__ void stage_bias(float *dst, const float *b, int rows_
 }
 
 // ------------------------------------------------------------------------------------------------------------------------- shared pieces
-// acc[blk] += W[32 blk .. 32 blk + 31][16 s ..] . b[s]: A fragments from the staged image (row stride `stride`), B fragments from registers
-// FENCE: the scheduler keeps each k step's loads with its MFMAs (the 7-block output layer: all 56 fragments ahead of their use do not fit the registers)
-template <int NB, int KS, bool FENCE = false>
-__device__ __forceinline__ void mm(f32x16 (&acc)[NB], const bf16x8 *b, const bf16_t *w, int stride, int lane) {
-    const bf16_t *base = w + (lane & 31) * stride + 8 * (lane >> 5);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-#pragma unroll
-        for (int blk = 0; blk < NB; ++blk) {
-            const bf16x8 a = *reinterpret_cast<const bf16x8 *>(base + blk * 32 * stride + 16 * s);
-            acc[blk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[s], acc[blk], 0, 0, 0);
-        }
-        if (FENCE) __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-template <int NB>
-__device__ __forceinline__ void init_bias(f32x16 (&acc)[NB], const float *bias, int h) {
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[blk][q] = bias[32 * blk + rho(q, h)];
-}
-
-template <int NB>
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NB]) {
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[blk][q] = 0.0f;
-}
-
-// accumulator blocks -> the next product's B fragments (2 per block), optionally through ReLU
-template <int NB>
-__device__ __forceinline__ void pack_frags(const f32x16 (&acc)[NB], bf16x8 *out, bool relu) {
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float v = acc[blk][8 * s + j];
-                out[2 * blk + s][j] = (bf16_t)(relu ? fmaxf(v, 0.0f) : v);
-            }
-}
-
-// backward: dz = acc where the saved activation is positive (native plane), rounded to bf16
-template <int NB>
-__device__ __forceinline__ void mask_frags(const f32x16 (&acc)[NB], const bf16_t *plane, int64_t tile, int lane, bf16x8 *out) {
-    const bf16x4 *p = reinterpret_cast<const bf16x4 *>(plane) + tile * (NB * 256) + lane;
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const bf16x4 a = p[(blk * 4 + g) * 64];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) out[2 * blk + (g >> 1)][4 * (g & 1) + i] = (bf16_t)((float)a[i] > 0.0f ? acc[blk][4 * g + i] : 0.0f);
-        }
-}
-
-template <int NB>
-__device__ __forceinline__ void store_native(bf16_t *plane, int64_t tile, int lane, const bf16x8 *f) {
-    bf16x4 *p = reinterpret_cast<bf16x4 *>(plane) + tile * (NB * 256) + lane;
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const bf16x8 v = f[2 * blk + (g >> 1)];
-            bf16x4 c;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) c[i] = v[4 * (g & 1) + i];
-            p[(blk * 4 + g) * 64] = c;
-        }
-}
-
 __device__ __forceinline__ bf16x4 cvt4(const f32x4 v) {
     bf16x4 r;
 #pragma unroll
     for (int i = 0; i < 4; ++i) r[i] = (bf16_t)v[i];
-    return r;
-}
-__device__ __forceinline__ bf16x4 zero4() {
-    bf16x4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = (bf16_t)0.0f;
     return r;
 }
 // the other half-wave's value (rows 4h .. of every 8 are on lane r + 32 h)
@@ -468,21 +381,6 @@ struct WgUnits {
     InForm in;
 };
 
-// dst[(column) * WT + sample] from the nblk column blocks of a native plane, for the two tiles 2 p, 2 p + 1
-__device__ __forceinline__ void stage_transposed(bf16_t *dst, const bf16_t *plane, int nblk, int64_t pair, int64_t ntile) {
-    const int n = nblk * 256;
-    for (int idx = threadIdx.x; idx < 2 * n; idx += H128_WG) {
-        const int sub = idx >= n, c = idx - sub * n;
-        const int64_t t = 2 * pair + sub;
-        bf16x4 v = zero4();
-        if (t < ntile) v = reinterpret_cast<const bf16x4 *>(plane)[t * nblk * 256 + c];
-        const int ln = c & 63, g = (c >> 6) & 3, blk = c >> 8;
-        bf16_t *d = dst + (32 * blk + 8 * g + 4 * (ln >> 5)) * WT + sub * 32 + (ln & 31);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) d[i * WT] = v[i];
-    }
-}
-
 // slab [n_split][rows_pad][128] f32 partial dW, then [n_split][rows_pad] partial db; workgroup (x, y) = slice x of the samples of unit y
 __global__ __launch_bounds__(H128_WG) void h128_wgrad_kernel(WgUnits U, int64_t ntile, int n_split) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -499,8 +397,8 @@ __global__ __launch_bounds__(H128_WG) void h128_wgrad_kernel(WgUnits U, int64_t 
     float bsum = 0.0f;
     for (int64_t p = blockIdx.x; p < npair; p += n_split) {
         __syncthreads();
-        stage_transposed(zT, u.dz, u.dz_nblk, p, ntile);
-        stage_transposed(aT, u.a, u.a_nblk, p, ntile);
+        stage_transposed<H128_WG>(zT, u.dz, u.dz_nblk, 0, u.dz_nblk, p, ntile);
+        stage_transposed<H128_WG>(aT, u.a, u.a_nblk, 0, u.a_nblk, p, ntile);
         __syncthreads();
         if (wave < u.dz_nblk) {
 #pragma unroll
@@ -556,14 +454,12 @@ __global__ void h128_wgrad_finish_kernel(WgUnits U, int n_split) {
 }
 
 // -------------------------------------------------------------------------------------------------------------------------------- host
-int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 int64_t tiles_padded(int64_t M) { return (M + H128_BATCH - 1) / H128_BATCH * 8; }
 // 32-row blocks the kernels are built for: 1, 4 or 7
 int out_blocks(int out_dim) { return out_dim <= 32 ? 1 : out_dim <= 128 ? 4 : OB_MAX; }
 int64_t slab_floats(int n_hidden, int ob, int n_split) { return (int64_t)n_split * (n_hidden * WH + ob * 32) * 129; }
 int64_t save_bytes(int64_t M, int n_hidden) { return align256(tiles_padded(M) * 32 * sv_h(n_hidden) * 2); }
 int64_t dz_bytes(int64_t M, int n_hidden, int ob) { return align256(tiles_padded(M) * 32 * (dz_col(n_hidden) + ob * 32) * 2); }
-
 
 int check_shape(const char *name, int n_hidden, int hidden, int in_dim, int out_dim, int64_t M) {
     PAG_CHECK_ARG(M >= 0 && M <= PAG_MLP128_MAX_M, "%s: M %lld outside [0, %lld]", name, (long long)M, (long long)PAG_MLP128_MAX_M);
@@ -593,8 +489,7 @@ int check_form(const char *name, int layout, int dtype, int k1, int levels, int 
 template <int NBO, int ACT>
 void launch_fwd_act(const FwdParams &P, hipStream_t st) {
     const int lds = FwdLds(P.n_hidden, NBO).bytes;
-    static const hipError_t once = hipFuncSetAttribute((const void *)h128_fwd_kernel<NBO, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BYTES);
-    (void)once;
+    raise_lds_limit<h128_fwd_kernel<NBO, ACT>>(LDS_MAX_BYTES);
     hipLaunchKernelGGL((h128_fwd_kernel<NBO, ACT>), dim3((unsigned)std::min<int64_t>(P.ntile / 8, NUM_CU)), dim3(H128_WG), lds, st, P);
 }
 template <int NBO>
@@ -608,8 +503,7 @@ void launch_fwd(const FwdParams &P, hipStream_t st) {
 template <int NBO>
 void launch_bwd(const BwdParams &P, hipStream_t st) {
     const int lds = BwdLds(P.n_hidden, NBO).bytes;
-    static const hipError_t once = hipFuncSetAttribute((const void *)h128_bwd_kernel<NBO>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BYTES);
-    (void)once;
+    raise_lds_limit<h128_bwd_kernel<NBO>>(LDS_MAX_BYTES);
     hipLaunchKernelGGL(h128_bwd_kernel<NBO>, dim3((unsigned)std::min<int64_t>(P.ntile / 8, NUM_CU)), dim3(H128_WG), lds, st, P);
 }
 

@@ -1,6 +1,7 @@
 // Dynamic-LDS layouts of the 128-wide decoder kernels in mlp_h128.hip (nothing else includes this), in the idiom of mlp_lds.h: ONE description per
 // kernel serves the carve-up inside the kernel (lds_at<T>(smem, L.region)) and the byte count its launcher asks for (L.bytes).
-// Constants and constexpr code only.  Every member is an offset in BYTES from the start of the dynamic segment.
+// Constants and constexpr code only; WT is mlp_common.h's (pagmlp), which mlp_h128.hip includes first.  Every member is an offset in BYTES from the
+// start of the dynamic segment.
 #pragma once
 
 namespace pagmlp128 {
@@ -11,7 +12,7 @@ constexpr int K0 = 64;                          // layer-0 input positions (in_d
 constexpr int S128 = 136, S64 = 72;             // LDS row strides (bf16 elements): width + 16 B, an odd number of 16-B granules (ds_read_b128 conflict-free)
 constexpr int MAX_HIDDEN = 3;                   // Linear + ReLU layers
 constexpr int OB_MAX = 7;                       // 32-row blocks of the widest output layer (out_dim <= 224)
-constexpr int WT = 72;                          // row stride of the weight-gradient kernel's transposed [column][64 samples] images
+using pagmlp::WT;                               // mlp_common.h, included first: row stride of the weight-gradient kernel's transposed images
 
 // h128_fwd_kernel: every layer's image is resident for the whole launch.  W0 [128][S64], W1 / W2 [128][S128] (n_hidden - 1 of them), WL [ob*32][S128],
 // all with the input index permuted (swap23); then the f32 biases b0 .. b(n_hidden-1) [128] each and bL [ob*32]

@@ -2,8 +2,8 @@
 """Per-kernel digest of the gfx950 device code of sources under pagnerf_amd/csrc (no GPU needed): what a refactor that must not change
 a kernel is checked with.
 
-    python scripts/kernel_digest.py mlp_fwd.hip mlp_bwd.hip > after.txt
-    python scripts/kernel_digest.py --csrc OTHER_TREE/pagnerf_amd/csrc --like mlp_fwd.hip decoders.hip > before.txt
+    python scripts/kernel_digest.py mlp_deep.hip mlp_h128.hip > after.txt
+    python scripts/kernel_digest.py --csrc OTHER_TREE/pagnerf_amd/csrc mlp_deep.hip mlp_h128.hip > before.txt
     diff before.txt after.txt
 
 Each source is compiled with build.py's flags for it plus --offload-device-only; one line per FUNC symbol of the gfx950 code object:
