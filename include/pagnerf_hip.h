@@ -764,6 +764,39 @@ int pag_map_select(const float *points_in, int64_t n, const float *value, float 
                    int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Panoptic surface-mesh export: surface nets on the density lattice (csrc/mesh.hip; beyond the reference, which exports points only).  Additive to
+ * ABI 14.  field f32 [nx, ny, nz] (z fastest, device): a lattice point is INSIDE when v >= iso (a NaN is outside), a cell (i, j, k) with the corners
+ * (i + bx, j + by, k + bz) ACTIVE when its 8 corners are finite and neither all inside nor all outside.  Every active cell owns one vertex, every
+ * lattice edge whose ends differ in `inside` and whose four cells own a vertex one quad.  Both calls are ordered appends with the contract of the
+ * map export above: kept rows land in row order behind *count (i64 [1], device), a slot at or past the capacity is counted and not written, three
+ * launches, no host synchronisation, no atomics; the order of vertices and faces does not depend on the launch geometry.  Every axis needs 2 points;
+ * fewer than 2^31 cells (vertex ids are i32) and fewer than 2^32 / 3 points (one thread per edge row).
+ * ------------------------------------------------------------------------------------------ */
+
+/* Workspace of either call on an nx x ny x nz lattice (0 for a lattice the calls refuse); about points / 21 bytes. */
+int64_t pag_mesh_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+
+/* A row is a cell in linear order (x slowest).  The vertex of an active cell, all in fp32 and in this order: over the 12 cell edges taken axis-major
+ * (axis a = 0, 1, 2; the two other axes in increasing order with bits (bu, bv) = 00, 01, 10, 11, the lower axis's bit slower; the edge runs from
+ * corner A with bit 0 on axis a to corner B with bit 1) every edge whose ends differ in `inside` adds the point p = A's bits with
+ * p[a] = (iso - vA) / (vB - vA) to S and 1 to n;  local = S / n;  vertex = ((float)(index0 + cell index) + local) * h + lo per axis (two roundings after
+ * the add).  Normal: g[a] = the chain sum of (vB - vA) over the axis's four edges, m = sqrt((g0 g0 + g1 g1) + g2 g2), normal = -g / m, 0 when
+ * m == 0 (towards falling density).  lo_host f32 [3], index0_host i32 [3] (the global index of field[0,0,0], >= 0) are host arrays.
+ * -> vertices, normals f32 [cap, 3]; cell_vertex i32 [(nx-1)(ny-1)(nz-1)] receives EVERY cell's slot (the vertex id when *count was 0), -1 for a
+ * cell without vertex, also for slots at or past cap. */
+int pag_mesh_vertices(const float *field, int64_t nx, int64_t ny, int64_t nz, float iso, const float *lo_host, float h, const int32_t *index0_host,
+                      float *vertices, float *normals, int64_t cap, int32_t *cell_vertex, int64_t *count, void *workspace, int64_t workspace_bytes,
+                      void *stream);
+
+/* A row is r = ((i ny + j) nz + k) 3 + a: the lattice edge from P = (i, j, k) to P + e_a (no edge when P[a] + 1 leaves the lattice).  It gives a quad
+ * when its ends differ in `inside` and the four cells at P with the offsets (du, dv) = (-1,-1), (0,-1), (0,0), (-1,0) on the axes u = (a + 1) % 3,
+ * v = (a + 2) % 3 exist and have a vertex in cell_vertex (as pag_mesh_vertices wrote it): q0..q3, reversed when P is outside.  The s-th kept row
+ * writes the triangles (q0, q1, q2), (q0, q2, q3) to rows 2s, 2s + 1 of faces i32 [cap, 3]; *count counts QUADS, and a quad whose two rows do not
+ * both fit below cap is counted and not written.  Face normals point from inside to outside. */
+int pag_mesh_faces(const float *field, int64_t nx, int64_t ny, int64_t nz, float iso, const int32_t *cell_vertex, int32_t *faces, int64_t cap,
+                   int64_t *count, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused panoptic voxel map: the exported points of all views reduced to one row per occupied voxel, and the per-instance table of that map
  * (csrc/voxelmap.hip).  Additive to ABI 14.  The two reductions are ordered appends behind a device counter with the contract of the map export
  * above: kept runs land in row order behind *count (i64 [1], device), a slot at or past `cap` is counted and not written, three launches, no host

@@ -26,6 +26,8 @@
             map split into connected components of equal-id voxels (floaters dropped, reused ids told apart)
             overlap_table, associate_maps, relabel_map, merge_maps, merge_map_sequence and their *_reference definitions (map_export.py): the ids of
             two windows' fused maps matched by voxel overlap and the maps merged (`python -m pagnerf_amd.map_export merge`)
+            surface_nets, surface_nets_reference, density_lattice, extract_mesh, save_mesh, load_mesh, mesh_report (mesh.py): the labelled,
+            coloured triangle mesh of the trained field (surface nets on the density lattice, csrc/mesh.hip); no counterpart in the reference
     regularizers: tv_loss, tv_l1_loss, tv_l2_loss, grid_tv_loss, grid_tv_l1_loss, grid_tv_l2_loss, step_tv_terms (regularizers.py)
              <- loss/regularizers.py:41-70, pc_nerf/trainer.py:556-574 (the grid total-variation terms)
     dataset: DeviceMultiviewDataset, BatchSampler, SampleRays, sample_indices, epoch_views (dataset.py)
@@ -63,6 +65,8 @@ from .map_export import (MapAccumulator, generate_pc_map, generate_pc_map_from_v
                          clean_map, clean_map_reference, component_table, connected_components, connected_components_reference,
                          associate_maps, associate_maps_reference, merge_map_sequence, merge_map_sequence_reference, merge_maps,
                          merge_maps_reference, overlap_table, overlap_table_reference, relabel_map)
+from .mesh import (density_lattice, extract_mesh, load_mesh, mesh_report, save_mesh, surface_nets,    # noqa: F401
+                   surface_nets_reference)
 from .regularizers import (grid_tv_l1_loss, grid_tv_l2_loss, grid_tv_loss, step_tv_terms, tv_l1_loss, tv_l2_loss,    # noqa: F401
                            tv_loss)
 from .dataset import BatchSampler, DeviceMultiviewDataset, SampleRays, epoch_views, sample_indices    # noqa: F401

@@ -246,6 +246,9 @@ _SIGS = {
     "pag_map_points": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp,
                                c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "pag_map_select": (c_i32, [c_vp, c_i64, c_vp, c_f32, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "pag_mesh_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "pag_mesh_vertices": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_f32, c_fp, c_f32, c_ip, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "pag_mesh_faces": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_f32, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "pag_voxel_workspace_bytes": (c_i64, [c_i64]),
     "pag_voxel_keys": (c_i32, [c_vp, c_i64, c_fp, c_f32, c_fp, c_vp, c_vp]),
     "pag_voxel_fuse": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),

@@ -41,6 +41,7 @@ SOURCES = {
     "cluster.hip": ["-ffp-contract=off"],    # mean-shift clustering: the fp64 distances and sums in the written op order
     "panoptic.hip": ["-ffp-contract=off"],   # panoptic evaluation: the f32 IoU quotients and fp64 distances in the written op order
     "map.hip": ["-ffp-contract=off"],        # map export: the unprojection in pose.hip's op order
+    "mesh.hip": ["-ffp-contract=off"],       # surface-mesh export: the vertex and the normal in the definition's op order (mesh.py)
     "voxelmap.hip": ["-ffp-contract=off"],   # voxel map fusion: the key's subtract / divide / floor and the means' one division as written
     "vm.hip": ["-ffp-contract=off"],         # TensoRF vector-matrix grid: grid_sample's bilinear op order
     "triplanar.hip": ["-ffp-contract=off"],  # tri-plane grid: grid_sample's bilinear / reflection op order

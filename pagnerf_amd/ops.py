@@ -1977,6 +1977,49 @@ def map_select(points_in, points, count, value=None, threshold=0.0, inst=None, i
           ids_out.data_ptr() if ids_out is not None else None, points.shape[0], count.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
 
 
+# ------------------------------------------------------------------------------------------- surface-mesh export (csrc/mesh.hip)
+def _mesh_lattice(name, field, cell_vertex):
+    """-> (nx, ny, nz, workspace) of the lattice `field` f32 [nx,ny,nz] with its cell table i32 [(nx-1)(ny-1)(nz-1)]; refuses what the library refuses."""
+    if field.dim() != 3 or field.dtype != torch.float32 or not field.is_contiguous():
+        raise RuntimeError("%s: field must be f32 [nx,ny,nz], contiguous, got %s %s" % (name, field.dtype, tuple(field.shape)))
+    nx, ny, nz = (int(s) for s in field.shape)
+    need = int(L.load().pag_mesh_workspace_bytes(nx, ny, nz))
+    if need == 0:
+        raise RuntimeError("%s: lattice %d x %d x %d: every axis needs 2 points, fewer than 2^31 cells and 2^32 / 3 points" % (name, nx, ny, nz))
+    cells = (nx - 1) * (ny - 1) * (nz - 1)
+    if cell_vertex.dtype != torch.int32 or cell_vertex.numel() != cells or not cell_vertex.is_contiguous():
+        raise RuntimeError("%s: cell_vertex must be int32 with the lattice's %d cells, contiguous" % (name, cells))
+    return nx, ny, nz, torch.empty(need, dtype=torch.uint8, device=field.device)
+
+
+def mesh_vertices(field, iso, lo, h, index0, vertices, normals, cell_vertex, count):
+    """Surface nets, the vertices: the active cells of field f32 [nx,ny,nz] in cell order -> their vertex and normal appended to vertices / normals
+    f32 [cap,3] (None, None: count only) behind the device counter `count` i64 [1], and every cell's slot (-1: no vertex) in cell_vertex i32
+    [nx-1,ny-1,nz-1] (pag_mesh_vertices; lo three floats, h a float, index0 three ints are host values; no host synchronisation)."""
+    _check_gpu(field, vertices, normals, cell_vertex, count)
+    nx, ny, nz, ws = _mesh_lattice("mesh_vertices", field, cell_vertex)
+    cap = 0 if vertices is None else vertices.shape[0]
+    if count.dtype != torch.int64 or (vertices is None) != (normals is None) or (vertices is not None and _bad_columns(
+            [(vertices, torch.float32, (cap, 3)), (normals, torch.float32, (cap, 3))])):
+        raise RuntimeError("mesh_vertices: vertices / normals f32 [cap,3], contiguous; count int64 [1]")
+    lo3, idx3 = (ctypes.c_float * 3)(*[float(v) for v in lo]), (ctypes.c_int * 3)(*[int(v) for v in index0])
+    _call("pag_mesh_vertices", field.data_ptr(), nx, ny, nz, float(iso), lo3, float(h), idx3, _ptr(vertices), _ptr(normals), cap, cell_vertex.data_ptr(),
+          count.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
+
+
+def mesh_faces(field, iso, cell_vertex, faces, count):
+    """Surface nets, the faces: the sign-changing lattice edges of `field` whose four cells have a vertex in cell_vertex (as mesh_vertices wrote it),
+    in edge-row order -> two triangles each, appended to faces i32 [cap,3] (None: count only) behind the device counter `count` i64 [1], which counts
+    quads (pag_mesh_faces; no host synchronisation)."""
+    _check_gpu(field, cell_vertex, faces, count)
+    nx, ny, nz, ws = _mesh_lattice("mesh_faces", field, cell_vertex)
+    cap = 0 if faces is None else faces.shape[0]
+    if count.dtype != torch.int64 or (faces is not None and _bad_columns([(faces, torch.int32, (cap, 3))])):
+        raise RuntimeError("mesh_faces: faces int32 [cap,3], contiguous; count int64 [1]")
+    _call("pag_mesh_faces", field.data_ptr(), nx, ny, nz, float(iso), cell_vertex.data_ptr(), _ptr(faces), cap, count.data_ptr(), ws.data_ptr(), ws.numel(),
+          L.stream())
+
+
 # ------------------------------------------------------------------------------------------- voxel map fusion (csrc/voxelmap.hip)
 def voxel_keys(points, origin, voxel_size, limits=None):
     """points f32 [n,3] -> keys i64 [n]: iz | iy << 21 | ix << 42 with i = floor((p - origin) / voxel_size) in fp32, INT64_MAX for a row that is not

@@ -1,5 +1,6 @@
 """python -m pagnerf_amd.train --config YAML --dataset TRAIN.npz|DIR [--val-dataset VAL.npz|DIR] [--log-dir DIR] [--resume CKPT] [--valid-only]
-                              [--val-pictures] [--save-map PATH [--map-voxel-size V [--map-min-votes N] [--map-min-component N] [--map-split MODE]]] [--set key=value ...]
+                              [--val-pictures] [--save-map PATH [--map-voxel-size V [--map-min-votes N] [--map-min-component N] [--map-split MODE]]]
+                              [--save-mesh PATH.ply [--mesh-resolution R] [--mesh-min-density D]] [--set key=value ...]
 
 The native counterpart of the reference's main_interactive.py: a shipped YAML, a dataset, and the trainer of trainer.py.
 
@@ -117,6 +118,18 @@ def save_map(trainer, dataset, path, voxel_size=None, min_votes=1, min_component
     return path
 
 
+def save_mesh(trainer, path, resolution=256, min_density=None):
+    """--save-mesh: the panoptic triangle mesh of the trained field (mesh.extract_mesh: surface nets on the density lattice of `resolution` cells per
+    axis at iso = min_density, the vertices labelled by instance and class and coloured) as a binary PLY, and its report line on stdout.  It needs the
+    trained nef alone: no base rays, no BAPipeline."""
+    from . import mesh
+    nef = getattr(trainer.pipeline, "nef", trainer.pipeline)
+    m = mesh.extract_mesh(nef, resolution=resolution, min_density=min_density)
+    mesh.save_mesh(m, path)
+    print(mesh.report_line(mesh.mesh_report(m)))
+    return path
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m pagnerf_amd.train", description=__doc__.split("\n\n")[1])
     ap.add_argument("--config", required=True, help="a YAML in the reference's layout (configs/bup20/*.yaml)")
@@ -136,6 +149,11 @@ def main(argv=None):
                     "than N voxels; the map gets a component label per voxel and the table one row per component")
     ap.add_argument("--map-split", choices=("keep", "largest", "split"), metavar="MODE", help="with --map-voxel-size: an id with several components keeps "
                     "them (keep), keeps only the largest (largest) or gives every further component a new id (split)")
+    ap.add_argument("--save-mesh", metavar="PATH.ply", help="after training export the labelled, coloured triangle mesh of the field (surface nets on the "
+                    "density lattice) as a binary PLY and print its report (counts, closed / oriented, Euler characteristic, area, volume)")
+    ap.add_argument("--mesh-resolution", type=int, default=256, metavar="R", help="--save-mesh: lattice cells per axis (default 256)")
+    ap.add_argument("--mesh-min-density", type=float, metavar="D", help="--save-mesh: the density of the surface (default: the dense map export's "
+                    "0.01 * 512 / sqrt(3))")
     ap.add_argument("--set", action="append", default=[], metavar="key=value", help="override an option of the flattened namespace (repeatable)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
@@ -174,6 +192,8 @@ def main(argv=None):
         trainer.validate(trainer.epoch - 1)
     if args.save_map:
         save_map(trainer, dataset, args.save_map, args.map_voxel_size, args.map_min_votes, args.map_min_component, args.map_split)
+    if args.save_mesh:
+        save_mesh(trainer, args.save_mesh, args.mesh_resolution, args.mesh_min_density)
     return 0
 
 
