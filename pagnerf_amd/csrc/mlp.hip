@@ -3528,20 +3528,85 @@ inline unsigned mlp_grid(int64_t M) {
     return (unsigned)(blocks < cap ? (blocks > 0 ? blocks : 1) : cap);
 }
 
-// the wide softmax head whose forward writes softmax statistics and the last hidden layer instead of its [M, out_dim] output (mlp_fwd_wide_stats, head_fwd_once_kernel)
-bool is_wide_stats_head(const pag_mlp_fwd_args *a) {
-    return a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && a->x1_layout == PAG_LAYOUT_XCD8 && !a->out && a->n_layers == 3 && a->softmax_stats &&
-           a->out_act == PAG_ACT_SOFTMAX && a->out_dim > 192 && a->out_dim <= 224 && a->hidden_save[1];
+// The decoder shapes that have kernels of their own, forward (mlp_fwd_fast, mlp_fwd_wide_stats, head_fwd_once_kernel) and backward (mlp_bwd_fused,
+// mlp_bwd_wide_blocks); anything else runs the generic kernels.  The first three are the KIND template argument of mlp_fwd_fast / mlp_bwd_fused.
+enum DecoderFamily {
+    FAM_GENERIC = -1,
+    FAM_DENSITY = 0,      // XCD8 input, no output activation, bf16 output of a multiple of 4 channels <= 32
+    FAM_COLOUR = 1,       // strided bf16 [M,16] input + per-ray x2 [R,32], sigmoid, f32 output of <= 4 channels, the density read off column 0 of x1
+    FAM_SOFTMAX = 2,      // XCD8 input, softmax, bf16 output of <= 8 channels (the semantic head)
+    FAM_WIDE = 3,         // XCD8 input, three layers, softmax over 193 .. 224 channels kept as statistics + last hidden layer (the instance head)
+};
+
+// ---- forward: one predicate per family, on the argument struct alone.  They hold what pag_mlp_fwd's selection asks; what an entry point asks beyond the
+//      family stands beside its call.
+bool fwd_bf16_path(const pag_mlp_fwd_args *a) { return a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16; }
+bool fwd_density_like(const pag_mlp_fwd_args *a) {
+    return fwd_bf16_path(a) && a->x1_layout == PAG_LAYOUT_XCD8 && a->out && a->out_dtype == PAG_BF16 && a->out_act == PAG_ACT_NONE && a->out_dim % 4 == 0 && a->out_dim <= 32;
+}
+bool fwd_colour_like(const pag_mlp_fwd_args *a) {      // says nothing about x1_layout: see fwd_family
+    return fwd_bf16_path(a) && a->k1 == 16 && a->x2 && a->k2p == 32 && a->in_dim <= 48 && a->out && a->out_dtype == PAG_F32 && a->out_act == PAG_ACT_SIGMOID &&
+           a->out_dim <= 4 && a->x1_col0_relu;
+}
+bool fwd_softmax_like(const pag_mlp_fwd_args *a) {
+    return fwd_bf16_path(a) && a->x1_layout == PAG_LAYOUT_XCD8 && a->out && a->out_dtype == PAG_BF16 && a->out_act == PAG_ACT_SOFTMAX && a->out_dim <= 8;
+}
+bool fwd_wide_like(const pag_mlp_fwd_args *a) {
+    return fwd_bf16_path(a) && a->x1_layout == PAG_LAYOUT_XCD8 && !a->out && a->n_layers == 3 && a->softmax_stats && a->out_act == PAG_ACT_SOFTMAX && a->out_dim > 192 &&
+           a->out_dim <= 224 && a->hidden_save[1];
+}
+// an XCD8 x1 as the kernels stage it: what pag_mlp_fwd requires of every such input
+bool fwd_xcd8_staged(const pag_mlp_fwd_args *a) {
+    return fwd_bf16_path(a) && a->k1 == 64 && a->x2 == nullptr && a->x1_feats >= 1 && ((a->x1_levels + 7) / 8) * a->x1_feats <= 8 && a->in_dim == a->x1_levels * a->x1_feats;
+}
+// pag_mlp_fwd's selection, for arguments that passed its checks (an XCD8 input is then fwd_xcd8_staged; x1_levels = 0 under the XCD8 flag is a strided input)
+DecoderFamily fwd_family(const pag_mlp_fwd_args *a) {
+    if (!(a->x1_layout == PAG_LAYOUT_XCD8 && a->x1_levels > 0)) return fwd_colour_like(a) ? FAM_COLOUR : FAM_GENERIC;
+    return fwd_density_like(a) ? FAM_DENSITY : fwd_softmax_like(a) ? FAM_SOFTMAX : fwd_wide_like(a) ? FAM_WIDE : FAM_GENERIC;
 }
 
-// the companion narrow head of a wide head (args->pair, validated by pag_mlp_fwd_pair_supported)
-void set_pair_head(FwdParams &p, const pag_mlp_fwd_args *b) {
-    p.W2[0] = b->W[0];
-    p.W2[1] = b->W[1];
-    p.b2[0] = b->b[0];
-    p.b2[1] = b->b[1];
-    p.out2 = b->out;
-    p.out2_dim = b->out_dim;
+// The kernel parameters of one argument block: the decoder itself, and its x1_producer (a block of its own).  A companion head (args->pair) rides in the fields
+// W2 / b2 / out2 of its wide head's block.
+FwdParams fwd_params(const pag_mlp_fwd_args *a, int64_t M) {
+    FwdParams p;
+    p.x1 = a->x1;
+    p.x2 = a->x2;
+    p.x2_index = a->x2_index;
+    p.k1 = a->k1;
+    p.k2p = a->x2 ? a->k2p : 0;
+    p.in_dim = a->in_dim;
+    p.grp_L = a->x1_layout == PAG_LAYOUT_XCD8 ? a->x1_levels : 0;
+    p.grp_F = a->x1_feats;
+    p.in_pad = p.grp_L ? 64 : ((a->k1 + p.k2p + 15) / 16) * 16;
+    p.out_dim = a->out_dim;
+    p.act = a->out_act;
+    for (int l = 0; l < 3; ++l) {
+        p.W[l] = l < a->n_layers ? a->W[l] : nullptr;
+        p.b[l] = l < a->n_layers ? a->b[l] : nullptr;
+    }
+    p.out = a->out;
+    p.hsave[0] = a->hidden_save[0];
+    p.hsave[1] = a->n_layers == 3 ? a->hidden_save[1] : nullptr;
+    p.M = M;
+    p.stats = (a->mode == PAG_MLP_MFMA_BF16 && a->out_dim > 64) ? a->softmax_stats : nullptr;
+    p.col0_relu = a->x1_col0_relu;
+    const pag_mlp_fwd_args *b = fwd_family(a) == FAM_WIDE ? a->pair : nullptr;      // no other block carries a companion head, whatever its `pair` says
+    for (int l = 0; l < 2; ++l) {
+        p.W2[l] = b ? b->W[l] : nullptr;
+        p.b2[l] = b ? b->b[l] : nullptr;
+    }
+    p.out2 = b ? b->out : nullptr;
+    p.out2_dim = b ? b->out_dim : 0;
+    return p;
+}
+
+// f(T0{}, T1{}) with T = float where the flag says f32, else bf16_t: the dtype ladder of the generic and the parity kernels
+template <typename Fn>
+void with_dtypes(bool f32_0, bool f32_1, Fn &&f) {
+    if (f32_0 && f32_1) f(float{}, float{});
+    else if (f32_0) f(float{}, bf16_t{});
+    else if (f32_1) f(bf16_t{}, float{});
+    else f(bf16_t{}, bf16_t{});
 }
 
 template <typename X1T, typename OutT, int NL>
@@ -3611,13 +3676,13 @@ void launch_bwd_fused(const BwdParams &p, unsigned grid, hipStream_t st) {
     hipLaunchKernelGGL((mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>), dim3(grid), dim3(256), FusedLds(NL, OBL, DZ0).bytes, st, p);
 }
 template <int NL>
-void launch_bwd_fused_kind(const BwdParams &p, int kind, bool acc, int dz0, unsigned grid, hipStream_t st) {
-    if (kind == 0) launch_bwd_fused<NL, 0, false>(p, grid, st);
-    else if (kind == 1 && dz0 == 2) launch_bwd_fused<NL, 1, false, 1, 2>(p, grid, st);
-    else if (kind == 1 && dz0 == 1) launch_bwd_fused<NL, 1, false, 1, 1>(p, grid, st);
-    else if (kind == 1) launch_bwd_fused<NL, 1, false>(p, grid, st);
-    else if (acc) launch_bwd_fused<NL, 2, true>(p, grid, st);
-    else launch_bwd_fused<NL, 2, false>(p, grid, st);
+void launch_bwd_fused_family(const BwdParams &p, DecoderFamily fam, bool acc, int dz0, unsigned grid, hipStream_t st) {
+    if (fam == FAM_DENSITY) launch_bwd_fused<NL, FAM_DENSITY, false>(p, grid, st);
+    else if (fam == FAM_COLOUR && dz0 == 2) launch_bwd_fused<NL, FAM_COLOUR, false, 1, 2>(p, grid, st);
+    else if (fam == FAM_COLOUR && dz0 == 1) launch_bwd_fused<NL, FAM_COLOUR, false, 1, 1>(p, grid, st);
+    else if (fam == FAM_COLOUR) launch_bwd_fused<NL, FAM_COLOUR, false>(p, grid, st);
+    else if (acc) launch_bwd_fused<NL, FAM_SOFTMAX, true>(p, grid, st);
+    else launch_bwd_fused<NL, FAM_SOFTMAX, false>(p, grid, st);
 }
 
 // stage A of the fused wide-head backward
@@ -3642,29 +3707,27 @@ void launch_bwd_wide_mfma(const BwdParams &p, hipStream_t st) {
 
 extern "C" int pag_mlp_fwd_pair_supported(const pag_mlp_fwd_args *a, const pag_mlp_fwd_args *b) {
     if (!a || !b || b->pair) return 0;
-    const bool wide = is_wide_stats_head(a) && !a->hidden_save[0];
-    const bool narrow = b->mode == PAG_MLP_MFMA_BF16 && b->x1 == a->x1 && b->x1_dtype == PAG_BF16 && b->x1_layout == PAG_LAYOUT_XCD8 && b->x1_levels == a->x1_levels &&
-                        b->x1_feats == a->x1_feats && b->in_dim == a->in_dim && b->n_layers == 2 && b->out && b->out_dtype == PAG_BF16 &&
-                        b->out_act == PAG_ACT_SOFTMAX && b->out_dim >= 1 && b->out_dim <= 8 && !b->hidden_save[0] && !b->hidden_save[1] && !b->x2 &&
-                        !b->x1_col0_relu && b->W[0] && b->W[1] && b->b[0] && b->b[1];
+    // the wide head without its first hidden layer saved; beside it a two-layer head on the same tensor that writes nothing but its output
+    const bool wide = fwd_wide_like(a) && !a->hidden_save[0];
+    const bool narrow = fwd_softmax_like(b) && b->out_dim >= 1 && b->n_layers == 2 && b->x1 == a->x1 && b->x1_levels == a->x1_levels && b->x1_feats == a->x1_feats &&
+                        b->in_dim == a->in_dim && !b->hidden_save[0] && !b->hidden_save[1] && !b->x2 && !b->x1_col0_relu && b->W[0] && b->W[1] && b->b[0] && b->b[1];
     return wide && narrow ? 1 : 0;
 }
 
 extern "C" int pag_mlp_fwd_producer_supported(const pag_mlp_fwd_args *a, const pag_mlp_fwd_args *d, int64_t M) {
     if (!a || !d || M < 1 || M > PAG_MLP_FUSED_WIDE_MAX_M) return 0;
-    const bool density = d->mode == PAG_MLP_MFMA_BF16 && d->x1_dtype == PAG_BF16 && d->x1_layout == PAG_LAYOUT_XCD8 && d->k1 == 64 && !d->x2 && d->n_layers == 2 &&
-                         d->out && d->out_dtype == PAG_BF16 && d->out_act == PAG_ACT_NONE && d->out_dim == 16 && !d->hidden_save[0] && !d->hidden_save[1] &&
-                         !d->softmax_stats && !d->x1_col0_relu && !d->pair && !d->composite && !d->x1_producer && d->W[0] && d->W[1] && d->b[0] && d->b[1] &&
-                         d->in_dim == d->x1_levels * d->x1_feats && d->x1_feats >= 1 && ((d->x1_levels + 7) / 8) * d->x1_feats <= 8;
-    const bool colour = a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && a->x1_layout != PAG_LAYOUT_XCD8 && a->k1 == 16 && a->x1 == d->out && a->x2 &&
-                        a->k2p == 32 && a->x2_index && a->in_dim <= 48 && a->n_layers == 3 && a->out && a->out_dtype == PAG_F32 && a->out_act == PAG_ACT_SIGMOID &&
-                        a->out_dim <= 4 && a->x1_col0_relu && !a->hidden_save[0] && !a->hidden_save[1] && !a->pair && !a->composite;
+    // the producer is not checked by pag_mlp_fwd: what that asks of an XCD8 decoder is asked here; two layers to 16 channels, nothing else written or attached
+    const bool density = fwd_density_like(d) && fwd_xcd8_staged(d) && d->n_layers == 2 && d->out_dim == 16 && !d->hidden_save[0] && !d->hidden_save[1] && !d->softmax_stats &&
+                         !d->x1_col0_relu && !d->pair && !d->composite && !d->x1_producer && d->W[0] && d->W[1] && d->b[0] && d->b[1];
+    // three layers on the producer's output, nothing saved or attached (here the XCD8 flag with x1_levels = 0 does not pass for strided)
+    const bool colour = fwd_colour_like(a) && a->x1_layout != PAG_LAYOUT_XCD8 && a->x1 == d->out && a->x2_index && a->n_layers == 3 && !a->hidden_save[0] && !a->hidden_save[1] &&
+                        !a->pair && !a->composite;
     return density && colour ? 1 : 0;
 }
 
 extern "C" int pag_mlp_fwd_composite_supported(const pag_mlp_fwd_args *a, int64_t M) {
     if (!a || M < 1 || M > PAG_MLP_FUSED_WIDE_MAX_M) return 0;
-    const bool wide = is_wide_stats_head(a) && !a->hidden_save[0];
+    const bool wide = fwd_wide_like(a) && !a->hidden_save[0];
     return wide && (!a->pair || pag_mlp_fwd_pair_supported(a, a->pair) == 1) ? 1 : 0;
 }
 
@@ -3687,57 +3750,20 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
     PAG_CHECK_ARG(a->x1, "pag_mlp_fwd: NULL x1");
     PAG_CHECK_ARG(a->out || (a->softmax_stats && a->mode == PAG_MLP_MFMA_BF16 && a->out_dim > 64 && a->out_act == PAG_ACT_SOFTMAX),
                   "pag_mlp_fwd: NULL out (allowed only for wide softmax heads that write softmax_stats)");
-    FwdParams p;
-    for (int l = 0; l < 3; ++l) p.b[l] = a->b[l];
-    p.x1 = a->x1;
-    p.x2 = a->x2;
-    p.x2_index = a->x2_index;
-    p.k1 = a->k1;
-    p.k2p = k2p;
-    p.in_dim = a->in_dim;
-    p.in_pad = ((a->k1 + k2p + 15) / 16) * 16;
-    p.out_dim = a->out_dim;
-    p.act = a->out_act;
-    p.stats = (a->mode == PAG_MLP_MFMA_BF16 && a->out_dim > 64) ? a->softmax_stats : nullptr;
-    PAG_CHECK_ARG(!a->x1_col0_relu || (a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && a->x1_layout != PAG_LAYOUT_XCD8 && a->out_dim <= 64),
+    PAG_CHECK_ARG(!a->x1_col0_relu || (fwd_bf16_path(a) && a->x1_layout != PAG_LAYOUT_XCD8 && a->out_dim <= 64),
                   "pag_mlp_fwd: x1_col0_relu needs MFMA mode, a strided bf16 x1 and out_dim <= 64");
-    p.col0_relu = a->x1_col0_relu;
-    p.W2[0] = p.W2[1] = p.b2[0] = p.b2[1] = nullptr;
-    p.out2 = nullptr;
-    p.out2_dim = 0;
-    for (int l = 0; l < 3; ++l) {
-        p.W[l] = l < a->n_layers ? a->W[l] : nullptr;
-        p.b[l] = l < a->n_layers ? a->b[l] : nullptr;
-    }
-    p.out = a->out;
-    p.hsave[0] = a->hidden_save[0];
-    p.hsave[1] = a->n_layers == 3 ? a->hidden_save[1] : nullptr;
-    p.M = M;
-    p.grp_L = a->x1_layout == PAG_LAYOUT_XCD8 ? a->x1_levels : 0;
-    p.grp_F = a->x1_feats;
-    if (p.grp_L) {
-        PAG_CHECK_ARG(a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && a->k1 == 64 && a->x2 == nullptr && p.grp_F >= 1 &&
-                          ((p.grp_L + 7) / 8) * p.grp_F <= 8 && a->in_dim == p.grp_L * p.grp_F,
-                      "pag_mlp_fwd: XCD8 input needs MFMA mode, bf16, k1 = 64, no x2 and in_dim = levels*feats");
-        p.in_pad = 64;
-    }
+    PAG_CHECK_ARG(a->x1_layout != PAG_LAYOUT_XCD8 || a->x1_levels == 0 || fwd_xcd8_staged(a),
+                  "pag_mlp_fwd: XCD8 input needs MFMA mode, bf16, k1 = 64, no x2 and in_dim = levels*feats");
+    const FwdParams p = fwd_params(a, M);
     hipStream_t st = (hipStream_t)stream;
     // ---- the panoptic nef's decoder shapes on the bf16 path: dedicated straight-line kernels
-    if (a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16 && M <= PAG_MLP_FUSED_WIDE_MAX_M) {
-        const bool grp = p.grp_L > 0;
+    if (fwd_bf16_path(a) && M <= PAG_MLP_FUSED_WIDE_MAX_M) {
+        const DecoderFamily fam = fwd_family(a);
         const bool save_all = a->hidden_save[0] && (a->n_layers == 2 || a->hidden_save[1]);
         const bool save_none = !a->hidden_save[0] && !a->hidden_save[1];
-        int kind = -1;
-        if (grp && a->out && a->out_dtype == PAG_BF16 && a->out_act == PAG_ACT_NONE && a->out_dim % 4 == 0 && a->out_dim <= 32) kind = 0;
-        else if (!grp && a->k1 == 16 && a->x2 && a->k2p == 32 && a->in_dim <= 48 && a->out && a->out_dtype == PAG_F32 && a->out_act == PAG_ACT_SIGMOID &&
-                 a->out_dim <= 4 && a->x1_col0_relu)
-            kind = 1;
-        else if (grp && a->out && a->out_dtype == PAG_BF16 && a->out_act == PAG_ACT_SOFTMAX && a->out_dim <= 8) kind = 2;
-        else if (grp && is_wide_stats_head(a)) kind = 3;
-        PAG_CHECK_ARG(!a->pair || (kind == 3 && pag_mlp_fwd_pair_supported(a, a->pair) == 1), "pag_mlp_fwd: pair is not supported for these arguments (pag_mlp_fwd_pair_supported)");
-        PAG_CHECK_ARG(!a->composite || kind == 3, "pag_mlp_fwd: composite rides only in the statistics-only wide softmax head (pag_mlp_fwd_composite_supported)");
-        if (kind == 3) {
-            if (a->pair) set_pair_head(p, a->pair);
+        PAG_CHECK_ARG(!a->pair || (fam == FAM_WIDE && pag_mlp_fwd_pair_supported(a, a->pair) == 1), "pag_mlp_fwd: pair is not supported for these arguments (pag_mlp_fwd_pair_supported)");
+        PAG_CHECK_ARG(!a->composite || fam == FAM_WIDE, "pag_mlp_fwd: composite rides only in the statistics-only wide softmax head (pag_mlp_fwd_composite_supported)");
+        if (fam == FAM_WIDE) {
             if (a->composite) {      // decoder + per-ray weighted sum in one pass over the logits (head_fwd_once_kernel)
                 const pag_head_composite_args *hc = a->composite;
                 PAG_CHECK_ARG(hc->P >= 0 && (hc->P == 0 || (hc->pack_start && hc->ray_of_pack && hc->weights && hc->alpha && hc->out)),
@@ -3768,38 +3794,18 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
             PAG_CHECK_LAUNCH("pag_mlp_fwd (wide head statistics)");
             return PAG_OK;
         }
-        PAG_CHECK_ARG(!a->x1_producer || (kind == 1 && pag_mlp_fwd_producer_supported(a, a->x1_producer, M) == 1),
+        PAG_CHECK_ARG(!a->x1_producer || (fam == FAM_COLOUR && pag_mlp_fwd_producer_supported(a, a->x1_producer, M) == 1),
                       "pag_mlp_fwd: x1_producer is not supported for these arguments (pag_mlp_fwd_producer_supported)");
         if (a->x1_producer) {      // density decoder + colour decoder in one launch (mlp_fwd_density_colour)
-            const pag_mlp_fwd_args *d = a->x1_producer;
-            FwdParams pd = p;
-            pd.x1 = d->x1;
-            pd.x2 = nullptr;
-            pd.x2_index = nullptr;
-            pd.k1 = 64;
-            pd.k2p = 0;
-            pd.in_dim = d->in_dim;
-            pd.in_pad = 64;
-            pd.out_dim = d->out_dim;
-            pd.act = d->out_act;
-            pd.stats = nullptr;
-            pd.col0_relu = nullptr;
-            for (int l = 0; l < 3; ++l) {
-                pd.W[l] = l < 2 ? d->W[l] : nullptr;
-                pd.b[l] = l < 2 ? d->b[l] : nullptr;
-            }
-            pd.out = d->out;
-            pd.hsave[0] = pd.hsave[1] = nullptr;
-            pd.grp_L = d->x1_levels;
-            pd.grp_F = d->x1_feats;
+            const FwdParams pd = fwd_params(a->x1_producer, M);
             hipLaunchKernelGGL(mlp_fwd_density_colour, dim3(std::min<unsigned>(mlp_grid(M), FAST_FWD_GRID_CAP)), dim3(256), DensityColourLds{}.bytes, st, pd, p);
             PAG_CHECK_LAUNCH("pag_mlp_fwd (density + colour)");
             return PAG_OK;
         }
-        if (kind >= 0 && (save_all || save_none)) {
-            if (kind == 0) launch_fwd_fast<0>(p, a->n_layers, save_all, st);
-            else if (kind == 1) launch_fwd_fast<1>(p, a->n_layers, save_all, st);
-            else launch_fwd_fast<2>(p, a->n_layers, save_all, st);
+        if (fam != FAM_GENERIC && (save_all || save_none)) {
+            if (fam == FAM_DENSITY) launch_fwd_fast<FAM_DENSITY>(p, a->n_layers, save_all, st);
+            else if (fam == FAM_COLOUR) launch_fwd_fast<FAM_COLOUR>(p, a->n_layers, save_all, st);
+            else launch_fwd_fast<FAM_SOFTMAX>(p, a->n_layers, save_all, st);
             PAG_CHECK_LAUNCH("pag_mlp_fwd (straight-line)");
             return PAG_OK;
         }
@@ -3807,22 +3813,12 @@ extern "C" int pag_mlp_fwd(const pag_mlp_fwd_args *a, int64_t M, void *stream) {
     PAG_CHECK_ARG(!a->composite, "pag_mlp_fwd: composite rides only in the straight-line wide-head launch (pag_mlp_fwd_composite_supported)");
     PAG_CHECK_ARG(!a->x1_producer, "pag_mlp_fwd: x1_producer rides only in the straight-line colour launch (pag_mlp_fwd_producer_supported)");
     PAG_CHECK_ARG(!a->pair, "pag_mlp_fwd: pair rides only in the straight-line wide-head launch (M <= %lld)", (long long)PAG_MLP_FUSED_WIDE_MAX_M);
+    const bool x1_f32 = a->x1_dtype == PAG_F32, out_f32 = a->out_dtype == PAG_F32;
     if (a->mode == PAG_MLP_MFMA_BF16) {
-        if (a->x1_dtype == PAG_F32 && a->out_dtype == PAG_F32) launch_fwd_mfma<float, float>(p, a->n_layers, st);
-        else if (a->x1_dtype == PAG_F32) launch_fwd_mfma<float, bf16_t>(p, a->n_layers, st);
-        else if (a->out_dtype == PAG_F32) launch_fwd_mfma<bf16_t, float>(p, a->n_layers, st);
-        else launch_fwd_mfma<bf16_t, bf16_t>(p, a->n_layers, st);
+        with_dtypes(x1_f32, out_f32, [&](auto x, auto o) { launch_fwd_mfma<decltype(x), decltype(o)>(p, a->n_layers, st); });
     } else {
-        const size_t lds = F32Lds(64).bytes;
-        dim3 grid((unsigned)((M + PT - 1) / PT)), block(PT);
-        if (a->x1_dtype == PAG_F32 && a->out_dtype == PAG_F32)
-            hipLaunchKernelGGL((mlp_fwd_f32<float, float>), grid, block, lds, st, p, a->n_layers);
-        else if (a->x1_dtype == PAG_F32)
-            hipLaunchKernelGGL((mlp_fwd_f32<float, bf16_t>), grid, block, lds, st, p, a->n_layers);
-        else if (a->out_dtype == PAG_F32)
-            hipLaunchKernelGGL((mlp_fwd_f32<bf16_t, float>), grid, block, lds, st, p, a->n_layers);
-        else
-            hipLaunchKernelGGL((mlp_fwd_f32<bf16_t, bf16_t>), grid, block, lds, st, p, a->n_layers);
+        const dim3 grid((unsigned)((M + PT - 1) / PT)), block(PT);
+        with_dtypes(x1_f32, out_f32, [&](auto x, auto o) { hipLaunchKernelGGL((mlp_fwd_f32<decltype(x), decltype(o)>), grid, block, F32Lds(64).bytes, st, p, a->n_layers); });
     }
     PAG_CHECK_LAUNCH("pag_mlp_fwd");
     return PAG_OK;
@@ -3870,56 +3866,127 @@ void pagmlp::launch_wgrad_finish(const FinishBatch &fb, int max_out, int n_layer
     hipLaunchKernelGGL(wgrad_finish_kernel, dim3(max_out, n_layers), dim3(WF_SPLITS * WG_SLAB_COLS), 0, st, fb);
 }
 
-static unsigned fused_grid(int64_t M) {
+namespace {
+
+unsigned fused_grid(int64_t M) {
     const int64_t tiles = (M + 31) / 32;
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + 3) / 4, 256 * FUSED_WAVES));      // one 4-wave workgroup per CU, tiles grid-strided
 }
 
-// which mlp_bwd_fused instantiation serves these arguments: 0 density-like, 1 colour-like, 2 semantic-like, -1 none
-static int fused_kind(const pag_mlp_bwd_args *a) {
-    if (!a || a->mode != PAG_MLP_MFMA_BF16 || a->out_dim < 1 || a->out_dim > 224 || !a->dx1 || a->dx1_dtype != PAG_BF16) return -1;
-    if (a->n_layers != 2 && a->n_layers != 3) return -1;
-    if (!a->x1 || a->x1_dtype != PAG_BF16) return -1;
-    const bool rank1 = a->g_ray != nullptr;
-    if (a->out_dim > 32) {      // wide softmax head: stage A (output layer, mlp_bwd_wide_blocks) + stage B (the two layers below it)
-        if (a->out_dim <= 192 || a->out_dim > 224 || a->n_layers != 3 || !a->g_ray || !a->g_scale || !a->g_index || !a->g_ray_scale) return -1;
-        if (a->out_act != PAG_ACT_SOFTMAX || !a->softmax_stats || !a->b_last || a->out_dtype != PAG_BF16 || !a->dx1 || a->dx1_dtype != PAG_BF16) return -1;
-        if (!a->x1 || a->x1_dtype != PAG_BF16 || a->x1_layout != PAG_LAYOUT_XCD8 || a->k1 != 64 || a->x2 || a->dx1_col0_add || a->dx1_accumulate) return -1;
-        if (a->x1_levels < 1 || a->x1_feats < 1 || ((a->x1_levels + 7) / 8) * a->x1_feats > 8 || !xcd8_has_bias_slot(a->x1_levels, a->x1_feats)) return -1;
-        return 3;
-    }
-    if (a->x1_layout == PAG_LAYOUT_XCD8) {
-        if (a->k1 != 64 || a->x1_levels < 1 || a->x1_feats < 1 || ((a->x1_levels + 7) / 8) * a->x1_feats > 8 || !xcd8_has_bias_slot(a->x1_levels, a->x1_feats)) return -1;
-        if (a->x2 || a->dx1_col0_add) return -1;
-        if (!rank1 && a->grad_out && a->out_dtype == PAG_BF16 && a->out_act == PAG_ACT_NONE && a->out_dim % 4 == 0 && !a->dx1_accumulate) return 0;
-        if (rank1 && a->g_scale && a->g_index && a->g_ray_scale && a->out && a->out_dtype == PAG_BF16 && a->out_act == PAG_ACT_SOFTMAX &&
-            a->out_dim <= 8)
-            return 2;
-        return -1;
-    }
-    if (a->k1 == 16 && a->x2 && a->k2p == 32 && a->x2_index && a->in_dim <= 48 && !rank1 && a->grad_out && a->out && a->out_dtype == PAG_F32 &&
-        a->out_act == PAG_ACT_SIGMOID && a->out_dim <= 4 && a->dx1_col0_add && a->dx1_col0_gate && !a->dx1_accumulate)
-        return 1;
-    return -1;
+// ---- backward with fused weight gradients: one predicate per family, on the argument struct alone
+// what every fused kernel needs: bf16 operands on the MFMA path, the forward's input (the activations are recomputed) and an input gradient to write
+bool bwd_fused_common(const pag_mlp_bwd_args *a) {
+    return a && a->mode == PAG_MLP_MFMA_BF16 && a->out_dim >= 1 && a->out_dim <= 224 && a->dx1 && a->dx1_dtype == PAG_BF16 && (a->n_layers == 2 || a->n_layers == 3) &&
+           a->x1 && a->x1_dtype == PAG_BF16;
+}
+// an XCD8 input alone, with staged position 63 free for the constant 1 whose weight gradient is the layer-0 bias gradient
+bool bwd_xcd8_with_bias_slot(const pag_mlp_bwd_args *a) {
+    return a->x1_layout == PAG_LAYOUT_XCD8 && a->k1 == 64 && a->x1_levels >= 1 && a->x1_feats >= 1 && ((a->x1_levels + 7) / 8) * a->x1_feats <= 8 &&
+           xcd8_has_bias_slot(a->x1_levels, a->x1_feats) && !a->x2 && !a->dx1_col0_add;
+}
+bool bwd_rank1(const pag_mlp_bwd_args *a) { return a->g_ray && a->g_scale && a->g_index && a->g_ray_scale; }
+bool bwd_density_like(const pag_mlp_bwd_args *a) {
+    return bwd_xcd8_with_bias_slot(a) && !a->g_ray && a->grad_out && a->out_dtype == PAG_BF16 && a->out_act == PAG_ACT_NONE && a->out_dim % 4 == 0 && a->out_dim <= 32 &&
+           !a->dx1_accumulate;
+}
+bool bwd_colour_like(const pag_mlp_bwd_args *a) {
+    return a->x1_layout != PAG_LAYOUT_XCD8 && a->k1 == 16 && a->x2 && a->k2p == 32 && a->x2_index && a->in_dim <= 48 && !a->g_ray && a->grad_out && a->out &&
+           a->out_dtype == PAG_F32 && a->out_act == PAG_ACT_SIGMOID && a->out_dim <= 4 && a->dx1_col0_add && a->dx1_col0_gate && !a->dx1_accumulate;
+}
+bool bwd_softmax_like(const pag_mlp_bwd_args *a) {
+    return bwd_xcd8_with_bias_slot(a) && bwd_rank1(a) && a->out && a->out_dtype == PAG_BF16 && a->out_act == PAG_ACT_SOFTMAX && a->out_dim <= 8;
+}
+// stage A (output layer, mlp_bwd_wide_blocks) + stage B (the two layers below it)
+bool bwd_wide_like(const pag_mlp_bwd_args *a) {
+    return bwd_xcd8_with_bias_slot(a) && bwd_rank1(a) && a->out_dim > 192 && a->out_dim <= 224 && a->n_layers == 3 && a->out_act == PAG_ACT_SOFTMAX && a->softmax_stats &&
+           a->b_last && a->out_dtype == PAG_BF16 && !a->dx1_accumulate;
+}
+// which fused kernel serves these arguments; FAM_GENERIC: none
+DecoderFamily bwd_fused_family(const pag_mlp_bwd_args *a) {
+    if (!bwd_fused_common(a)) return FAM_GENERIC;
+    return bwd_density_like(a) ? FAM_DENSITY : bwd_colour_like(a) ? FAM_COLOUR : bwd_softmax_like(a) ? FAM_SOFTMAX : bwd_wide_like(a) ? FAM_WIDE : FAM_GENERIC;
 }
 
-extern "C" int pag_mlp_bwd_fused_supported(const pag_mlp_bwd_args *a) { return fused_kind(a) >= 0 ? 1 : 0; }
-
-extern "C" int pag_mlp_bwd_pair_supported(const pag_mlp_bwd_args *a, const pag_mlp_bwd_args *b) {
-    if (!a || !b || fused_kind(a) != 3 || fused_kind(b) != 2 || b->n_layers != 2) return 0;
-    return (b->x1 == a->x1 && b->x1_layout == PAG_LAYOUT_XCD8 && b->x1_levels == a->x1_levels && b->x1_feats == a->x1_feats && b->in_dim == a->in_dim &&
-            a->dx1 && b->dx1 == a->dx1 && b->dx1_accumulate && !a->dx1_accumulate)
-               ? 1
-               : 0;
+// The companion-head rule (args->pair): nullptr when `b` can ride in wide head a's call, else the condition it violates
+const char *bwd_pair_refusal(const pag_mlp_bwd_args *a, const pag_mlp_bwd_args *b) {
+    if (bwd_fused_family(a) != FAM_WIDE || bwd_fused_family(b) != FAM_SOFTMAX || b->n_layers != 2) return "pair must be a two-layer narrow softmax head beside a wide softmax head";
+    if (!(b->x1 == a->x1 && b->x1_layout == PAG_LAYOUT_XCD8 && b->x1_levels == a->x1_levels && b->x1_feats == a->x1_feats && b->in_dim == a->in_dim))
+        return "pair must read the same XCD8 input";
+    if (!(a->dx1 && b->dx1 == a->dx1 && b->dx1_accumulate && !a->dx1_accumulate)) return "pair must accumulate into this decoder's dx1";
+    return nullptr;
 }
+
+// Layout of the fused backward's workspace (args->wgrad_workspace), byte offsets: one description for pag_mlp_bwd_fused_workspace_bytes and for pag_mlp_bwd's
+// pointers.  A slab is f32 [grid][rows][WG_SLAB_COLS], one [rows][96] block per workgroup, summed by wgrad_finish_kernel.
+//   wide head  slab[2] (stage A: the output layer, 224 rows), slab[0], slab[1] (stage B: the layers below, 64 rows each), then dzh: the bf16 [M,64] hidden
+//              gradient stage A hands to stage B, in whole 32-sample tiles plus a dump tile
+//   otherwise  slab[l] per layer in layer order: 64 rows for a hidden layer, 32 for the output layer (a companion head's two slabs as well)
+struct FusedWorkspace {
+    int64_t slab[3] = {0, 0, 0}, dzh = 0, bytes = 0;
+    FusedWorkspace(DecoderFamily fam, int n_layers, int64_t M) {
+        const int64_t row = (int64_t)fused_grid(M) * WG_SLAB_COLS * (int64_t)sizeof(float);      // one slab row of every workgroup
+        auto take = [this](int64_t n) { const int64_t at = bytes; bytes += n; return at; };
+        if (fam == FAM_WIDE) {
+            slab[2] = take(224 * row);
+            slab[0] = take(64 * row);
+            slab[1] = take(64 * row);
+            dzh = take(((M + 31) / 32 + 1) * 32 * HID * 2);
+        } else {
+            for (int l = 0; l < n_layers; ++l) slab[l] = take((l + 1 < n_layers ? 64 : 32) * row);
+        }
+    }
+    float *slab_at(float *ws, int l) const { return ws + slab[l] / (int64_t)sizeof(float); }
+};
+
+// The kernel parameters of one argument block (the decoder, or its companion head): stage A and stage B of the wide head start from a copy.  slabs, and the
+// dz[0] / dz0_slots of the fused kernels, are the launch's to set.
+BwdParams bwd_params(const pag_mlp_bwd_args *a, int64_t M) {
+    BwdParams p;
+    p.g_ray = a->g_ray;
+    p.g_scale = a->g_scale;
+    p.g_ray_scale = a->g_ray_scale;
+    p.g_index = a->g_index;
+    p.grad_out = a->grad_out ? a->grad_out : (const void *)a->out;      // never dereferenced in rank-1 mode
+    p.out = a->out ? a->out : (const void *)a->grad_out;
+    p.k1 = a->k1;
+    p.in_dim = a->in_dim;
+    p.in_pad = 64;
+    p.out_dim = a->out_dim;
+    p.act = a->out_act;
+    for (int l = 0; l < 3; ++l) {
+        p.W[l] = l < a->n_layers ? a->W[l] : nullptr;
+        p.dz[l] = l < a->n_layers ? a->dz[l] : nullptr;
+        p.b[l] = a->b[l];
+        p.slabs[l] = nullptr;
+    }
+    p.hsave[0] = a->hidden_save[0];
+    p.hsave[1] = a->n_layers == 3 ? a->hidden_save[1] : nullptr;
+    p.dx1 = a->dx1;
+    p.M = M;
+    p.grp_L = a->x1_layout == PAG_LAYOUT_XCD8 ? a->x1_levels : 0;
+    p.grp_F = a->x1_feats;
+    p.stats = a->softmax_stats;
+    p.b_last = a->b_last;
+    p.dx1_acc = a->dx1_accumulate;
+    p.dx_col0 = a->dx1_col0_add;
+    p.dx_col0_gate = a->dx1_col0_gate;
+    p.x1 = a->x1;
+    p.x2 = a->x2;
+    p.x2_index = a->x2_index;
+    p.k2p = a->x2 ? a->k2p : 0;
+    p.dz0_slots = nullptr;
+    return p;
+}
+
+}  // namespace
+
+extern "C" int pag_mlp_bwd_fused_supported(const pag_mlp_bwd_args *a) { return bwd_fused_family(a) != FAM_GENERIC ? 1 : 0; }
+
+extern "C" int pag_mlp_bwd_pair_supported(const pag_mlp_bwd_args *a, const pag_mlp_bwd_args *b) { return a && b && !bwd_pair_refusal(a, b) ? 1 : 0; }
 
 extern "C" int64_t pag_mlp_bwd_fused_workspace_bytes(const pag_mlp_bwd_args *a, int64_t M) {
-    const int kind = fused_kind(a);
-    if (kind < 0 || M < 1) return 0;
-    const int64_t grid = fused_grid(M);
-    if (kind == 3)      // stage A: one [224][96] slab per workgroup; stage B: per-wave slabs of two 64-row layers; + the [M,64] bf16 hidden gradient
-        return (grid * 224 + grid * 128) * WG_SLAB_COLS * (int64_t)sizeof(float) + ((M + 31) / 32 + 1) * 32 * HID * 2;      // + a dump tile
-    return grid * ((int64_t)(a->n_layers - 1) * 64 + 32) * WG_SLAB_COLS * (int64_t)sizeof(float);
+    const DecoderFamily fam = bwd_fused_family(a);
+    return fam == FAM_GENERIC || M < 1 ? 0 : FusedWorkspace(fam, a->n_layers, M).bytes;
 }
 
 extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
@@ -3940,9 +4007,9 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
     PAG_CHECK_ARG(!a->g_ray || (a->mode == PAG_MLP_MFMA_BF16 && (a->out || a->softmax_stats)),
                   "pag_mlp_bwd: rank-1 gradients need MFMA mode and the saved output");
     const bool fuse = a->wgrad_workspace != nullptr;
-    const int kind = fuse ? fused_kind(a) : -1;
+    const DecoderFamily fam = fuse ? bwd_fused_family(a) : FAM_GENERIC;
     if (fuse) {
-        PAG_CHECK_ARG(kind >= 0, "pag_mlp_bwd: this decoder shape has no fused weight-gradient kernel (pag_mlp_bwd_fused_supported)");
+        PAG_CHECK_ARG(fam != FAM_GENERIC, "pag_mlp_bwd: this decoder shape has no fused weight-gradient kernel (pag_mlp_bwd_fused_supported)");
         PAG_CHECK_ARG(a->wgrad_workspace_bytes >= pag_mlp_bwd_fused_workspace_bytes(a, M), "pag_mlp_bwd: wgrad_workspace too small");
         for (int l = 0; l < a->n_layers; ++l) PAG_CHECK_ARG(a->dW[l] && a->db[l], "pag_mlp_bwd: NULL dW/db of layer %d", l);
         for (int l = 0; l + 1 < a->n_layers; ++l) PAG_CHECK_ARG(a->b[l], "pag_mlp_bwd: fused mode recomputes the hidden activations: NULL bias b[%d]", l);
@@ -3950,28 +4017,7 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
     for (int l = 0; l < a->n_layers; ++l) PAG_CHECK_ARG(a->W[l] && (fuse || a->dz[l]), "pag_mlp_bwd: NULL weight/dz of layer %d", l);
     for (int l = 0; l + 1 < a->n_layers; ++l)
         PAG_CHECK_ARG(a->hidden_save[l] || (a->wgrad_workspace && (a->out_dim <= 32 || l + 2 < a->n_layers)), "pag_mlp_bwd: NULL hidden_save[%d]", l);
-    BwdParams p;
-    p.g_ray = a->g_ray;
-    p.g_scale = a->g_scale;
-    p.g_ray_scale = a->g_ray_scale;
-    p.g_index = a->g_index;
-    p.grad_out = a->grad_out ? a->grad_out : (const void *)a->out;      // never dereferenced in rank-1 mode
-    p.out = a->out ? a->out : (const void *)a->grad_out;
-    p.k1 = a->k1;
-    p.in_dim = a->in_dim;
-    p.in_pad = 64;
-    p.out_dim = a->out_dim;
-    p.act = a->out_act;
-    for (int l = 0; l < 3; ++l) {
-        p.W[l] = l < a->n_layers ? a->W[l] : nullptr;
-        p.dz[l] = l < a->n_layers ? a->dz[l] : nullptr;
-    }
-    p.hsave[0] = a->hidden_save[0];
-    p.hsave[1] = a->n_layers == 3 ? a->hidden_save[1] : nullptr;
-    p.dx1 = a->dx1;
-    p.M = M;
-    p.grp_L = a->x1_layout == PAG_LAYOUT_XCD8 ? a->x1_levels : 0;
-    p.grp_F = a->x1_feats;
+    BwdParams p = bwd_params(a, M);
     if (p.grp_L)
         PAG_CHECK_ARG(a->mode == PAG_MLP_MFMA_BF16 && (a->dx1 == nullptr || a->dx1_dtype == PAG_BF16) && a->k1 == 64 &&
                           ((p.grp_L + 7) / 8) * p.grp_F <= 8 && a->in_dim == p.grp_L * p.grp_F,
@@ -3979,35 +4025,19 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     const bool out_f32 = a->out_dtype == PAG_F32;      // dtype of grad_out and of the saved activated output
     const bool dx_f32 = a->dx1 == nullptr || a->dx1_dtype == PAG_F32;
-    p.stats = a->softmax_stats;
-    p.b_last = a->b_last;
-    p.dx1_acc = a->dx1_accumulate;
-    p.dx_col0 = a->dx1_col0_add;
-    p.dx_col0_gate = a->dx1_col0_gate;
     PAG_CHECK_ARG(!a->dx1_col0_gate || a->dx1_col0_add, "pag_mlp_bwd: dx1_col0_gate without dx1_col0_add");
     PAG_CHECK_ARG(!a->dx1_col0_add || (a->dx1 && !p.grp_L && a->mode == PAG_MLP_MFMA_BF16 && a->out_dim <= 64),
                   "pag_mlp_bwd: dx1_col0_add needs a strided dx1, MFMA mode and out_dim <= 64");
     PAG_CHECK_ARG(!a->dx1_accumulate || (p.grp_L && a->dx1), "pag_mlp_bwd: dx1_accumulate needs an XCD8 dx1");
-    for (int l = 0; l < 3; ++l) p.b[l] = a->b[l];
-    p.x1 = a->x1;
-    p.x2 = a->x2;
-    p.x2_index = a->x2_index;
-    p.k2p = a->x2 ? a->k2p : 0;
-    for (int l = 0; l < 3; ++l) p.slabs[l] = nullptr;
-    if (fuse && kind == 3) {
+    if (fam == FAM_WIDE) {
         // ---- wide softmax head: stage A (output layer + dW_L) then stage B (layers 0, 1 as a 2-layer decoder whose upstream gradient is
         //      the hidden gradient stage A wrote)
         PAG_CHECK_ARG(M <= PAG_MLP_FUSED_WIDE_MAX_M, "pag_mlp_bwd: the fused wide-head backward addresses [M,64] bf16 tensors with 32-bit byte offsets: M %lld > %lld, split the batch",
                       (long long)M, (long long)PAG_MLP_FUSED_WIDE_MAX_M);
         const unsigned grid = fused_grid(M);
-        float *ws = a->wgrad_workspace;
-        float *slabA = ws;
-        ws += (int64_t)grid * 224 * WG_SLAB_COLS;
-        float *slabB0 = ws;
-        ws += (int64_t)grid * 64 * WG_SLAB_COLS;
-        float *slabB1 = ws;
-        ws += (int64_t)grid * 64 * WG_SLAB_COLS;
-        bf16_t *dzh = reinterpret_cast<bf16_t *>(ws);
+        const FusedWorkspace ws(fam, 3, M);
+        float *slabA = ws.slab_at(a->wgrad_workspace, 2), *slabB0 = ws.slab_at(a->wgrad_workspace, 0), *slabB1 = ws.slab_at(a->wgrad_workspace, 1);
+        bf16_t *dzh = reinterpret_cast<bf16_t *>(reinterpret_cast<char *>(a->wgrad_workspace) + ws.dzh);
         BwdParams pa = p;
         pa.W[0] = a->W[2];
         pa.hsave[0] = a->hidden_save[1];
@@ -4016,53 +4046,28 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
         // ---- a companion head on the same input (args->pair): validated before anything is launched
         const pag_mlp_bwd_args *b = a->pair;
         BwdParams ps{};
-        float *slabS0 = nullptr, *slabS1 = nullptr;
         if (b) {
-            PAG_CHECK_ARG(b->wgrad_workspace && fused_kind(b) == 2 && b->n_layers == 2 && !b->pair, "pag_mlp_bwd: pair must be a two-layer narrow softmax head with a fused workspace");
-            PAG_CHECK_ARG(b->x1 == a->x1 && b->x1_layout == PAG_LAYOUT_XCD8 && b->x1_levels == a->x1_levels && b->x1_feats == a->x1_feats && b->in_dim == a->in_dim,
-                          "pag_mlp_bwd: pair must read the same XCD8 input");
-            PAG_CHECK_ARG(b->dx1 == a->dx1 && b->dx1_accumulate && a->dx1 && !a->dx1_accumulate, "pag_mlp_bwd: pair must accumulate into this decoder's dx1");
+            const char *refusal = bwd_pair_refusal(a, b);
+            PAG_CHECK_ARG(!refusal, "pag_mlp_bwd: %s", refusal);
+            PAG_CHECK_ARG(b->wgrad_workspace && !b->pair, "pag_mlp_bwd: pair must bring a fused workspace and no pair of its own");
             PAG_CHECK_ARG(b->wgrad_workspace_bytes >= pag_mlp_bwd_fused_workspace_bytes(b, M), "pag_mlp_bwd: pair wgrad_workspace too small");
             PAG_CHECK_ARG(b->W[0] && b->W[1] && b->b[0] && b->dW[0] && b->dW[1] && b->db[0] && b->db[1] && b->out && b->g_ray && b->g_scale && b->g_index && b->g_ray_scale,
                           "pag_mlp_bwd: pair: NULL weight / bias / gradient / saved output");
-            ps.g_ray = b->g_ray;
-            ps.g_scale = b->g_scale;
-            ps.g_ray_scale = b->g_ray_scale;
-            ps.g_index = b->g_index;
-            ps.out = b->out;
-            ps.grad_out = b->out;
-            ps.k1 = 64;
-            ps.in_dim = b->in_dim;
-            ps.in_pad = 64;
-            ps.out_dim = b->out_dim;
-            ps.act = PAG_ACT_SOFTMAX;
-            ps.W[0] = b->W[0];
-            ps.W[1] = b->W[1];
-            ps.b[0] = b->b[0];
-            ps.M = M;
-            ps.grp_L = p.grp_L;
-            ps.grp_F = p.grp_F;
-            ps.x1 = a->x1;
-            ps.dx1 = a->dx1;
-            slabS0 = b->wgrad_workspace;
-            slabS1 = slabS0 + (int64_t)grid * 64 * WG_SLAB_COLS;
-            ps.slabs[0] = slabS0;
-            ps.slabs[1] = slabS1;
+            const FusedWorkspace wss(FAM_SOFTMAX, 2, M);
+            ps = bwd_params(b, M);
+            ps.slabs[0] = wss.slab_at(b->wgrad_workspace, 0);
+            ps.slabs[1] = wss.slab_at(b->wgrad_workspace, 1);
         }
         launch_bwd_wide_blocks(pa, grid, st);
         PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, wide head)");
-        BwdParams pb = p;
+        BwdParams pb = p;      // a two-layer decoder with a 64-wide "output" layer and no activation, on the dense gradient dzh
         pb.grad_out = dzh;
         pb.out = dzh;
         pb.g_ray = nullptr;
         pb.out_dim = HID;
         pb.act = PAG_ACT_NONE;
-        pb.W[0] = a->W[0];
-        pb.W[1] = a->W[1];
         pb.W[2] = nullptr;
-        pb.b[0] = a->b[0];
         pb.b[1] = nullptr;
-        pb.hsave[0] = a->hidden_save[0];
         pb.hsave[1] = nullptr;
         pb.slabs[0] = slabB0;
         pb.slabs[1] = slabB1;
@@ -4077,11 +4082,11 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
             PairParams pp{pb, ps};
             hipLaunchKernelGGL(mlp_bwd_pair, dim3(grid), dim3(256), PairLds{}.bytes, st, pp);
             PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, layers below the wide head + companion head)");
-            fb.p[3] = FinishParams{slabS0, (int)grid, HID, 64, b->in_dim, p.grp_L, p.grp_F, b->dW[0], b->db[0]};
-            fb.p[4] = FinishParams{slabS1, (int)grid, b->out_dim, 32, HID, 0, 0, b->dW[1], b->db[1]};
+            fb.p[3] = FinishParams{ps.slabs[0], (int)grid, HID, 64, b->in_dim, p.grp_L, p.grp_F, b->dW[0], b->db[0]};
+            fb.p[4] = FinishParams{ps.slabs[1], (int)grid, b->out_dim, 32, HID, 0, 0, b->dW[1], b->db[1]};
             n_fin = 5;
         } else {
-            launch_bwd_fused<2, 0, false, 2>(pb, grid, st);
+            launch_bwd_fused<2, FAM_DENSITY, false, 2>(pb, grid, st);
             PAG_CHECK_LAUNCH("pag_mlp_bwd (fused, layers below the wide head)");
         }
         launch_wgrad_finish(fb, a->out_dim, n_fin, st);
@@ -4089,19 +4094,16 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
         return PAG_OK;
     }
     if (fuse) {
-        // one workgroup per CU, one slab each (its four waves are summed in LDS): [grid][rows_pad][96] f32 per layer, hidden layers first
+        // one workgroup per CU, one slab each (its four waves are summed in LDS), hidden layers first
         const unsigned grid = fused_grid(M);
-        float *ws = a->wgrad_workspace;
-        for (int l = 0; l < a->n_layers; ++l) {
-            p.slabs[l] = ws;
-            ws += (int64_t)grid * (l + 1 < a->n_layers ? 64 : 32) * WG_SLAB_COLS;
-        }
-        p.dz[0] = kind == 1 ? a->dz[0] : nullptr;
-        p.dz0_slots = kind == 1 ? a->dz0_slots : nullptr;
+        const FusedWorkspace ws(fam, a->n_layers, M);
+        for (int l = 0; l < a->n_layers; ++l) p.slabs[l] = ws.slab_at(a->wgrad_workspace, l);
+        p.dz[0] = fam == FAM_COLOUR ? a->dz[0] : nullptr;
+        p.dz0_slots = fam == FAM_COLOUR ? a->dz0_slots : nullptr;
         // colour-like with the per-ray input's gradient requested: dz_0 is written as well (1) or, samples packed ray by ray, summed per (tile, ray) (2)
-        const int dz0 = kind != 1 ? 0 : (a->dz0_slots ? 2 : (a->dz[0] ? 1 : 0));
-        if (a->n_layers == 2) launch_bwd_fused_kind<2>(p, kind, a->dx1_accumulate != 0, dz0, grid, st);
-        else launch_bwd_fused_kind<3>(p, kind, a->dx1_accumulate != 0, dz0, grid, st);
+        const int dz0 = fam != FAM_COLOUR ? 0 : (a->dz0_slots ? 2 : (a->dz[0] ? 1 : 0));
+        if (a->n_layers == 2) launch_bwd_fused_family<2>(p, fam, a->dx1_accumulate != 0, dz0, grid, st);
+        else launch_bwd_fused_family<3>(p, fam, a->dx1_accumulate != 0, dz0, grid, st);
         PAG_CHECK_LAUNCH("pag_mlp_bwd (fused)");
         FinishBatch fb{};
         int max_out = 0;
@@ -4123,15 +4125,9 @@ extern "C" int pag_mlp_bwd(const pag_mlp_bwd_args *a, int64_t M, void *stream) {
         else if (a->n_layers == 2) launch_bwd_wide_mfma<bf16_t, 2>(p, st);
         else launch_bwd_wide_mfma<bf16_t, 3>(p, st);
     } else if (a->mode == PAG_MLP_MFMA_BF16) {
-        if (out_f32 && dx_f32) launch_bwd_mfma<float, float>(p, a->n_layers, st);
-        else if (out_f32) launch_bwd_mfma<float, bf16_t>(p, a->n_layers, st);
-        else if (dx_f32) launch_bwd_mfma<bf16_t, float>(p, a->n_layers, st);
-        else launch_bwd_mfma<bf16_t, bf16_t>(p, a->n_layers, st);
+        with_dtypes(out_f32, dx_f32, [&](auto o, auto dx) { launch_bwd_mfma<decltype(o), decltype(dx)>(p, a->n_layers, st); });
     } else {
-        if (out_f32 && dx_f32) launch_bwd_f32<float, float>(p, a->n_layers, st);
-        else if (out_f32) launch_bwd_f32<float, bf16_t>(p, a->n_layers, st);
-        else if (dx_f32) launch_bwd_f32<bf16_t, float>(p, a->n_layers, st);
-        else launch_bwd_f32<bf16_t, bf16_t>(p, a->n_layers, st);
+        with_dtypes(out_f32, dx_f32, [&](auto o, auto dx) { launch_bwd_f32<decltype(o), decltype(dx)>(p, a->n_layers, st); });
     }
     PAG_CHECK_LAUNCH("pag_mlp_bwd");
     return PAG_OK;

@@ -643,6 +643,28 @@ def test_forward_time_fused_backward_decision(lib):
         ops.WGRAD_FUSED = was
 
 
+def test_decoder_launch_rules_answer_as_recorded(lib):
+    """The host-only decoder launch rules (pag_mlp_fwd_pair / _producer / _composite_supported, pag_mlp_bwd_fused / _pair_supported and
+    pag_mlp_bwd_fused_workspace_bytes) answer on the shipped shapes and on every one- and two-field change of them (tests/mlp_launch_rules.py)
+    what the library answered before the host layer of csrc/mlp.hip was rewritten: the table was recorded from that commit's build."""
+    import json
+    import mlp_launch_rules as R
+    with open(R.FIXTURE) as fh:
+        want = json.load(fh)
+    # recorded elsewhere, not from the code under test: the fixture names the commit whose build answered, and that commit's mlp.hip is not this one
+    assert re.fullmatch(r"[0-9a-f]{40}", want["recorded_from_commit"])
+    assert want["recorded_from_mlp_hip_sha256"] != R.host_layer_sha(os.path.join(REPO, "pagnerf_amd", "csrc", "mlp.hip"))
+    bits, nbytes, flips, base_answers = R.sweep(lib)
+    assert [b for b in base_answers if b[2] != 1] == [], "every base case is a supported shape"
+    assert sorted(k for k, v in flips.items() if not v) == [], "every field of the value lists decides at least one answer"
+    assert len(bits) == want["n_bits"] and len(nbytes) == len(want["bytes"])
+    got = R.to_hex(bits)
+    if got != want["bits"]:
+        first = next(i for i, (g, w) in enumerate(zip(got, want["bits"])) if g != w)
+        pytest.fail("launch rules differ from the recorded table from answer %d on" % (4 * first))
+    assert nbytes == want["bytes"]
+
+
 def test_graph_capacity_buckets_are_geometric_with_hysteresis():
     """pagnerf_amd/graphs.py::_State.capacity: every new capacity is a capture (two warm-up steps, a private memory pool), so batch-to-batch
     noise must not move it: geometric buckets (<= 1/32 of a power of two of filler), immediate growth, shrink only after SHRINK_WINDOW
