@@ -22,425 +22,34 @@
 // FP32 path (PAG_MLP_FP32): one lane per sample, fp32 FMA chains in k order with the weights
 // broadcast from LDS - the parity path (tolerance 1e-5 against the fp32 oracle).
 //
+// ONE translation unit (profiles/README.md, round 10: in units of their own 50 kernels compile to another instruction sequence).  The parameter
+// structs, the shared tile code, the generic kernels and the FP32 path stand in headers that only this file includes:
+//   mlp_params.h   the kernels' parameter structs, DecoderFamily, mlp_grid
+//   mlp_tile.h     the tile code that more than one family uses
+//   mlp_generic.h  mlp_fwd_mfma, mlp_bwd_mfma with their launchers: any shape
+//   mlp_f32.h      mlp_fwd_f32, mlp_bwd_f32: the FP32 path
+// Here, as three sections: the narrow decoders (mlp_fwd_fast, mlp_fwd_density_colour, mlp_bwd_fused, mlp_bwd_pair), the wide softmax head
+// (mlp_fwd_wide_stats, mlp_bwd_wide_blocks, mlp_bwd_wide_mfma, head_composite_fwd_kernel, head_fwd_once_kernel) - in each the helpers that this
+// family alone uses, then its kernels, every launcher behind its kernel - and the host layer: which family an argument block belongs to, the
+// kernels' parameters, the workspace of the fused backward, the extern "C" entry points, with wgrad_finish_kernel and dz0_slots_sum_kernel.
+//
 // Dynamic LDS: a kernel takes its regions from its layout struct in mlp_lds.h (lds_at<T>(smem, L.region)) and its launcher passes the same
-// struct's `bytes` - a region is added there, once.  mlp_fwd_mfma and head_composite_fwd_kernel are the exceptions (mlp_lds.h says why): their
-// carve-up is still a chain that has to be kept in step with FwdLds / HeadCompLds by hand.
+// struct's `bytes` - a region is added there, once.  mlp_fwd_mfma (mlp_generic.h) and head_composite_fwd_kernel are the exceptions (mlp_lds.h
+// says why): their carve-up is still a chain that has to be kept in step with FwdLds / HeadCompLds by hand.
 #include "mlp_common.h"
 #include "mlp_lds.h"
+#include "mlp_params.h"
+#include "mlp_tile.h"
+#include "mlp_generic.h"
+#include "mlp_f32.h"
 
 namespace {
 
-struct FwdParams {
-    const void *x1;
-    const float *x2;
-    const int32_t *x2_index;
-    int k1, k2p, in_dim, in_pad, out_dim, act;
-    const float *W[3];
-    const float *b[3];
-    void *out;
-    void *hsave[2];
-    int64_t M;
-    int grp_L, grp_F;      // x1 in PAG_LAYOUT_XCD8 (bf16 [8][M][8]) when grp_L > 0
-    float *stats;          // optional f32 [M,2]: (max logit * log2e, 1 / sum exp) of the output softmax
-    float *col0_relu;      // optional f32 [M]: relu(x1[m][0]) (strided bf16 x1) - the density read off the colour decoder's input
-    // companion head of mlp_fwd_wide_stats<.., PAIR = true>: a two-layer softmax decoder (out2_dim <= 8, bf16 out2 [M, out2_dim]) on the same x1
-    const float *W2[2];
-    const float *b2[2];
-    void *out2;
-    int out2_dim;
-};
+// ============================================================================================================ the narrow decoders
+// Density-like, colour-like and semantic-like, the first three values of DecoderFamily: the helpers that these kernels alone use, then
+// mlp_fwd_fast, mlp_fwd_density_colour, mlp_bwd_fused and mlp_bwd_pair, each followed by its launcher where it has one (mlp_fwd_density_colour and
+// mlp_bwd_pair are launched by pag_mlp_fwd / pag_mlp_bwd themselves).
 
-struct BwdParams {
-    const void *grad_out;      // same dtype as `out` (autograd hands back the output's dtype); unused in rank-1 mode
-    // rank-1 upstream gradient (composited panoptic heads): g[m][c] = g_scale[m] * g_ray[g_index[m]][c]
-    const float *g_ray;
-    const float *g_scale;
-    const float *g_ray_scale;  // optional per-ray factor: g[m][c] = g_scale[m] * g_ray_scale[g_index[m]] * g_ray[g_index[m]][c]
-    const int32_t *g_index;
-    const void *out;
-    int k1, in_dim, in_pad, out_dim, act;
-    const float *W[3];
-    const void *hsave[2];
-    void *dz[3];
-    void *dx1;
-    int64_t M;
-    int grp_L, grp_F;      // dx1 (and layer-0 weight columns) in PAG_LAYOUT_XCD8 order when grp_L > 0
-    const float *stats;    // forward's softmax statistics + last-layer bias: the wide kernel recomputes the probabilities
-    const float *b_last;
-    int dx1_acc;           // XCD8 dx1: add to the existing contents instead of overwriting
-    const float *dx_col0;  // strided dx1: f32 [M] added to column 0
-    const float *dx_col0_gate;   // optional f32 [M]: the addend counts only where gate[m] > 0 (relu of that column)
-    // fused weight gradients (mlp_bwd_mfma<.., FUSE = true>): the forward's layer-0 input and one slab set per layer
-    const void *x1;            // bf16: [8][M][8] (grp_L > 0) or [M, k1]
-    const float *x2;           // optional f32 [R, k2p] gathered through x2_index (view embedding)
-    const int32_t *x2_index;
-    int k2p;
-    float *slabs[3];           // per layer: f32 [4 * gridDim.x][rows_pad][WG_SLAB_COLS]  (cols 0..63 dW, col 64 db)
-    const float *b[3];         // biases of the hidden layers: mlp_bwd_fused recomputes the hidden activations instead of reading saved ones
-    float *dz0_slots;          // colour-like fused kernel, DZ0 == 2: f32 [(ceil(M / 32) + R)][64] column sums of dz_0 per (tile, ray), row = tile + ray
-};
-
-// Stage W [n_out x n_in] f32 row-major into LDS as bf16 [rows_pad][stride]; zero padding;
-// optional bit-2/3 swap of the column index (see header).
-// Every decoder kernel starts with 3 - 8 of these matrices.  As a loop of one element per iteration (a predicated load, then its store) the
-// prologue ran at one L2 round trip per element - 80 dependent round trips per thread, 23 - 27 k clocks = 10 us per launch whatever the batch
-// (in-kernel clocks: profiles/README.md, round 3).  Here eight loads are issued back to back - unconditionally, from clamped addresses, so that no branch separates them -
-// and the padding is applied to the values afterwards.
-constexpr int STAGE_BATCH = 8;      // 16: slower (registers / code size)
-__device__ void stage_weight(bf16_t *dst, int stride, int rows_pad, int cols_pad, const float *W, int n_out, int n_in,
-                             bool permute, int grp_L = 0, int grp_F = 0) {
-    const int total = rows_pad * cols_pad, step = (int)blockDim.x, last = n_out * n_in - 1;
-    for (int e0 = threadIdx.x; e0 < total; e0 += STAGE_BATCH * step) {
-        float v[STAGE_BATCH];
-        int at[STAGE_BATCH];
-#pragma unroll
-        for (int k = 0; k < STAGE_BATCH; ++k) {
-            const int e = e0 + k * step;
-            const int o = udiv_uniform(e, cols_pad), a = e - o * cols_pad;
-            const int col = grp_L ? grp_col(a, grp_L, grp_F) : a;
-            const bool ok = e < total && o < n_out && col >= 0 && col < n_in;
-            at[k] = e < total ? o * stride + (permute ? swap23(a) : a) : -1;
-            v[k] = W[min(max(o * n_in + col, 0), last)];
-            v[k] = ok ? v[k] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < STAGE_BATCH; ++k)
-            if (at[k] >= 0) dst[at[k]] = (bf16_t)v[k];
-    }
-}
-// Stage W^T: dst[row = input a][col = output o (permuted)]
-__device__ void stage_weight_t(bf16_t *dst, int stride, int rows_pad, int cols_pad, const float *W, int n_out, int n_in,
-                               int grp_L = 0, int grp_F = 0) {
-    const int total = rows_pad * cols_pad, step = (int)blockDim.x, last = n_out * n_in - 1;
-    for (int e0 = threadIdx.x; e0 < total; e0 += STAGE_BATCH * step) {
-        float v[STAGE_BATCH];
-        int at[STAGE_BATCH];
-#pragma unroll
-        for (int k = 0; k < STAGE_BATCH; ++k) {
-            const int e = e0 + k * step;
-            const int o = udiv_uniform(e, rows_pad), a = e - o * rows_pad;      // W's own row-major order (input index fastest): whole cache lines per
-                                                                                // wave load, the transposition happens in the 2-byte LDS stores
-            const int col = grp_L ? grp_col(a, grp_L, grp_F) : a;
-            const bool ok = e < total && o < n_out && col >= 0 && col < n_in;
-            at[k] = e < total ? a * stride + swap23(o) : -1;
-            v[k] = W[min(max(o * n_in + col, 0), last)];
-            v[k] = ok ? v[k] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < STAGE_BATCH; ++k)
-            if (at[k] >= 0) dst[at[k]] = (bf16_t)v[k];
-    }
-}
-
-// Both images of one matrix from ONE pass over it: the natural image (as stage_weight: dst_s[o][a], optionally with the bit-2/3 swap) and the
-// transposed one (as stage_weight_t: dst_t[a][o permuted]).  The backward kernels need W_0 (and W_1) both ways - recomputed forward and W^T chain.
-__device__ void stage_weight_both(bf16_t *dst_s, int stride_s, bool permute_s, bf16_t *dst_t, int stride_t, int out_pad, int in_pad, const float *W,
-                                  int n_out, int n_in, int grp_L = 0, int grp_F = 0) {
-    const int total = out_pad * in_pad, step = (int)blockDim.x, last = n_out * n_in - 1;
-    for (int e0 = threadIdx.x; e0 < total; e0 += STAGE_BATCH * step) {
-        float v[STAGE_BATCH];
-        int as[STAGE_BATCH], at[STAGE_BATCH];
-#pragma unroll
-        for (int k = 0; k < STAGE_BATCH; ++k) {
-            const int e = e0 + k * step;
-            const int o = udiv_uniform(e, in_pad), a = e - o * in_pad;
-            const int col = grp_L ? grp_col(a, grp_L, grp_F) : a;
-            const bool ok = e < total && o < n_out && col >= 0 && col < n_in;
-            as[k] = e < total ? o * stride_s + (permute_s ? swap23(a) : a) : -1;
-            at[k] = a * stride_t + swap23(o);
-            v[k] = W[min(max(o * n_in + col, 0), last)];
-            v[k] = ok ? v[k] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < STAGE_BATCH; ++k)
-            if (as[k] >= 0) {
-                dst_s[as[k]] = (bf16_t)v[k];
-                dst_t[at[k]] = (bf16_t)v[k];
-            }
-    }
-}
-
-// accumulator block -> two B fragments (k-steps 2*blk, 2*blk+1)
-__device__ __forceinline__ void pack_block(const f32x16 &acc, bf16x8 &lo, bf16x8 &hi) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        lo[j] = (bf16_t)acc[j];
-        hi[j] = (bf16_t)acc[8 + j];
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ void store_block_full(T *row_ptr, int ch_base, int h, const f32x16 &acc);
-
-// store one 32-row accumulator block of sample m as 4 groups of 4 consecutive channels
-template <typename T>
-__device__ __forceinline__ void store_block(T *row_ptr, int ch_base, int h, const f32x16 &acc, int n_valid, bool vec_ok) {
-    if (vec_ok && ch_base + 32 <= n_valid) {
-        store_block_full(row_ptr, ch_base, h, acc);
-    } else if (vec_ok) {      // n_valid % 4 == 0: whole groups only
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int c0 = ch_base + 8 * g + 4 * h;
-            if (c0 < n_valid) {
-                if constexpr (sizeof(T) == 4) {
-                    f32x4 v = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-                    *reinterpret_cast<f32x4 *>(row_ptr + c0) = v;
-                } else {
-                    bf16x4 v = {(bf16_t)acc[4 * g], (bf16_t)acc[4 * g + 1], (bf16_t)acc[4 * g + 2], (bf16_t)acc[4 * g + 3]};
-                    *reinterpret_cast<bf16x4 *>(row_ptr + c0) = v;
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int c0 = ch_base + 8 * g + 4 * h;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (c0 + j < n_valid) pag_st(row_ptr + c0 + j, acc[4 * g + j]);
-        }
-    }
-}
-
-// load one 32-row block of sample m in two phases: issue every load of a block first (raw registers), convert later, so that
-// the compiler can keep all of a tile's loads in flight instead of waiting on each one before its conversion
-template <typename T> struct RawVec { typedef f32x4 type; };
-template <> struct RawVec<bf16_t> { typedef bf16x4 type; };
-
-template <typename T>
-__device__ __forceinline__ void load_block_raw(const T *row_ptr, int ch_base, int h, typename RawVec<T>::type (&raw)[4], int n_valid,
-                                               bool vec_ok) {
-    typedef typename RawVec<T>::type V;
-    if (vec_ok && ch_base + 32 <= n_valid) {      // block wholly in range (all but the last block): plain vector loads
-#pragma unroll
-        for (int g = 0; g < 4; ++g) raw[g] = *reinterpret_cast<const V *>(row_ptr + ch_base + 8 * g + 4 * h);
-    } else if (vec_ok) {      // n_valid % 4 == 0: a group is wholly in range or wholly out; branch-free (clamped address + select)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int c0 = ch_base + 8 * g + 4 * h;
-            const bool ok = c0 < n_valid;
-            V v = *reinterpret_cast<const V *>(row_ptr + (ok ? c0 : 0));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = ok ? v[j] : (T)0.0f;
-            raw[g] = v;
-        }
-    } else {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int c0 = ch_base + 8 * g + 4 * h;
-            V v;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = (c0 + j < n_valid) ? row_ptr[c0 + j] : (T)0.0f;
-            raw[g] = v;
-        }
-    }
-}
-template <typename T>
-__device__ __forceinline__ void store_block_full(T *row_ptr, int ch_base, int h, const f32x16 &acc) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        typename RawVec<T>::type v;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = (T)acc[4 * g + j];
-        *reinterpret_cast<typename RawVec<T>::type *>(row_ptr + ch_base + 8 * g + 4 * h) = v;
-    }
-}
-
-template <typename V>
-__device__ __forceinline__ void raw_to_block(const V (&raw)[4], f32x16 &acc) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[4 * g + j] = (float)raw[g][j];
-}
-
-// ---------------------------------------------------------------------------------------- LDS staging
-// In the accumulator layout every lane owns ONE sample row, so a direct global access touches 32 different rows per
-// wave-instruction: rocprofv3 showed the texture-address unit busy 75-85 % of these kernels' time (TA_BUSY_avr vs
-// GRBM_GUI_ACTIVE).  Row-major [M,64] bf16 tiles (32 rows = 4 KiB contiguous) and 32-column blocks of the wide
-// [M,W] tensors therefore go through a wave-private LDS buffer: global side = fully coalesced 16-byte-per-lane
-// accesses, register side = ds_read/ds_write_b64 in accumulator layout.
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// accumulator blocks acc[0..1] (64 columns) of a 32-row tile -> row-major [M,64] bf16 at gtile (= tensor + tile*32*64)
-__device__ __forceinline__ void tile64_store(bf16_t *stg, bf16_t *gtile, int rows_valid, int lane, int r, int h, const f32x16 (&acc)[2]) {
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            bf16x4 v = {(bf16_t)acc[mb][4 * g], (bf16_t)acc[mb][4 * g + 1], (bf16_t)acc[mb][4 * g + 2], (bf16_t)acc[mb][4 * g + 3]};
-            *reinterpret_cast<bf16x4 *>(stg + r * ST_RS + 32 * mb + 8 * g + 4 * h) = v;
-        }
-    wave_lds_sync();
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + (lane >> 3), c = (lane & 7) * 8;
-        bf16x8 v = *reinterpret_cast<const bf16x8 *>(stg + row * ST_RS + c);
-        if (row < rows_valid) *reinterpret_cast<bf16x8 *>(gtile + row * HID + c) = v;
-    }
-    wave_lds_sync();
-}
-// row-major [M,64] bf16 tile -> accumulator-layout raw pieces raw[mb][g]
-__device__ __forceinline__ void tile64_load(bf16_t *stg, const bf16_t *gtile, int rows_valid, int lane, int r, int h, bf16x4 (&raw)[2][4]) {
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + (lane >> 3), c = (lane & 7) * 8;
-        bf16x8 v = zero8();
-        if (row < rows_valid) v = *reinterpret_cast<const bf16x8 *>(gtile + row * HID + c);
-        *reinterpret_cast<bf16x8 *>(stg + row * ST_RS + c) = v;
-    }
-    wave_lds_sync();
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) raw[mb][g] = *reinterpret_cast<const bf16x4 *>(stg + r * ST_RS + 32 * mb + 8 * g + 4 * h);
-    wave_lds_sync();
-}
-// tile64_load in two phases so that the global request of the NEXT tile can be in flight during the current tile's work
-// (these kernels run 2 waves per SIMD: an exposed round trip per tile costs more than anything else in them)
-__device__ __forceinline__ void tile64_fetch(const bf16_t *gtile, int rows_valid, int lane, bf16x8 (&v)[4]) {
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + (lane >> 3), c = (lane & 7) * 8;
-        v[it] = zero8();
-        if (row < rows_valid) v[it] = *reinterpret_cast<const bf16x8 *>(gtile + row * HID + c);
-    }
-}
-__device__ __forceinline__ void tile64_unstage(bf16_t *stg, const bf16x8 (&v)[4], int lane, int r, int h, bf16x4 (&raw)[2][4]) {
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + (lane >> 3), c = (lane & 7) * 8;
-        *reinterpret_cast<bf16x8 *>(stg + row * ST_RS + c) = v[it];
-    }
-    wave_lds_sync();
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) raw[mb][g] = *reinterpret_cast<const bf16x4 *>(stg + r * ST_RS + 32 * mb + 8 * g + 4 * h);
-    wave_lds_sync();
-}
-// columns [col0, col0+32) of rows [0,32) of a row-major [M,W] bf16 tensor (W % 8 == 0) at gtile (= tensor + tile*32*W):
-// staged into LDS columns [lcol, lcol+32) (two tensors can share the buffer: lcol = 0 / 32)
-__device__ __forceinline__ void block32_stage_in(bf16_t *stg, int lcol, const bf16_t *gtile, int W, int col0, int rows_valid, int lane) {
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int row = it * 16 + (lane >> 2), c = (lane & 3) * 8;
-        bf16x8 v = zero8();
-        if (row < rows_valid && col0 + c < W) v = *reinterpret_cast<const bf16x8 *>(gtile + (int64_t)row * W + col0 + c);
-        *reinterpret_cast<bf16x8 *>(stg + row * ST_RS + lcol + c) = v;
-    }
-}
-__device__ __forceinline__ void block32_read(const bf16_t *stg, int lcol, int r, int h, bf16x4 (&raw)[4]) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) raw[g] = *reinterpret_cast<const bf16x4 *>(stg + r * ST_RS + lcol + 8 * g + 4 * h);
-}
-// accumulator block -> columns [col0, col0+32) of the row-major [M,W] bf16 tensor
-__device__ __forceinline__ void block32_store(bf16_t *stg, bf16_t *gtile, int W, int col0, int rows_valid, int lane, int r, int h, const f32x16 &acc) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        bf16x4 v = {(bf16_t)acc[4 * g], (bf16_t)acc[4 * g + 1], (bf16_t)acc[4 * g + 2], (bf16_t)acc[4 * g + 3]};
-        *reinterpret_cast<bf16x4 *>(stg + r * ST_RS + 8 * g + 4 * h) = v;
-    }
-    wave_lds_sync();
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int row = it * 16 + (lane >> 2), c = (lane & 3) * 8;
-        bf16x8 v = *reinterpret_cast<const bf16x8 *>(stg + row * ST_RS + c);
-        if (row < rows_valid && col0 + c < W) *reinterpret_cast<bf16x8 *>(gtile + (int64_t)row * W + col0 + c) = v;
-    }
-    wave_lds_sync();
-}
-
-// upstream gradient block in rank-1 form: z[q] = scale * g_row[32ob + rho(q,h)] (g_row = this sample's ray row, f32 [n])
-__device__ __forceinline__ void rank1_block(const float *g_row, float scale, int ch_base, int h, int n_valid, f32x16 &z) {
-    const bool vec = (n_valid & 3) == 0;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int c0 = ch_base + 8 * g + 4 * h;
-        if (vec) {
-            const bool ok = c0 < n_valid;
-            f32x4 v = *reinterpret_cast<const f32x4 *>(g_row + (ok ? c0 : 0));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[4 * g + j] = ok ? scale * v[j] : 0.0f;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[4 * g + j] = (c0 + j < n_valid) ? scale * g_row[c0 + j] : 0.0f;
-        }
-    }
-}
-
-// same, when every lane of the wave belongs to ONE ray: the row pointer is wave-uniform, so the 8 floats of a group
-// (both lane halves) come from scalar loads and each lane picks its half - no vector-memory traffic at all
-__device__ __forceinline__ void rank1_block_uniform(const float *g_row_u, float scale, int ch_base, int h, int n_valid, f32x16 &z) {
-    // read-only for the whole launch: address space 4 (constant) lets the compiler use s_load for the uniform address
-    typedef const float __attribute__((address_space(4))) cfloat;
-    cfloat *gc = (cfloat *)(uintptr_t)g_row_u;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int c0 = ch_base + 8 * g;                     // uniform
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (c0 + j < n_valid) ? gc[c0 + j] : 0.0f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) z[4 * g + j] = scale * (h ? v[4 + j] : v[j]);
-    }
-}
-
-// hidden layer: acc[2] = bias + W(64 x K) . frags ; K = 16 * nks
-template <int NKS>
-__device__ __forceinline__ void hidden_layer(const bf16_t *Ws, const float *bs, const bf16x8 (&frag)[NKS], int nks, int r, int h,
-                                             f32x16 (&acc)[2]) {
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[mb][q] = bs[32 * mb + rho(q, h)];
-#pragma unroll
-        for (int s = 0; s < NKS; ++s) {
-            if (s < nks) {
-                bf16x8 a = *reinterpret_cast<const bf16x8 *>(Ws + (32 * mb + r) * RS + 16 * s + 8 * h);
-                acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, frag[s], acc[mb], 0, 0, 0);
-            }
-        }
-    }
-}
-
-// The same for the one-wave-per-SIMD fused backward kernels, with the instruction order PINNED.  Left to itself the scheduler emits
-// "ds_read fragment, s_waitcnt lgkmcnt(0), v_mfma" once per k-step - a full LDS round trip in front of every MFMA, and a lone wave
-// has nothing else to run meanwhile (20 such steps were half of a tile's time).  Here: every read of the first two k-steps first,
-// then per k-step its two MFMAs (independent accumulators) while the reads two steps ahead are in flight.
-template <int MBS, int NS, int LEAD_READS>
-__device__ __forceinline__ void mfma_chain_pinned(const bf16_t *Wt, int stride, const bf16x8 (&frag)[NS], int r, int h, f32x16 (&acc)[2]) {
-    bf16x8 a[MBS][NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int mb = 0; mb < MBS; ++mb) a[mb][s] = *reinterpret_cast<const bf16x8 *>(Wt + (32 * mb + r) * stride + 16 * s + 8 * h);
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int mb = 0; mb < MBS; ++mb) acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mb][s], frag[s], acc[mb], 0, 0, 0);
-    constexpr int AHEAD = NS < 2 ? NS : 2;
-    __builtin_amdgcn_sched_group_barrier(0x100, LEAD_READS + AHEAD * MBS, 0);
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        __builtin_amdgcn_sched_group_barrier(0x008, MBS, 0);
-        if (s + AHEAD < NS) __builtin_amdgcn_sched_group_barrier(0x100, MBS, 0);
-    }
-}
-template <int NS>
-__device__ __forceinline__ void hidden_layer_pinned(const bf16_t *Ws, const float *bs, const bf16x8 (&frag)[NS], int r, int h, f32x16 (&acc)[2]) {
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[mb][q] = bs[32 * mb + rho(q, h)];
-    mfma_chain_pinned<2, NS, 8>(Ws, RS, frag, r, h, acc);          // 8 leading reads: the bias blocks (4 x 16 bytes per block)
-    __builtin_amdgcn_sched_barrier(0);
-}
 // acc = W^T-layout weight . fragments, from zero
 template <int MBS, int NS>
 __device__ __forceinline__ void wt_chain_pinned(const bf16_t *Wt, int stride, const bf16x8 (&frag)[NS], int r, int h, f32x16 (&acc)[2]) {
@@ -453,26 +62,7 @@ __device__ __forceinline__ void wt_chain_pinned(const bf16_t *Wt, int stride, co
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// ---------------------------------------------------------------------- swizzled tiles for the fused weight gradients
-// dW = dz^T . a sums over the SAMPLES, which sit on the lanes in every register layout of the backward kernel - both MFMA
-// operands need one transpose.  A wave keeps its 32-sample tiles ([32 samples][64 channels] bf16, 128-byte rows, 4 KiB) in LDS
-// and reads operand fragments with ds_read_b64_tr_b16 (a 4-row x 16-column block per 16 lanes, delivered column-major).
-// 8-byte chunk `c` of row `s` lives at chunk position c ^ tw_f(s): the accumulator-layout stores (lane = sample, 16 lanes =
-// 16 rows, one chunk column) land in 16 different bank pairs, and the 4 rows of a transposed block use 4 different chunk
-// groups, so neither access pattern has bank conflicts (the 32-lane ds_read_b64 of a whole column is 2-way).
-typedef short i16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ int tw_f(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int tw_off(int row, int chunk) { return row * 64 + ((chunk ^ tw_f(row)) << 2); }
-// row-major global pieces (tile64_fetch: piece `it` of a lane = row it*8 + lane/8, channels 8*(lane%8)..+7)
-__device__ __forceinline__ void tw_put_rows(bf16_t *T, const bf16x8 (&v)[4], int lane) {
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + (lane >> 3), ch = (lane & 7) * 2;
-        bf16x4 lo = {v[it][0], v[it][1], v[it][2], v[it][3]}, hi = {v[it][4], v[it][5], v[it][6], v[it][7]};
-        *reinterpret_cast<bf16x4 *>(T + tw_off(row, ch)) = lo;
-        *reinterpret_cast<bf16x4 *>(T + tw_off(row, ch + 1)) = hi;
-    }
-}
+// writers of the swizzled tiles (tw_off, mlp_tile.h)
 // forward-style B fragments of this lane's sample: xf[s] = channels 16s + 8h .. +7
 __device__ __forceinline__ void tw_put_frags(bf16_t *T, const bf16x8 (&xf)[4], int r, int h) {
 #pragma unroll
@@ -519,18 +109,8 @@ __device__ __forceinline__ void relu_mask_pack_put(const bf16_t *Th, bf16_t *Tz,
         hb[2 * mb + 1] = __builtin_bit_cast(bf16x8, u32x4_t{zp[4], zp[5], zp[6], zp[7]});
     }
 }
-// MFMA 32x32x16 operand fragment with k = sample: lane (c = lane & 31, h) gets samples 16ks + 8h .. +7 of channel 32 blk + c
-__device__ __forceinline__ bf16x8 tw_frag(const bf16_t *T, int blk, int ks, int lane) {
-    typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
-    const int li = lane & 15, q = li >> 2, pp = li & 3, g1 = (lane >> 4) & 1, h = lane >> 5;
-    const int chunk = 8 * blk + 4 * g1 + pp, row0 = 16 * ks + 8 * h + q;
-    const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4 *)(T + tw_off(row0, chunk)));
-    const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4 *)(T + tw_off(row0 + 4, chunk)));
-    union { i16x4 v[2]; bf16x8 f; } u;
-    u.v[0] = lo;
-    u.v[1] = hi;
-    return u.f;
-}
+
+// f(std::integral_constant<int, i>{}) for i = 0 .. N - 1
 template <int N, typename Fn>
 __device__ __forceinline__ void static_for(Fn &&f) {
     if constexpr (N > 0) {
@@ -539,295 +119,14 @@ __device__ __forceinline__ void static_for(Fn &&f) {
     }
 }
 
-// ------------------------------------------------------------------------------------------ forward
-constexpr int FWD_WAVES_WIDE = 3;
-constexpr int FWD_WAVES_NARROW = 1;
-template <typename X1T, typename OutT, int NL, int OBMAX>
-__global__ __launch_bounds__(256, (OBMAX > 2 ? FWD_WAVES_WIDE : FWD_WAVES_NARROW)) void mlp_fwd_mfma(FwdParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int OB = (p.out_dim + 31) / 32;
-    // FwdLds(NL, OB), written as a chain: with the run-time OB, absolute offsets compile to different code (see mlp_lds.h)
-    bf16_t *W0s = reinterpret_cast<bf16_t *>(smem);                  // [64][RS] natural k
-    bf16_t *W1s = W0s + 64 * RS;                                     // [64][RS] permuted k (NL == 3)
-    bf16_t *WLs = W1s + (NL == 3 ? 64 * RS : 0);                     // [OB*32][RS] permuted k
-    float *b0s = reinterpret_cast<float *>(WLs + OB * 32 * RS);
-    float *b1s = b0s + 64;
-    float *bLs = b1s + 64;
-    bf16_t *stg = reinterpret_cast<bf16_t *>(bLs + OB * 32) + (threadIdx.x >> 6) * (ST_BYTES / 2);      // wave-private staging tile
-
-    stage_weight(W0s, RS, 64, 64, p.W[0], HID, p.in_dim, false, p.grp_L, p.grp_F);
-    if (NL == 3) stage_weight(W1s, RS, 64, 64, p.W[1], HID, HID, true);
-    stage_weight(WLs, RS, OB * 32, 64, p.W[NL - 1], p.out_dim, HID, true);
-    for (int e = threadIdx.x; e < 64; e += blockDim.x) {
-        b0s[e] = p.b[0][e];
-        b1s[e] = NL == 3 ? p.b[1][e] : 0.0f;
-    }
-    for (int e = threadIdx.x; e < OB * 32; e += blockDim.x) bLs[e] = e < p.out_dim ? p.b[NL - 1][e] : 0.0f;
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int r = lane & 31, h = lane >> 5;
-    const int nks0 = p.in_pad / 16;
-    const int64_t ntiles = (p.M + 31) / 32;
-    const bool vec_out = (p.out_dim % 4) == 0;
-    const X1T *x1 = reinterpret_cast<const X1T *>(p.x1);
-    OutT *out = reinterpret_cast<OutT *>(p.out);
-
-    // layer-0 B fragments straight from memory (features 16s + 8h .. +7 of sample m); the NEXT tile's fragments are
-    // requested before the current tile is computed so that their HBM latency hides under the MFMA / epilogue work
-    auto load_x = [&](int64_t tile, bf16x8 (&xf)[4]) {
-        const int64_t m = tile * 32 + r;
-        const bool live = tile < ntiles && m < p.M;
-        const int64_t mc = live ? m : 0;
-        const int32_t ray = (p.x2 && live) ? p.x2_index[mc] : 0;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int f0 = 16 * s + 8 * h;
-            if (p.grp_L && live)
-                xf[s] = load8(reinterpret_cast<const bf16_t *>(p.x1) + ((int64_t)(2 * s + h) * p.M + mc) * 8);
-            else if (s < nks0 && live && f0 < p.k1)
-                xf[s] = load8(x1 + mc * p.k1 + f0);
-            else if (s < nks0 && live && f0 < p.k1 + p.k2p)
-                xf[s] = load8(p.x2 + (int64_t)ray * p.k2p + (f0 - p.k1));
-            else
-                xf[s] = zero8();
-            // columns at or beyond in_dim are absent, whatever they hold: a NaN there must not meet its zero weight (the group of 8 that
-            // straddles in_dim and those behind it; XCD8 has in_dim = levels * feats, its padding positions are the encoders' zeros)
-            if (!p.grp_L && f0 + 8 > p.in_dim) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (f0 + j >= p.in_dim) xf[s][j] = (bf16_t)0.0f;
-            }
-        }
-    };
-    const int64_t tile_step = (int64_t)gridDim.x * 4;
-    bf16x8 xnext[4];
-    load_x((int64_t)blockIdx.x * 4 + wave, xnext);
-    for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < ntiles; tile += tile_step) {
-        const int64_t m = tile * 32 + r;
-        const bool live = m < p.M;
-        bf16x8 xb[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) xb[s] = xnext[s];
-        load_x(tile + tile_step, xnext);
-        if constexpr (OBMAX <= 2) {     // narrow decoders only (the colour decoder): density = relu(column 0 of its input)
-            if (p.col0_relu && h == 0 && live) p.col0_relu[m] = fmaxf((float)xb[0][0], 0.0f);
-        }
-        if constexpr (OBMAX > 2) {      // keep lane-constant addresses from being hoisted out of the tile loop and spilled
-            asm volatile("" : "+v"(r), "+v"(h));
-        }
-        f32x16 acc[2];
-        bf16x8 hb[4];
-        hidden_layer<4>(W0s, b0s, xb, nks0, r, h, acc);
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[mb][q] = fmaxf(acc[mb][q], 0.0f);
-            pack_block(acc[mb], hb[2 * mb], hb[2 * mb + 1]);
-        }
-        const int rows_valid = (int)min((int64_t)32, p.M - tile * 32);
-        if (p.hsave[0]) tile64_store(stg, reinterpret_cast<bf16_t *>(p.hsave[0]) + tile * 32 * HID, rows_valid, lane, r, h, acc);
-        if (NL == 3) {
-            hidden_layer<4>(W1s, b1s, hb, 4, r, h, acc);
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) acc[mb][q] = fmaxf(acc[mb][q], 0.0f);
-                pack_block(acc[mb], hb[2 * mb], hb[2 * mb + 1]);
-            }
-            if (p.hsave[1]) tile64_store(stg, reinterpret_cast<bf16_t *>(p.hsave[1]) + tile * 32 * HID, rows_valid, lane, r, h, acc);
-        }
-        // ---- output layer
-        auto out_block = [&](int ob, f32x16 &o) __attribute__((always_inline)) {      // bias + W_L[32ob .. 32ob+31, :] . h : 4 MFMAs
-#pragma unroll
-            for (int q = 0; q < 16; ++q) o[q] = bLs[32 * ob + rho(q, h)];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                bf16x8 a = *reinterpret_cast<const bf16x8 *>(WLs + (32 * ob + r) * RS + 16 * s + 8 * h);
-                o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, hb[s], o, 0, 0, 0);
-            }
-        };
-        constexpr float LOG2E = 1.4426950408889634f;
-        if constexpr (OBMAX > 2) {
-            // Wide heads (e.g. 200 instance logits): ONE 32-channel block is live at a time.  Softmax is computed online
-            // (running max / sum over the blocks), then the blocks are recomputed (4 MFMAs each - the matrix cores are
-            // idle anyway) to be normalised and stored.  Holding all 7 blocks took 256 VGPRs = 1 wave per SIMD with every
-            // latency exposed; this form fits 128 VGPRs = 4 waves per SIMD.
-            float M_ = 0.0f, inv = 1.0f;
-            if (p.act == PAG_ACT_SOFTMAX) {
-                float mrun = -INFINITY, srun = 0.0f;
-                for (int ob = 0; ob < OB; ++ob) {
-                    f32x16 o;
-                    out_block(ob, o);
-                    const bool lastb = ob == OB - 1;
-                    float bm = -INFINITY;
-#pragma unroll
-                    for (int q = 0; q < 16; ++q)
-                        if (!lastb || 32 * ob + rho(q, h) < p.out_dim) bm = fmaxf(bm, o[q]);
-                    const float mn = fmaxf(mrun, bm);
-                    float bs = 0.0f;
-                    const float mns = mn * LOG2E;
-#pragma unroll
-                    for (int q = 0; q < 16; ++q)
-                        if (!lastb || 32 * ob + rho(q, h) < p.out_dim) bs += __builtin_amdgcn_exp2f(fmaf(o[q], LOG2E, -mns));
-                    srun = srun * __builtin_amdgcn_exp2f((mrun - mn) * LOG2E) + bs;
-                    mrun = mn;
-                }
-                const float mo = __shfl_xor(mrun, 32), so = __shfl_xor(srun, 32);
-                M_ = fmaxf(mrun, mo);
-                const float S_ = srun * __builtin_amdgcn_exp2f((mrun - M_) * LOG2E) + so * __builtin_amdgcn_exp2f((mo - M_) * LOG2E);
-                inv = 1.0f / S_;
-            }
-            const float Ms = M_ * LOG2E;
-            if (p.stats && p.act == PAG_ACT_SOFTMAX && live && h == 0) {
-                float2 st2 = {Ms, inv};
-                *reinterpret_cast<float2 *>(p.stats + 2 * m) = st2;
-            }
-            for (int ob = 0; ob < (p.out ? OB : 0); ++ob) {      // out == NULL: statistics only (pag_head_composite_fwd rebuilds)
-                f32x16 o;
-                out_block(ob, o);
-                if (p.act == PAG_ACT_SOFTMAX) {
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) o[q] = __builtin_amdgcn_exp2f(fmaf(o[q], LOG2E, -Ms)) * inv;
-                } else if (p.act == PAG_ACT_SIGMOID) {
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) o[q] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-LOG2E * o[q]));
-                }
-                if constexpr (sizeof(OutT) == 2) {
-                    if ((p.out_dim & 7) == 0)
-                        block32_store(stg, reinterpret_cast<bf16_t *>(p.out) + tile * 32 * p.out_dim, p.out_dim, 32 * ob, rows_valid, lane, r, h, o);
-                    else if (live)
-                        store_block(out + m * p.out_dim, 32 * ob, h, o, p.out_dim, vec_out);
-                } else {
-                    if (live) store_block(out + m * p.out_dim, 32 * ob, h, o, p.out_dim, vec_out);
-                }
-            }
-        } else {
-            f32x16 o[OBMAX];
-#pragma unroll
-            for (int ob = 0; ob < OBMAX; ++ob)
-                if (ob < OB) out_block(ob, o[ob]);
-            // Output activations on the accumulators.  The bf16 path uses the hardware exp2 / rcp (v_exp_f32, v_rcp_f32:
-            // ~1 ulp) - an accurate expf() and a true division per element made this epilogue 5400 VALU instructions per
-            // 32-sample tile and the kernel VALU-bound (rocprofv3 SQ_INSTS_VALU); only the last block can hold padding rows.
-            if (p.act == PAG_ACT_SIGMOID) {
-#pragma unroll
-                for (int ob = 0; ob < OBMAX; ++ob)
-                    if (ob < OB)
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) o[ob][q] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-LOG2E * o[ob][q]));
-            } else if (p.act == PAG_ACT_SOFTMAX) {
-                float mx = -INFINITY;
-#pragma unroll
-                for (int ob = 0; ob < OBMAX; ++ob)
-                    if (ob < OB)
-#pragma unroll
-                        for (int q = 0; q < 16; ++q)
-                            if (ob < OB - 1 || 32 * ob + rho(q, h) < p.out_dim) mx = fmaxf(mx, o[ob][q]);
-                mx = fmaxf(mx, __shfl_xor(mx, 32));
-                const float mxs = mx * LOG2E;
-                float sum = 0.0f;
-#pragma unroll
-                for (int ob = 0; ob < OBMAX; ++ob)
-                    if (ob < OB)
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) {
-                            const float e = (ob < OB - 1 || 32 * ob + rho(q, h) < p.out_dim) ? __builtin_amdgcn_exp2f(fmaf(o[ob][q], LOG2E, -mxs)) : 0.0f;
-                            o[ob][q] = e;
-                            sum += e;
-                        }
-                sum += __shfl_xor(sum, 32);
-                const float inv = 1.0f / sum;
-#pragma unroll
-                for (int ob = 0; ob < OBMAX; ++ob)
-                    if (ob < OB)
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) o[ob][q] *= inv;
-            }
-            if (live) {
-#pragma unroll
-                for (int ob = 0; ob < OBMAX; ++ob)
-                    if (ob < OB) store_block(out + m * p.out_dim, 32 * ob, h, o[ob], p.out_dim, vec_out);
-            }
-        }
-    }
-}
-
 // ------------------------------------------------------------------ forward, production decoder shapes: straight-line tile loops
-// mlp_fwd_mfma above serves every layout / dtype / activation through run-time branches: 62 branches per tile, and past every join the
+// mlp_fwd_mfma (mlp_generic.h) serves every layout / dtype / activation through run-time branches: 62 branches per tile, and past every join the
 // compiler waits for ALL loads in flight (it no longer counts them) - the next tile's prefetch was waited for right after it was
 // issued; 45 - 58 % VALU-busy, the rest stalls.  The decoder shapes of the panoptic nef (pc_nerf/panoptic_nef.py:114-164: density-like,
 // colour-like, semantic-like, the wide instance head) get dedicated kernels, like their backward (mlp_bwd_fused): no branch in the tile
 // loop at all.  Every global access goes through a buffer descriptor - out-of-range lanes (rows past M, channels past out_dim, the
 // half-waves that hold no output channel) get an offset past the end: their loads return 0, their stores are dropped - the weight chains
 // use the pinned read-ahead order, and the element-wise arithmetic is written on pairs (packed fp32).
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-constexpr unsigned BUF_OOB = 0x80000000u;         // added to an offset < 2^30: past any descriptor's range (tensors here are <= 2^30 bytes:
-constexpr unsigned BUF_OOB_ROW = 0x40000000u;     // M <= 2^24 rows of <= 64 bytes).  Dead PIECE + dead ROW = 0xC0000000: the sum must not wrap to 0
-
-__device__ __forceinline__ void out_block_pinned(const bf16_t *WLs, const float *bLs, int ob, const bf16x8 (&hb)[4], int r, int h, f32x16 &o) {
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) o[q] = bLs[32 * ob + rho(q, h)];
-    bf16x8 a[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) a[s] = *reinterpret_cast<const bf16x8 *>(WLs + (32 * ob + r) * RS + 16 * s + 8 * h);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], hb[s], o, 0, 0, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);          // 4 bias reads + 4 weight fragments, then the chain
-    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-    __builtin_amdgcn_sched_barrier(0);
-}
-// relu + bf16 B fragments of the next layer
-__device__ __forceinline__ void relu_pack(f32x16 (&acc)[2], bf16x8 (&hb)[4]) {
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[mb][q] = fmaxf(acc[mb][q], 0.0f);
-        pack_block(acc[mb], hb[2 * mb], hb[2 * mb + 1]);
-    }
-}
-// accumulator blocks (64 columns, 32 rows) -> row-major [M,64] bf16 through the wave's staging buffer; rows past M are dropped
-template <typename RS_T>
-__device__ __forceinline__ void tile64_store_buf(bf16_t *stg, RS_T rs, unsigned tile_off, int lane, int r, int h, const f32x16 (&acc)[2]) {
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            bf16x4 v = {(bf16_t)acc[mb][4 * g], (bf16_t)acc[mb][4 * g + 1], (bf16_t)acc[mb][4 * g + 2], (bf16_t)acc[mb][4 * g + 3]};
-            *reinterpret_cast<bf16x4 *>(stg + r * ST_RS + 32 * mb + 8 * g + 4 * h) = v;
-        }
-    wave_lds_sync();
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + (lane >> 3), c = (lane & 7) * 8;
-        const u32x4 v = *reinterpret_cast<const u32x4 *>(stg + row * ST_RS + c);
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs, tile_off + row * (HID * 2) + c * 2, 0, 0);
-    }
-    wave_lds_sync();
-}
-
-// the same with only the first rows_valid rows written (tiles that end with their ray)
-template <typename RS_T>
-__device__ __forceinline__ void tile64_store_buf_rows(bf16_t *stg, RS_T rs, unsigned tile_off, int rows_valid, int lane, int r, int h, const f32x16 (&acc)[2]) {
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            bf16x4 v = {(bf16_t)acc[mb][4 * g], (bf16_t)acc[mb][4 * g + 1], (bf16_t)acc[mb][4 * g + 2], (bf16_t)acc[mb][4 * g + 3]};
-            *reinterpret_cast<bf16x4 *>(stg + r * ST_RS + 32 * mb + 8 * g + 4 * h) = v;
-        }
-    wave_lds_sync();
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + (lane >> 3), c = (lane & 7) * 8;
-        const u32x4 v = *reinterpret_cast<const u32x4 *>(stg + row * ST_RS + c);
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs, row < rows_valid ? tile_off + row * (HID * 2) + c * 2 : BUF_OOB, 0, 0);
-    }
-    wave_lds_sync();
-}
 
 // KIND 0: XCD8 bf16 input, no output activation, bf16 out, out_dim % 4 == 0 (<= 32)                 (density decoder)
 // KIND 1: bf16 x1 [M,16] + f32 x2 [R,32] through x2_index, sigmoid, f32 out, out_dim <= 4, col0_relu   (colour decoder)
@@ -964,6 +263,17 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_fast(FwdParams p) {
     }
 }
 
+constexpr int FAST_FWD_GRID_CAP = 768;      // three workgroups per CU are resident: one round, tiles grid-strided (1536 ran two rounds with a ragged second: colour forward 63 -> 57 us)
+template <int KIND>
+void launch_fwd_fast(const FwdParams &p, int n_layers, bool save, hipStream_t st) {
+    const dim3 grid(std::min<unsigned>(mlp_grid(p.M), FAST_FWD_GRID_CAP)), block(256);
+    const size_t lds = FwdLds(n_layers, 1).bytes;
+    if (n_layers == 2 && save) hipLaunchKernelGGL((mlp_fwd_fast<2, KIND, true>), grid, block, lds, st, p);
+    else if (n_layers == 2) hipLaunchKernelGGL((mlp_fwd_fast<2, KIND, false>), grid, block, lds, st, p);
+    else if (save) hipLaunchKernelGGL((mlp_fwd_fast<3, KIND, true>), grid, block, lds, st, p);
+    else hipLaunchKernelGGL((mlp_fwd_fast<3, KIND, false>), grid, block, lds, st, p);
+}
+
 // Density decoder and colour decoder in ONE launch (pag_mlp_fwd_args.x1_producer): the colour decoder's x1 is the density decoder's [M,16] output
 // (pc_nerf/panoptic_delta_nef.py:184 -> :198-203).  As two launches the second re-reads what the first just wrote and each pays its own ramp and tail
 // (81 + 58 us per 2.1 M samples).  Here a wave runs mlp_fwd_fast<2, 0> and then mlp_fwd_fast<3, 1> on its tile: the density features are written as
@@ -1071,499 +381,6 @@ __global__ __launch_bounds__(256, CD_WAVES) void mlp_fwd_density_colour(FwdParam
         for (int j = 0; j < 4; ++j) {
             const float y = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-LOG2E * o[j]));
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y), rs_oc, ooff_c[j] + obase_c, 0, 0);
-        }
-    }
-}
-
-// Wide softmax head (three layers, XCD8 input, 192 < out_dim <= 224), statistics only: the forward of the instance head writes the
-// per-sample (max logit * log2e, 1 / sum exp) and the last hidden layer; pag_head_composite_fwd and the backward rebuild the
-// probabilities from them.  One 32-channel block is live at a time (online softmax over the blocks); block k+1's MFMAs are issued
-// before block k's exponentials so that the matrix pipe runs under them.
-// PAIR: a second, narrow softmax decoder on the same input (the semantic head next to the instance head: both read the panoptic
-// features) is evaluated on the tile while it is in registers - its own launch was one more 268 MB read of the features.  The weights
-// of both decoders then take 66 KiB: 8 waves share them (512 threads, one workgroup per CU) instead of two 4-wave workgroups.
-constexpr int WIDE_FWD_PAIR_THREADS = 1024;
-constexpr int wide_fwd_waves(bool pair) { return (pair ? WIDE_FWD_PAIR_THREADS : 256) / 64; }
-template <bool SAVE0, bool PAIR>
-__global__ __launch_bounds__(PAIR ? WIDE_FWD_PAIR_THREADS : 256, PAIR ? 1 : 2) void mlp_fwd_wide_stats(FwdParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int OB = 7;
-    constexpr float LOG2E = 1.4426950408889634f;
-    const int NW = blockDim.x >> 6;
-    constexpr FwdLds L(3, OB, wide_fwd_waves(PAIR), PAIR);
-    bf16_t *W0s = lds_at<bf16_t>(smem, L.W0), *W1s = lds_at<bf16_t>(smem, L.W1);
-    bf16_t *WLs = lds_at<bf16_t>(smem, L.WL);                        // [OB*32][RS] permuted k
-    bf16_t *W0s2 = lds_at<bf16_t>(smem, L.W0p), *WLs2 = lds_at<bf16_t>(smem, L.WLp);      // PAIR: [64][RS] natural k, [32][RS] permuted k
-    float *b0s = lds_at<float>(smem, L.b0), *b1s = lds_at<float>(smem, L.b1), *bLs = lds_at<float>(smem, L.bL);
-    float *b0s2 = lds_at<float>(smem, L.b0p), *bLs2 = lds_at<float>(smem, L.bLp);
-    bf16_t *stg = lds_at<bf16_t>(smem, L.stg) + (threadIdx.x >> 6) * (L.stg_stride / 2);
-    stage_weight(W0s, RS, 64, 64, p.W[0], HID, p.in_dim, false, p.grp_L, p.grp_F);
-    stage_weight(W1s, RS, 64, 64, p.W[1], HID, HID, true);
-    stage_weight(WLs, RS, OB * 32, 64, p.W[2], p.out_dim, HID, true);
-    if constexpr (PAIR) {
-        stage_weight(W0s2, RS, 64, 64, p.W2[0], HID, p.in_dim, false, p.grp_L, p.grp_F);
-        stage_weight(WLs2, RS, 32, 64, p.W2[1], p.out2_dim, HID, true);
-        for (int e = threadIdx.x; e < 64; e += blockDim.x) b0s2[e] = p.b2[0][e];
-        for (int e = threadIdx.x; e < 32; e += blockDim.x) bLs2[e] = e < p.out2_dim ? p.b2[1][e] : 0.0f;
-    }
-    for (int e = threadIdx.x; e < 64; e += blockDim.x) {
-        b0s[e] = p.b[0][e];
-        b1s[e] = p.b[1][e];
-    }
-    // padding channels: a bias of -1e30 makes their exponential exactly 0 and never the maximum
-    for (int e = threadIdx.x; e < OB * 32; e += blockDim.x) bLs[e] = e < p.out_dim ? p.b[2][e] : -1e30f;
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int64_t M = p.M, ntiles = (M + 31) / 32;
-    const int64_t tile_step = (int64_t)gridDim.x * NW;
-    const auto rs_x1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.x1), 0, (int)(M * 128), 0x00020000);
-    const auto rs_st = __builtin_amdgcn_make_buffer_rsrc(p.stats, 0, (int)(M * 8), 0x00020000);
-    const auto rs_o2 = __builtin_amdgcn_make_buffer_rsrc(PAIR ? p.out2 : nullptr, 0, (int)(M * (PAIR ? p.out2_dim : 0) * 2), 0x00020000);
-    unsigned ooff2[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ooff2[j] = (PAIR && 4 * h + j < p.out2_dim) ? (unsigned)((r * p.out2_dim + 4 * h + j) * 2) : BUF_OOB;
-    const auto rs_h0 = __builtin_amdgcn_make_buffer_rsrc(SAVE0 ? p.hsave[0] : nullptr, 0, (int)(M * HID * 2), 0x00020000);
-    const auto rs_h1 = __builtin_amdgcn_make_buffer_rsrc(p.hsave[1], 0, (int)(M * HID * 2), 0x00020000);
-    unsigned xoff[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) xoff[s] = (unsigned)(((int64_t)(2 * s + h) * M + r) * 16);
-    const unsigned soff = h == 0 ? (unsigned)(r * 8) : BUF_OOB;
-    auto row_live = [&](int64_t tile) __attribute__((always_inline)) { return tile * 32 + r < M; };
-    auto load_x = [&](int64_t tile, bf16x8 (&xf)[4]) __attribute__((always_inline)) {
-        const unsigned base = row_live(tile) ? (unsigned)(tile * 32) * 16u : BUF_OOB;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) xf[s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_x1, xoff[s] + base, 0, 0));
-    };
-    int64_t tile = (int64_t)blockIdx.x * NW + wave;
-    bf16x8 xn[4];
-    load_x(tile, xn);
-    for (; tile < ntiles; tile += tile_step) {
-        const bool live = row_live(tile);
-        const unsigned row0 = (unsigned)(tile * 32);
-        bf16x8 xb[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) xb[s] = xn[s];
-        load_x(tile + tile_step, xn);
-        f32x16 acc[2];
-        bf16x8 hb[4];
-        if constexpr (PAIR) {      // the companion head: hidden layer, <= 8 logits, softmax (as mlp_fwd_fast<2, 2, false>)
-            f32x16 o2;
-            hidden_layer_pinned<4>(W0s2, b0s2, xb, r, h, acc);
-            relu_pack(acc, hb);
-            out_block_pinned(WLs2, bLs2, 0, hb, r, h, o2);
-            float mx = -INFINITY;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * h + j < p.out2_dim) mx = fmaxf(mx, o2[j]);
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float mxs = mx * LOG2E;
-            float e[4], sum = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                e[j] = (4 * h + j < p.out2_dim) ? __builtin_amdgcn_exp2f(fmaf(o2[j], LOG2E, -mxs)) : 0.0f;
-                sum += e[j];
-            }
-            sum += __shfl_xor(sum, 32);
-            const float inv2 = 1.0f / sum;
-            const unsigned obase = live ? row0 * (unsigned)(p.out2_dim * 2) : BUF_OOB_ROW;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bf16_t y = (bf16_t)(e[j] * inv2);
-                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, y), rs_o2, ooff2[j] + obase, 0, 0);
-            }
-        }
-        hidden_layer_pinned<4>(W0s, b0s, xb, r, h, acc);
-        relu_pack(acc, hb);
-        if constexpr (SAVE0) tile64_store_buf(stg, rs_h0, row0 * (HID * 2), lane, r, h, acc);
-        hidden_layer_pinned<4>(W1s, b1s, hb, r, h, acc);
-        relu_pack(acc, hb);
-        tile64_store_buf(stg, rs_h1, row0 * (HID * 2), lane, r, h, acc);
-        // online softmax statistics over the OB blocks
-        float mrun = -INFINITY, srun = 0.0f;
-        f32x16 o, on;
-        out_block_pinned(WLs, bLs, 0, hb, r, h, o);
-#pragma unroll
-        for (int ob = 0; ob < OB; ++ob) {
-            if (ob + 1 < OB) out_block_pinned(WLs, bLs, ob + 1, hb, r, h, on);
-            float bm = fmaxf(o[0], o[1]);
-#pragma unroll
-            for (int q = 2; q < 16; ++q) bm = fmaxf(bm, o[q]);
-            const float mn = fmaxf(mrun, bm);
-            const f32x2 l2 = {LOG2E, LOG2E}, nm2 = {-mn * LOG2E, -mn * LOG2E};
-            f32x2 bs2 = {0.0f, 0.0f};
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const f32x2 t = f32x2{o[2 * q], o[2 * q + 1]} * l2 + nm2;
-                bs2 += f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-            }
-            srun = srun * __builtin_amdgcn_exp2f((mrun - mn) * LOG2E) + (bs2[0] + bs2[1]);
-            mrun = mn;
-            if (ob + 1 < OB) o = on;
-        }
-        const float mo = __shfl_xor(mrun, 32), so = __shfl_xor(srun, 32);
-        const float M_ = fmaxf(mrun, mo);
-        const float S_ = srun * __builtin_amdgcn_exp2f((mrun - M_) * LOG2E) + so * __builtin_amdgcn_exp2f((mo - M_) * LOG2E);
-        const u32x2 st2 = {__builtin_bit_cast(unsigned, M_ * LOG2E), __builtin_bit_cast(unsigned, 1.0f / S_)};
-        __builtin_amdgcn_raw_buffer_store_b64(st2, rs_st, live ? soff + row0 * 8 : BUF_OOB, 0, 0);
-    }
-}
-
-// ----------------------------------------------------------------------------------------- backward
-// 2 waves per SIMD: without the bound the 3-layer narrow variants took 252 VGPRs + 36 AGPRs (1 wave per SIMD); asking for 2 makes them fit 254 with no
-// scratch.  The 33..64-output variants (OBMAX 2) would spill 150 - 350 B and stay at 1.
-constexpr int BWD_WAVES = 2;
-template <typename OutT, typename DxT, int NL, int OBMAX>
-__global__ __launch_bounds__(256, (OBMAX == 2 ? 1 : BWD_WAVES)) void mlp_bwd_mfma(BwdParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int OB = (p.out_dim + 31) / 32;
-    const BwdLds L(NL, OB);
-    const int RSL = L.rsl;
-    bf16_t *WLt = lds_at<bf16_t>(smem, L.WLt);                   // [64 in][RSL]  k = output channel (permuted)
-    bf16_t *W1t = lds_at<bf16_t>(smem, L.W1t);                   // [64][RS]      (NL == 3)
-    bf16_t *W0t = lds_at<bf16_t>(smem, L.W0t);                   // [64 in-feature rows][RS]
-    stage_weight_t(WLt, RSL, 64, OB * 32, p.W[NL - 1], p.out_dim, HID);
-    if (NL == 3) stage_weight_t(W1t, RS, 64, 64, p.W[1], HID, HID);
-    if (p.dx1) stage_weight_t(W0t, RS, 64, 64, p.W[0], HID, p.in_dim, p.grp_L, p.grp_F);
-    bf16_t *stg = lds_at<bf16_t>(smem, L.stg) + (threadIdx.x >> 6) * (L.stg_stride / 2);      // wave-private staging tile
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int r = lane & 31, h = lane >> 5;
-    const int64_t ntiles = (p.M + 31) / 32;
-    const bool vec_out = (p.out_dim % 4) == 0;
-    const OutT *outp = reinterpret_cast<const OutT *>(p.out);
-
-    typedef typename RawVec<OutT>::type RawO;
-    constexpr bool PREFETCH = OBMAX <= 2;          // registers allow keeping the next tile's gradients in flight
-    auto load_g = [&](int64_t tile, RawO (&rz)[OBMAX][4], RawO (&ry)[OBMAX][4]) {
-        const int64_t m = tile * 32 + r;
-        const int64_t mc = (tile < ntiles && m < p.M) ? m : p.M - 1;
-        const OutT *gop = reinterpret_cast<const OutT *>(p.grad_out) + mc * p.out_dim;
-        if (!p.g_ray) {
-#pragma unroll
-            for (int ob = 0; ob < OBMAX; ++ob)
-                if (ob < OB) load_block_raw(gop, 32 * ob, h, rz[ob], p.out_dim, vec_out);
-        }
-        if (p.act != PAG_ACT_NONE) {
-#pragma unroll
-            for (int ob = 0; ob < OBMAX; ++ob)
-                if (ob < OB) load_block_raw(outp + mc * p.out_dim, 32 * ob, h, ry[ob], p.out_dim, vec_out);
-        }
-    };
-    const int64_t tile_step = (int64_t)gridDim.x * 4;
-    RawO nz[PREFETCH ? OBMAX : 1][4], ny[PREFETCH ? OBMAX : 1][4];
-    if constexpr (PREFETCH) load_g((int64_t)blockIdx.x * 4 + wave, nz, ny);
-    bf16x8 hnext[PREFETCH ? NL - 1 : 1][4];      // next tile's hidden rows, in flight during the current tile
-    auto fetch_h = [&](int64_t tile, bf16x8 (&hn)[PREFETCH ? NL - 1 : 1][4]) __attribute__((always_inline)) {
-        if (tile < ntiles) {
-            const int rv = (int)min((int64_t)32, p.M - tile * 32);
-#pragma unroll
-            for (int l = 0; l < NL - 1; ++l)
-                tile64_fetch(reinterpret_cast<const bf16_t *>(p.hsave[l]) + tile * 32 * HID, rv, lane, hn[l]);
-        }
-    };
-    if constexpr (PREFETCH) fetch_h((int64_t)blockIdx.x * 4 + wave, hnext);
-    for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < ntiles; tile += tile_step) {
-        if constexpr (OBMAX > 2) {      // keep lane-constant addresses from being hoisted out of the tile loop and spilled
-            asm volatile("" : "+v"(r), "+v"(h));
-        }
-        const int64_t m = tile * 32 + r;
-        const bool live = m < p.M;
-        const int64_t mc = live ? m : p.M - 1;
-        // ReLU masks of the hidden layers: requested first, consumed after the first MFMA chain
-        const int rows_valid = (int)min((int64_t)32, p.M - tile * 32);
-        bf16x4 hraw[NL - 1][2][4];
-        if constexpr (PREFETCH) {
-#pragma unroll
-            for (int l = 0; l < NL - 1; ++l) tile64_unstage(stg, hnext[l], lane, r, h, hraw[l]);
-            fetch_h(tile + tile_step, hnext);
-        } else {
-#pragma unroll
-            for (int l = 0; l < NL - 1; ++l)
-                tile64_load(stg, reinterpret_cast<const bf16_t *>(p.hsave[l]) + tile * 32 * HID, rows_valid, lane, r, h, hraw[l]);
-        }
-        // dx1_accumulate: the other decoder's gradient pieces are requested now and added at the end of the tile
-        bf16x4 oldx[2][4];
-        if (p.dx1_acc) {
-            const bf16_t *dg = reinterpret_cast<const bf16_t *>(p.dx1);
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    oldx[mb][g] = *reinterpret_cast<const bf16x4 *>(dg + ((int64_t)(4 * mb + g) * p.M + mc) * 8 + 4 * h);
-        }
-        // ---- dz of the output layer -> bf16 B fragments (k-steps of the first backward MFMA chain W_L^T . dz_L)
-        bf16x8 zb[OBMAX > 2 ? 2 : 2 * OBMAX];          // wide heads consume each block's two fragments immediately
-        f32x16 acc[2];
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[mb][q] = 0.0f;
-        const bool tile_full = (tile + 1) * 32 <= p.M;      // wave-uniform: only the last tile has dead lanes
-        auto finish_block = [&](int ob, f32x16 &zz) __attribute__((always_inline)) {      // zero dead lanes, store dz, pack
-            if (!tile_full) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) zz[q] = live ? zz[q] : 0.0f;
-            }
-            const int zi = OBMAX > 2 ? 0 : 2 * ob;
-            pack_block(zz, zb[zi], zb[zi + 1]);
-            if (OBMAX > 2 && (p.out_dim & 7) == 0)
-                block32_store(stg, reinterpret_cast<bf16_t *>(p.dz[NL - 1]) + tile * 32 * p.out_dim, p.out_dim, 32 * ob, rows_valid, lane, r, h, zz);
-            else if (live)
-                store_block(reinterpret_cast<bf16_t *>(p.dz[NL - 1]) + m * p.out_dim, 32 * ob, h, zz, p.out_dim, vec_out);
-            if constexpr (OBMAX > 2) {
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                    for (int half = 0; half < 2; ++half) {
-                        bf16x8 a = *reinterpret_cast<const bf16x8 *>(WLt + (32 * mb + r) * RSL + 16 * (2 * ob + half) + 8 * h);
-                        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, zb[half], acc[mb], 0, 0, 0);
-                    }
-            }
-        };
-        if constexpr (PREFETCH) {
-            f32x16 z[OBMAX];
-            RawO rz[OBMAX][4], ry[OBMAX][4];
-#pragma unroll
-            for (int ob = 0; ob < OBMAX; ++ob)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    rz[ob][g] = nz[ob][g];
-                    ry[ob][g] = ny[ob][g];
-                }
-            load_g(tile + tile_step, nz, ny);
-#pragma unroll
-            for (int ob = 0; ob < OBMAX; ++ob)
-                if (ob < OB) raw_to_block(rz[ob], z[ob]);
-            if (p.g_ray) {
-                const int gi = p.g_index[mc], gi0 = __builtin_amdgcn_readfirstlane(gi);
-                const float sc = p.g_ray_scale ? __fmul_rn(p.g_scale[mc], p.g_ray_scale[gi]) : p.g_scale[mc];
-                if (__all(gi == gi0)) {
-                    const float *g_row_u = p.g_ray + (int64_t)gi0 * p.out_dim;
-#pragma unroll
-                    for (int ob = 0; ob < OBMAX; ++ob)
-                        if (ob < OB) rank1_block_uniform(g_row_u, sc, 32 * ob, h, p.out_dim, z[ob]);
-                } else {
-                    const float *g_row = p.g_ray + (int64_t)gi * p.out_dim;
-#pragma unroll
-                    for (int ob = 0; ob < OBMAX; ++ob)
-                        if (ob < OB) rank1_block(g_row, sc, 32 * ob, h, p.out_dim, z[ob]);
-                }
-            }
-            if (p.act == PAG_ACT_SIGMOID) {
-#pragma unroll
-                for (int ob = 0; ob < OBMAX; ++ob)
-                    if (ob < OB)
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) {
-                            const float y = (float)ry[ob][q >> 2][q & 3];
-                            z[ob][q] = z[ob][q] * y * (1.0f - y);
-                        }
-            } else if (p.act == PAG_ACT_SOFTMAX) {
-                float dot = 0.0f;
-#pragma unroll
-                for (int ob = 0; ob < OBMAX; ++ob)
-                    if (ob < OB)
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) dot += z[ob][q] * (float)ry[ob][q >> 2][q & 3];
-                dot += __shfl_xor(dot, 32);
-#pragma unroll
-                for (int ob = 0; ob < OBMAX; ++ob)
-                    if (ob < OB)
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) z[ob][q] = (float)ry[ob][q >> 2][q & 3] * (z[ob][q] - dot);
-            }
-#pragma unroll
-            for (int ob = 0; ob < OBMAX; ++ob) {
-                if (ob < OB) {
-                    finish_block(ob, z[ob]);
-                } else {
-                    zb[2 * ob] = zero8();
-                    zb[2 * ob + 1] = zero8();
-                }
-            }
-        } else {
-            // wide heads: two passes over the gradient / probability rows (dot product for the softmax backward, then dz)
-            // keep only ONE 32-channel block live at a time instead of all of them (256 VGPRs -> 1 wave per SIMD before).
-            // The passes form one software pipeline over 2*OB steps: the global loads of step s+1 (16 bytes per lane,
-            // fully coalesced) are in flight while step s goes through the LDS staging tile and the MFMAs - profiling
-            // showed this kernel parked on memory 69 % of the time with one exposed round trip per block.
-            const int g_idx1 = p.g_ray ? p.g_index[mc] : 0;
-            const int g_idx0 = __builtin_amdgcn_readfirstlane(g_idx1);
-            const bool g_uni = __all(g_idx1 == g_idx0);      // whole tile inside one ray (the common case)
-            const float *g_row1 = p.g_ray ? p.g_ray + (int64_t)g_idx1 * p.out_dim : nullptr;
-            const float *g_row_u = p.g_ray ? p.g_ray + (int64_t)g_idx0 * p.out_dim : nullptr;
-            const float g_sc1 = p.g_ray ? (p.g_ray_scale ? __fmul_rn(p.g_scale[mc], p.g_ray_scale[g_idx1]) : p.g_scale[mc]) : 0.0f;
-            const bool r1 = p.g_ray != nullptr;
-            const bool need_y = p.act != PAG_ACT_NONE;
-            const int n1 = p.act == PAG_ACT_SOFTMAX ? OB : 0, n_steps = n1 + OB;
-            float dot = 0.0f;
-            bool fast = false;
-            if constexpr (sizeof(OutT) == 2) fast = (p.out_dim & 7) == 0;
-            if (fast) {
-                const bf16_t *gtile_g = reinterpret_cast<const bf16_t *>(p.grad_out) + tile * 32 * p.out_dim;
-                const bf16_t *gtile_y = reinterpret_cast<const bf16_t *>(p.out) + tile * 32 * p.out_dim;
-                bf16x8 cz[2], cy[2], nzr[2], nyr[2];
-                auto gfetch = [&](int ob, bf16x8 (&fz)[2], bf16x8 (&fy)[2]) __attribute__((always_inline)) {
-#pragma unroll
-                    for (int it = 0; it < 2; ++it) {
-                        const int row = it * 16 + (lane >> 2), c = 32 * ob + (lane & 3) * 8;
-                        const bool ok = row < rows_valid && c < p.out_dim;
-                        fz[it] = (ok && !r1) ? *reinterpret_cast<const bf16x8 *>(gtile_g + (int64_t)row * p.out_dim + c) : zero8();
-                        fy[it] = (ok && need_y) ? *reinterpret_cast<const bf16x8 *>(gtile_y + (int64_t)row * p.out_dim + c) : zero8();
-                    }
-                };
-                gfetch(0, cz, cy);
-                for (int step = 0; step < n_steps; ++step) {
-                    const int ob = step < n1 ? step : step - n1;
-                    if (step + 1 < n_steps) gfetch(step + 1 < n1 ? step + 1 : step + 1 - n1, nzr, nyr);
-                    bf16x4 rz1[4], ry1[4];
-#pragma unroll
-                    for (int it = 0; it < 2; ++it) {
-                        const int row = it * 16 + (lane >> 2), c = (lane & 3) * 8;
-                        *reinterpret_cast<bf16x8 *>(stg + row * ST_RS + c) = cz[it];
-                        *reinterpret_cast<bf16x8 *>(stg + row * ST_RS + 32 + c) = cy[it];
-                    }
-                    wave_lds_sync();
-                    block32_read(stg, 0, r, h, rz1);
-                    block32_read(stg, 32, r, h, ry1);
-                    wave_lds_sync();
-                    f32x16 zz;
-                    if (r1 && g_uni) rank1_block_uniform(g_row_u, g_sc1, 32 * ob, h, p.out_dim, zz);
-                    else if (r1) rank1_block(g_row1, g_sc1, 32 * ob, h, p.out_dim, zz);
-                    else raw_to_block(rz1, zz);
-                    if (step < n1) {
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) dot += zz[q] * (float)ry1[q >> 2][q & 3];
-                        if (step == n1 - 1) dot += __shfl_xor(dot, 32);
-                    } else {
-                        if (p.act == PAG_ACT_SIGMOID) {
-#pragma unroll
-                            for (int q = 0; q < 16; ++q) {
-                                const float y = (float)ry1[q >> 2][q & 3];
-                                zz[q] = zz[q] * y * (1.0f - y);
-                            }
-                        } else if (p.act == PAG_ACT_SOFTMAX) {
-#pragma unroll
-                            for (int q = 0; q < 16; ++q) zz[q] = (float)ry1[q >> 2][q & 3] * (zz[q] - dot);
-                        }
-                        finish_block(ob, zz);
-                    }
-#pragma unroll
-                    for (int it = 0; it < 2; ++it) {
-                        cz[it] = nzr[it];
-                        cy[it] = nyr[it];
-                    }
-                }
-            } else {      // generic wide path (fp32 outputs or out_dim % 8 != 0): direct per-lane row accesses
-                const OutT *gop = reinterpret_cast<const OutT *>(p.grad_out) + mc * p.out_dim;
-                const OutT *yop = outp + mc * p.out_dim;
-                for (int step = 0; step < n_steps; ++step) {
-                    const int ob = step < n1 ? step : step - n1;
-                    RawO rz1[4], ry1[4];
-                    if (!r1) load_block_raw(gop, 32 * ob, h, rz1, p.out_dim, vec_out);
-                    if (need_y) load_block_raw(yop, 32 * ob, h, ry1, p.out_dim, vec_out);
-                    f32x16 zz;
-                    if (r1) rank1_block(g_row1, g_sc1, 32 * ob, h, p.out_dim, zz);
-                    else raw_to_block(rz1, zz);
-                    if (step < n1) {
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) dot += zz[q] * (float)ry1[q >> 2][q & 3];
-                        if (step == n1 - 1) dot += __shfl_xor(dot, 32);
-                    } else {
-                        if (p.act == PAG_ACT_SIGMOID) {
-#pragma unroll
-                            for (int q = 0; q < 16; ++q) {
-                                const float y = (float)ry1[q >> 2][q & 3];
-                                zz[q] = zz[q] * y * (1.0f - y);
-                            }
-                        } else if (p.act == PAG_ACT_SOFTMAX) {
-#pragma unroll
-                            for (int q = 0; q < 16; ++q) zz[q] = (float)ry1[q >> 2][q & 3] * (zz[q] - dot);
-                        }
-                        finish_block(ob, zz);
-                    }
-                }
-            }
-        }
-        // ---- back through the output layer: dA = W_L^T . dz_L (already accumulated per block for wide heads),
-        //      masked by the saved ReLU output
-        bf16x8 hb[4];
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-            if constexpr (OBMAX <= 2) {
-#pragma unroll
-                for (int s = 0; s < 2 * OBMAX; ++s) {
-                    if (s < 2 * OB) {
-                        bf16x8 a = *reinterpret_cast<const bf16x8 *>(WLt + (32 * mb + r) * RSL + 16 * s + 8 * h);
-                        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, zb[s], acc[mb], 0, 0, 0);
-                    }
-                }
-            }
-            f32x16 hv;
-            raw_to_block(hraw[NL - 2][mb], hv);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[mb][q] = (hv[q] > 0.0f && live) ? acc[mb][q] : 0.0f;
-            pack_block(acc[mb], hb[2 * mb], hb[2 * mb + 1]);
-        }
-        tile64_store(stg, reinterpret_cast<bf16_t *>(p.dz[NL - 2]) + tile * 32 * HID, rows_valid, lane, r, h, acc);
-        if (NL == 3) {
-            bf16x8 hb2[4];
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) acc[mb][q] = 0.0f;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    bf16x8 a = *reinterpret_cast<const bf16x8 *>(W1t + (32 * mb + r) * RS + 16 * s + 8 * h);
-                    acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, hb[s], acc[mb], 0, 0, 0);
-                }
-                f32x16 hv;
-                raw_to_block(hraw[0][mb], hv);
-#pragma unroll
-                for (int q = 0; q < 16; ++q) acc[mb][q] = (hv[q] > 0.0f && live) ? acc[mb][q] : 0.0f;
-                pack_block(acc[mb], hb2[2 * mb], hb2[2 * mb + 1]);
-            }
-            tile64_store(stg, reinterpret_cast<bf16_t *>(p.dz[0]) + tile * 32 * HID, rows_valid, lane, r, h, acc);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) hb[s] = hb2[s];
-        }
-        // ---- dx1 = (W_0^T . dz_0)[0:k1]
-        if (p.dx1) {
-            DxT *dx = reinterpret_cast<DxT *>(p.dx1);
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) {
-                if (32 * mb < p.k1) {
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) acc[mb][q] = 0.0f;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        bf16x8 a = *reinterpret_cast<const bf16x8 *>(W0t + (32 * mb + r) * RS + 16 * s + 8 * h);
-                        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, hb[s], acc[mb], 0, 0, 0);
-                    }
-                    if (live && !p.grp_L) {
-                        // extra gradient of input column 0 (the density read off the density decoder's first output,
-                        // pc_nerf/panoptic_delta_nef.py:188): added here instead of a zero-padded [M,k1] tensor + add pass
-                        if (p.dx_col0 && mb == 0 && h == 0 && (!p.dx_col0_gate || p.dx_col0_gate[m] > 0.0f)) acc[0][0] += p.dx_col0[m];
-                        store_block(dx + m * p.k1, 32 * mb, h, acc[mb], p.k1, true);
-                    }
-                    if (live && p.grp_L) {      // XCD8: row 32mb + 8g + 4h + j of dx^T -> piece [4mb + g][m][4h + j]
-                        bf16_t *dg = reinterpret_cast<bf16_t *>(p.dx1);
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            bf16x4 *dst = reinterpret_cast<bf16x4 *>(dg + ((int64_t)(4 * mb + g) * p.M + m) * 8 + 4 * h);
-                            if (p.dx1_acc) {      // second decoder on the same input: add to the first one's gradient in place
-#pragma unroll
-                                for (int j = 0; j < 4; ++j) acc[mb][4 * g + j] += (float)oldx[mb][g][j];
-                            }
-                            bf16x4 v = {(bf16_t)acc[mb][4 * g], (bf16_t)acc[mb][4 * g + 1], (bf16_t)acc[mb][4 * g + 2], (bf16_t)acc[mb][4 * g + 3]};
-                            *dst = v;
-                        }
-                    }
-                }
-            }
         }
     }
 }
@@ -2045,6 +862,21 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void mlp_bwd_fused(BwdParams p) {
     });
 }
 
+template <int NL, int KIND, bool DXACC, int OBL = 1, int DZ0 = 0>
+void launch_bwd_fused(const BwdParams &p, unsigned grid, hipStream_t st) {
+    raise_lds_limit<mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>>(LDS_MAX_BYTES);
+    hipLaunchKernelGGL((mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>), dim3(grid), dim3(256), FusedLds(NL, OBL, DZ0).bytes, st, p);
+}
+template <int NL>
+void launch_bwd_fused_family(const BwdParams &p, DecoderFamily fam, bool acc, int dz0, unsigned grid, hipStream_t st) {
+    if (fam == FAM_DENSITY) launch_bwd_fused<NL, FAM_DENSITY, false>(p, grid, st);
+    else if (fam == FAM_COLOUR && dz0 == 2) launch_bwd_fused<NL, FAM_COLOUR, false, 1, 2>(p, grid, st);
+    else if (fam == FAM_COLOUR && dz0 == 1) launch_bwd_fused<NL, FAM_COLOUR, false, 1, 1>(p, grid, st);
+    else if (fam == FAM_COLOUR) launch_bwd_fused<NL, FAM_COLOUR, false>(p, grid, st);
+    else if (acc) launch_bwd_fused<NL, FAM_SOFTMAX, true>(p, grid, st);
+    else launch_bwd_fused<NL, FAM_SOFTMAX, false>(p, grid, st);
+}
+
 // ------------------------------------------------ two decoders on the same XCD8 input, backward in one launch (panoptic heads)
 // The semantic head and the two layers below the instance head's output layer read the same panoptic features and their input
 // gradients are summed.  As two launches (stage B of the instance head writes dx, the semantic head reads it back and adds) the
@@ -2054,9 +886,6 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void mlp_bwd_fused(BwdParams p) {
 //   .s  two layers, rank-1 upstream gradient, softmax with saved bf16 probabilities, out_dim <= 8
 // Same tile images, fragments and instruction sequences as mlp_bwd_fused<2, 0, false, 2> and <2, 2, *>: the weight gradients are
 // bit-identical to the two launches, dx differs by one bf16 rounding less (the sum is formed in fp32).
-struct PairParams {
-    BwdParams i, s;
-};
 __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
     const BwdParams &pi = pp.i, &ps = pp.s;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2384,6 +1213,197 @@ __global__ __launch_bounds__(256, 1) void mlp_bwd_pair(PairParams pp) {
             }
         }
     });
+}
+
+// ========================================================================================================= the wide softmax head
+// Three layers, 193 .. 224 outputs kept as softmax statistics (FAM_WIDE): the helpers that these kernels alone use, then the forward
+// mlp_fwd_wide_stats, the backward mlp_bwd_wide_blocks (fused weight gradients, stage A) and mlp_bwd_wide_mfma, and the per-ray weighted sum of the
+// head's probabilities, head_composite_fwd_kernel and - decoder and sum in one pass - head_fwd_once_kernel; each followed by its launcher
+// (head_composite_fwd_kernel is launched by pag_head_composite_fwd itself).
+
+// columns [col0, col0+32) of rows [0,32) of a row-major [M,W] bf16 tensor (W % 8 == 0) at gtile (= tensor + tile*32*W):
+// staged into LDS columns [lcol, lcol+32) (two tensors can share the buffer: lcol = 0 / 32)
+__device__ __forceinline__ void block32_stage_in(bf16_t *stg, int lcol, const bf16_t *gtile, int W, int col0, int rows_valid, int lane) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int row = it * 16 + (lane >> 2), c = (lane & 3) * 8;
+        bf16x8 v = zero8();
+        if (row < rows_valid && col0 + c < W) v = *reinterpret_cast<const bf16x8 *>(gtile + (int64_t)row * W + col0 + c);
+        *reinterpret_cast<bf16x8 *>(stg + row * ST_RS + lcol + c) = v;
+    }
+}
+
+// writer of a swizzled tile (tw_off, mlp_tile.h) from row-major global pieces (tile64_fetch: piece `it` of a lane = row it*8 + lane/8, channels 8*(lane%8)..+7)
+__device__ __forceinline__ void tw_put_rows(bf16_t *T, const bf16x8 (&v)[4], int lane) {
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const int row = it * 8 + (lane >> 3), ch = (lane & 7) * 2;
+        bf16x4 lo = {v[it][0], v[it][1], v[it][2], v[it][3]}, hi = {v[it][4], v[it][5], v[it][6], v[it][7]};
+        *reinterpret_cast<bf16x4 *>(T + tw_off(row, ch)) = lo;
+        *reinterpret_cast<bf16x4 *>(T + tw_off(row, ch + 1)) = hi;
+    }
+}
+
+// tile64_store_buf (mlp_tile.h) with only the first rows_valid rows written (tiles that end with their ray)
+template <typename RS_T>
+__device__ __forceinline__ void tile64_store_buf_rows(bf16_t *stg, RS_T rs, unsigned tile_off, int rows_valid, int lane, int r, int h, const f32x16 (&acc)[2]) {
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            bf16x4 v = {(bf16_t)acc[mb][4 * g], (bf16_t)acc[mb][4 * g + 1], (bf16_t)acc[mb][4 * g + 2], (bf16_t)acc[mb][4 * g + 3]};
+            *reinterpret_cast<bf16x4 *>(stg + r * ST_RS + 32 * mb + 8 * g + 4 * h) = v;
+        }
+    wave_lds_sync();
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const int row = it * 8 + (lane >> 3), c = (lane & 7) * 8;
+        const u32x4 v = *reinterpret_cast<const u32x4 *>(stg + row * ST_RS + c);
+        __builtin_amdgcn_raw_buffer_store_b128(v, rs, row < rows_valid ? tile_off + row * (HID * 2) + c * 2 : BUF_OOB, 0, 0);
+    }
+    wave_lds_sync();
+}
+
+// Wide softmax head (three layers, XCD8 input, 192 < out_dim <= 224), statistics only: the forward of the instance head writes the
+// per-sample (max logit * log2e, 1 / sum exp) and the last hidden layer; pag_head_composite_fwd and the backward rebuild the
+// probabilities from them.  One 32-channel block is live at a time (online softmax over the blocks); block k+1's MFMAs are issued
+// before block k's exponentials so that the matrix pipe runs under them.
+// PAIR: a second, narrow softmax decoder on the same input (the semantic head next to the instance head: both read the panoptic
+// features) is evaluated on the tile while it is in registers - its own launch was one more 268 MB read of the features.  The weights
+// of both decoders then take 66 KiB: 8 waves share them (512 threads, one workgroup per CU) instead of two 4-wave workgroups.
+constexpr int WIDE_FWD_PAIR_THREADS = 1024;
+constexpr int wide_fwd_waves(bool pair) { return (pair ? WIDE_FWD_PAIR_THREADS : 256) / 64; }
+template <bool SAVE0, bool PAIR>
+__global__ __launch_bounds__(PAIR ? WIDE_FWD_PAIR_THREADS : 256, PAIR ? 1 : 2) void mlp_fwd_wide_stats(FwdParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int OB = 7;
+    constexpr float LOG2E = 1.4426950408889634f;
+    const int NW = blockDim.x >> 6;
+    constexpr FwdLds L(3, OB, wide_fwd_waves(PAIR), PAIR);
+    bf16_t *W0s = lds_at<bf16_t>(smem, L.W0), *W1s = lds_at<bf16_t>(smem, L.W1);
+    bf16_t *WLs = lds_at<bf16_t>(smem, L.WL);                        // [OB*32][RS] permuted k
+    bf16_t *W0s2 = lds_at<bf16_t>(smem, L.W0p), *WLs2 = lds_at<bf16_t>(smem, L.WLp);      // PAIR: [64][RS] natural k, [32][RS] permuted k
+    float *b0s = lds_at<float>(smem, L.b0), *b1s = lds_at<float>(smem, L.b1), *bLs = lds_at<float>(smem, L.bL);
+    float *b0s2 = lds_at<float>(smem, L.b0p), *bLs2 = lds_at<float>(smem, L.bLp);
+    bf16_t *stg = lds_at<bf16_t>(smem, L.stg) + (threadIdx.x >> 6) * (L.stg_stride / 2);
+    stage_weight(W0s, RS, 64, 64, p.W[0], HID, p.in_dim, false, p.grp_L, p.grp_F);
+    stage_weight(W1s, RS, 64, 64, p.W[1], HID, HID, true);
+    stage_weight(WLs, RS, OB * 32, 64, p.W[2], p.out_dim, HID, true);
+    if constexpr (PAIR) {
+        stage_weight(W0s2, RS, 64, 64, p.W2[0], HID, p.in_dim, false, p.grp_L, p.grp_F);
+        stage_weight(WLs2, RS, 32, 64, p.W2[1], p.out2_dim, HID, true);
+        for (int e = threadIdx.x; e < 64; e += blockDim.x) b0s2[e] = p.b2[0][e];
+        for (int e = threadIdx.x; e < 32; e += blockDim.x) bLs2[e] = e < p.out2_dim ? p.b2[1][e] : 0.0f;
+    }
+    for (int e = threadIdx.x; e < 64; e += blockDim.x) {
+        b0s[e] = p.b[0][e];
+        b1s[e] = p.b[1][e];
+    }
+    // padding channels: a bias of -1e30 makes their exponential exactly 0 and never the maximum
+    for (int e = threadIdx.x; e < OB * 32; e += blockDim.x) bLs[e] = e < p.out_dim ? p.b[2][e] : -1e30f;
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int64_t M = p.M, ntiles = (M + 31) / 32;
+    const int64_t tile_step = (int64_t)gridDim.x * NW;
+    const auto rs_x1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.x1), 0, (int)(M * 128), 0x00020000);
+    const auto rs_st = __builtin_amdgcn_make_buffer_rsrc(p.stats, 0, (int)(M * 8), 0x00020000);
+    const auto rs_o2 = __builtin_amdgcn_make_buffer_rsrc(PAIR ? p.out2 : nullptr, 0, (int)(M * (PAIR ? p.out2_dim : 0) * 2), 0x00020000);
+    unsigned ooff2[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ooff2[j] = (PAIR && 4 * h + j < p.out2_dim) ? (unsigned)((r * p.out2_dim + 4 * h + j) * 2) : BUF_OOB;
+    const auto rs_h0 = __builtin_amdgcn_make_buffer_rsrc(SAVE0 ? p.hsave[0] : nullptr, 0, (int)(M * HID * 2), 0x00020000);
+    const auto rs_h1 = __builtin_amdgcn_make_buffer_rsrc(p.hsave[1], 0, (int)(M * HID * 2), 0x00020000);
+    unsigned xoff[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) xoff[s] = (unsigned)(((int64_t)(2 * s + h) * M + r) * 16);
+    const unsigned soff = h == 0 ? (unsigned)(r * 8) : BUF_OOB;
+    auto row_live = [&](int64_t tile) __attribute__((always_inline)) { return tile * 32 + r < M; };
+    auto load_x = [&](int64_t tile, bf16x8 (&xf)[4]) __attribute__((always_inline)) {
+        const unsigned base = row_live(tile) ? (unsigned)(tile * 32) * 16u : BUF_OOB;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) xf[s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_x1, xoff[s] + base, 0, 0));
+    };
+    int64_t tile = (int64_t)blockIdx.x * NW + wave;
+    bf16x8 xn[4];
+    load_x(tile, xn);
+    for (; tile < ntiles; tile += tile_step) {
+        const bool live = row_live(tile);
+        const unsigned row0 = (unsigned)(tile * 32);
+        bf16x8 xb[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) xb[s] = xn[s];
+        load_x(tile + tile_step, xn);
+        f32x16 acc[2];
+        bf16x8 hb[4];
+        if constexpr (PAIR) {      // the companion head: hidden layer, <= 8 logits, softmax (as mlp_fwd_fast<2, 2, false>)
+            f32x16 o2;
+            hidden_layer_pinned<4>(W0s2, b0s2, xb, r, h, acc);
+            relu_pack(acc, hb);
+            out_block_pinned(WLs2, bLs2, 0, hb, r, h, o2);
+            float mx = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (4 * h + j < p.out2_dim) mx = fmaxf(mx, o2[j]);
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const float mxs = mx * LOG2E;
+            float e[4], sum = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                e[j] = (4 * h + j < p.out2_dim) ? __builtin_amdgcn_exp2f(fmaf(o2[j], LOG2E, -mxs)) : 0.0f;
+                sum += e[j];
+            }
+            sum += __shfl_xor(sum, 32);
+            const float inv2 = 1.0f / sum;
+            const unsigned obase = live ? row0 * (unsigned)(p.out2_dim * 2) : BUF_OOB_ROW;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bf16_t y = (bf16_t)(e[j] * inv2);
+                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, y), rs_o2, ooff2[j] + obase, 0, 0);
+            }
+        }
+        hidden_layer_pinned<4>(W0s, b0s, xb, r, h, acc);
+        relu_pack(acc, hb);
+        if constexpr (SAVE0) tile64_store_buf(stg, rs_h0, row0 * (HID * 2), lane, r, h, acc);
+        hidden_layer_pinned<4>(W1s, b1s, hb, r, h, acc);
+        relu_pack(acc, hb);
+        tile64_store_buf(stg, rs_h1, row0 * (HID * 2), lane, r, h, acc);
+        // online softmax statistics over the OB blocks
+        float mrun = -INFINITY, srun = 0.0f;
+        f32x16 o, on;
+        out_block_pinned(WLs, bLs, 0, hb, r, h, o);
+#pragma unroll
+        for (int ob = 0; ob < OB; ++ob) {
+            if (ob + 1 < OB) out_block_pinned(WLs, bLs, ob + 1, hb, r, h, on);
+            float bm = fmaxf(o[0], o[1]);
+#pragma unroll
+            for (int q = 2; q < 16; ++q) bm = fmaxf(bm, o[q]);
+            const float mn = fmaxf(mrun, bm);
+            const f32x2 l2 = {LOG2E, LOG2E}, nm2 = {-mn * LOG2E, -mn * LOG2E};
+            f32x2 bs2 = {0.0f, 0.0f};
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const f32x2 t = f32x2{o[2 * q], o[2 * q + 1]} * l2 + nm2;
+                bs2 += f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
+            }
+            srun = srun * __builtin_amdgcn_exp2f((mrun - mn) * LOG2E) + (bs2[0] + bs2[1]);
+            mrun = mn;
+            if (ob + 1 < OB) o = on;
+        }
+        const float mo = __shfl_xor(mrun, 32), so = __shfl_xor(srun, 32);
+        const float M_ = fmaxf(mrun, mo);
+        const float S_ = srun * __builtin_amdgcn_exp2f((mrun - M_) * LOG2E) + so * __builtin_amdgcn_exp2f((mo - M_) * LOG2E);
+        const u32x2 st2 = {__builtin_bit_cast(unsigned, M_ * LOG2E), __builtin_bit_cast(unsigned, 1.0f / S_)};
+        __builtin_amdgcn_raw_buffer_store_b64(st2, rs_st, live ? soff + row0 * 8 : BUF_OOB, 0, 0);
+    }
+}
+
+template <bool SAVE0, bool PAIR>
+void launch_fwd_wide_stats(const FwdParams &p, unsigned grid, hipStream_t st) {
+    constexpr int NW = wide_fwd_waves(PAIR);
+    raise_lds_limit<mlp_fwd_wide_stats<SAVE0, PAIR>>(LDS_MAX_BYTES);
+    hipLaunchKernelGGL((mlp_fwd_wide_stats<SAVE0, PAIR>), dim3(grid), dim3(NW * 64), FwdLds(3, OB_MAX, NW, PAIR).bytes, st, p);
 }
 
 // -------------------------------------------- wide softmax head: output layer backward + its weight gradient (one launch)
@@ -2727,6 +1747,13 @@ __global__ __launch_bounds__((OB + 1) * 64) void mlp_bwd_wide_blocks(BwdParams p
     }
 }
 
+// stage A of the fused wide-head backward
+void launch_bwd_wide_blocks(const BwdParams &p, unsigned grid, hipStream_t st) {
+    constexpr int OBW = 7;
+    raise_lds_limit<mlp_bwd_wide_blocks<OBW>>(LDS_MAX_BYTES);
+    hipLaunchKernelGGL((mlp_bwd_wide_blocks<OBW>), dim3(grid), dim3((OBW + 1) * 64), WideBlocksLds(OBW).bytes, st, p);
+}
+
 // ------------------------------------------------------------------- backward of wide softmax heads
 // The 200-way instance head dominated the decoder backward: its [M,200] probabilities were streamed through twice
 // (dot product of the softmax backward, then dz) - 1.7 GB per launch.  With the forward's per-sample softmax statistics
@@ -2982,6 +2009,17 @@ __global__ __launch_bounds__(NW * 64) void mlp_bwd_wide_mfma(BwdParams p) {
     }
 }
 
+template <typename DxT, int NL>
+void launch_bwd_wide_mfma(const BwdParams &p, hipStream_t st) {
+    constexpr int NW = WIDE_BWD_WAVES;
+    const int OB = (p.out_dim + 31) / 32;
+    const size_t lds = WideMfmaLds(NL, OB, NW).bytes;
+    const int64_t tiles = (p.M + 31) / 32;
+    const unsigned grid = (unsigned)std::min<int64_t>((tiles + NW - 1) / NW, 256);      // one workgroup per CU, tiles grid-strided
+    raise_lds_limit<mlp_bwd_wide_mfma<DxT, NL, NW>>(LDS_MAX_BYTES);
+    hipLaunchKernelGGL((mlp_bwd_wide_mfma<DxT, NL, NW>), dim3(grid), dim3(NW * 64), lds, st, p);
+}
+
 // --------------------------------------------------- wide softmax head + per-ray weighted sum, forward
 // out[ray][c] = alpha[ray] * sum_i w_i * softmax(W_L h_i + b_L)[c]   (tracer :197-205 on the instance head) WITHOUT the
 // [M,200] probability tensor: the decoder forward only writes the per-sample softmax statistics, and this kernel -
@@ -2991,19 +2029,6 @@ __global__ __launch_bounds__(NW * 64) void mlp_bwd_wide_mfma(BwdParams p) {
 // sum over a tile's 32 samples is a sum over lanes: DPP row_shr 1/2/4/8 + row_bcast:15 put it on lanes 31 / 63, LDS
 // combines the four waves.  Reads 128 B per sample instead of 400 B, and the 839 MB tensor is never written.
 constexpr int HC_PER_WAVE_P = 2048;      // pack count from which each pack gets its own wave (why: pag_head_composite_fwd)
-struct HeadCompParams {
-    const int64_t *pack_start;
-    const int32_t *ray_of_pack;
-    int64_t P;
-    const bf16_t *hidden;      // [M,64] last hidden layer (hidden_save of the forward)
-    const float *W, *b;        // [out_dim,64], [out_dim]
-    int out_dim;
-    const float *stats;        // [M,2]
-    int per_wave;              // 1: one WAVE per pack (short packs: the voxel regime has ~80 samples per ray), 0: one workgroup per pack
-    const float *weights;      // [M]
-    const float *alpha;        // [N]
-    float *out;                // [N,out_dim]
-};
 
 // One step of a sum over lanes on 16 values at once: v[q] += v[q] of the lane that the DPP control `ctl` names, for float v[16].  Written as one asm
 // block of 16 v_add_f32_dpp: left to itself the compiler pairs the values into v_pk_add_f32 fed by two DPP moves each - 1.5 instructions per value
@@ -3364,180 +2389,13 @@ __global__ __launch_bounds__(256, 1) void head_fwd_once_kernel(FwdParams p, Head
     }
 }
 
-// ------------------------------------------------------------------------------------ FP32 parity path
-// One lane per sample.  Weights transposed in LDS ([k][j]) so the 64 outputs of a layer are 16
-// broadcast ds_read_b128; the per-sample activation column lives in LDS ([k][lane]).
-
-__device__ void stage_f32_t(float *dst, const float *W, int n_out, int n_in, int out_pad) {   // dst[k][out_pad]
-    for (int e = threadIdx.x; e < n_in * out_pad; e += blockDim.x) {
-        int k = e / out_pad, j = e - k * out_pad;
-        dst[e] = j < n_out ? W[(int64_t)j * n_in + k] : 0.0f;
-    }
+template <bool PAIR>
+void launch_head_fwd_once(const FwdParams &p, const HeadCompParams &c, unsigned grid, hipStream_t st) {
+    raise_lds_limit<head_fwd_once_kernel<PAIR>>(LDS_MAX_BYTES);
+    hipLaunchKernelGGL((head_fwd_once_kernel<PAIR>), dim3(grid), dim3(256), FwdLds(3, OB_MAX, 4, PAIR, true).bytes, st, p, c);
 }
 
-template <typename X1T, typename OutT>
-__global__ __launch_bounds__(PT) void mlp_fwd_f32(FwdParams p, int n_layers) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr F32Lds L(64);
-    float *xs = lds_at<float>(smem, L.cols);              // [64][PT] activation columns
-    float *wt = lds_at<float>(smem, L.wt);                // current layer's W^T [k][out_pad]
-    const int t = threadIdx.x;
-    const int64_t m = (int64_t)blockIdx.x * PT + t;
-    const bool live = m < p.M;
-    const int64_t mc = live ? m : p.M - 1;
-    const X1T *x1 = reinterpret_cast<const X1T *>(p.x1);
-    OutT *out = reinterpret_cast<OutT *>(p.out);
-    // input column
-    const int32_t ray = p.x2 ? p.x2_index[mc] : 0;
-    for (int k = 0; k < p.in_dim; ++k)
-        xs[k * PT + t] = k < p.k1 ? pag_ld(x1 + mc * p.k1 + k) : p.x2[(int64_t)ray * p.k2p + (k - p.k1)];
-    int n_in = p.in_dim;
-    for (int l = 0; l < n_layers; ++l) {
-        const bool last = l == n_layers - 1;
-        const int n_out = last ? p.out_dim : HID;
-        const int chunks = (n_out + 63) / 64;
-        for (int c = 0; c < chunks; ++c) {
-            __syncthreads();
-            const int rows = min(64, n_out - 64 * c);
-            stage_f32_t(wt, p.W[l] + (int64_t)64 * c * n_in, rows, n_in, 64);
-            __syncthreads();
-            float acc[64];
-#pragma unroll
-            for (int j = 0; j < 64; ++j) acc[j] = j < rows ? p.b[l][64 * c + j] : 0.0f;
-            for (int k = 0; k < n_in; ++k) {
-                const float xk = xs[k * PT + t];
-                const f32x4 *wrow = reinterpret_cast<const f32x4 *>(wt + k * 64);
-#pragma unroll
-                for (int j4 = 0; j4 < 16; ++j4) {
-                    f32x4 w = wrow[j4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[4 * j4 + j] = fmaf(w[j], xk, acc[4 * j4 + j]);
-                }
-            }
-            if (!last) {
-                __syncthreads();   // everyone finished reading xs of the previous layer
-#pragma unroll
-                for (int j = 0; j < 64; ++j) {
-                    float v = fmaxf(acc[j], 0.0f);
-                    xs[j * PT + t] = v;
-                    if (p.hsave[l] && live) reinterpret_cast<float *>(p.hsave[l])[m * HID + j] = v;
-                }
-            } else if (live) {
-#pragma unroll
-                for (int j = 0; j < 64; ++j)
-                    if (j < rows) {
-                        float v = acc[j];
-                        if (p.act == PAG_ACT_SIGMOID) v = 1.0f / (1.0f + expf(-v));
-                        pag_st(out + m * p.out_dim + 64 * c + j, v);
-                    }
-            }
-        }
-        n_in = HID;
-    }
-    if (p.act == PAG_ACT_SOFTMAX && live) {   // second pass over this sample's logits
-        OutT *row = out + m * p.out_dim;
-        float mx = -INFINITY;
-        for (int j = 0; j < p.out_dim; ++j) mx = fmaxf(mx, pag_ld(row + j));
-        float sum = 0.0f;
-        for (int j = 0; j < p.out_dim; ++j) sum += expf(pag_ld(row + j) - mx);
-        for (int j = 0; j < p.out_dim; ++j) pag_st(row + j, expf(pag_ld(row + j) - mx) / sum);
-    }
-}
-
-__device__ void stage_f32_n(float *dst, const float *W, int row0, int rows, int n_in) {   // dst[j][64] = W[row0+j][0:n_in]
-    for (int e = threadIdx.x; e < rows * 64; e += blockDim.x) {
-        int j = e / 64, k = e - j * 64;
-        dst[e] = k < n_in ? W[(int64_t)(row0 + j) * n_in + k] : 0.0f;
-    }
-}
-
-template <typename OutT, typename DxT>
-__global__ __launch_bounds__(PT) void mlp_bwd_f32(BwdParams p, int n_layers) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr F32Lds L(224);
-    float *zs = lds_at<float>(smem, L.cols);              // [224][PT] dz column of the current layer
-    float *wt = lds_at<float>(smem, L.wt);                // [64 rows j][64 k]
-    const int t = threadIdx.x;
-    const int64_t m = (int64_t)blockIdx.x * PT + t;
-    const bool live = m < p.M;
-    const int64_t mc = live ? m : p.M - 1;
-    const OutT *y = reinterpret_cast<const OutT *>(p.out) + mc * p.out_dim;
-    const OutT *g = reinterpret_cast<const OutT *>(p.grad_out) + mc * p.out_dim;
-    float dot = 0.0f;
-    if (p.act == PAG_ACT_SOFTMAX)
-        for (int j = 0; j < p.out_dim; ++j) dot += pag_ld(g + j) * pag_ld(y + j);
-    for (int j = 0; j < p.out_dim; ++j) {
-        float v = pag_ld(g + j);
-        if (p.act == PAG_ACT_SIGMOID) {
-            float yy = pag_ld(y + j);
-            v = v * yy * (1.0f - yy);
-        } else if (p.act == PAG_ACT_SOFTMAX) {
-            v = pag_ld(y + j) * (v - dot);
-        }
-        v = live ? v : 0.0f;
-        zs[j * PT + t] = v;
-        if (live) reinterpret_cast<float *>(p.dz[n_layers - 1])[m * p.out_dim + j] = v;
-    }
-    int n_out = p.out_dim;
-    for (int l = n_layers - 1; l >= 0; --l) {
-        const int n_in = l == 0 ? p.in_dim : HID;
-        if (l == 0 && !p.dx1) break;
-        float acc[64];
-#pragma unroll
-        for (int k = 0; k < 64; ++k) acc[k] = 0.0f;
-        const int chunks = (n_out + 63) / 64;
-        for (int c = 0; c < chunks; ++c) {
-            __syncthreads();
-            const int rows = min(64, n_out - 64 * c);
-            stage_f32_n(wt, p.W[l], 64 * c, rows, n_in);
-            __syncthreads();
-            for (int j = 0; j < rows; ++j) {
-                const float zj = zs[(64 * c + j) * PT + t];
-                const f32x4 *wrow = reinterpret_cast<const f32x4 *>(wt + j * 64);
-#pragma unroll
-                for (int k4 = 0; k4 < 16; ++k4) {
-                    f32x4 w = wrow[k4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) acc[4 * k4 + k] = fmaf(w[k], zj, acc[4 * k4 + k]);
-                }
-            }
-        }
-        __syncthreads();
-        if (l > 0) {
-            const float *hv = reinterpret_cast<const float *>(p.hsave[l - 1]) + mc * HID;
-#pragma unroll
-            for (int k = 0; k < 64; ++k) {
-                float v = (live && hv[k] > 0.0f) ? acc[k] : 0.0f;
-                zs[k * PT + t] = v;
-                if (live) reinterpret_cast<float *>(p.dz[l - 1])[m * HID + k] = v;
-            }
-            n_out = HID;
-        } else if (live) {
-            DxT *dx = reinterpret_cast<DxT *>(p.dx1) + m * p.k1;
-#pragma unroll
-            for (int k = 0; k < 64; ++k)
-                if (k < p.k1) pag_st(dx + k, acc[k]);
-        }
-    }
-}
-
-inline unsigned mlp_grid(int64_t M) {
-    int64_t tiles = (M + 31) / 32;
-    int64_t blocks = (tiles + 3) / 4;
-    int64_t cap = 256 * 6;   // a few workgroups per CU; tiles are grid-strided
-    return (unsigned)(blocks < cap ? (blocks > 0 ? blocks : 1) : cap);
-}
-
-// The decoder shapes that have kernels of their own, forward (mlp_fwd_fast, mlp_fwd_wide_stats, head_fwd_once_kernel) and backward (mlp_bwd_fused,
-// mlp_bwd_wide_blocks); anything else runs the generic kernels.  The first three are the KIND template argument of mlp_fwd_fast / mlp_bwd_fused.
-enum DecoderFamily {
-    FAM_GENERIC = -1,
-    FAM_DENSITY = 0,      // XCD8 input, no output activation, bf16 output of a multiple of 4 channels <= 32
-    FAM_COLOUR = 1,       // strided bf16 [M,16] input + per-ray x2 [R,32], sigmoid, f32 output of <= 4 channels, the density read off column 0 of x1
-    FAM_SOFTMAX = 2,      // XCD8 input, softmax, bf16 output of <= 8 channels (the semantic head)
-    FAM_WIDE = 3,         // XCD8 input, three layers, softmax over 193 .. 224 channels kept as statistics + last hidden layer (the instance head)
-};
-
+// ===================================================================================================================== host layer
 // ---- forward: one predicate per family, on the argument struct alone.  They hold what pag_mlp_fwd's selection asks; what an entry point asks beyond the
 //      family stands beside its call.
 bool fwd_bf16_path(const pag_mlp_fwd_args *a) { return a->mode == PAG_MLP_MFMA_BF16 && a->x1_dtype == PAG_BF16; }
@@ -3607,100 +2465,6 @@ void with_dtypes(bool f32_0, bool f32_1, Fn &&f) {
     else if (f32_0) f(float{}, bf16_t{});
     else if (f32_1) f(bf16_t{}, float{});
     else f(bf16_t{}, bf16_t{});
-}
-
-template <typename X1T, typename OutT, int NL>
-void launch_fwd_mfma_nl(const FwdParams &p, hipStream_t st) {
-    const dim3 grid(mlp_grid(p.M)), block(256);
-    const int OB = (p.out_dim + 31) / 32;
-    const size_t lds = FwdLds(NL, OB).bytes;
-    if (OB <= 1) hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 1>), grid, block, lds, st, p);
-    else if (OB <= 2) hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 2>), grid, block, lds, st, p);
-    else if (OB <= 4) hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 4>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((mlp_fwd_mfma<X1T, OutT, NL, 7>), grid, block, lds, st, p);
-}
-template <typename X1T, typename OutT>
-void launch_fwd_mfma(const FwdParams &p, int n_layers, hipStream_t st) {
-    if (n_layers == 2) launch_fwd_mfma_nl<X1T, OutT, 2>(p, st);
-    else launch_fwd_mfma_nl<X1T, OutT, 3>(p, st);
-}
-
-constexpr int FAST_FWD_GRID_CAP = 768;      // three workgroups per CU are resident: one round, tiles grid-strided (1536 ran two rounds with a ragged second: colour forward 63 -> 57 us)
-template <int KIND>
-void launch_fwd_fast(const FwdParams &p, int n_layers, bool save, hipStream_t st) {
-    const dim3 grid(std::min<unsigned>(mlp_grid(p.M), FAST_FWD_GRID_CAP)), block(256);
-    const size_t lds = FwdLds(n_layers, 1).bytes;
-    if (n_layers == 2 && save) hipLaunchKernelGGL((mlp_fwd_fast<2, KIND, true>), grid, block, lds, st, p);
-    else if (n_layers == 2) hipLaunchKernelGGL((mlp_fwd_fast<2, KIND, false>), grid, block, lds, st, p);
-    else if (save) hipLaunchKernelGGL((mlp_fwd_fast<3, KIND, true>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((mlp_fwd_fast<3, KIND, false>), grid, block, lds, st, p);
-}
-template <bool SAVE0, bool PAIR>
-void launch_fwd_wide_stats(const FwdParams &p, unsigned grid, hipStream_t st) {
-    constexpr int NW = wide_fwd_waves(PAIR);
-    raise_lds_limit<mlp_fwd_wide_stats<SAVE0, PAIR>>(LDS_MAX_BYTES);
-    hipLaunchKernelGGL((mlp_fwd_wide_stats<SAVE0, PAIR>), dim3(grid), dim3(NW * 64), FwdLds(3, OB_MAX, NW, PAIR).bytes, st, p);
-}
-template <bool PAIR>
-void launch_head_fwd_once(const FwdParams &p, const HeadCompParams &c, unsigned grid, hipStream_t st) {
-    raise_lds_limit<head_fwd_once_kernel<PAIR>>(LDS_MAX_BYTES);
-    hipLaunchKernelGGL((head_fwd_once_kernel<PAIR>), dim3(grid), dim3(256), FwdLds(3, OB_MAX, 4, PAIR, true).bytes, st, p, c);
-}
-
-template <typename OutT, typename DxT, int NL>
-void launch_bwd_mfma_nl(const BwdParams &p, hipStream_t st) {
-    const dim3 grid(mlp_grid(p.M)), block(256);
-    const int OB = (p.out_dim + 31) / 32;
-    const size_t lds = BwdLds(NL, OB).bytes;
-    if (OB <= 1) hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 1>), grid, block, lds, st, p);
-    else if (OB <= 2) hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 2>), grid, block, lds, st, p);
-    else if (OB <= 4) hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 4>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((mlp_bwd_mfma<OutT, DxT, NL, 7>), grid, block, lds, st, p);
-}
-template <typename OutT, typename DxT>
-void launch_bwd_mfma(const BwdParams &p, int n_layers, hipStream_t st) {
-    if (n_layers == 2) launch_bwd_mfma_nl<OutT, DxT, 2>(p, st);
-    else launch_bwd_mfma_nl<OutT, DxT, 3>(p, st);
-}
-
-template <typename OutT, typename DxT>
-void launch_bwd_f32(const BwdParams &p, int n_layers, hipStream_t st) {
-    constexpr F32Lds L(224);      // 128 KiB
-    raise_lds_limit<mlp_bwd_f32<OutT, DxT>>(L.bytes);
-    hipLaunchKernelGGL((mlp_bwd_f32<OutT, DxT>), dim3((unsigned)((p.M + PT - 1) / PT)), dim3(PT), L.bytes, st, p, n_layers);
-}
-
-template <int NL, int KIND, bool DXACC, int OBL = 1, int DZ0 = 0>
-void launch_bwd_fused(const BwdParams &p, unsigned grid, hipStream_t st) {
-    raise_lds_limit<mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>>(LDS_MAX_BYTES);
-    hipLaunchKernelGGL((mlp_bwd_fused<NL, KIND, DXACC, OBL, DZ0>), dim3(grid), dim3(256), FusedLds(NL, OBL, DZ0).bytes, st, p);
-}
-template <int NL>
-void launch_bwd_fused_family(const BwdParams &p, DecoderFamily fam, bool acc, int dz0, unsigned grid, hipStream_t st) {
-    if (fam == FAM_DENSITY) launch_bwd_fused<NL, FAM_DENSITY, false>(p, grid, st);
-    else if (fam == FAM_COLOUR && dz0 == 2) launch_bwd_fused<NL, FAM_COLOUR, false, 1, 2>(p, grid, st);
-    else if (fam == FAM_COLOUR && dz0 == 1) launch_bwd_fused<NL, FAM_COLOUR, false, 1, 1>(p, grid, st);
-    else if (fam == FAM_COLOUR) launch_bwd_fused<NL, FAM_COLOUR, false>(p, grid, st);
-    else if (acc) launch_bwd_fused<NL, FAM_SOFTMAX, true>(p, grid, st);
-    else launch_bwd_fused<NL, FAM_SOFTMAX, false>(p, grid, st);
-}
-
-// stage A of the fused wide-head backward
-void launch_bwd_wide_blocks(const BwdParams &p, unsigned grid, hipStream_t st) {
-    constexpr int OBW = 7;
-    raise_lds_limit<mlp_bwd_wide_blocks<OBW>>(LDS_MAX_BYTES);
-    hipLaunchKernelGGL((mlp_bwd_wide_blocks<OBW>), dim3(grid), dim3((OBW + 1) * 64), WideBlocksLds(OBW).bytes, st, p);
-}
-
-template <typename DxT, int NL>
-void launch_bwd_wide_mfma(const BwdParams &p, hipStream_t st) {
-    constexpr int NW = WIDE_BWD_WAVES;
-    const int OB = (p.out_dim + 31) / 32;
-    const size_t lds = WideMfmaLds(NL, OB, NW).bytes;
-    const int64_t tiles = (p.M + 31) / 32;
-    const unsigned grid = (unsigned)std::min<int64_t>((tiles + NW - 1) / NW, 256);      // one workgroup per CU, tiles grid-strided
-    raise_lds_limit<mlp_bwd_wide_mfma<DxT, NL, NW>>(LDS_MAX_BYTES);
-    hipLaunchKernelGGL((mlp_bwd_wide_mfma<DxT, NL, NW>), dim3(grid), dim3(NW * 64), lds, st, p);
 }
 
 }  // namespace

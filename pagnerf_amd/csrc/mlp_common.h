@@ -1,4 +1,4 @@
-// Shared by the decoder translation units (mlp.hip, mlp_wgrad.hip, mlp_affine.hip directly; mlp_deep.hip and mlp_h128.hip through mlp_native.h, which adds
+// Shared by the decoder translation units (mlp.hip with its headers mlp_params.h .. mlp_f32.h, mlp_wgrad.hip, mlp_affine.hip directly; mlp_deep.hip and mlp_h128.hip through mlp_native.h, which adds
 // the tile code those two share; nothing else includes it): what more than one of them uses.
 // The transposed-MFMA scheme of the decoders is described at the top of mlp.hip.
 #pragma once

@@ -1,4 +1,5 @@
-// Dynamic-LDS layouts of the decoder kernels in mlp.hip and mlp_wgrad.hip (nothing else includes this): ONE description per kernel serves the
+// Dynamic-LDS layouts of the decoder kernels in mlp.hip (the file itself and its headers mlp_generic.h and mlp_f32.h hold them; mlp_tile.h takes the
+// constants) and mlp_wgrad.hip - nothing else includes this: ONE description per kernel serves the
 // carve-up inside the kernel (lds_at<T>(smem, L.region)) and the byte count its launcher asks for (L.bytes), so the two cannot drift apart.
 // Constants and constexpr code only - a plain host program can include this file and print every size.
 // Conventions: every member is an offset in BYTES from the start of the dynamic segment; regions follow each other in declaration order; a

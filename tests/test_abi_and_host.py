@@ -665,6 +665,27 @@ def test_decoder_launch_rules_answer_as_recorded(lib):
     assert nbytes == want["bytes"]
 
 
+def test_every_csrc_header_is_included_by_a_built_source():
+    """Every csrc/*.h is reached through `#include "..."` lines from at least one unit of build.SOURCES: a header that a cut of a source left behind
+    is compiled by nothing and noticed by nothing else.  Text only - no compiler."""
+    from pagnerf_amd import build
+    names = set(os.listdir(build.CSRC))
+
+    def includes(name):
+        with open(os.path.join(build.CSRC, name)) as fh:
+            return [i for i in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', fh.read(), re.M) if i in names]
+    assert set(build.SOURCES) <= names, set(build.SOURCES) - names
+    reached, todo = set(), list(build.SOURCES)
+    while todo:
+        name = todo.pop()
+        if name not in reached:
+            reached.add(name)
+            todo += includes(name)
+    headers = {n for n in names if n.endswith(".h")}
+    assert headers, "no headers found"
+    assert sorted(headers - reached) == []
+
+
 def test_graph_capacity_buckets_are_geometric_with_hysteresis():
     """pagnerf_amd/graphs.py::_State.capacity: every new capacity is a capture (two warm-up steps, a private memory pool), so batch-to-batch
     noise must not move it: geometric buckets (<= 1/32 of a power of two of filler), immediate growth, shrink only after SHRINK_WINDOW
