@@ -1155,7 +1155,10 @@ extern "C" int pag_composite_feats_fwd(const int64_t *pack_start, const int32_t 
         hipLaunchKernelGGL(composite_feats64_bf16_fwd_kernel, dim3((unsigned)P), dim3(256), 0, (hipStream_t)stream, pack_start, ray_of_pack, weights, alpha,
                            (const bf16_t *)feats, out);
     } else {
-        const bool vec = (C % 4) == 0;
+        // the vector kernel reads a row as 4-element vectors (16 bytes f32, 8 bytes bf16): rows keep the base's alignment when C % 4 == 0, and a base
+        // that is not a multiple of the vector's size (a contiguous view into a larger buffer) takes the scalar kernel - the same sums in the same order
+        const uintptr_t vec_bytes = feat_dtype == PAG_F32 ? 16 : 8;
+        const bool vec = (C % 4) == 0 && (reinterpret_cast<uintptr_t>(feats) & (vec_bytes - 1)) == 0;
         const dim3 g((unsigned)P);
         hipStream_t st = (hipStream_t)stream;
         if (feat_dtype == PAG_F32 && vec)
