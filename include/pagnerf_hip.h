@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PAG_ABI_VERSION 14
+#define PAG_ABI_VERSION 15
 
 enum { PAG_F32 = 0, PAG_F16 = 1, PAG_BF16 = 2 };
 enum { PAG_OK = 0, PAG_ERR_ARG = -1, PAG_ERR_LAUNCH = -2, PAG_ERR_UNSUPPORTED = -3 };
@@ -426,51 +426,30 @@ int pag_raymarch_pack(const float *origins, const float *dirs, int64_t N, int S,
 
 /* 'voxel' mode (wisp OctreeAS.raymarch after pc_nerf/trainer.py:362-366 switches the tracer): every ray is walked
  * through the 2^blas_level occupancy grid (3-D DDA); each occupied cell it crosses (a "nugget") receives
- * samples_per_voxel samples.  Pass 1 counts nuggets per ray; pass 2 (offsets = exclusive prefix sum) writes
+ * samples_per_voxel samples.  ONE walk per ray: _count_nuggets records every kept nugget (t_in, t_out) and its cell and
+ * counts them; _pack_nuggets (offsets = pag_pack_offsets() of the counts) turns them into the packed arrays in parallel
+ * (one wave per ray):
  *   ridx i32 [M'], pidx i32 [M'] per nugget; samples f32 [M',k,3], depths f32 [M',k], deltas f32 [M'*k],
  *   boundary u8 [M'*k] (1 at the first sample of a ray's first nugget) - the shapes
- *   tracers/panoptic_packed_rf_tracer.py:88-108 indexes. */
-/* counts (out, i32 [N]) are in SAMPLES (nuggets * samples_per_voxel): pag_pack_offsets() of them is at once the pack
+ *   tracers/panoptic_packed_rf_tracer.py:88-108 indexes.
+ * counts (out, i32 [N]) are in SAMPLES (nuggets * samples_per_voxel): pag_pack_offsets() of them is at once the pack
  * pass's offset table and the compositing kernels' pack_start (one pack per ray, empty packs allowed).
- *   max_travel        the travel filter of tracers/panoptic_packed_rf_tracer.py:88-108 applied inside the walk: a nugget is kept
- *                     iff (depth of its first sample) - (depth of the ray's first sample) < max_travel (strict; fp32 subtraction
- *                     as in the tensor expression :91-92).  INFINITY disables it (plain OctreeAS.raymarch 'voxel' output).
- *   occupancy_coarse  optional u32 bitfield of the (2^blas_level / 4)^3 grid from pag_occupancy_coarse(): the walk consults it
- *                     from LDS and reads the fine word only inside non-empty coarse cells.  Same result with or without.
- *   ridx_sample       optional i32 [M'*k]: the ray of every SAMPLE (the decoders' per-sample ray index); ridx64 optional
- *                     i64 [M'] copy of ridx (wisp hands out int64 ray ids). */
-int pag_raymarch_voxel_count(const float *origins, const float *dirs, int64_t N, int samples_per_voxel,
-                             float dist_min, float dist_max, const uint32_t *occupancy_bits,
-                             const uint32_t *occupancy_coarse, int blas_level, float max_travel,
-                             int32_t *counts, void *stream);
-int pag_raymarch_voxel_pack(const float *origins, const float *dirs, int64_t N, int samples_per_voxel,
-                            float dist_min, float dist_max, const uint32_t *occupancy_bits,
-                            const uint32_t *occupancy_coarse, int blas_level, float max_travel,
-                            const int64_t *offsets, int32_t *ridx, int32_t *pidx, float *samples,
-                            float *depths, float *deltas, uint8_t *boundary, int32_t *ridx_sample,
-                            int64_t *ridx64, void *stream);
-
-/* The same two passes with ONE walk: pass 1 also records every kept nugget (t_in, t_out) and its cell, pass 2 turns them into the
- * packed arrays in parallel (one wave per ray) instead of walking every ray a second time.  Outputs are bit-identical to
- * pag_raymarch_voxel_count / _pack.
+ *   max_travel   the travel filter of tracers/panoptic_packed_rf_tracer.py:88-108 applied inside the march: a nugget is kept
+ *                iff (depth of its first sample) - (depth of the ray's first sample) < max_travel (strict; fp32 subtraction
+ *                as in the tensor expression :91-92).  INFINITY disables it (plain OctreeAS.raymarch 'voxel' output).
  *   nugget_t     f32 [2][cap][N][2], nugget_cell i32 [2][cap][N]  caller-allocated scratch, cap = pag_raymarch_voxel_nugget_capacity(blas_level)
  *                (3 * 2^blas_level + 3: the most cells a ray can cross).  First half: the walk's candidates, [step][ray]; second half (ABI 11): the
- *                kept nuggets ray-major, [ray][slot] - what _pack_nuggets (which takes blas_level for `cap`) reads */
+ *                kept nuggets ray-major, [ray][slot] - what _pack_nuggets (which takes blas_level for `cap`) reads
+ *   ridx_sample  optional i32 [M'*k]: the ray of every SAMPLE (the decoders' per-sample ray index); ridx64 optional
+ *                i64 [M'] copy of ridx (wisp hands out int64 ray ids). */
 int64_t pag_raymarch_voxel_nugget_capacity(int blas_level);
 int pag_raymarch_voxel_count_nuggets(const float *origins, const float *dirs, int64_t N, int samples_per_voxel,
-                                     float dist_min, float dist_max, const uint32_t *occupancy_bits,
-                                     const uint32_t *occupancy_coarse, int blas_level, float max_travel,
-                                     int32_t *counts, float *nugget_t, int32_t *nugget_cell, void *stream);
+                                     float dist_min, float dist_max, const uint32_t *occupancy_bits, int blas_level,
+                                     float max_travel, int32_t *counts, float *nugget_t, int32_t *nugget_cell, void *stream);
 int pag_raymarch_voxel_pack_nuggets(const float *origins, const float *dirs, int64_t N, int samples_per_voxel,
                                     const int64_t *offsets, const float *nugget_t, const int32_t *nugget_cell, int blas_level,
                                     int32_t *ridx, int32_t *pidx, float *samples, float *depths, float *deltas,
                                     uint8_t *boundary, int32_t *ridx_sample, int64_t *ridx64, void *stream);
-
-/* Coarse occupancy for the voxel march: bit ((x/4)*RC + y/4)*RC + z/4 (RC = 2^blas_level / 4) is set iff any of the 64 fine
- * cells under it is.  pag_occupancy_coarse_bytes() = size of `coarse` in bytes, 0 when blas_level is outside [5,8]
- * (the march then runs without it).  Rebuild after every prune (pc_nerf/panoptic_delta_nef.py:98-104). */
-int64_t pag_occupancy_coarse_bytes(int blas_level);
-int pag_occupancy_coarse(const uint32_t *occupancy_bits, int blas_level, uint32_t *coarse, void *stream);
 
 /* Occupancy update of pc_nerf/panoptic_delta_nef.py:63-104 (prune), one launch:
  *   occupancy[i] <- max(density[i * density_stride], occupancy[i] * decay)     (:74, :90)

@@ -172,7 +172,7 @@ def raymarch_voxel(origins, dirs, dist_min, dist_max, num_samples, occupancy=Non
     PARITY UNPINNED: upstream this is kaolin unbatched_raytrace + wisp OctreeAS.raymarch (third party, not in the
     reference tree); the reference only fixes the output contract (tracers/panoptic_packed_rf_tracer.py:88-108 and
     SURVEY Appendix A5): ridx per nugget [M'], samples [M',k,3], depths [M',k,1], deltas [M'*k,1], boundary [M'*k].
-    Scalar fp32 arithmetic in the exact order of the HIP kernel (pagnerf_amd/csrc/render.hip voxel_march_kernel)."""
+    Scalar fp32 arithmetic in the exact order of the HIP kernels (pagnerf_amd/csrc/render.hip voxel_walk_kernel, voxel_pack_nuggets_kernel)."""
     import numpy as np
     f = np.float32
     R = 2 ** blas_level

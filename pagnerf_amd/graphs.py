@@ -433,11 +433,10 @@ class GraphRunner:
         bits = None if g._all_occupied else g.blas_bits
         if bits is not None and bits.device != dev:
             g.blas_bits = bits = bits.to(dev)
-        coarse = g._coarse_bits(bits) if (bits is not None and raymarch_type == "voxel") else None
         # count -> offsets + padding to `cap` + the directions into the static tensor (one launch) -> pack
         mailbox, jitter = ops.march_into(buf, rays.origins, rays.dirs, rays.dist_min, rays.dist_max, num_steps, jitter=jitter,
                                          occupancy_bits=bits, blas_level=g.blas_level,
-                                         max_travel=tracer.ray_max_travel if raymarch_type == "voxel" else None, occupancy_coarse_bits=coarse,
+                                         max_travel=tracer.ray_max_travel if raymarch_type == "voxel" else None,
                                          pad_capacity=cap, dirs_out=st.dirs)
         args = (buf.samples[:cap], buf.depths[:cap], buf.deltas[:cap], st.dirs) + ((st.orig0,) if pose else ())
         live = (rays.dirs, rays.origins) if pose else ()

@@ -34,7 +34,6 @@ class OccupancyBLAS(nn.Module):
         self._dense_points = None
         self._all_occupied = True
         self._pack_cache = None
-        self._coarse = None          # (blas_bits identity, version) -> coarse bitfield of the voxel march (ops.occupancy_coarse)
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         """A checkpoint replaces buffers the kernels do not read directly: the march takes `_all_occupied`, the encoders a host copy of
@@ -46,14 +45,6 @@ class OccupancyBLAS(nn.Module):
     def _refresh_derived(self):
         self._all_occupied = bool((self.blas_bits == -1).all()) if self.num_cells >= 32 else False
         self._pack_cache = None
-        self._coarse = None
-
-    def _coarse_bits(self, bits):
-        """Coarse occupancy for the voxel march, rebuilt when the bitfield object or its contents (version counter) change."""
-        key = (id(bits), bits._version, str(bits.device))
-        if self._coarse is None or self._coarse[0] != key:
-            self._coarse = (key, ops.occupancy_coarse(bits, self.blas_level))
-        return self._coarse[1]
 
     @property
     def dense_points(self):
@@ -74,7 +65,7 @@ class OccupancyBLAS(nn.Module):
         w = (mask.reshape(-1, 32).long() << torch.arange(32, device=mask.device)).sum(1)
         w = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
         self.blas_bits = w.to(self.blas_bits.device)
-        self._refresh_derived()              # also drops the coarse-occupancy and pack caches keyed on the old tensor
+        self._refresh_derived()              # also drops the pack cache keyed on the old tensor
 
     def blas_init_bits(self, bits):
         """Adopt a packed bitfield produced on the device (ops.occupancy_update)."""
@@ -92,9 +83,8 @@ class OccupancyBLAS(nn.Module):
         bits = None if self._all_occupied else self.blas_bits
         if bits is not None and bits.device != rays.origins.device:
             self.blas_bits = bits = bits.to(rays.origins.device)
-        coarse = self._coarse_bits(bits) if bits is not None else None
         return ops.raymarch_voxel_begin(rays.origins, rays.dirs, rays.dist_min, rays.dist_max, num_samples, bits, self.blas_level, max_travel=max_travel,
-                                        occupancy_coarse_bits=coarse, want_packs=True)
+                                        want_packs=True)
 
     def raymarch_voxel_finish(self, state, rays, num_samples):
         ridx, pidx, samples, depths, deltas, boundary, pack_start, ray_of_pack, ridx_sample, ridx64 = ops.raymarch_voxel_finish(state)

@@ -1273,70 +1273,78 @@ def _tvals(S, dev):
     return _TVALS[key]
 
 
-def occupancy_coarse(occupancy_bits, blas_level):
-    """u32 bitfield of the (2^level / 4)^3 coarse occupancy the voxel march keeps in LDS, or None when the level has none."""
-    nbytes = L.load().pag_occupancy_coarse_bytes(int(blas_level))
-    if occupancy_bits is None or nbytes == 0:
-        return None
-    coarse = torch.empty(nbytes // 4, device=occupancy_bits.device, dtype=torch.int32)
-    _call("pag_occupancy_coarse", L.ptr(occupancy_bits), int(blas_level), L.ptr(coarse), L.stream())
-    return coarse
+VOXEL_SCRATCH_MAX = 1 << 30      # bytes of nugget scratch raymarch_voxel() may hold at a time: more rays than that are marched in chunks
 
 
-VOXEL_SCRATCH_MAX = 1 << 30      # bytes of nugget scratch raymarch_voxel() may allocate per call
-
-
-def raymarch_voxel(origins, dirs, dist_min, dist_max, samples_per_voxel, occupancy_bits=None, blas_level=7, max_travel=None,
-                   occupancy_coarse_bits=None, want_packs=False):
+def raymarch_voxel(origins, dirs, dist_min, dist_max, samples_per_voxel, occupancy_bits=None, blas_level=7, max_travel=None, want_packs=False):
     """'voxel'-mode march (3-D DDA over the occupancy grid).  Returns per NUGGET ridx i32[M'], pidx i32[M'] and per sample
     samples f32[M',k,3], depths f32[M',k], deltas f32[M'*k], boundary bool[M'*k].
     max_travel: the tracer's travel filter (tracers/panoptic_packed_rf_tracer.py:88-108) applied inside the walk (None = off).
     want_packs: also (pack_start i64[N+1] in samples, ray_of_pack i32[N] = arange, ridx_sample i32[M'*k], ridx64 i64[M']) - one
     (possibly empty) pack per ray, straight from the kernels: no unique / nonzero / repeat_interleave passes, and the sample
     count reaches the host through the polled mailbox of raymarch_ray()."""
-    return raymarch_voxel_finish(raymarch_voxel_begin(origins, dirs, dist_min, dist_max, samples_per_voxel, occupancy_bits, blas_level, max_travel,
-                                                      occupancy_coarse_bits, want_packs))
+    return raymarch_voxel_finish(raymarch_voxel_begin(origins, dirs, dist_min, dist_max, samples_per_voxel, occupancy_bits, blas_level, max_travel, want_packs))
 
 
-def raymarch_voxel_begin(origins, dirs, dist_min, dist_max, samples_per_voxel, occupancy_bits=None, blas_level=7, max_travel=None,
-                         occupancy_coarse_bits=None, want_packs=False):
-    """First half of raymarch_voxel(): the walk (nugget counts / candidates) and the pack offsets are QUEUED, nothing is waited for.  -> state for
+def raymarch_voxel_begin(origins, dirs, dist_min, dist_max, samples_per_voxel, occupancy_bits=None, blas_level=7, max_travel=None, want_packs=False):
+    """First half of raymarch_voxel(): the walk (nugget candidates, selection, counts) and the pack offsets are QUEUED, nothing is waited for.  -> state for
     raymarch_voxel_finish(), which reads the sample count, sizes the packed tensors and queues the expansion.  A caller with several marches to do
     (PanopticPackedRFTracer.render_packs) begins the next one before it finishes this one: the walk - a latency-bound DDA per ray - then runs while the
-    host is busy elsewhere, and the count is there when it is asked for."""
+    host is busy elsewhere, and the count is there when it is asked for.
+    More rays than VOXEL_SCRATCH_MAX bytes of nugget scratch serve (2 x [cap][N] entries of 12 bytes) queue nothing here: raymarch_voxel_finish() marches
+    them in chunks."""
     _check_gpu(origins, dirs)
     dev = origins.device
     N, k = origins.shape[0], int(samples_per_voxel)
+    cap = int(L.load().pag_raymarch_voxel_nugget_capacity(blas_level))
+    chunk = max(1, VOXEL_SCRATCH_MAX // (24 * cap))
+    if N > chunk:
+        return chunk, (origins, dirs, dist_min, dist_max, k, occupancy_bits, blas_level, max_travel, want_packs)
     origins = origins.detach().contiguous().float()
     dirs = dirs.detach().contiguous().float()
     counts = torch.empty(N, device=dev, dtype=torch.int32)
-    occ = L.ptr(occupancy_bits) if occupancy_bits is not None else None
-    coarse = L.ptr(occupancy_coarse_bits) if (occupancy_coarse_bits is not None and occupancy_bits is not None) else None
-    travel = float("inf") if max_travel is None else float(max_travel)
     st = L.stream()
-    # one walk: pass 1 records the nuggets ([cap][N] scratch, 12 bytes each), pass 2 expands them in parallel; above VOXEL_SCRATCH_MAX
-    # bytes of scratch the rays are walked twice instead (pag_raymarch_voxel_count / _pack)
-    cap = int(L.load().pag_raymarch_voxel_nugget_capacity(blas_level))
     nug_t = nug_cell = None
-    if N and 2 * cap * N * 12 <= VOXEL_SCRATCH_MAX:
+    if N:
         nug_t = torch.empty(2, cap, N, 2, device=dev)              # [0]: the walk's candidates [step][ray], [1]: the kept nuggets [ray][slot]
         nug_cell = torch.empty(2, cap, N, device=dev, dtype=torch.int32)
-        _call("pag_raymarch_voxel_count_nuggets", L.ptr(origins), L.ptr(dirs), N, k, float(dist_min), float(dist_max), occ, coarse,
-              blas_level, travel, L.ptr(counts), L.ptr(nug_t), L.ptr(nug_cell), st)
-    elif N:
-        _call("pag_raymarch_voxel_count", L.ptr(origins), L.ptr(dirs), N, k, float(dist_min), float(dist_max), occ, coarse, blas_level,
-              travel, L.ptr(counts), st)
+        _call("pag_raymarch_voxel_count_nuggets", L.ptr(origins), L.ptr(dirs), N, k, float(dist_min), float(dist_max),
+              L.ptr(occupancy_bits) if occupancy_bits is not None else None, blas_level, float("inf") if max_travel is None else float(max_travel),
+              L.ptr(counts), L.ptr(nug_t), L.ptr(nug_cell), st)
     pack_start = torch.empty(N + 1, device=dev, dtype=torch.int64)      # [i] = first SAMPLE of ray i, [N] = M' * k
     mailbox = _count_mailbox() if POLL_SAMPLE_COUNT else None
     if mailbox is not None:
         mailbox[1][0] = -1
     _call("pag_pack_offsets", L.ptr(counts), N, L.ptr(pack_start), mailbox[0].data_ptr() if mailbox is not None else None, st)
-    return (origins, dirs, N, k, float(dist_min), float(dist_max), occupancy_bits, occupancy_coarse_bits, occ, coarse, blas_level, travel, counts, nug_t, nug_cell,
-            pack_start, mailbox, want_packs)
+    return None, (origins, dirs, N, k, occupancy_bits, blas_level, counts, nug_t, nug_cell, pack_start, mailbox, want_packs)
+
+
+def _raymarch_voxel_chunks(chunk, origins, dirs, *rest):
+    """raymarch_voxel() of more rays than one call's scratch serves: consecutive chunks of rays through the same code, one after the other (so one chunk's
+    scratch is alive at a time), and the results joined.  Rays are independent: bit for bit the result of one march of them all."""
+    N, want_packs = origins.shape[0], rest[-1]
+    parts, s0 = [], 0                    # s0: samples before the chunk
+    for r0 in range(0, N, chunk):
+        part = list(raymarch_voxel_finish(raymarch_voxel_begin(origins[r0:r0 + chunk], dirs[r0:r0 + chunk], *rest)))
+        part[0] += r0                                   # ridx
+        if want_packs:
+            part[6] = part[6][:-1] + s0                 # pack_start, without the chunk's total
+            part[8] += r0                               # ridx_sample
+            part[9] += r0                               # ridx64
+        s0 += part[3].numel()
+        parts.append(part)
+    out = [torch.cat(p) for p in zip(*parts)]
+    if want_packs:
+        out[6] = torch.cat([out[6], torch.full((1,), s0, device=origins.device, dtype=torch.int64)])
+        out[7] = _ray_iota(N, origins.device)
+    return tuple(out)
 
 
 def raymarch_voxel_finish(state):
-    (origins, dirs, N, k, dist_min, dist_max, _occ_t, _coarse_t, occ, coarse, blas_level, travel, counts, nug_t, nug_cell, pack_start, mailbox, want_packs) = state
+    chunk, state = state
+    if chunk is not None:
+        return _raymarch_voxel_chunks(chunk, *state)
+    (origins, dirs, N, k, _occ_t, blas_level, counts, nug_t, nug_cell, pack_start, mailbox, want_packs) = state
     dev = origins.device
     st = L.stream()
     total = _poll_count(mailbox) if mailbox is not None else -1
@@ -1355,13 +1363,9 @@ def raymarch_voxel_finish(state):
     boundary = torch.empty(Mn * k, device=dev, dtype=torch.uint8)
     ridx_sample = torch.empty(Mn * k, device=dev, dtype=torch.int32) if want_packs else None
     ridx64 = torch.empty(Mn, device=dev, dtype=torch.int64) if want_packs else None
-    if Mn and nug_t is not None:
+    if Mn:
         _call("pag_raymarch_voxel_pack_nuggets", L.ptr(origins), L.ptr(dirs), N, k, L.ptr(pack_start), L.ptr(nug_t), L.ptr(nug_cell), blas_level,
               L.ptr(ridx), L.ptr(pidx), L.ptr(samples), L.ptr(depths), L.ptr(deltas), L.ptr(boundary), L.ptr(ridx_sample), L.ptr(ridx64), st)
-    elif Mn:
-        _call("pag_raymarch_voxel_pack", L.ptr(origins), L.ptr(dirs), N, k, dist_min, dist_max, occ, coarse, blas_level,
-              travel, L.ptr(pack_start), L.ptr(ridx), L.ptr(pidx), L.ptr(samples), L.ptr(depths), L.ptr(deltas), L.ptr(boundary),
-              L.ptr(ridx_sample), L.ptr(ridx64), st)
     if want_packs:
         return (ridx, pidx, samples, depths, deltas, boundary.view(torch.bool), pack_start, _ray_iota(N, dev), ridx_sample, ridx64)
     return ridx, pidx, samples, depths, deltas, boundary.view(torch.bool)
@@ -1415,8 +1419,8 @@ def _offsets(buf, N, mb_ptr, st, pad_capacity, dirs, dirs_out):
           L.ptr(buf.boundary), L.ptr(buf.pack_start_c), L.ptr(dirs) if copy else None, L.ptr(dirs_out) if copy else None, st)
 
 
-def march_into(buf, origins, dirs, dist_min, dist_max, num_samples, jitter=None, occupancy_bits=None, blas_level=7, max_travel=None,
-               occupancy_coarse_bits=None, pad_capacity=None, dirs_out=None):
+def march_into(buf, origins, dirs, dist_min, dist_max, num_samples, jitter=None, occupancy_bits=None, blas_level=7, max_travel=None, pad_capacity=None,
+               dirs_out=None):
     """The ray march of raymarch_ray() / raymarch_voxel() written into `buf` (MarchBuffers) WITHOUT waiting for the sample count:
     count -> offsets (+ pinned mailbox) -> pack are queued back to back.  -> the mailbox (poll it with _poll_count() when convenient;
     give it back with _release_mailbox()) or None when polling is disabled (the caller then reads buf.pack_start[N] itself).
@@ -1448,9 +1452,8 @@ def march_into(buf, origins, dirs, dist_min, dist_max, num_samples, jitter=None,
               L.ptr(buf.deltas), L.ptr(buf.boundary), L.ptr(buf.ridx64), st)
     else:
         k = buf.k
-        coarse = L.ptr(occupancy_coarse_bits) if (occupancy_coarse_bits is not None and occupancy_bits is not None) else None
         travel = float("inf") if max_travel is None else float(max_travel)
-        _call("pag_raymarch_voxel_count_nuggets", L.ptr(origins), L.ptr(dirs), N, k, float(dist_min), float(dist_max), occ, coarse,
+        _call("pag_raymarch_voxel_count_nuggets", L.ptr(origins), L.ptr(dirs), N, k, float(dist_min), float(dist_max), occ,
               blas_level, travel, L.ptr(buf.counts), L.ptr(buf.nug_t), L.ptr(buf.nug_cell), st)
         _offsets(buf, N, mb_ptr, st, pad_capacity, dirs, dirs_out)
         _call("pag_raymarch_voxel_pack_nuggets", L.ptr(origins), L.ptr(dirs), N, k, L.ptr(buf.pack_start), L.ptr(buf.nug_t), L.ptr(buf.nug_cell), blas_level,

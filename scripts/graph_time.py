@@ -26,8 +26,7 @@ def ev(fn, n=20):
 print("fwd graph replay %.3f ms" % ev(g.fwd.replay))
 print("bwd graph replay %.3f ms" % ev(g.bwd.replay))
 def march():
-    mb, _ = ops.march_into(st.buf, rays.origins, rays.dirs, rays.dist_min, rays.dist_max, 2, occupancy_bits=nef.grid.blas_bits, blas_level=7, max_travel=6.0,
-                           occupancy_coarse_bits=nef.grid._coarse_bits(nef.grid.blas_bits))
+    mb, _ = ops.march_into(st.buf, rays.origins, rays.dirs, rays.dist_min, rays.dist_max, 2, occupancy_bits=nef.grid.blas_bits, blas_level=7, max_travel=6.0)
     st.buf.pad_to(list(st.buckets)[0])
     if mb is not None:
         ops._poll_count(mb); ops._release_mailbox(mb)

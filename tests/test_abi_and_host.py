@@ -27,7 +27,7 @@ def test_every_declared_symbol_is_exported(lib):
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     for name in declared:
         assert hasattr(lib, name), name
-    assert lib.pag_abi_version() == _lib.ABI_VERSION == 14
+    assert lib.pag_abi_version() == _lib.ABI_VERSION == 15
 
 
 @pytest.mark.parametrize("n", [0, 1, 256, 257, 65536, 65537, 2 ** 31 - 1, 2 ** 31, 2 ** 31 + 1])

@@ -244,7 +244,7 @@ def lib():
 
 def test_mesh_entry_points_resolve_and_refuse_bad_arguments(lib):
     from pagnerf_amd import _lib
-    assert {"pag_mesh_workspace_bytes", "pag_mesh_vertices", "pag_mesh_faces"} <= set(_lib.EXPORTS) and lib.pag_abi_version() == 14
+    assert {"pag_mesh_workspace_bytes", "pag_mesh_vertices", "pag_mesh_faces"} <= set(_lib.EXPORTS) and lib.pag_abi_version() == 15
     size = lib.pag_mesh_workspace_bytes
     assert 0 < size(17, 17, 17) < size(33, 33, 33) < size(257, 257, 257) < size(1025, 1025, 1025)
     assert size(257, 257, 257) >= (257 ** 3 * 3 + 255) // 256 * 12                        # an i64 and an i32 per block of 256 edge rows
