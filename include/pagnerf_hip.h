@@ -1091,11 +1091,11 @@ int pag_vm_bwd(const pag_vm_args *args, int64_t M, void *stream);
 
 /* Tri-plane feature grid (wisp TriplanarGrid, selected by configs/bup20/mean_shift_contrastive_app.yaml:137-144; additive, ABI 14): triplanar.hip.
  * Replaces the tensor-op form of pagnerf_amd/triplanar.py (per level three torch grid_sample calls and their sum).  f32 tables, f32 arithmetic.
- * Level l has resolution res[l] (a HOST array of n_levels ints, 2 <= res <= 8193) and three planes fmx, fmy, fmz; `tables` is ONE flat f32 buffer, 16-byte
+ * Level l has resolution res_host[l] (a HOST array of n_levels ints, 2 <= res <= 8193) and three planes fmx, fmy, fmz; `tables` is ONE flat f32 buffer, 16-byte
  * aligned, level after level, each level [3][R][R][F] channel-last (plane, row, column, feature).  Plane fmx reads (y, z), fmy (x, z), fmz (x, y): the
  * pair's first coordinate indexes the columns, the second the rows.  Sampling is grid_sample's bilinear / align_corners / reflection padding:
  *   pixel = ((c + 1) / 2) * (R - 1), reflected about [0, R - 1], clipped; the taps nw, ne, sw, se; the tap at index R is skipped.
- *   out[m, l*F + f] = ((fmx_l + fmy_l) + fmz_l)[f] * feat_scale[l*F + f]        (feat_scale: HOST array of n_levels * n_feat floats, or NULL = 1)
+ *   out[m, l*F + f] = ((fmx_l + fmy_l) + fmz_l)[f] * feat_scale_host[l*F + f]   (a HOST array of n_levels * n_feat floats, or NULL = 1)
  * n_levels in [1, 8], n_feat in {2, 4, 8}.
  *   pag_triplanar_fwd          xyz f32 [M,3] -> out [M, L*F] via strides, PAG_F32 or PAG_BF16 (the f32 result rounded once)
  *   pag_triplanar_bwd_tables   grad_out [M, L*F] via strides (PAG_F32 or PAG_BF16) -> grad_tables f32 (the flat layout), ADDED with float atomics (the
@@ -1103,12 +1103,12 @@ int pag_vm_bwd(const pag_vm_args *args, int64_t M, void *stream);
  *   pag_triplanar_bwd_xyz      d loss / d xyz f32 [M,3], OVERWRITTEN, from grad_out and the tables: d pixel / d c = +-(R - 1) / 2 by the parity of the
  *                              reflection, 0 where the clip is active (grid_sample's backward).  No atomics: fixed bits.
  * Bad sizes and NULL buffers are refused before any launch; M == 0 is a no-op (nothing is written). */
-int pag_triplanar_fwd(const float *xyz, int64_t M, const float *tables, int n_levels, int n_feat, const int *res, const float *feat_scale, void *out,
-                      int out_dtype, int64_t stride_m, int64_t stride_c, void *stream);
+int pag_triplanar_fwd(const float *xyz, int64_t M, const float *tables, int n_levels, int n_feat, const int *res_host, const float *feat_scale_host,
+                      void *out, int out_dtype, int64_t stride_m, int64_t stride_c, void *stream);
 int pag_triplanar_bwd_tables(const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t stride_m, int64_t stride_c, int n_levels, int n_feat,
-                             const int *res, const float *feat_scale, float *grad_tables, void *stream);
+                             const int *res_host, const float *feat_scale_host, float *grad_tables, void *stream);
 int pag_triplanar_bwd_xyz(const float *xyz, int64_t M, const float *tables, const void *grad_out, int grad_dtype, int64_t stride_m, int64_t stride_c,
-                          int n_levels, int n_feat, const int *res, const float *feat_scale, float *d_xyz, void *stream);
+                          int n_levels, int n_feat, const int *res_host, const float *feat_scale_host, float *d_xyz, void *stream);
 
 /* Lattice total variation (loss/regularizers.py:41-54, the grid TV terms of pc_nerf/trainer.py:556-574; additive, ABI 14): regularizer.hip.
  * `values` is channel-last and contiguous, viewed as [d0, d1, d2, C] (the lattice extents of the input padded with trailing 1s, then the channels), dtype

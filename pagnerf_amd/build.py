@@ -15,6 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpagnerf_hip.so")
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
+HEADER = os.path.join(INCLUDE, "pagnerf_hip.h")     # the C ABI: the sources include it, _lib.py binds the library from it
 ARCH = "gfx950"
 
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-munsafe-fp-atomics", "-Wno-unused-value"]
@@ -90,7 +92,7 @@ def _digest():
     h = hashlib.sha256()
     h.update(repr((COMMON, sorted(SOURCES.items()))).encode())
     h.update(_compiler_id().encode())
-    for root in (CSRC, os.path.join(os.path.dirname(HERE), "include")):
+    for root in (CSRC, INCLUDE):
         for f in sorted(os.listdir(root)):
             if not os.path.isfile(os.path.join(root, f)):
                 continue

@@ -288,24 +288,24 @@ __global__ __launch_bounds__(BLOCK) void tri_bwd_xyz_kernel(TriLevels lv, TriSca
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------ host
-int tri_setup(const char *name, int64_t M, int n_levels, int n_feat, const int *res, const float *feat_scale, TriLevels &lv, TriScale &sc) {
+int tri_setup(const char *name, int64_t M, int n_levels, int n_feat, const int *res_host, const float *feat_scale_host, TriLevels &lv, TriScale &sc) {
     PAG_CHECK_ARG(M >= 0 && M <= ((int64_t)1 << 31), "%s: M %lld not in [0,2^31]", name, (long long)M);
     PAG_CHECK_ARG(n_levels >= 1 && n_levels <= MAX_L, "%s: n_levels %d not in [1,%d]", name, n_levels, MAX_L);
     PAG_CHECK_ARG(n_feat == 2 || n_feat == 4 || n_feat == 8, "%s: n_feat %d not in {2,4,8}", name, n_feat);
-    PAG_CHECK_ARG(res, "%s: NULL res", name);
+    PAG_CHECK_ARG(res_host, "%s: NULL res", name);
     int64_t off = 0;
     for (int l = 0; l < MAX_L; ++l) {
         lv.off[l] = 0;
         lv.R[l] = 2;
     }
     for (int l = 0; l < n_levels; ++l) {
-        PAG_CHECK_ARG(res[l] >= 2 && res[l] <= 8193, "%s: res[%d] = %d not in [2,8193]", name, l, res[l]);
+        PAG_CHECK_ARG(res_host[l] >= 2 && res_host[l] <= 8193, "%s: res[%d] = %d not in [2,8193]", name, l, res_host[l]);
         lv.off[l] = off;
-        lv.R[l] = res[l];
-        off += (int64_t)3 * res[l] * res[l] * n_feat;
+        lv.R[l] = res_host[l];
+        off += (int64_t)3 * res_host[l] * res_host[l] * n_feat;
     }
     lv.L = n_levels;
-    for (int i = 0; i < MAX_L * 8; ++i) sc.v[i] = (feat_scale && i < n_levels * n_feat) ? feat_scale[i] : 1.0f;
+    for (int i = 0; i < MAX_L * 8; ++i) sc.v[i] = (feat_scale_host && i < n_levels * n_feat) ? feat_scale_host[i] : 1.0f;
     return PAG_OK;
 }
 
@@ -322,11 +322,11 @@ int tri_setup(const char *name, int64_t M, int n_levels, int n_feat, const int *
 
 }  // namespace
 
-extern "C" int pag_triplanar_fwd(const float *xyz, int64_t M, const float *tables, int n_levels, int n_feat, const int *res, const float *feat_scale, void *out,
-                                 int out_dtype, int64_t stride_m, int64_t stride_c, void *stream) {
+extern "C" int pag_triplanar_fwd(const float *xyz, int64_t M, const float *tables, int n_levels, int n_feat, const int *res_host, const float *feat_scale_host,
+                                 void *out, int out_dtype, int64_t stride_m, int64_t stride_c, void *stream) {
     TriLevels lv;
     TriScale sc;
-    int rc = tri_setup("pag_triplanar_fwd", M, n_levels, n_feat, res, feat_scale, lv, sc);
+    int rc = tri_setup("pag_triplanar_fwd", M, n_levels, n_feat, res_host, feat_scale_host, lv, sc);
     if (rc != PAG_OK) return rc;
     PAG_CHECK_ARG(out_dtype == PAG_F32 || out_dtype == PAG_BF16, "pag_triplanar_fwd: out_dtype %d (f32 or bf16)", out_dtype);
     if (M == 0) return PAG_OK;
@@ -352,10 +352,10 @@ extern "C" int pag_triplanar_fwd(const float *xyz, int64_t M, const float *table
 }
 
 extern "C" int pag_triplanar_bwd_tables(const float *xyz, int64_t M, const void *grad_out, int grad_dtype, int64_t stride_m, int64_t stride_c, int n_levels,
-                                        int n_feat, const int *res, const float *feat_scale, float *grad_tables, void *stream) {
+                                        int n_feat, const int *res_host, const float *feat_scale_host, float *grad_tables, void *stream) {
     TriLevels lv;
     TriScale sc;
-    int rc = tri_setup("pag_triplanar_bwd_tables", M, n_levels, n_feat, res, feat_scale, lv, sc);
+    int rc = tri_setup("pag_triplanar_bwd_tables", M, n_levels, n_feat, res_host, feat_scale_host, lv, sc);
     if (rc != PAG_OK) return rc;
     PAG_CHECK_ARG(grad_dtype == PAG_F32 || grad_dtype == PAG_BF16, "pag_triplanar_bwd_tables: grad_dtype %d (f32 or bf16)", grad_dtype);
     if (M == 0) return PAG_OK;
@@ -377,10 +377,10 @@ extern "C" int pag_triplanar_bwd_tables(const float *xyz, int64_t M, const void 
 }
 
 extern "C" int pag_triplanar_bwd_xyz(const float *xyz, int64_t M, const float *tables, const void *grad_out, int grad_dtype, int64_t stride_m, int64_t stride_c,
-                                     int n_levels, int n_feat, const int *res, const float *feat_scale, float *d_xyz, void *stream) {
+                                     int n_levels, int n_feat, const int *res_host, const float *feat_scale_host, float *d_xyz, void *stream) {
     TriLevels lv;
     TriScale sc;
-    int rc = tri_setup("pag_triplanar_bwd_xyz", M, n_levels, n_feat, res, feat_scale, lv, sc);
+    int rc = tri_setup("pag_triplanar_bwd_xyz", M, n_levels, n_feat, res_host, feat_scale_host, lv, sc);
     if (rc != PAG_OK) return rc;
     PAG_CHECK_ARG(grad_dtype == PAG_F32 || grad_dtype == PAG_BF16, "pag_triplanar_bwd_xyz: grad_dtype %d (f32 or bf16)", grad_dtype);
     if (M == 0) return PAG_OK;

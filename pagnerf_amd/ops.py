@@ -88,7 +88,7 @@ class _EncodeSpec:
             self.vertices, self._mid = 4, (self.capacity, self.sf, self.shift)
 
     def mid(self, feat_scale):
-        """The kind-specific middle of every pag_<kind>_encode_* argument list (_lib._ENC_MID): hash log2_T, resolutions, feat_scale; permuto capacity,
+        """The kind-specific middle of every pag_<kind>_encode_* argument list (the prototypes of include/pagnerf_hip.h): hash log2_T, resolutions, feat_scale; permuto capacity,
         scale_factor, shift, feat_scale."""
         return self._mid + (L.host_floats(feat_scale),)
 

@@ -30,6 +30,84 @@ def test_every_declared_symbol_is_exported(lib):
     assert lib.pag_abi_version() == _lib.ABI_VERSION == 15
 
 
+_MINI_HEADER = """\
+/* every construct include/pagnerf_hip.h uses; a name in a comment is not a prototype: pag_ghost(int)
+ * nor is one on a second comment line */
+#ifndef MINI_H
+#define MINI_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define PAG_N 4                        // a line comment
+#define PAG_BIG ((int64_t)1 << 24)
+enum { PAG_A = 2, PAG_B, PAG_C = -3, PAG_D };
+typedef struct pag_node {
+    int a, b; float w[3]; int32_t n[PAG_N];      /* several declarators, a literal and a named extent */
+    const struct pag_node *next; const struct pag_leaf *leaf, *leaves[2];
+    const unsigned char *bytes; void *const *rows; uint32_t u; double d;
+} pag_node;
+typedef struct pag_leaf { int64_t count; unsigned char tag[2]; } pag_leaf;
+int pag_version(void);
+const char *pag_name(void);
+int64_t pag_walk(const pag_node *node, pag_leaf *leaf,
+                 uint32_t flags, double scale, const float *x_host,
+                 void *const *rows, const unsigned char *bytes, void *stream);
+#ifdef __cplusplus
+}
+#endif
+#endif /* MINI_H */
+"""
+
+
+def test_header_parser_on_a_synthetic_header():
+    """_lib.parse_header on a header small enough to state its whole result: exact constants, field lists and signatures - and a header it cannot
+    read in full raises instead of binding the part it can read."""
+    from pagnerf_amd import _lib
+    C = ctypes
+    consts, structs, sigs = _lib.parse_header(_MINI_HEADER)
+    assert consts == {"PAG_N": 4, "PAG_BIG": 1 << 24, "PAG_A": 2, "PAG_B": 3, "PAG_C": -3, "PAG_D": -2}
+    assert list(structs) == ["pag_node", "pag_leaf"] and all(issubclass(s, C.Structure) and s.__name__ == n for n, s in structs.items())
+    node, leaf = structs["pag_node"], structs["pag_leaf"]
+    assert node._fields_ == [("a", C.c_int), ("b", C.c_int), ("w", C.c_float * 3), ("n", C.c_int32 * 4), ("next", C.POINTER(node)),
+                             ("leaf", C.POINTER(leaf)), ("leaves", C.POINTER(leaf) * 2), ("bytes", C.c_void_p), ("rows", C.c_void_p),
+                             ("u", C.c_uint32), ("d", C.c_double)]
+    assert leaf._fields_ == [("count", C.c_int64), ("tag", C.c_ubyte * 2)]
+    assert sigs == {"pag_version": (C.c_int, []), "pag_name": (C.c_char_p, []),
+                    "pag_walk": (C.c_int64, [C.POINTER(node), C.POINTER(leaf), C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])}
+    for good, bad, message in [("double scale", "long scale", "unknown type"),                          # a type word it does not know
+                               ("int pag_version(void);", "int pag_version(void)", "cannot split"),    # a missing semicolon
+                               ("uint32_t u; double d;", "uint32_t u; double d", "no ';' after"),      # ... and one inside a struct
+                               ('extern "C" {', 'extern "C" { int pag_hidden(int x);', r"no prototype read for \['pag_hidden'\]"),    # a prototype in a part it skips
+                               ("#define PAG_N 4 ", "#define PAG_N (2 + 2) ", "cannot evaluate"),
+                               ("#include <stdint.h>", "#if 1", "unknown preprocessor line")]:
+        assert _MINI_HEADER.count(good) == 1
+        with pytest.raises(ValueError, match=message):
+            _lib.parse_header(_MINI_HEADER.replace(good, bad))
+
+
+def test_ctypes_layouts_are_the_compilers(tmp_path):
+    """sizeof of every argument struct and offsetof / sizeof of every field, printed by a host program that includes the header and is compiled by the
+    compiler the library is built with, against what ctypes laid out from the parsed header: the widths, the order and the padding at the call boundary."""
+    import subprocess
+    from pagnerf_amd import _lib, build
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "pagnerf_hip.h"', "int main(void) {"]
+    expected = []
+    assert len(_lib._STRUCTS) == 13
+    for name, cls in _lib._STRUCTS.items():
+        lines.append('    printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        expected.append("%s %d" % (name, ctypes.sizeof(cls)))
+        for field, _ in cls._fields_:
+            lines.append('    printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (name, field, name, field, name, field))
+            expected.append("%s.%s %d %d" % (name, field, getattr(cls, field).offset, getattr(cls, field).size))
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    subprocess.run([build._hipcc(), "-I", build.INCLUDE, str(src), "-o", str(exe)], check=True, capture_output=True, text=True, timeout=300)    # a .c file: host only
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=60).stdout.splitlines()
+    assert len(out) == len(expected) > 13 + 200
+    assert out == expected, [(a, b) for a, b in zip(out, expected) if a != b]
+
+
 @pytest.mark.parametrize("n", [0, 1, 256, 257, 65536, 65537, 2 ** 31 - 1, 2 ** 31, 2 ** 31 + 1])
 def test_ordered_append_workspace_formulas(lib, n):
     """The three workspace sizes of the ordered appends, from their documented layouts: block_offset i64 [nb] and block_count i32 [nb] for the
