@@ -460,6 +460,29 @@ int pag_occupancy_update(const float *density, int64_t density_stride, float *oc
                          uint32_t *occupancy_bits, int64_t num_cells, float decay,
                          float min_density, void *stream);
 
+/* Occupancy carving from depth images (csrc/carve.hip; the tensor-op definitions are carve_reference / carve_finish_reference of pagnerf_amd/carve.py).
+ * Additive to ABI 15.  An addition of this package: the reference has no such step.
+ * pag_carve_rays: ray i = (origins[i], dirs[i]) f32 [N,3] in the world frame, t_hit f32 [N] the measured surface distance ALONG the ray in scene
+ *   units.  The ray is walked through the 2^blas_level lattice exactly as pag_raymarch_voxel_count_nuggets walks it (the same clip to
+ *   [dist_min, dist_max], first cell, DDA and fp32 roundings: the same candidates (t_in, t_out, cell), t_out > t_in).  A ray is valid iff t_hit is
+ *   finite and > 0; an invalid ray writes nothing.  With lo = t_hit - margin and hi = t_hit + margin (one fp32 rounding each) a candidate of a valid
+ *   ray is SURFACE iff t_in <= hi && t_out >= lo, else FREE iff t_out <= lo, else untouched (it lies behind the surface).  The bit (x*R + y)*R + z of
+ *   the cell is OR-ed into surface_bits / free_bits, u32 [max(1, R^3/32)] each, which the caller zeroes before the first call; calls accumulate.
+ *   One launch; integer atomic ORs, issued only where the bit is still clear.  The result is a set: it does not depend on the order of the rays or
+ *   on scheduling, so the same input gives the same bits.
+ * pag_carve_finish: D = surface_bits dilated `dilate` times by the 26-neighbourhood (Chebyshev radius `dilate`, no wrap-around at the cube's faces);
+ *   out_bits = ~free_bits | D (PAG_CARVE_HULL: a cell that no ray observed stays occupied) or D (PAG_CARVE_BAND: only the neighbourhood of measured
+ *   surfaces is kept).  Bits past R^3 in the last word are 0.  One launch, no atomics.  out_bits must not alias the inputs.
+ * Refused (PAG_ERR_ARG) before any launch: N < 0, NULL buffers (pag_carve_rays: with N > 0), blas_level outside [0, 10] (what
+ * pag_raymarch_voxel_nugget_capacity's march accepts), a negative or NaN margin, dilate outside [0, PAG_CARVE_MAX_DILATE], an unknown mode.
+ * N == 0 is a no-op. */
+#define PAG_CARVE_MAX_DILATE 4
+enum { PAG_CARVE_HULL = 0, PAG_CARVE_BAND = 1 };
+int pag_carve_rays(const float *origins, const float *dirs, const float *t_hit, int64_t N, float dist_min, float dist_max, float margin,
+                   int blas_level, uint32_t *free_bits, uint32_t *surface_bits, void *stream);
+int pag_carve_finish(const uint32_t *free_bits, const uint32_t *surface_bits, int blas_level, int dilate, int mode, uint32_t *out_bits,
+                     void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Alpha compositing - kaolin spc_render.exponential_integration / sum_reduce as used at
  * tracers/panoptic_packed_rf_tracer.py:134-182,197-205

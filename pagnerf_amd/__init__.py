@@ -28,6 +28,8 @@
             two windows' fused maps matched by voxel overlap and the maps merged (`python -m pagnerf_amd.map_export merge`)
             surface_nets, surface_nets_reference, density_lattice, extract_mesh, save_mesh, load_mesh, mesh_report (mesh.py): the labelled,
             coloured triangle mesh of the trained field (surface nets on the density lattice, csrc/mesh.hip); no counterpart in the reference
+    carve : carve_occupancy, carve_reference, carve_finish_reference, ray_lengths_from_depth (carve.py): the occupancy both grids start from, carved
+            from the dataset's depth images before training (csrc/carve.hip); no counterpart in the reference
     regularizers: tv_loss, tv_l1_loss, tv_l2_loss, grid_tv_loss, grid_tv_l1_loss, grid_tv_l2_loss, step_tv_terms (regularizers.py)
              <- loss/regularizers.py:41-70, pc_nerf/trainer.py:556-574 (the grid total-variation terms)
     dataset: DeviceMultiviewDataset, BatchSampler, SampleRays, sample_indices, epoch_views (dataset.py)
@@ -67,6 +69,7 @@ from .map_export import (MapAccumulator, generate_pc_map, generate_pc_map_from_v
                          merge_maps_reference, overlap_table, overlap_table_reference, relabel_map)
 from .mesh import (density_lattice, extract_mesh, load_mesh, mesh_report, save_mesh, surface_nets,    # noqa: F401
                    surface_nets_reference)
+from .carve import carve_finish_reference, carve_occupancy, carve_reference, ray_lengths_from_depth    # noqa: F401
 from .regularizers import (grid_tv_l1_loss, grid_tv_l2_loss, grid_tv_loss, step_tv_terms, tv_l1_loss, tv_l2_loss,    # noqa: F401
                            tv_loss)
 from .dataset import BatchSampler, DeviceMultiviewDataset, SampleRays, epoch_views, sample_indices    # noqa: F401

@@ -51,6 +51,7 @@ SOURCES = {
     "sample.hip": [],                        # the dataset's ray sampling: keyed permutation and row gather, integer and copy work only
     "visualize.hip": ["-ffp-contract=off"],  # validation pictures: the blends and the colour-map index in the tensor-op forms' op order
     "prepare.hip": ["-ffp-contract=off"],    # dataset view preparation: the alpha composite in the tensor-op form's op order (three roundings)
+    "carve.hip": ["-ffp-contract=off"],      # occupancy carving from depth: render.hip's voxel walk restated in the same fp32 op order
     "bup20.hip": ["-ffp-contract=off"],      # BUP20 loader: the fp64 line of a polygon's boundary points and the bilinear shrink in the written op order
 }
 

@@ -142,16 +142,20 @@ def semantic_info(class_labels=DEFAULT_CLASS_LABELS):
                 stuff_ids=[present[0]], things_ids=present[1:], num_instances=NUM_INSTANCES)
 
 
-def filter_load_modes(load_modes, split):
+def filter_load_modes(load_modes, split, keep_depths=False):
     """bup20.py:137-151 -> (preds_name, modes): the first mode with 'preds' in it names the prediction folder; split 'train' with predictions keeps only
     semantics / instance / instance_shuffled / sem_conf / inst_conf (so no depths, and the ground truth is whatever the window leaves), val and test drop
-    the prediction modes.  The reference indexes [0] of an empty list without a prediction mode; here that is a ValueError."""
+    the prediction modes.  The reference indexes [0] of an empty list without a prediction mode; here that is a ValueError.
+    keep_depths (an addition of this package, off by default): split 'train' carries 'depths' as well, whether load_modes names it or not - what the
+    depth carve (carve.carve_occupancy, the trainer's carve_from_depth) reads."""
     modes = list(load_modes) or list(DEFAULT_MODES)
     preds = [m for m in modes if "preds" in m]
     if not preds:
         raise ValueError("load_bup20: load_modes %r names no prediction folder (a mode with 'preds' in it, such as preds_mask2former)" % (modes,))
     if split == "train":
         modes = [m for m in modes if m in ("semantics", "instance", "instance_shuffled", "sem_conf", "inst_conf")]
+        if keep_depths:
+            modes.append("depths")
     elif split in ("val", "test"):
         modes = [m for m in modes if "preds" not in m]
     return preds[0], modes
@@ -769,7 +773,7 @@ def plan_frames(root, split, coco, image_sets, classes, dataset_center_idx=0, se
 
 def load_bup20(root, split, mip=0, bg_color="white", load_modes=(), class_labels=(), dataset_center_idx=0, pose_src="odom", max_depth=-1, scale=None,
                offset=None, model_rescaling="snap_to_bottom", seq_num_frames=40, device="cuda", num_workers=0, use_kernel=True,
-               add_noise_to_train_poses=False, dataset_mode="label_window", chunk_bytes=64 << 20):
+               add_noise_to_train_poses=False, dataset_mode="label_window", chunk_bytes=64 << 20, keep_depths=False):
     """The window of split `split` ('train' or 'val') about the dataset_center_idx-th usable eval frame of the BUP20 folder `root` ->
     DeviceMultiviewDataset on `device` with imgs, masks, rays, base_rays and, as the filtered load_modes ask (filter_load_modes), depths, semantics +
     semantics_pred, instance + instance_pred, sem_conf, inst_conf; carrying view_matrices, image_shape, filenames, scale, intrinsics and semantic_info
@@ -780,7 +784,8 @@ def load_bup20(root, split, mip=0, bg_color="white", load_modes=(), class_labels
     ground truth, pag_bup20_pred_stats (max_depth > 0) + pag_bup20_prepare for everything from the frames, pag_prepare_views for the rays.  A staging
     buffer is reused only after the event of its own copy has completed.  A polygon part beyond COCO_MAX_PART_KEYS keys is refused by the kernel's entry
     point before any launch; that image's label planes then come from the definition.  On a CPU device, or with use_kernel=False, the definition runs
-    throughout.  PREDICTIONS ARE PICKLES: only load a dataset you trust."""
+    throughout.  PREDICTIONS ARE PICKLES: only load a dataset you trust.
+    keep_depths: the 'train' split carries `depths` too (filter_load_modes drops it there, as the reference does): the depth carve needs it."""
     import yaml
     from .dataset import DeviceMultiviewDataset
     from .map_export import pinhole_base_rays
@@ -797,7 +802,7 @@ def load_bup20(root, split, mip=0, bg_color="white", load_modes=(), class_labels
     split = "val" if split == "valid" else split
     window_deltas(seq_num_frames, split)                                   # the split check
     class_labels = list(class_labels) or list(DEFAULT_CLASS_LABELS)
-    preds_name, modes = filter_load_modes(load_modes, split)
+    preds_name, modes = filter_load_modes(load_modes, split, keep_depths)
     json_path, yaml_path = dataset_files(root)
     coco = read_coco(json_path)
     with open(yaml_path) as f:
@@ -993,6 +998,7 @@ def main(argv=None):
     ap.add_argument("--dataset-center-idx", type=int, default=0)
     ap.add_argument("--pose-src", default="odom", choices=sorted(ODOMETRY_FILES))
     ap.add_argument("--max-depth", type=float, default=-1.0)
+    ap.add_argument("--keep-depths", action="store_true", help="--split train: write the depth images (metres) as well, for the trainer's carve_from_depth")
     ap.add_argument("--model-rescaling", default="snap_to_bottom", choices=("snap_to_bottom", "largest"))
     ap.add_argument("--seq-num-frames", type=int, default=40)
     ap.add_argument("--out", required=True, metavar="FILE.npz")
@@ -1001,7 +1007,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     ds = load_bup20(args.root, args.split, mip=args.mip, bg_color=args.bg_color, load_modes=args.load_modes, class_labels=args.class_labels,
                     dataset_center_idx=args.dataset_center_idx, pose_src=args.pose_src, max_depth=args.max_depth, model_rescaling=args.model_rescaling,
-                    seq_num_frames=args.seq_num_frames, device=args.device, num_workers=args.num_workers)
+                    seq_num_frames=args.seq_num_frames, device=args.device, num_workers=args.num_workers, keep_depths=args.keep_depths)
     with open(os.path.expanduser(args.out), "wb") as f:
         np.savez(f, **dataset_arrays(ds))
     return 0

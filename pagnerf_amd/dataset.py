@@ -236,6 +236,15 @@ class DeviceMultiviewDataset:
     def nbytes(self):
         return sum(l.src.numel() * l.src.element_size() for l in self._leaves)
 
+    def source(self, key, field=None):
+        """The stored array of mode `key` (`field` 'origins' / 'dirs' of a Rays mode) on the device - [V, H*W, C], a shared mode [H*W, C] - or None when
+        the dataset has no such mode.  What a pass over whole images reads (the depth carve); a uint8-stored mode comes as stored."""
+        return next((l.src for l in self._leaves if l.key == key and l.field == field), None)
+
+    def rays_range(self, key):
+        """(dist_min, dist_max) of the Rays mode `key`."""
+        return self._rays_range[key]
+
     # ------------------------------------------------------------------------------------------------------------------ state
     def seed(self, seed, draw=0):
         """Start the stream of (seed, draw): an asynchronous 16-byte copy on a CUDA device."""

@@ -30,16 +30,22 @@ class OccupancyBLAS(nn.Module):
         self.num_cells = R ** 3
         words = max(1, self.num_cells // 32)
         self.register_buffer("blas_bits", torch.full((words,), -1, dtype=torch.int32))
+        self.register_buffer("carve_bits", None)        # set_carve(): the cells a depth carve left; absent (and out of the state dict) by default
         self.occupancy = torch.zeros(self.num_cells)
         self._dense_points = None
         self._all_occupied = True
         self._pack_cache = None
 
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         """A checkpoint replaces buffers the kernels do not read directly: the march takes `_all_occupied`, the encoders a host copy of
         the per-level shifts (`_spec`).  Both are derived state - rebuild them from what was just loaded (resume pattern of the
         reference: main_hp_tunning.py:197 `pipeline.load_state_dict`)."""
-        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        key = prefix + "carve_bits"
+        if key in state_dict and self.carve_bits is None:          # a carved run's checkpoint into a fresh grid: the buffer comes with it
+            self.carve_bits = torch.zeros_like(self.blas_bits)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        if key not in state_dict and self.carve_bits is not None and key in missing_keys:
+            missing_keys.remove(key)                                   # a checkpoint without a carve: this grid keeps its own, nothing is missing
         self._refresh_derived()
 
     def _refresh_derived(self):
@@ -55,6 +61,22 @@ class OccupancyBLAS(nn.Module):
             self._dense_points = torch.stack(torch.meshgrid(ar, ar, ar, indexing="ij"), -1).reshape(-1, 3)
         return self._dense_points
 
+    def set_carve(self, bits):
+        """Keep `bits` (int32 words as blas_bits: carve.carve_occupancy) as the cells a depth carve left, or drop them (None).  From here on blas_init()
+        and blas_init_bits() AND their mask with it: the prune rebuilds the mask from the density every time and could otherwise re-open carved cells.
+        The current blas_bits are not touched - follow with blas_init_bits(bits) to start from the carve."""
+        if bits is not None:
+            assert bits.dtype == torch.int32 and bits.numel() == self.blas_bits.numel()
+            bits = bits.detach().reshape(-1).clone().to(self.blas_bits.device)
+        self.carve_bits = bits
+
+    def _carved(self, bits):
+        if self.carve_bits is None:
+            return bits
+        if self.carve_bits.device != bits.device:
+            self.carve_bits = self.carve_bits.to(bits.device)
+        return bits & self.carve_bits
+
     def blas_init(self, mask):
         """Rebuild from a bool [R^3] mask of kept cells (panoptic_delta_nef.py:98-104)."""
         mask = mask.reshape(-1).to(torch.bool)
@@ -64,13 +86,13 @@ class OccupancyBLAS(nn.Module):
             mask = torch.cat([mask, mask.new_zeros(pad)])
         w = (mask.reshape(-1, 32).long() << torch.arange(32, device=mask.device)).sum(1)
         w = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
-        self.blas_bits = w.to(self.blas_bits.device)
+        self.blas_bits = self._carved(w.to(self.blas_bits.device))
         self._refresh_derived()              # also drops the pack cache keyed on the old tensor
 
     def blas_init_bits(self, bits):
         """Adopt a packed bitfield produced on the device (ops.occupancy_update)."""
         assert bits.dtype == torch.int32 and bits.numel() == self.blas_bits.numel()
-        self.blas_bits = bits.clone()
+        self.blas_bits = self._carved(bits.clone())
         self._refresh_derived()
 
     def occupancy_mask(self):

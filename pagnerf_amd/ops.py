@@ -1498,6 +1498,44 @@ def occupancy_update(density, occupancy, bits, decay, min_density):
           float(min_density), L.stream())
 
 
+def _carve_bits(name, what, bits, blas_level):
+    words = max(1, (2 ** int(blas_level)) ** 3 // 32)
+    if bits.dtype != torch.int32 or bits.numel() != words or not bits.is_contiguous():
+        raise ValueError("%s: %s must be a contiguous int32 [%d] bitfield of level %d, got %s %s" % (name, what, words, blas_level, bits.dtype, tuple(bits.shape)))
+
+
+def carve_rays(origins, dirs, t_hit, dist_min, dist_max, margin, blas_level, free_bits, surface_bits):
+    """pag_carve_rays (carve.carve_reference is the definition): the cells that the rays (origins, dirs f32 [N,3]; t_hit f32 [N] the measured distance
+    along the ray, <= 0 / NaN / inf = no measurement) cross in front of t_hit - margin are OR-ed into free_bits, the cells within margin of t_hit
+    into surface_bits: int32 [max(1, R^3/32)] each, zeroed by the caller before the first call.  One launch."""
+    _check_gpu(origins, dirs, t_hit, free_bits, surface_bits)
+    N = t_hit.numel()
+    if origins.shape != (N, 3) or dirs.shape != (N, 3) or any(t.dtype != torch.float32 for t in (origins, dirs, t_hit)):
+        raise ValueError("carve_rays: origins / dirs must be f32 [N,3] and t_hit f32 [N], got %s %s %s" % (tuple(origins.shape), tuple(dirs.shape), tuple(t_hit.shape)))
+    _carve_bits("carve_rays", "free_bits", free_bits, blas_level)
+    _carve_bits("carve_rays", "surface_bits", surface_bits, blas_level)
+    _call("pag_carve_rays", L.ptr(origins), L.ptr(dirs), L.ptr(t_hit), N, float(dist_min), float(dist_max), float(margin), int(blas_level),
+          L.ptr(free_bits), L.ptr(surface_bits), L.stream())
+
+
+def carve_finish(free_bits, surface_bits, blas_level, dilate=1, mode="hull", out=None):
+    """pag_carve_finish (carve.carve_finish_reference is the definition): surface dilated `dilate` times by the 26-neighbourhood = D;
+    'hull': ~free | D, 'band': D -> int32 bits (a new tensor, or `out`).  One launch."""
+    _check_gpu(free_bits, surface_bits, out)
+    modes = {"hull": L.CARVE_HULL, "band": L.CARVE_BAND}
+    if mode not in modes:
+        raise ValueError("carve_finish: unknown mode %r (hull / band)" % (mode,))
+    _carve_bits("carve_finish", "free_bits", free_bits, blas_level)
+    _carve_bits("carve_finish", "surface_bits", surface_bits, blas_level)
+    if out is None:
+        out = torch.empty_like(free_bits)
+    _carve_bits("carve_finish", "out", out, blas_level)
+    if out.data_ptr() in (free_bits.data_ptr(), surface_bits.data_ptr()):
+        raise ValueError("carve_finish: out must not alias an input")
+    _call("pag_carve_finish", L.ptr(free_bits), L.ptr(surface_bits), int(blas_level), int(dilate), modes[mode], L.ptr(out), L.stream())
+    return out
+
+
 # ----------------------------------------------------------------------------------------- composite
 class _Composite(torch.autograd.Function):
     @staticmethod

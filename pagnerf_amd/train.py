@@ -1,6 +1,7 @@
 """python -m pagnerf_amd.train --config YAML --dataset TRAIN.npz|DIR [--val-dataset VAL.npz|DIR] [--log-dir DIR] [--resume CKPT] [--valid-only]
                               [--val-pictures] [--save-map PATH [--map-voxel-size V [--map-min-votes N] [--map-min-component N] [--map-split MODE]]]
                               [--save-mesh PATH.ply [--mesh-resolution R] [--mesh-min-density D]] [--set key=value ...]
+                              [--carve-from-depth [--carve-margin M] [--carve-dilate N] [--carve-mode hull|band] [--carve-stride S] [--carve-max-range METRES]]
 
 The native counterpart of the reference's main_interactive.py: a shipped YAML, a dataset, and the trainer of trainer.py.
 
@@ -72,7 +73,7 @@ def is_bup20(path, cfg):
 def load_dataset(path, split, cfg, device):
     """--dataset / --val-dataset: a BUP20 folder (is_bup20) goes to bup20.load_bup20 with load_modes, class_labels, dataset_center_idx, pose_src,
     max_depth, scale, offset and model_rescaling from the YAML namespace (and `seq_num_frames`, this package's own key: the reference fixes the window at
-    40), any other folder to formats.load_nerf_standard (split `split`; mip, bg_color
+    40; with `carve_from_depth` the training window keeps its `depths`, which the reference's mode filter drops), any other folder to formats.load_nerf_standard (split `split`; mip, bg_color
     and dataset_num_workers from the namespace for both), anything else to load_npz_dataset."""
     path = os.path.expanduser(path)
     if not os.path.isdir(path):
@@ -86,7 +87,7 @@ def load_dataset(path, split, cfg, device):
                                 max_depth=-1 if max_depth is None else max_depth, scale=cfg.get("scale"), offset=cfg.get("offset"),
                                 model_rescaling=cfg.get("model_rescaling") or "snap_to_bottom", seq_num_frames=int(cfg.get("seq_num_frames") or 40),
                                 add_noise_to_train_poses=bool(cfg.get("add_noise_to_train_poses")), dataset_mode=cfg.get("dataset_mode") or "label_window",
-                                **common)
+                                keep_depths=bool(cfg.get("carve_from_depth")) and split == "train", **common)
     return formats.load_nerf_standard(path, split=split, **common)
 
 
@@ -130,7 +131,7 @@ def save_mesh(trainer, path, resolution=256, min_density=None):
     return path
 
 
-def main(argv=None):
+def make_parser():
     ap = argparse.ArgumentParser(prog="python -m pagnerf_amd.train", description=__doc__.split("\n\n")[1])
     ap.add_argument("--config", required=True, help="a YAML in the reference's layout (configs/bup20/*.yaml)")
     ap.add_argument("--dataset", required=True, help="training views: a NeRF-standard folder or an .npz")
@@ -154,10 +155,26 @@ def main(argv=None):
     ap.add_argument("--mesh-resolution", type=int, default=256, metavar="R", help="--save-mesh: lattice cells per axis (default 256)")
     ap.add_argument("--mesh-min-density", type=float, metavar="D", help="--save-mesh: the density of the surface (default: the dense map export's "
                     "0.01 * 512 / sqrt(3))")
+    ap.add_argument("--carve-from-depth", action="store_true", help="before the first step carve both grids' occupancy from the training views' depth "
+                    "images (the dataset needs its 'depths' mode and `scale`; the YAML key carve_from_depth does the same)")
+    ap.add_argument("--carve-margin", type=float, metavar="M", help="--carve-from-depth: the band around a measured surface that stays occupied, in scene "
+                    "units (default: two cells of the occupancy lattice); with pose optimisation it must cover the expected pose error")
+    ap.add_argument("--carve-dilate", type=int, metavar="N", help="--carve-from-depth: rings of neighbour cells added to the surface cells, 0 .. 4 (default 1)")
+    ap.add_argument("--carve-mode", choices=("hull", "band"), help="--carve-from-depth: hull keeps every cell no ray saw to be empty (default), band only "
+                    "the neighbourhood of measured surfaces (depth holes lose geometry)")
+    ap.add_argument("--carve-stride", type=int, metavar="S", help="--carve-from-depth: walk every S-th pixel per axis (default 1)")
+    ap.add_argument("--carve-max-range", type=float, metavar="METRES", help="--carve-from-depth: depth readings beyond this many metres are not used")
     ap.add_argument("--set", action="append", default=[], metavar="key=value", help="override an option of the flattened namespace (repeatable)")
     ap.add_argument("--device", default="cuda")
-    args = ap.parse_args(argv)
+    return ap
 
+
+CARVE_KEYS = ("carve_margin", "carve_dilate", "carve_mode", "carve_stride", "carve_max_range")
+
+
+def config_from_args(args):
+    """The flattened namespace of a parsed command line: the YAML, then --set, then the flags that stand for a key (--log-dir, --valid-only,
+    --val-pictures, --carve-from-depth and the --carve-* options that were given)."""
     from . import config
     cfg = config.load_config(args.config)
     config.apply_overrides(cfg, args.set)
@@ -167,6 +184,18 @@ def main(argv=None):
         cfg["valid_only"] = True
     if args.val_pictures:
         cfg["val_pictures"] = True
+    if args.carve_from_depth:
+        cfg["carve_from_depth"] = True
+    for key in CARVE_KEYS:
+        if getattr(args, key) is not None:
+            cfg[key] = getattr(args, key)
+    return cfg
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
+    from . import config
+    cfg = config_from_args(args)
     logging.basicConfig(level=int(cfg.get("log_level") or logging.INFO), format="%(asctime)s|%(levelname)8s| %(message)s")
     device = torch.device(args.device)
     if device.type == "cuda" and device.index is None:

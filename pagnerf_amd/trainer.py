@@ -140,7 +140,9 @@ class PanopticTrainer:
     dataset / val_dataset: DeviceMultiviewDatasets.  Beside their modes the trainer reads these attributes when present: `semantic_info` (dict with
     things_ids / stuff_ids / num_classes), `image_shape` (H, W) of the validation images, `filenames`, `labelled` (per view: (semantics, instances)
     carry labels).  Additions of this build: `seed` (the samplers' stream), `use_graphs` (None: leave the tracer as it is), `val_pictures`
-    (validate() writes the frames of num_val_frames_to_save / render_val_labels as PNG files; off by default)."""
+    (validate() writes the frames of num_val_frames_to_save / render_val_labels as PNG files; off by default), `carve_from_depth` with carve_margin /
+    carve_dilate / carve_mode / carve_stride / carve_max_range / carve_depth_kind (carve.carve_occupancy's arguments): before the first step of a
+    fresh run the training dataset's depth images carve both grids' occupancy (carve_occupancy_from_depth); epoch_plan() does not know about it."""
 
     def __init__(self, pipeline, dataset, val_dataset=None, *, epochs=250, batch_size=512, num_rays_sampled_per_img=4096, lr=0.001, weight_decay=0,
                  grid_lr_weight=100.0, delta_grid_lr_weight=100.0, optimizer_type="adam", log_dir="_results/logs/runs/", exp_name=None,
@@ -155,7 +157,9 @@ class PanopticTrainer:
                  inst_num_dilations=-1, val_mip=None, num_clustering_samples=0, num_val_frames_to_save=0, render_val_labels=False,
                  dataset_num_workers=-1, optimize_val_extrinsics=False, val_extrinsics_start=0, val_extrinsics_end=-1, val_extrinsics_every=0,
                  prune_every=-1, prune_at_epoch=-1, prune_at_start=False, low_res_val=False, save_grid=False, save_preds=False, sem_softmax=False,
-                 voxel_raymarch_epoch_start=-1, samples_per_voxel=256, seed=0, use_graphs=None, val_pictures=False, **kwargs):
+                 voxel_raymarch_epoch_start=-1, samples_per_voxel=256, seed=0, use_graphs=None, val_pictures=False,
+                 carve_from_depth=False, carve_margin=None, carve_dilate=1, carve_mode="hull", carve_stride=1, carve_max_range=None,
+                 carve_depth_kind="z", **kwargs):
         self.pipeline, self.dataset, self.val_dataset = pipeline, dataset, val_dataset
         self.extra_args = kwargs
         self.num_epochs, self.batch_size, self.num_rays_sampled_per_img = int(epochs), int(batch_size), int(num_rays_sampled_per_img)
@@ -207,6 +211,11 @@ class PanopticTrainer:
         self.voxel_raymarch_epoch_start, self.samples_per_voxel = voxel_raymarch_epoch_start, samples_per_voxel
         self.seed = int(seed)
         self.val_pictures = bool(val_pictures)
+        self.carve_from_depth = bool(carve_from_depth)
+        self.carve = dict(margin=carve_margin, dilate=int(carve_dilate), mode=carve_mode, stride=int(carve_stride), max_range=carve_max_range,
+                          depth_kind=carve_depth_kind)
+        self.carve_report = None
+        self._carve_pending = self.carve_from_depth          # resume() clears it: a checkpoint brings the carved buffers with it
         self._pictures = self._picture_host = None
 
         tracer = getattr(pipeline, "tracer", None)
@@ -349,6 +358,8 @@ class PanopticTrainer:
         """:302-329: the extrinsics' requires_grad window; in a validation-pose epoch the validation loader and a frozen field."""
         plan = self.plan = self.epoch_plan(self.epoch)
         pipe, tracer = self.pipeline, self.pipeline.tracer
+        if self._carve_pending:
+            self.carve_occupancy_from_depth()
         self.training_val_poses = plan["val_pose_epoch"]
         if self.training_val_poses and self.val_sampler is None:
             raise RuntimeError("a validation-pose epoch needs the validation dataset (optimize_val_extrinsics)")
@@ -385,6 +396,18 @@ class PanopticTrainer:
         self.iteration = 0
         self.epoch_start_time = time.time()
         return plan
+
+    def carve_occupancy_from_depth(self):
+        """carve_from_depth: the training dataset's depth images -> the occupancy both grids start from (carve.carve_occupancy), kept on the grids
+        (set_carve) so that later prunes can only shrink it.  Runs once, before the first step of a fresh run.  -> the report."""
+        from .carve import carve_occupancy, report_line
+        self._carve_pending = False
+        bits, self.carve_report = carve_occupancy(self.dataset, self.pipeline, **self.carve)
+        for g in self._grids().values():
+            g.set_carve(bits)
+            g.blas_init_bits(bits)
+        log.info(report_line(self.carve_report))
+        return self.carve_report
 
     def run_epoch(self):
         """One epoch: begin_epoch(), a step per batch of the epoch's sampler, end_epoch()."""
@@ -753,6 +776,7 @@ class PanopticTrainer:
     def resume(self, path):
         """Continue the run of save_checkpoint(path) in a trainer built the same way."""
         state = torch.load(path, map_location="cpu", weights_only=False)
+        self._carve_pending = False
         pipe, nef, tracer = self.pipeline, self.pipeline.nef, self.pipeline.tracer
         res = state.get("grid_resolution")
         if res is not None and getattr(nef.grid, "current_resolution", res) != res:
